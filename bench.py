@@ -1,7 +1,22 @@
 """Benchmark: proximal-gradient iterations/s on (m,n,l) = (8192,16384,32) fp64 (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--method gl_ProxGD_primal] [--dtype f64]
-                    [--m 8192 --n 16384 --l 32] [--no-cpu-baseline] [--variant V]
+                    [--m 8192 --n 16384 --l 32] [--variant V] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-whole-solve]]
+
+A plain run does what the headline figure needs and no more: it builds the instance, pre-warms,
+warms up, times the K steps (with the in-run kernel events behind `roofline`), writes its outputs
+if --dump-outputs is given, and prints the JSON line. --full adds the legs that take runs of
+their own: `whole_solve` (the complete solve, checked against the reference's run of the same
+call) and `cpu_baseline` (the NumPy oracle on the host, and the GPU solver on the same sample);
+--no-whole-solve / --no-cpu-baseline drop one of them again. Without --full both fields are null.
+
+--dump-outputs DIR: after the timed steps, what the timed session hands its caller once its last
+step is done is written to DIR as .npy files (float64): `x` (the iterate, n x l), `f_hist` and
+`f_hist_best` (one entry per recorded iteration, warmup included) and `fval`. An output larger
+than DUMP_MAX_BYTES is stored as a fixed, seeded sample of its entries (the same flat indices
+in every run of the same shape, in increasing order). The instance is drawn from a fixed seed, so two runs with the same
+arguments start from identical inputs. N > 1: rank 0 writes (every rank holds the same x).
 
 One step = one recorded iteration of the solver (objective, stop rule, threshold, A^T(Ax-b),
 line search, prox) on one synthetic instance whose A, b, x live in HBM before timing starts.
@@ -41,7 +56,7 @@ of the iteration, with A@X a few us behind):
              2*FETCH_SIZE + WRITE_SIZE per the gfx950 correction) when that file holds the same
              config and kernel, else null;
   cpu_baseline — the repo's NumPy oracle (oracle/numpy_ref.py) on the host cores, on a bounded
-             sample of the same instance (rank 0, N = 1 only).
+             sample of the same instance (rank 0, N = 1, --full only).
 """
 from __future__ import annotations
 
@@ -288,6 +303,28 @@ def launch_ranks(args):
     return subprocess.call(cmd)
 
 
+DUMP_MAX_BYTES = 48 * 2 ** 20   # per array; x, f_hist, f_hist_best and fval stay under 64 MB in all
+DUMP_SEED = 97006855
+
+
+def dump_outputs(dest, x, res):
+    """--dump-outputs: the timed session's results after its last step, as float64 .npy files.
+    x (device tensor) is the iterate the session updated in place; res is Session.finish()."""
+    os.makedirs(dest, exist_ok=True)
+    xh = x.detach().cpu().numpy().astype(np.float64)
+    cap = DUMP_MAX_BYTES // 8
+    if xh.size > cap:
+        idx = np.sort(np.random.RandomState(DUMP_SEED).choice(xh.size, size=cap, replace=False))
+        xh = xh.reshape(-1)[idx]
+    arrays = {"x": xh,
+              "f_hist": np.asarray(res["f_hist"], dtype=np.float64)[-cap // 8:],
+              "f_hist_best": np.asarray(res["f_hist_best"], dtype=np.float64)[-cap // 8:],
+              "fval": np.asarray([res["fval"]], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dest, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def glx_env():
     """Every GLX_* knob set in the environment (empty at the measured defaults)."""
     return {k: v for k, v in sorted(os.environ.items()) if k.startswith("GLX_")}
@@ -312,9 +349,15 @@ def main():
                     help="seconds of a throwaway solver session before the warmup (0 = off)")
     ap.add_argument("--dry-run-launch", action="store_true",
                     help="print the launcher decision (child command, visible devices) and exit")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: the whole solve (checked "
+                         "against the reference's run) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed session's results after its last step to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-whole-solve", action="store_true",
-                    help="skip the whole-solve figure reported beside the timed window")
+                    help="with --full: skip the whole-solve figure reported beside the timed window")
     ap.add_argument("--force-comm", action="store_true",
                     help="create the communicator even at world size 1 (runs the N-GPU code path "
                          "with identity all-reduces: a one-GPU model of a rank's schedule)")
@@ -467,12 +510,16 @@ def main():
     s.close()
     if done != args.steps:
         log("warning: solver finished after %d of %d timed steps" % (done, args.steps))
-    # Beside the K-step window (iterations warmup+1 .. warmup+K of the first continuation phase),
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        dumped = dump_outputs(args.dump_outputs, x, res)
+    # --full only. Beside the K-step window (iterations warmup+1 .. warmup+K of the first continuation phase),
     # the complete solve from x0 to the solver's own stop rule, every rank (the same collectives),
     # timed by the solver itself (tt, synchronized): the split-candidate trials get slower later
     # in a solve (more rows flagged), so the window alone favours the start.
     whole = None
-    if not args.no_whole_solve:
+    if args.full and not args.no_whole_solve:
         wopts = {"alpha0": alpha0, "ax_variant": args.variant, "exact_objective": args.exact}
         _, kw, outw = glx.solve(args.method, x0.clone(), A, b, mu, wopts, comm=comm)
         torch.cuda.synchronize()
@@ -613,7 +660,9 @@ def main():
                      "device_decided_frac": (res["stats"][7] / max(1, res["k"])
                                              if args.method == "gl_ProxGD_primal" else 0.0)},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(args.method, A, b, x0, mu,
                                                     {"alpha0": alpha0})

@@ -7,7 +7,7 @@ O=gpurun_out/${OUT:-r6_axb}; rm -rf $O; mkdir -p $O
 for rep in 1 2; do
   for v in "k5:GLX_AXB_VARIANT=52228" "d78:GLX_AXB_VARIANT=92278" "d68:GLX_AXB_VARIANT=92268"; do
     name=${v%%:*}; envs=${v#*:}
-    env $envs timeout -k 10 300 python3 bench.py --method gl_FProxGD_primal --steps 20 --warmup 5 --no-cpu-baseline > $O/$name.$rep.json 2> $O/$name.$rep.err || { echo "$name failed"; tail -5 $O/$name.$rep.err; exit 1; }
+    env $envs timeout -k 10 300 python3 bench.py --full --method gl_FProxGD_primal --steps 20 --warmup 5 --no-cpu-baseline > $O/$name.$rep.json 2> $O/$name.$rep.err || { echo "$name failed"; tail -5 $O/$name.$rep.err; exit 1; }
     echo -n "$name ($rep): " | tee -a $O/status.txt; python3 scripts/bench_summary.py $O/$name.$rep.json | tee -a $O/status.txt
   done
 done

@@ -14,7 +14,7 @@ timeout -k 10 600 python -u -m pytest -v --timeout 150 --timeout-method thread -
 rc=$?; echo "tests rc=$rc"; tail -4 $OUT/pytest.log
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit 1
 for f in 0 1; do   # NS: A e fused into the dense pass against the gather form
-  GLX_AE_FUSED=$f timeout -k 10 150 python bench.py --steps 200 --warmup 20 --no-cpu-baseline \
+  GLX_AE_FUSED=$f timeout -k 10 150 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline \
     > $OUT/ns_fused$f.json 2> $OUT/ns_fused$f.err || { echo "ns fused$f failed"; exit 1; }
 done
 echo "ns ab ok"

@@ -13,7 +13,7 @@ for row in sorted(csv.DictReader(open(sys.argv[1])), key=lambda x: -float(x["Tot
     print("%-70s calls %5s avg %7.1f us" % (row["Name"][:70], row["Calls"], float(row["AverageNs"]) / 1e3))
 PY
 }
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/drv -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/drv.json 2> $O/drv.err || { tail -20 $O/drv.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/drv -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/drv.json 2> $O/drv.err || { tail -20 $O/drv.err; exit 1; }
 python3 scripts/bench_summary.py $O/drv.json
 stats $O/drv/run_kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do

@@ -8,7 +8,7 @@ tail -1 $O/pytest.log
 for rep in 1 2; do
   for v in "h0:GLX_AE_HYB_ROWS=0" "h1000:GLX_AE_HYB_ROWS=1000" "h1500:GLX_AE_HYB_ROWS=1500" "h2000:GLX_AE_HYB_ROWS=2000" "h2500:GLX_AE_HYB_ROWS=2500" "egat:GLX_AE_FUSED=1"; do
     name=${v%%:*}; envs=${v#*:}
-    env $envs timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/$name.$rep.json 2> $O/$name.$rep.err || exit 1
+    env $envs timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/$name.$rep.json 2> $O/$name.$rep.err || exit 1
     echo -n "$name ($rep): " | tee -a $O/status.txt; python3 scripts/bench_summary.py $O/$name.$rep.json | tee -a $O/status.txt
   done
 done

@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/${OUT:-r6_rehearse}; rm -rf $O; mkdir -p $O
 for N in 8 4; do
-  timeout -k 10 500 python3 bench.py --gpus $N --comm host --steps 10 --warmup 3 --no-cpu-baseline > $O/host$N.json 2> $O/host$N.err || { tail -30 $O/host$N.err; exit 1; }
+  timeout -k 10 500 python3 bench.py --full --gpus $N --comm host --steps 10 --warmup 3 --no-cpu-baseline > $O/host$N.json 2> $O/host$N.err || { tail -30 $O/host$N.err; exit 1; }
   python3 - $O/host$N.json <<'PY'
 import json, sys
 d = json.loads([x for x in open(sys.argv[1]) if x.startswith("{")][-1])

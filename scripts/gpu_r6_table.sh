@@ -7,8 +7,8 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/${OUT:-r6_table}; rm -rf $O; mkdir -p $O
 run() {   # tag, bench args
   local tag=$1; shift
-  timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $O/${tag}_d.json 2> $O/${tag}_d.err || return 1
-  timeout -k 10 300 python3 bench.py --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline "$@" > $O/${tag}_w.json 2> $O/${tag}_w.err || return 1
+  timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 "$@" > $O/${tag}_d.json 2> $O/${tag}_d.err || return 1
+  timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline "$@" > $O/${tag}_w.json 2> $O/${tag}_w.err || return 1
   python3 - $O $tag <<'PY' | tee -a $O/status.txt
 import json, sys
 O, tag = sys.argv[1], sys.argv[2]

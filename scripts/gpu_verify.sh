@@ -1,6 +1,6 @@
 #!/bin/bash
 # Verification on one MI355X: GPU test suite, smoke(), then bench lines.
-#   bash scripts/gpu_verify.sh TAG ["bench args 1" "bench args 2" ...]   (default: one default bench)
+#   bash scripts/gpu_verify.sh TAG ["bench args 1" "bench args 2" ...]   (default: one bench --full)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 TAG=${1:-verify}; shift
 O=gpurun_out/$TAG; rm -rf $O; mkdir -p $O
@@ -10,7 +10,7 @@ tail -3 $O/pytest.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?; echo "smoke rc=$rc" >> $O/status.txt
 tail -1 $O/smoke.log
 [ $rc -eq 0 ] || exit 1
-[ $# -eq 0 ] && set -- ""
+[ $# -eq 0 ] && set -- "--full"
 i=0
 for args in "$@"; do
   i=$((i+1))

@@ -43,6 +43,30 @@ def test_launcher_refuses_without_enough_gpus():
     assert "refusing" in out.stderr
 
 
+def test_dump_outputs_writes_float64_npy(tmp_path, monkeypatch):
+    """--dump-outputs: x, f_hist, f_hist_best and fval as float64 .npy; an x beyond the per-array
+    cap is stored as the same seeded sample of its entries in every run."""
+    import numpy as np
+    import torch
+
+    import bench
+    x = torch.arange(24, dtype=torch.float32).reshape(6, 4)
+    res = {"f_hist": [np.float64(3.0), np.float64(2.0)], "f_hist_best": [np.float64(3.0), np.float64(2.0)],
+           "fval": np.float64(2.0)}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), x, res)
+    assert shapes == {"x": [6, 4], "f_hist": [2], "f_hist_best": [2], "fval": [1]}
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in shapes}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["x"], x.numpy()) and np.array_equal(got["f_hist"], [3.0, 2.0])
+    assert got["fval"][0] == 2.0
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 10)
+    bench.dump_outputs(str(tmp_path / "b"), x, res)
+    bench.dump_outputs(str(tmp_path / "c"), x, res)
+    xb, xc = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert xb.shape == (10,) and np.array_equal(xb, xc)
+    assert np.all(np.diff(xb) > 0) and set(xb) <= set(range(24))
+
+
 def test_rank_world_mismatch_is_an_error():
     env = _env()
     env.update(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
