@@ -6,11 +6,13 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include <cstdlib>
 #include <string>
 #include <tuple>
 #include <utility>
 
 #include "glx.h"
+#include "glx_tiles.h"
 
 namespace glx {
 
@@ -146,35 +148,41 @@ struct Pub {
   double* dout[2] = {nullptr, nullptr};
 };
 
-// Launch plan of the two dense products for one (dtype, m, n, l).
+// Launch plan of the two dense products for one (dtype, m, n, l): the tiles (records of
+// glx_tiles.h, chosen at plan time; a launch never searches the table) and their splits.
 struct GemmPlan {
   int esize;        // 4 or 8
   int64_t m, n, l;
   // A @ X  ->  P[ax_S][m][l] partial slabs (summed by finalize_residual)
-  int ax_kind;      // 1 = MFMA direct row loads, 2 = MFMA quad loads + bpermute, 3 = VALU
-  int ax_mt, ax_pf; // MFMA: 16-row tiles per wave, chunks in flight per wave
-  int ax_code;      // MFMA variant code (kind*1000 + MT*100 + PF*10 + non-temporal)
-  int ax_S;         // K (= n) splits across workgroups
+  const AxTile* ax[4];   // per number of batched right-hand sides (index 1..3)
+  int ax_S;         // K (= n) splits across workgroups with one right-hand side
+  int axb_S[4];     // ... per number of right-hand sides ([1] mirrors ax_S)
   int ax_xmap;      // MFMA: group K splits by XCD (L2 locality of X)
   int ax_lb;        // VALU: column block width (1,2,4,8); ax_ncb = ceil(l / ax_lb)
   int ax_vec;       // VALU: 16-byte loads
-  // per number of batched right-hand sides (index 1..3; [1] mirrors ax_code / ax_S):
-  // MFMA variant code (kind 5 = X staged in LDS: 5 MT PF VPL WAVES) and its K split
-  int axb_code[4];
-  int axb_S[4];
   // A^T R  ->  Gp[atr_S][n][l]
-  int atr_kind;     // 1 = MFMA, 3 = VALU
-  int atr_wl, atr_pf; // MFMA: wave layout (0 = waves split rows, 1 = waves split columns), ring depth
-  int atr_ntl;      // non-temporal A loads
+  const AtrTile* atr;
   int atr_S;        // M (= m) splits across workgroups
-  int atr_lb, atr_vec;
+  int atr_lb, atr_vec;   // VALU
   // Infinity-Cache hand-off between the two non-temporal passes (Session sets them; 0 = off):
   // the last ~that many MiB a pass reads load with the default policy (kernel arguments, so
   // every session and device gets its own value)
   int ax_keep_mib = 0, atr_keep_mib = 0;
 };
 
+// ---- the launch planner (planner.cpp, host only) ----
+inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline int64_t clampi(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+constexpr int64_t kTargetWaves = 2048;   // 8 waves per CU on 256 CUs
+constexpr int kMaxSplit = 64;
+inline int env_int(const char* name, int dflt) {
+  const char* v = std::getenv(name);
+  return (v && *v) ? std::atoi(v) : dflt;
+}
+// ax_variant: a tile code of glx_tiles.h, or 0 (GLX_AX_VARIANT, else the planner's choice)
 GemmPlan make_plan(int esize, int64_t m, int64_t n, int64_t l, int ax_variant);
+// make_plan, then the method-level A^T R choice of a session (the fused trial's tiles)
+GemmPlan session_plan(const glx_problem& P, const glx_opts& O);
 // K split (number of partial slabs per source) of an A@X launch with nsrc right-hand sides
 inline int ax_split(const GemmPlan& p, int nsrc) { return nsrc > 1 ? p.axb_S[nsrc] : p.ax_S; }
 inline int ax_split_max(const GemmPlan& p) {
@@ -186,22 +194,26 @@ inline int ax_split_max(const GemmPlan& p) {
 int max_ax_split(int esize, int64_t m, int64_t n, int64_t l);
 // one-line description of the kernels and splits a plan launches (glx_plan_describe)
 std::string describe_plan(const GemmPlan& p);
+// what a plan can carry (the launchers' preconditions): the scalar packet, the fused A e form
+// (launch_ax_egat), the derive form (launch_ax_derive), a fused trial and its reducing slots
+bool ax_pub_ok(const GemmPlan& p, int nsrc);
+bool ax_egat_ok(const GemmPlan& p, int esize);
+bool ax_derive_ok(const GemmPlan& p, int esize);
+bool atr_prox_ok(const GemmPlan& p);
+int atr_prox_slots(const GemmPlan& p, bool pub);
 
 // ---- dense products (kernels_gemm.hip) ----
 // A @ [X[0] | .. | X[nsrc-1]] (nsrc <= 3, each n x l) in one pass over A: partial slabs
 // P[src][ax_split(p, nsrc)][m][l]; skipped entirely unless gate == NULL or *gate == epoch.
 // pub.host != NULL: the launch also hands that scalar packet to the host from its first
-// workgroup (needs ax_pub_ok: the kind-5 LDS tile for nsrc).
-bool ax_pub_ok(const GemmPlan& p, int nsrc);
+// workgroup (needs ax_pub_ok: an LDS or LDS-DMA tile for nsrc).
 template <typename T>
 void launch_ax(const GemmPlan& p, int nsrc, const T* A, const T* const* X, T* P, const int* gate,
                int epoch, hipStream_t st, Pub pub = Pub{});
-// the kind-8 (LDS-DMA, f64) A @ X tile of `code` (kernels_axdma.hip); false: unknown code.
-// dma_lds_need: its LDS bytes for l columns and nsrc right-hand sides (<= 160 KiB to launch).
+// an LDS-DMA A @ X tile (kernels_axdma.hip); false: not built for T and nsrc
 template <typename T>
-bool launch_ax_dma(const GemmPlan& p, int code, int nsrc, int S, const T* A, const T* const* X, T* P,
-                   const int* gate, int epoch, hipStream_t st, Pub pub);
-int dma_lds_need(int code, int64_t l, int nsrc, int esize);
+bool launch_ax_dma(const GemmPlan& p, const AxTile* tile, int nsrc, int S, const T* A, const T* const* X,
+                   T* P, const int* gate, int epoch, hipStream_t st, Pub pub);
 // Round 6: the split-candidate trial's A e inside its dense pass (NS's one-source f64 LDS-DMA tile
 // 92278): the pass streams A p (X = the candidate p) on MFMA and, for the entries the column
 // bitmaps behind zf flag (glx_device.h zf_bitmaps; there e = p), accumulates A[:, k] e[k, c] on
@@ -214,12 +226,9 @@ struct EGat {
   int64_t bstride = 0;                   // zf_npad(n) / 16
   void* Pe = nullptr;
 };
-bool ax_egat_ok(const GemmPlan& p, int esize);
 template <typename T>
 bool launch_ax_egat(const GemmPlan& p, const T* A, const T* X, T* P, const int* gate, int epoch,
                     hipStream_t st, Pub pub, const EGat& eg);
-int dma_waves(int code);   // waves per workgroup of a kind-8/9 code (last digit; 1 = 16)
-int dma_mt(int code);      // 16-row tiles per wave (kind 9: 2)
 // Infinity-Cache hand-off between the passes (tuning experiment; MiB of A fetched with the
 // default policy at the end of a non-temporal pass; 0 = off): A@X (LDS-DMA tile) / A^T R
 template <typename T>
@@ -230,7 +239,6 @@ void launch_atr(const GemmPlan& p, const T* A, const T* R, T* Gp, hipStream_t st
 // With S = atr_S > 1 K splits the blocks write slabs Gp[S][n][l] and the last block of each
 // 64-row panel (counter pcnt[panel], zero before the first launch, reset by that block) sums
 // them in slab order and runs the trial.
-bool atr_prox_ok(const GemmPlan& p);
 template <typename T>
 void launch_atr_prox(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, T* pp, T* pthr,
                      T* z, double t, double mu, double thres, Red red, hipStream_t st, Pub pub = Pub{},
@@ -369,8 +377,6 @@ struct ShardPub {
 void launch_shard_combine(const ShardPub& sp, hipStream_t st);
 // workgroups of launch_prox_pgd over n rows of l columns (without a packet)
 int prox_blocks(int64_t n, int64_t l);
-// reducing slots of launch_atr_prox (Red::parts_only partials: 6 values each)
-int atr_prox_slots(const GemmPlan& p, bool pub);
 // workgroups of launch_finalize_residual for these slabs and count length
 int finalize_blocks(int64_t ml, int S, int S0, int64_t cn);
 int finalize_fista_blocks(int64_t ml, int S, int S0, int64_t cn);
@@ -413,7 +419,6 @@ struct AxDerive {
   const double* blk = nullptr;
   int64_t bstride = 0, moff = 0, srows = 0;
 };
-bool ax_derive_ok(const GemmPlan& p, int esize);
 // rows of A per gather workgroup of the fused dense pass (AxDerive::ggx = ceil(m / this)), and
 // its p_thr workgroups
 constexpr int kDrvGatRows = 512;

@@ -1,6 +1,6 @@
 // glx_mfma.h — pieces shared by the dense-product kernels (kernels_gemm.hip: A @ X,
 // kernels_axdma.hip: the LDS-DMA A @ X tile, kernels_atr.hip: A^T R): MFMA operand types and
-// maps, load helpers, the (row block, K split) decode of a 1-D A @ X grid, and host-side plan
+// maps, load helpers, the (row block, K split) decode of a 1-D A @ X grid, and host-side launch
 // helpers.
 #pragma once
 
@@ -145,16 +145,13 @@ __device__ inline float wave_sum(float v) {
   return v;
 }
 
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int64_t clampi(int64_t v, int64_t lo, int64_t hi) {
-  return v < lo ? lo : (v > hi ? hi : v);
-}
-static constexpr int64_t kTargetWaves = 2048;   // 8 waves per CU on 256 CUs
-static constexpr int kMaxSplit = 64;
-
-static int env_int(const char* name, int dflt) {
-  const char* v = std::getenv(name);
-  return (v && *v) ? std::atoi(v) : dflt;
+// f(std::integral_constant<int, V>) for the V among V0, Vs... that equals v (the last one where
+// none does): a runtime NT = l / 16, source count or VALU column block as a template argument
+template <int V0, int... Vs, typename F>
+inline void with_const(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+  else if (v == V0) f(std::integral_constant<int, V0>{});
+  else with_const<Vs...>(v, f);
 }
 
 // Occupancy pad (tuning experiment, GLX_AX_LDS_PAD / GLX_ATR_LDS_PAD bytes): unused dynamic
@@ -168,10 +165,6 @@ static size_t lds_pad(K kernel, const char* env) {
                             hipFuncAttributeMaxDynamicSharedMemorySize, pad);
   return (size_t)pad;
 }
-
-// Defaults chosen by the sweep in scripts/kbench.py on MI355X.
-// ax code: kind*1000 + MT*100 + PF*10 + NTL (kind 1 = direct row loads, 2 = quad + bpermute).
-// kind 5 (X staged in LDS) code: 5 MT PF VPL WAVES. Kind-5 defaults fall back to the register
 
 }  // namespace glx
 // In-kernel clock probe (diagnostic builds only: scripts/clock_probe.sh compiles the library with

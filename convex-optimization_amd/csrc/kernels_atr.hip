@@ -558,63 +558,37 @@ static void atr_mfma_go(const GemmPlan& p, const T* A, const T* R, T* Gp, hipStr
              p.atr_keep_mib);
 }
 
-// Round 6: only the tiles the planner picks are built — the f64
-// default (WL 0, PF 8; non-temporal A beyond the Infinity Cache), the f32 default (WL 1, PF 4,
-// non-temporal), the fp32 fused trial's eight-wave panel (WL 2) and the f64 32-column panel
-// (WL 3). The measured-slower ring depths (PF 2-6) and the 8-wave 32-column panel (WL 4) of
-// rounds 1-5 are gone; their numbers stay in DESIGN.md's tuning record.
-// the switch key of a plan's A^T R tile: NTL * 1000 + WL * 100 + PF
-static inline int atr_key(const GemmPlan& p) { return p.atr_ntl * 1000 + p.atr_wl * 100 + p.atr_pf; }
-
-template <typename T, int NT>
-static void atr_mfma_nt(const GemmPlan& p, const T* A, const T* R, T* Gp, hipStream_t st) {
-  switch (atr_key(p)) {
-    case 8: atr_mfma_go<T, NT, 8, 0, false>(p, A, R, Gp, st); break;
-    case 1008: atr_mfma_go<T, NT, 8, 0, true>(p, A, R, Gp, st); break;
-    case 1104: atr_mfma_go<T, NT, 4, 1, true>(p, A, R, Gp, st); break;
-    case 1208: atr_mfma_go<T, NT, 8, 2, true>(p, A, R, Gp, st); break;
-    case 308:
-    case 1308:
-      if constexpr (sizeof(T) == 8) {
-        if (p.atr_ntl) atr_mfma_go<T, NT, 8, 3, true>(p, A, R, Gp, st);
-        else atr_mfma_go<T, NT, 8, 3, false>(p, A, R, Gp, st);
-        break;
+// The tile visitor of the three A^T R launchers: f(index of the plan's tile in kAtrTiles, NT) as
+// compile-time constants, if its kernels (FUSED: k_atr_prox / k_atr_fista) are built for T.
+template <typename T, bool FUSED, typename F>
+static void atr_visit(const GemmPlan& p, const char* what, F&& f) {
+  bool built = false;
+  with_const<1, 2>((int)(p.l / 16), [&](auto nt) {
+    visit_tile(kAtrTiles, p.atr, [&](auto i) {
+      constexpr const AtrTile& t = kAtrTiles[decltype(i)::value];
+      if constexpr (t.fam == Fam::Mfma && ((FUSED ? t.fused : t.dtypes) & dtype_bit(sizeof(T))) != 0) {
+        f(i, nt);
+        built = true;
       }
-      throw Error{GLX_E_INVALID, "A^T R: the 32-column panel is f64"};
-    default:
-      throw Error{GLX_E_INVALID, "A^T R: tile WL" + std::to_string(p.atr_wl) + " PF" + std::to_string(p.atr_pf) +
-                                     " NTL" + std::to_string(p.atr_ntl) + " is not built (round 6 pruning)"};
-  }
+    });
+  });
+  if (!built && !FUSED && p.atr->wl == 3) throw Error{GLX_E_INVALID, "A^T R: the 32-column panel is f64"};
+  if (!built)
+    throw Error{GLX_E_INVALID, std::string(what) + ": tile WL" + std::to_string(p.atr->wl) + " PF" +
+                                   std::to_string(p.atr->pf) + " NTL" + std::to_string((int)p.atr->ntl) +
+                                   " is not built (round 6 pruning)"};
 }
 
 template <typename T>
 void launch_atr(const GemmPlan& p, const T* A, const T* R, T* Gp, hipStream_t st) {
-  if (p.atr_kind == 3) {
-    switch (p.atr_lb) {
-      case 1: atr_valu_lb<T, 1>(p, A, R, Gp, st); break;
-      case 2: atr_valu_lb<T, 2>(p, A, R, Gp, st); break;
-      case 4: atr_valu_lb<T, 4>(p, A, R, Gp, st); break;
-      default: atr_valu_lb<T, 8>(p, A, R, Gp, st); break;
-    }
+  if (p.atr->fam == Fam::Valu) {
+    with_const<1, 2, 4, 8>(p.atr_lb, [&](auto lb) { atr_valu_lb<T, decltype(lb)::value>(p, A, R, Gp, st); });
     return;
   }
-  if (p.l == 16) atr_mfma_nt<T, 1>(p, A, R, Gp, st);
-  else atr_mfma_nt<T, 2>(p, A, R, Gp, st);
-}
-
-
-int atr_prox_slots(const GemmPlan& p, bool pub) {
-  return (int)(p.n / (p.atr_wl == 3 ? 32 : 64)) + (pub ? 1 : 0);
-}
-
-bool atr_prox_ok(const GemmPlan& p) {
-  if (p.atr_wl == 3)   // the 32-column panel: f64, no K splits (session_plan)
-    return p.atr_kind == 1 && p.esize == 8 && p.atr_S == 1 && (p.l == 16 || p.l == 32) &&
-           p.n % 32 == 0 && p.n / 32 < kMaxBlocks;
-  return p.atr_kind == 1 && (p.atr_wl == 0 || p.atr_wl == 2) && p.atr_S >= 1 && p.atr_S <= 8 &&
-         (p.l == 16 || p.l == 32) && p.n % 64 == 0 &&
-         p.n / 64 < kMaxBlocks &&   // reducing slots (one per panel) + the publisher
-         (p.atr_S == 1 || env_int("GLX_ATR_FUSE_SPLIT", 1) != 0);
+  atr_visit<T, false>(p, "A^T R", [&](auto i, auto nt) {
+    constexpr const AtrTile& t = kAtrTiles[decltype(i)::value];
+    atr_mfma_go<T, decltype(nt)::value, t.pf, t.wl, t.ntl>(p, A, R, Gp, st);
+  });
 }
 
 template <typename T, int NT, int PF, bool NTL, int WL>
@@ -632,36 +606,17 @@ static void atr_prox_go(const GemmPlan& p, const T* A, const T* R, T* G, const T
   glx_launch((k_atr_prox<T, NT, PF, NTL, false, WL>), grid, block, pad, st, A, R, G, p.m,
                      p.n, x, pp, pthr, z, t, t * mu, thres, red, pub, 1, Gp, pcnt, zf, p.atr_keep_mib);
 }
-template <typename T, int NT>
-static void atr_prox_nt(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, T* pp,
-                        T* pthr, T* z, double t, double mu, double thres, Red red, hipStream_t st,
-                        Pub pub, T* Gp, unsigned* pcnt, unsigned* zf) {
-  // the planner's fused tiles only (see atr_mfma_nt): f64 WL 0 PF 8 (+ non-temporal), WL 3
-  // (32-column panel); WL 2 non-temporal (fp32's eight-wave panel; f64 through GLX_ATR_VARIANT)
-  const int code = atr_key(p);
-  if constexpr (sizeof(T) == 8) {
-    switch (code) {
-      case 8: atr_prox_go<T, NT, 8, false, 0>(p, A, R, G, x, pp, pthr, z, t, mu, thres, red, st, pub, Gp, pcnt, zf); return;
-      case 308: atr_prox_go<T, NT, 8, false, 3>(p, A, R, G, x, pp, pthr, z, t, mu, thres, red, st, pub, Gp, pcnt, zf); return;
-      case 1308: atr_prox_go<T, NT, 8, true, 3>(p, A, R, G, x, pp, pthr, z, t, mu, thres, red, st, pub, Gp, pcnt, zf); return;
-      default: break;
-    }
-  }
-  switch (code) {
-    case 1008: atr_prox_go<T, NT, 8, true, 0>(p, A, R, G, x, pp, pthr, z, t, mu, thres, red, st, pub, Gp, pcnt, zf); return;
-    case 1208: atr_prox_go<T, NT, 8, true, 2>(p, A, R, G, x, pp, pthr, z, t, mu, thres, red, st, pub, Gp, pcnt, zf); return;
-    default:
-      throw Error{GLX_E_INVALID, "fused A^T R + trial: tile code " + std::to_string(code) + " is not built"};
-  }
-}
 template <typename T>
 void launch_atr_prox(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, T* pp, T* pthr,
                      T* z, double t, double mu, double thres, Red red, hipStream_t st, Pub pub,
                      T* Gp, unsigned* pcnt, unsigned* zf) {
   if (p.atr_S > 1 && (Gp == nullptr || pcnt == nullptr))
     throw Error{GLX_E_INVALID, "fused A^T R with K splits needs slab and counter buffers"};
-  if (p.l == 16) atr_prox_nt<T, 1>(p, A, R, G, x, pp, pthr, z, t, mu, thres, red, st, pub, Gp, pcnt, zf);
-  else atr_prox_nt<T, 2>(p, A, R, G, x, pp, pthr, z, t, mu, thres, red, st, pub, Gp, pcnt, zf);
+  atr_visit<T, true>(p, "fused A^T R + trial", [&](auto i, auto nt) {
+    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
+    atr_prox_go<T, decltype(nt)::value, tile.pf, tile.ntl, tile.wl>(p, A, R, G, x, pp, pthr, z, t, mu, thres, red,
+                                                                  st, pub, Gp, pcnt, zf);
+  });
 }
 
 template <typename T, int NT, int PF, bool NTL, int WL>
@@ -682,36 +637,18 @@ static void atr_fista_go(const GemmPlan& p, const T* A, const T* R, T* G, const 
                      p.n, y, xk, xc, vn, yn, t, t * mu, thres, theta, 1.0 - theta_next, theta_next,
                      red, pub, 1, Gp, pcnt, ec, zf, p.atr_keep_mib);
 }
-template <typename T, int NT>
-static void atr_fista_nt(const GemmPlan& p, const T* A, const T* R, T* G, const T* y, const T* xk,
-                         T* xc, T* vn, T* yn, double t, double mu, double thres, double theta,
-                         double theta_next, Red red, hipStream_t st, Pub pub, T* Gp, unsigned* pcnt,
-                         T* ec, unsigned* zf) {
-  const int code = atr_key(p);   // the tiles of atr_prox_nt
-  if constexpr (sizeof(T) == 8) {
-    switch (code) {
-      case 8: atr_fista_go<T, NT, 8, false, 0>(p, A, R, G, y, xk, xc, vn, yn, t, mu, thres, theta, theta_next, red, st, pub, Gp, pcnt, ec, zf); return;
-      case 308: atr_fista_go<T, NT, 8, false, 3>(p, A, R, G, y, xk, xc, vn, yn, t, mu, thres, theta, theta_next, red, st, pub, Gp, pcnt, ec, zf); return;
-      case 1308: atr_fista_go<T, NT, 8, true, 3>(p, A, R, G, y, xk, xc, vn, yn, t, mu, thres, theta, theta_next, red, st, pub, Gp, pcnt, ec, zf); return;
-      default: break;
-    }
-  }
-  switch (code) {
-    case 1008: atr_fista_go<T, NT, 8, true, 0>(p, A, R, G, y, xk, xc, vn, yn, t, mu, thres, theta, theta_next, red, st, pub, Gp, pcnt, ec, zf); return;
-    case 1208: atr_fista_go<T, NT, 8, true, 2>(p, A, R, G, y, xk, xc, vn, yn, t, mu, thres, theta, theta_next, red, st, pub, Gp, pcnt, ec, zf); return;
-    default:
-      throw Error{GLX_E_INVALID, "fused A^T R + FISTA trial: tile code " + std::to_string(code) + " is not built"};
-  }
-}
 template <typename T>
 void launch_atr_fista(const GemmPlan& p, const T* A, const T* R, T* G, const T* y, const T* xk,
                       T* xc, T* vn, T* yn, double t, double mu, double thres, double theta,
                       double theta_next, Red red, hipStream_t st, Pub pub, T* Gp, unsigned* pcnt,
-                         T* ec, unsigned* zf) {
+                      T* ec, unsigned* zf) {
   if (p.atr_S > 1 && (Gp == nullptr || pcnt == nullptr))
     throw Error{GLX_E_INVALID, "fused A^T R with K splits needs slab and counter buffers"};
-  if (p.l == 16) atr_fista_nt<T, 1>(p, A, R, G, y, xk, xc, vn, yn, t, mu, thres, theta, theta_next, red, st, pub, Gp, pcnt, ec, zf);
-  else atr_fista_nt<T, 2>(p, A, R, G, y, xk, xc, vn, yn, t, mu, thres, theta, theta_next, red, st, pub, Gp, pcnt, ec, zf);
+  atr_visit<T, true>(p, "fused A^T R + FISTA trial", [&](auto i, auto nt) {
+    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
+    atr_fista_go<T, decltype(nt)::value, tile.pf, tile.ntl, tile.wl>(p, A, R, G, y, xk, xc, vn, yn, t, mu, thres,
+                                                                   theta, theta_next, red, st, pub, Gp, pcnt, ec, zf);
+  });
 }
 
 template void launch_atr<double>(const GemmPlan&, const double*, const double*, double*, hipStream_t);

@@ -1,5 +1,5 @@
 // kernels_axdma.hip — A @ X (reference: gl_ProxGD_primal.py:25,61,129 `A @ x`) with A and X
-// staged in LDS by LDS-DMA, f64 and f32 (kinds 8/9 of the A @ X planner, kernels_gemm.hip).
+// staged in LDS by LDS-DMA, f64 and f32 (the Dma family of glx_tiles.h, planned in planner.cpp).
 #include "glx_mfma.h"
 
 namespace glx {
@@ -442,72 +442,46 @@ __global__ __launch_bounds__(64 * WAVES) void k_ax_dma(const T* __restrict__ A,
   GLX_CLK(3);
 }
 
-template <typename T, int NT, int NSRC, int NS, int KC, int WAVES, bool NTL, bool HOIST = false,
-          bool PIPE = false, int MT = 1, bool EG = false>
+// The launcher takes its tile as the index I into kAxTiles (glx_tiles.h) and reads the kernel's
+// template arguments and the grid geometry from that record.
+template <typename T, int NT, int NSRC, std::size_t I, bool EG = false>
 static void ax_dma_go(const GemmPlan& p, int S, const T* A, const T* const* X, T* P,
                       const int* gate, int epoch, hipStream_t st, Pub pub, const EGat& eg = EGat{}) {
-  if constexpr (dma_lds_bytes<T, NT, NSRC, NS, KC, WAVES, MT>() > 160 * 1024) {
+  constexpr const AxTile& t = kAxTiles[I];
+  if constexpr (dma_lds_bytes<T, NT, NSRC, t.slots, t.kc, t.waves, t.mt>() > 160 * 1024) {
     throw Error{GLX_E_INVALID, "A@X: this LDS-DMA tile does not fit (160 KiB of LDS)"};
   } else {
-    const int gx = (int)cdiv(p.m, 16 * MT * WAVES);
+    const int gx = (int)cdiv(p.m, ax_tile_rows(t));
     const int xmap = ax_xmap_flags(p, S);
     const dim3 grid((unsigned)ax_grid(xmap, gx, S) + (pub.host ? 1u : 0u));
-    glx_launch((k_ax_dma<T, NT, NSRC, NS, KC, WAVES, NTL, HOIST, PIPE, MT, EG>), grid, dim3(64 * WAVES), 0, st,
-                       A, X[0], X[1], X[2], P, p.m, p.n, p.n / KC, S, gx, xmap, gate, epoch, pub,
-                       p.ax_keep_mib, eg);
+    glx_launch((k_ax_dma<T, NT, NSRC, t.slots, t.kc, t.waves, t.ntl, t.hoist, t.pipe, t.mt, EG>), grid,
+               dim3(64 * t.waves), 0, st, A, X[0], X[1], X[2], P, p.m, p.n, p.n / t.kc, S, gx, xmap, gate, epoch,
+               pub, p.ax_keep_mib, eg);
   }
-}
-
-// The planner's LDS-DMA tiles (kernels_gemm.hip lds_plan). Code: 9 NS KC/16 flags WAVES, kind 9 =
-// two 16-row tiles per wave; flags 7 = non-temporal A + hoisted, pipelined operand reads with the
-// DMA issues interleaved into the MFMAs, 6 = the same with the default load policy. The round-3
-// sweep's other forms (one row tile per wave, 3-4 ring slots, 16-wave blocks, 16-column chunks,
-// no hoisting / pipelining) measured slower and are no longer instantiated.
-template <typename T, int NT, int NSRC>
-static bool dma_code(const GemmPlan& p, int code, int S, const T* A, const T* const* X, T* P,
-                     const int* gate, int epoch, hipStream_t st, Pub pub) {
-  switch (code) {
-    case 92278: ax_dma_go<T, NT, NSRC, 2, 32, 8, true, true, true, 2>(p, S, A, X, P, gate, epoch, st, pub); return true;
-    case 92268: ax_dma_go<T, NT, NSRC, 2, 32, 8, false, true, true, 2>(p, S, A, X, P, gate, epoch, st, pub); return true;
-    // f32 (round 4): 64-column chunks, the same 256-B row pieces and LDS image as 92278 in f64
-    case 92478:
-      if constexpr (sizeof(T) == 4 && NSRC == 1) {
-        ax_dma_go<T, NT, NSRC, 2, 64, 8, true, true, true, 2>(p, S, A, X, P, gate, epoch, st, pub);
-        return true;
-      }
-      return false;
-    default: return false;
-  }
-}
-
-int dma_waves(int code) { return code % 10 == 1 ? 16 : code % 10; }
-
-int dma_mt(int code) { return code / 10000 == 9 ? 2 : 1; }
-
-int dma_lds_need(int code, int64_t l, int nsrc, int esize) {
-  const int ns = (code / 1000) % 10, kc = 16 * ((code / 100) % 10), waves = dma_waves(code);
-  const int xb = nsrc * kc * (int)l * esize;
-  return ns * (waves * 16 * dma_mt(code) * kc * esize + xb) + ((xb / 1024) % waves ? 1024 : 0);
 }
 
 template <typename T>
-bool launch_ax_dma(const GemmPlan& p, int code, int nsrc, int S, const T* A, const T* const* X, T* P,
-                   const int* gate, int epoch, hipStream_t st, Pub pub) {
-  if (p.l == 16) {
-    if (nsrc == 1) return dma_code<T, 1, 1>(p, code, S, A, X, P, gate, epoch, st, pub);
-    if (nsrc == 2) return dma_code<T, 1, 2>(p, code, S, A, X, P, gate, epoch, st, pub);
-    return dma_code<T, 1, 3>(p, code, S, A, X, P, gate, epoch, st, pub);
-  }
-  if (nsrc == 1) return dma_code<T, 2, 1>(p, code, S, A, X, P, gate, epoch, st, pub);
-  if (nsrc == 2) return dma_code<T, 2, 2>(p, code, S, A, X, P, gate, epoch, st, pub);
-  return dma_code<T, 2, 3>(p, code, S, A, X, P, gate, epoch, st, pub);
+bool launch_ax_dma(const GemmPlan& p, const AxTile* tile, int nsrc, int S, const T* A, const T* const* X,
+                   T* P, const int* gate, int epoch, hipStream_t st, Pub pub) {
+  bool built = false;
+  visit_tile(kAxTiles, tile, [&](auto i) {
+    constexpr const AxTile& t = kAxTiles[decltype(i)::value];
+    if constexpr (t.fam == Fam::Dma && (t.built & dtype_bit(sizeof(T))) != 0) {
+      with_const<1, 2>((int)(p.l / 16), [&](auto nt) {
+        with_const<1, 2, 3>(nsrc, [&](auto ns) {
+          if constexpr (decltype(ns)::value <= t.nsrc_max) {
+            ax_dma_go<T, decltype(nt)::value, decltype(ns)::value, decltype(i)::value>(p, S, A, X, P, gate, epoch,
+                                                                                    st, pub);
+            built = true;
+          }
+        });
+      });
+    }
+  });
+  return built;
 }
 
-// the fused A e form of the one-source f64 pass 92278 (EGat)
-bool ax_egat_ok(const GemmPlan& p, int esize) {
-  return esize == 8 && p.ax_kind != 3 && p.axb_code[1] == 92278 && (p.l == 16 || p.l == 32) && p.n % 32 == 0 &&
-         p.n <= 65535;
-}
+// the fused A e form of the one-source f64 pass 92278 (EGat; ax_egat_ok: that is the plan's tile)
 template <typename T>
 bool launch_ax_egat(const GemmPlan& p, const T* A, const T* X, T* P, const int* gate, int epoch,
                     hipStream_t st, Pub pub, const EGat& eg) {
@@ -516,11 +490,10 @@ bool launch_ax_egat(const GemmPlan& p, const T* A, const T* X, T* P, const int* 
   } else {
     if (!ax_egat_ok(p, 8)) return false;
     const T* xs[3] = {X, nullptr, nullptr};
-    const int S = p.axb_S[1];
-    if (p.l == 16)
-      ax_dma_go<T, 1, 1, 2, 32, 8, true, true, true, 2, true>(p, S, A, xs, P, gate, epoch, st, pub, eg);
-    else
-      ax_dma_go<T, 2, 1, 2, 32, 8, true, true, true, 2, true>(p, S, A, xs, P, gate, epoch, st, pub, eg);
+    constexpr std::size_t kDma = ax_tile(92278) - kAxTiles;
+    with_const<1, 2>((int)(p.l / 16), [&](auto nt) {
+      ax_dma_go<T, decltype(nt)::value, 1, kDma, true>(p, p.axb_S[1], A, xs, P, gate, epoch, st, pub, eg);
+    });
     return true;
   }
 }
@@ -529,9 +502,9 @@ template bool launch_ax_egat<double>(const GemmPlan&, const double*, const doubl
 template bool launch_ax_egat<float>(const GemmPlan&, const float*, const float*, float*, const int*, int,
                                     hipStream_t, Pub, const EGat&);
 
-template bool launch_ax_dma<double>(const GemmPlan&, int, int, int, const double*, const double* const*,
+template bool launch_ax_dma<double>(const GemmPlan&, const AxTile*, int, int, const double*, const double* const*,
                                     double*, const int*, int, hipStream_t, Pub);
-template bool launch_ax_dma<float>(const GemmPlan&, int, int, int, const float*, const float* const*,
+template bool launch_ax_dma<float>(const GemmPlan&, const AxTile*, int, int, const float*, const float* const*,
                                    float*, const int*, int, hipStream_t, Pub);
 
 }  // namespace glx

@@ -1,5 +1,5 @@
-// kernels_gemm.hip — the residual contraction of the prox-grad iteration on CDNA4 (gfx950) and
-// the launch planner of both dense products.
+// kernels_gemm.hip — the residual contraction of the prox-grad iteration on CDNA4 (gfx950).
+// The tiles of both dense products are listed in glx_tiles.h and planned in planner.cpp.
 //
 //   A @ X   (reference: gl_ProxGD_primal.py:25,61,129 — `A @ x`):   M = m, K = n, N = l
 //   A^T R   (reference: gl_ProxGD_primal.py:129 — `A.T @ (...)`):  M = n, K = m, N = l
@@ -620,284 +620,7 @@ __global__ __launch_bounds__(256) void k_ax_valu(const T* __restrict__ A, const 
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// planning + launch
-// ------------------------------------------------------------------------------------------
-// tiles below when the shape does not fit them (l not 16/32, n not a multiple of 4*E*VPL).
-static constexpr int kAxDefault = 52228;       // f64 single RHS: LDS, MT 2, PF 2, VPL 2, 8 waves
-static constexpr int kAxFallback = 21820;      // f64: VPL 2, direct loads, MT 8, PF 2
-static constexpr int kAxDefault32 = 21410;     // f32: VPL 2, direct loads, MT 4, PF 1
-static constexpr int kAxDma32 = 92478;         // f32 one RHS, A beyond the Infinity Cache (LDS-DMA)
-// A^T R code: NTL*1000 + WL*10 + PF (WL 1 = four panels of a block share rows, PF = ring depth)
-static constexpr int kAtrDefault = 108;        // f64: WL 0, PF 8 (A that stays in the MALL)
-static constexpr int kAtrDefaultBig = 1008;    // f64: non-temporal A, WL 0, PF 8
-// Non-temporal A loads pay only when A cannot stay in the 256 MiB Infinity Cache between the
-// passes: NS (1 GiB) 2278 -> 2326 it/s, FProxGD 2397 -> 2451, but C2 (256 MiB) 7477 -> 6250 and
-// the 1024-row shard (128 MiB) 9477 -> 8323 (profiles/r2_axat/)
-static constexpr double kAtrNtBytes = 384.0 * 1024 * 1024;
-static constexpr int kAtrDefault32 = 1114;     // f32: non-temporal A, WL 1, PF 4
-// batched right-hand sides (MFMA-bound at l = 32, both dtypes): the LDS tile, 2 waves per SIMD
-// (end-to-end sweep, profiles/r1_tuning: f64 8-wave blocks, f32 4-wave blocks with PF 3)
-static int axb_default(int nsrc, int esize) {
-  (void)nsrc;
-  return esize == 8 ? 52228 : 52324;
-}
-
-// the tiles the planner picks (lds_plan); the LDS-DMA sweep's other codes are in DESIGN.md
-static constexpr int kLdsCodes[] = {52224, 52324, 52228, 51328,
-                                     // kind 9 (LDS-DMA, two row tiles per wave): 9 NS KC/16 flags WAVES;
-                                     // 92278 / 92268 f64, 92478 f32 (one source)
-                                     92278, 92268, 92478};
-static inline bool dma_kind(int c) { return c / 10000 == 8 || c / 10000 == 9; }
-static inline bool lds_kind(int c) { return c / 10000 == 5 || dma_kind(c); }
-static bool lds_code_ok(int c, int64_t n, int64_t l, int esize, int nsrc = 1) {
-  bool known = false;
-  for (int k : kLdsCodes) known |= (k == c);
-  if (!known) return false;
-  if (dma_kind(c))
-    return (c == kAxDma32 ? (esize == 4 && nsrc == 1) : esize == 8) && (l == 16 || l == 32) &&
-           n % (16 * ((c / 100) % 10)) == 0 && dma_lds_need(c, l, nsrc, esize) <= 160 * 1024;
-  const int E = 16 / esize, vpl = (c / 10) % 10;
-  return (l == 16 || l == 32) && n % (4 * E * vpl) == 0;
-}
-// K split of a kind-5/8 launch: enough blocks for 2 (4-wave) blocks per CU
-static int lds_split(int esize, int64_t m, int64_t n, int code, int64_t target = 0) {
-  const int E = 16 / esize, waves = code % 10;
-  int64_t rb, chunks;
-  if (dma_kind(code)) {   // MT 16-row tiles per wave, KC = 16 * digit-3 columns per chunk
-    rb = cdiv(m, 16 * dma_mt(code) * dma_waves(code));
-    chunks = n / (16 * ((code / 100) % 10));
-  } else {
-    const int mt = (code / 1000) % 10, vpl = (code / 10) % 10;
-    rb = cdiv(m, 16 * mt * waves);
-    chunks = n / (4 * E * vpl);
-  }
-  if (target <= 0) target = env_int("GLX_AXL_BLOCKS", (waves == 8 || waves == 1) ? 256 : 512);
-  return (int)clampi(cdiv(target, rb), 1, std::max<int64_t>(1, std::min<int64_t>(kMaxSplit, chunks / 8)));
-}
-// A K-split launch writes S partial slabs of m x (nsrc*l) that the finalize kernel reads back.
-// With few rows (the per-rank shards of a multi-GPU run) a 256-block target lets S reach 64 and
-// the slabs rival A itself. When they exceed 1/6 of A, use the 4-wave tile at 256 blocks, which
-// halves them. Shard-shape sweep (profiles/r1_tuning/shard_shapes.txt): at m = 1024 this is
-// +10 % end to end despite a slower A@X; at m >= 2048 the default tile stays ahead.
-//
-// Per-rank shards at l = 32 (m <= 2048: the 4- and 8-GPU runs of the north-star size) take the
-// 8-wave tile with ONE 16-row tile per wave and a 3-deep ring (51328): at these row counts the
-// K splits are short, and two waves per SIMD with half the rows per block keep the slab volume
-// of the 4-wave tile. Measured end to end with the communicator path
-// (profiles/r1_tuning/small_kernels/ax_shard_tile.log): +4.7 % at m = 1024, +3 % at 2048,
-// neutral at 4096; at m = 8192 the default tile stays ahead (A@X 290 vs 306 us).
-//
-// One right-hand side at l = 32, f64 (round 2: the split-candidate trial's dense pass A p_thr is
-// HBM-bound): 51328 with its 4 K splits, A@X 246-250 vs 252-254 us incl. the A e gather, NS
-// ProxGD 2266-2269 vs 2231-2232 it/s on one box (profiles/r2_axtile/).
-//
-// Round 3, the LDS-DMA tile (kernels_axdma.hip): one right-hand side in fp64 with A beyond the
-// Infinity Cache (the split-candidate dense pass A p_thr at NS, FProxGD's A xc, C5's shard) takes
-// 92278 (two 16-row tiles per wave, 256-B row pieces, 2-slot ring, non-temporal A, DMA issues and
-// operand reads interleaved into the MFMA stream): NS 164 vs 193-196 us (6.57 TB/s), the 16384-row
-// shard 334 vs 399 us. fp64 C2 (two right-hand sides, l = 16, A in the Infinity Cache) takes
-// 92268 (default policy): 46.2 vs 49.3 us. Interleaved kernel-trace A/B, profiles/r3_axdma/.
-static void lds_plan(int esize, int64_t m, int64_t n, int64_t l, int nsrc, int& code, int& S) {
-  S = lds_split(esize, m, n, code);
-  if (std::getenv("GLX_AXL_BLOCKS") || std::getenv("GLX_AXB_VARIANT")) return;
-  const bool big = (double)m * (double)n * esize > kAtrNtBytes;
-  if (esize == 8 && nsrc == 1 && big && code == 52228 && lds_code_ok(92278, n, l, esize, 1) &&
-      env_int("GLX_AX_DMA", 1) != 0 && !std::getenv("GLX_AX_VARIANT")) {
-    code = 92278;
-    S = lds_split(esize, m, n, code);
-    return;
-  }
-  if (esize == 8 && nsrc == 2 && l == 16 && !big && code == 52228 &&
-      lds_code_ok(92268, n, l, esize, 2) && env_int("GLX_AX_DMA", 1) != 0) {
-    code = 92268;
-    S = lds_split(esize, m, n, code);
-    return;
-  }
-  if (esize == 8 && nsrc == 1 && l == 32 && code == 52228 && lds_code_ok(51328, n, l, esize) &&
-      !std::getenv("GLX_AX_VARIANT")) {
-    code = 51328;
-    S = lds_split(esize, m, n, code);
-    return;
-  }
-  if (esize == 8 && nsrc == 2 && l == 32 && m <= 2048 && code == 52228 &&
-      lds_code_ok(51328, n, l, esize) && env_int("GLX_SHARD_TILE", 1) != 0) {
-    code = 51328;
-    S = lds_split(esize, m, n, code);
-    return;
-  }
-  if ((double)S * (double)m * nsrc * l * 6.0 <= (double)m * n) return;
-  const int c4 = esize == 8 ? 52224 : 52324;
-  if (!lds_code_ok(c4, n, l, esize)) return;
-  const int S4 = lds_split(esize, m, n, c4, 256);
-  if (S4 < S) { code = c4; S = S4; }
-}
-
-static bool valid_ax_code(int c) { return c == 21820 || c == 21410 || c == 1820; }
-
-GemmPlan make_plan(int esize, int64_t m, int64_t n, int64_t l, int ax_variant) {
-  GemmPlan p{};
-  p.esize = esize;
-  p.m = m; p.n = n; p.l = l;
-  const int E = 16 / esize;
-  const bool mfma_l = (l == 16 || l == 32);
-  // ---- A @ X ----
-  if (ax_variant == 0) ax_variant = env_int("GLX_AX_VARIANT", 0);
-  if (ax_variant == 1 || ax_variant == 2) ax_variant = esize == 8 ? kAxFallback : kAxDefault32;
-  const bool ax_mfma_ok = mfma_l && (n % (4 * E) == 0);
-  if (ax_variant == 3 || !ax_mfma_ok) {
-    p.ax_kind = 3;
-    p.ax_lb = l >= 8 ? 8 : (l >= 4 ? 4 : (l >= 2 ? 2 : 1));
-    if (l == 3) p.ax_lb = 4;
-    if (l > 4 && l < 8) p.ax_lb = 8;
-    p.ax_vec = (n % E == 0) ? 1 : 0;
-    const int64_t waves = cdiv(m, 4);                    // RW = 4 rows per wave
-    const int64_t kunits = n / (64 * (p.ax_vec ? E : 1)); // 64-lane strides per row
-    p.ax_S = (int)clampi(cdiv(kTargetWaves, waves), 1, std::max<int64_t>(1, std::min<int64_t>(kMaxSplit, kunits / 4)));
-  } else if (esize == 4 && ax_variant == 0 && (double)m * (double)n * esize > kAtrNtBytes &&
-             lds_code_ok(kAxDma32, n, l, esize, 1) && env_int("GLX_AX_DMA", 1) != 0 &&
-             env_int("GLX_AX_DMA32", 1) != 0) {
-    // Round 4: f32 with one right-hand side and A beyond the Infinity Cache (C3's split-candidate
-    // dense pass A xc) on the LDS-DMA tile, as 92278 does for f64: 85-88 us = 6.1-6.3 TB/s
-    // against 115 us for the direct-load tile 21410 (profiles/r4_exp3/). GLX_AX_DMA32=0: off.
-    p.ax_code = kAxDma32;
-    p.ax_kind = 5;
-    p.ax_S = lds_split(esize, m, n, kAxDma32);
-    p.ax_mt = 2;
-    p.ax_pf = 0;
-  } else if (lds_code_ok(ax_variant ? ax_variant : (esize == 8 ? kAxDefault : kAxDefault32), n, l, esize)) {
-    int code = ax_variant ? ax_variant : (esize == 8 ? kAxDefault : kAxDefault32);
-    if (ax_variant) p.ax_S = lds_split(esize, m, n, code);
-    else lds_plan(esize, m, n, l, 1, code, p.ax_S);
-    p.ax_code = code;
-    p.ax_kind = 5;
-    p.ax_mt = (code / 1000) % 10;
-    p.ax_pf = (code / 100) % 10;
-  } else {
-    int code = valid_ax_code(ax_variant) ? ax_variant : (esize == 8 ? kAxFallback : kAxDefault32);
-    int vpl = code / 10000 ? code / 10000 : 1;
-    if (n % (4 * E * vpl) != 0) { code = 1820; vpl = 1; }   // wider chunks need n % 4*E*VPL
-    p.ax_code = code;
-    p.ax_kind = (code / 1000) % 10;
-    p.ax_mt = (code / 100) % 10;
-    p.ax_pf = (code / 10) % 10;
-    const int64_t blocks = cdiv(m, 16 * p.ax_mt);
-    const int64_t chunks = n / (4 * E * vpl);
-    // sweep (scripts/kbench.py): f64 at MT 8 wants 1024 waves, f32 4096
-    const int64_t target = esize == 8 ? (p.ax_mt == 8 ? kTargetWaves / 2 : kTargetWaves) : 2 * kTargetWaves;
-    p.ax_S = (int)clampi(cdiv(target, blocks * 4), 1,
-                         std::max<int64_t>(1, std::min<int64_t>(kMaxSplit, chunks / 16)));
-  }
-  const int s_ax = env_int("GLX_AX_S", 0);
-  if (s_ax > 0) p.ax_S = (int)std::min<int64_t>(s_ax, kMaxSplit);
-  p.ax_xmap = (env_int("GLX_AX_XCD", 1) ? 1 : 0) | (env_int("GLX_AX_ROT", 1) ? 2 : 0);
-  // batched right-hand sides
-  p.axb_code[0] = p.axb_code[1] = p.ax_code;
-  p.axb_S[0] = p.axb_S[1] = p.ax_S;
-  for (int ns = 2; ns <= 3; ++ns) {
-    int code = env_int("GLX_AXB_VARIANT", axb_default(ns, esize));
-    int S = p.ax_S;
-    if (p.ax_kind == 3) {
-      code = 0;
-    } else if (lds_kind(code)) {
-      if (lds_code_ok(code, n, l, esize, ns)) lds_plan(esize, m, n, l, ns, code, S);
-      else code = ns == 2 ? 1420 : 1220;
-    } else if (code >= 10000 && n % (4 * E * (code / 10000)) != 0) {
-      code = ns == 2 ? 1420 : 1220;
-    }
-    const int s_axb = env_int("GLX_AXB_S", 0);
-    if (s_axb > 0 && lds_kind(code)) S = (int)std::min<int64_t>(s_axb, kMaxSplit);
-    p.axb_code[ns] = code;
-    p.axb_S[ns] = S;
-  }
-  // ---- A^T R ----
-  int atr_code = env_int("GLX_ATR_VARIANT", 0);
-  if (atr_code == 0)
-    atr_code = esize == 8 ? ((double)m * n * esize > kAtrNtBytes ? kAtrDefaultBig : kAtrDefault)
-                          : kAtrDefault32;
-  int ntl = atr_code >= 1000 ? 1 : 0;
-  int wl = (atr_code / 10) % 10;
-  int pf = atr_code % 10;
-  if (wl == 1 && n % 256 != 0) wl = 0;   // four shared-row panels need n % 256: one panel per block
-  if (wl > 3 || (wl == 3 && (esize != 8 || n % 32 != 0))) wl = 0;   // 3: the 32-column f64 panel (4 waves)
-  // Round 6: only the planner's tiles are built (kernels_atr.hip atr_mfma_nt): WL 0 / 3 with the
-  // PF 8 ring, WL 2 with PF 8 and non-temporal A, WL 1 with PF 4 and non-temporal A
-  if (wl == 1) { pf = 4; ntl = 1; }
-  else { pf = 8; if (wl == 2) ntl = 1; }
-  const bool atr_mfma_ok = mfma_l && (n % 64 == 0) && (m % 4 == 0);
-  if (ax_variant == 3 || atr_code == 3 || !atr_mfma_ok) {
-    p.atr_kind = 3;
-    p.atr_lb = l >= 8 ? 8 : (l >= 4 ? 4 : (l >= 2 ? 2 : 1));
-    if (l == 3) p.atr_lb = 4;
-    if (l > 4 && l < 8) p.atr_lb = 8;
-    p.atr_vec = (n % E == 0) ? 1 : 0;
-    const int64_t cols_per_block = 256 * (p.atr_vec ? E : 1);
-    const int64_t blocks = cdiv(n, cols_per_block);
-    p.atr_S = (int)clampi(cdiv(kTargetWaves / 4, blocks), 1, std::max<int64_t>(1, std::min<int64_t>(kMaxSplit, m / 16)));
-  } else {
-    p.atr_kind = 1;
-    p.atr_wl = wl;   // 0: 4 waves split a panel's rows, 1: 4 panels per block, 2: 8 waves
-    p.atr_pf = (pf >= 2 && pf <= 8) ? pf : 2;   // in-place ring: lookahead PF - 1 steps
-    p.atr_ntl = ntl;
-    const int64_t steps = m / 4;
-    if (p.atr_wl != 1) {
-      const int64_t blocks = n / (p.atr_wl == 3 ? 32 : 64);
-      // f64: one wave per SIMD is enough with the PF-8 ring (and S = 1 at n = 16384 lets the
-      // ProxGD trial fuse into the kernel); f32 wants 4 per SIMD
-      const int64_t target = esize == 8 ? kTargetWaves / 2 : 2 * kTargetWaves;
-      p.atr_S = (int)clampi(cdiv(target, blocks * 4), 1,
-                            std::max<int64_t>(1, std::min<int64_t>(kMaxSplit, steps / 16)));
-    } else {
-      const int64_t blocks = n / 256;
-      p.atr_S = (int)clampi(cdiv(kTargetWaves / 4, blocks), 1,
-                            std::max<int64_t>(1, std::min<int64_t>(kMaxSplit, steps / 16)));
-    }
-  }
-  const int s_atr = env_int("GLX_ATR_S", 0);
-  if (s_atr > 0) p.atr_S = (int)std::min<int64_t>(s_atr, kMaxSplit);
-  return p;
-}
-
-static std::string ax_name(const GemmPlan& p, int nsrc) {
-  const int code = p.axb_code[nsrc];
-  char buf[128];
-  if (p.ax_kind == 3 || code == 0) {
-    std::snprintf(buf, sizeof buf, "k_ax_valu<LB%d,VEC%d> S=%d", p.ax_lb, p.ax_vec, ax_split(p, nsrc));
-  } else if (dma_kind(code)) {
-    std::snprintf(buf, sizeof buf, "k_ax_dma<MT%d,NS%d,KC%d,NTL%d,HOIST%d(2:PIPE),W%d> S=%d", dma_mt(code), (code / 1000) % 10,
-                  16 * ((code / 100) % 10), (code / 10) % 2, (code / 20) % 2 + 2 * ((code / 40) % 2),
-                  dma_waves(code),
-                  ax_split(p, nsrc));
-  } else if (code / 10000 == 5) {
-    std::snprintf(buf, sizeof buf, "k_ax_lds<MT%d,PF%d,VPL%d,W%d> S=%d", (code / 1000) % 10,
-                  (code / 100) % 10, (code / 10) % 10, code % 10, ax_split(p, nsrc));
-  } else {
-    const int vpl = code / 10000 ? code / 10000 : 1;
-    std::snprintf(buf, sizeof buf, "k_ax_mfma<kind%d,MT%d,PF%d,NTL%d,VPL%d> S=%d", (code / 1000) % 10,
-                  (code / 100) % 10, (code / 10) % 10, code % 10, vpl, ax_split(p, nsrc));
-  }
-  return buf;
-}
-
-std::string describe_plan(const GemmPlan& p) {
-  std::string s;
-  for (int ns = 1; ns <= 3; ++ns) s += "ax" + std::to_string(ns) + "=" + ax_name(p, ns) + "; ";
-  char buf[128];
-  if (p.atr_kind == 3)
-    std::snprintf(buf, sizeof buf, "atr=k_atr_valu<LB%d,VEC%d> S=%d", p.atr_lb, p.atr_vec, p.atr_S);
-  else
-    std::snprintf(buf, sizeof buf, "atr=k_atr_mfma<WL%d,PF%d,NTL%d> S=%d%s", p.atr_wl, p.atr_pf, p.atr_ntl, p.atr_S,
-                  p.atr_wl == 3 ? " (32-column panels)" : "");
-  return s + buf;
-}
-
-int max_ax_split(int esize, int64_t m, int64_t n, int64_t l) {
-  int s = 1;
-  for (int v : {0, 3, 1820, 21820, 21410}) s = std::max(s, ax_split_max(make_plan(esize, m, n, l, v)));
-  for (int v : kLdsCodes) s = std::max(s, ax_split_max(make_plan(esize, m, n, l, v)));
-  return s;
-}
-
+// ---- launch (the planner is planner.cpp; the tiles are glx_tiles.h) ----
 template <typename T, int LB, int NSRC>
 static void ax_valu_lb(const GemmPlan& p, const T* A, const T* const* X, T* P, const int* gate,
                        int epoch, hipStream_t st) {
@@ -912,35 +635,28 @@ static void ax_valu_lb(const GemmPlan& p, const T* A, const T* const* X, T* P, c
   }
 }
 
-template <typename T, int NSRC>
-static void ax_valu_src(const GemmPlan& p, const T* A, const T* const* X, T* P, const int* gate,
-                        int epoch, hipStream_t st) {
-  switch (p.ax_lb) {
-    case 1: ax_valu_lb<T, 1, NSRC>(p, A, X, P, gate, epoch, st); break;
-    case 2: ax_valu_lb<T, 2, NSRC>(p, A, X, P, gate, epoch, st); break;
-    case 4: ax_valu_lb<T, 4, NSRC>(p, A, X, P, gate, epoch, st); break;
-    default: ax_valu_lb<T, 8, NSRC>(p, A, X, P, gate, epoch, st); break;
-  }
-}
-
-template <typename T, int NT, int NSRC, int MT, int PF, bool QUAD, bool NTL, int VPL = 1>
+// The MFMA launchers take their tile as its index I into kAxTiles and read the kernel's template
+// arguments and the grid geometry from that record.
+template <typename T, int NT, std::size_t I>
 static void ax_mfma_go(const GemmPlan& p, const T* A, const T* const* X, T* P, const int* gate,
                        int epoch, hipStream_t st) {
-  constexpr int E = 16 / sizeof(T);
-  const int gx = (int)cdiv(p.m, 16 * MT);
+  constexpr const AxTile& t = kAxTiles[I];
+  static_assert(t.fam == Fam::Mfma && t.nsrc_min == t.nsrc_max, "one kernel per source count");
+  const int gx = (int)cdiv(p.m, ax_tile_rows(t));
   const int xmap = ((p.ax_xmap & 1) && ax_xmap_ok(p.ax_S)) ? 1 : 0;
   const dim3 grid((unsigned)ax_grid(xmap, gx, p.ax_S));
-  glx_launch((k_ax_mfma<T, MT, NT, NSRC, PF, QUAD, NTL, VPL>), grid, dim3(256), 0, st, A,
-                     X[0], X[1], X[2], P, p.m, p.n, p.n / (4 * VPL * E), p.ax_S, gx, xmap, gate,
+  glx_launch((k_ax_mfma<T, t.mt, NT, t.nsrc_min, t.pf, false, t.ntl, t.vpl>), grid, dim3(256), 0, st, A,
+                     X[0], X[1], X[2], P, p.m, p.n, p.n / ax_tile_chunk(t, sizeof(T)), p.ax_S, gx, xmap, gate,
                      epoch);
 }
 
-template <typename T, int NT, int NSRC, int MT, int PF, int VPL, int WAVES, int DRV = 0>
+template <typename T, int NT, int NSRC, std::size_t I, int DRV = 0>
 static void ax_lds_go(const GemmPlan& p, int S, const T* A, const T* const* X, T* P,
                       const int* gate, int epoch, hipStream_t st, Pub pub = Pub{},
                       const AxDerive& drv = AxDerive{}) {
-  constexpr int E = 16 / sizeof(T);
-  const int gx = (int)cdiv(p.m, 16 * MT * WAVES);
+  constexpr const AxTile& t = kAxTiles[I];
+  const int gx = (int)cdiv(p.m, ax_tile_rows(t));
+  const int64_t chunks = p.n / ax_tile_chunk(t, sizeof(T));
   const int xmap = ax_xmap_flags(p, S);
   const unsigned dense = (unsigned)ax_grid(xmap, gx, S) + (pub.host ? 1u : 0u);
   AxDerive dv = drv;
@@ -948,68 +664,14 @@ static void ax_lds_go(const GemmPlan& p, int S, const T* A, const T* const* X, T
   dv.gat0 = (int)dense + dv.nd;
   const dim3 grid(dense + (DRV ? (unsigned)(dv.nd + dv.ggx * p.l) : 0u));
   if constexpr (DRV) {
-    static const size_t pad = lds_pad(k_ax_lds_drv<T, MT, NT, NSRC, PF, VPL, WAVES, DRV>, "GLX_AX_LDS_PAD");
-    glx_launch((k_ax_lds_drv<T, MT, NT, NSRC, PF, VPL, WAVES, DRV>), grid, dim3(64 * WAVES), pad, st, A, X[0],
-               X[1], X[2], P, p.m, p.n, p.n / (4 * VPL * E), S, gx, xmap, gate, epoch, pub, dv);
+    static const size_t pad = lds_pad(k_ax_lds_drv<T, t.mt, NT, NSRC, t.pf, t.vpl, t.waves, DRV>, "GLX_AX_LDS_PAD");
+    glx_launch((k_ax_lds_drv<T, t.mt, NT, NSRC, t.pf, t.vpl, t.waves, DRV>), grid, dim3(64 * t.waves), pad, st, A,
+               X[0], X[1], X[2], P, p.m, p.n, chunks, S, gx, xmap, gate, epoch, pub, dv);
   } else {
-    static const size_t pad = lds_pad(k_ax_lds<T, MT, NT, NSRC, PF, VPL, WAVES>, "GLX_AX_LDS_PAD");
-    glx_launch((k_ax_lds<T, MT, NT, NSRC, PF, VPL, WAVES>), grid, dim3(64 * WAVES), pad, st, A, X[0], X[1],
-               X[2], P, p.m, p.n, p.n / (4 * VPL * E), S, gx, xmap, gate, epoch, pub, dv);
+    static const size_t pad = lds_pad(k_ax_lds<T, t.mt, NT, NSRC, t.pf, t.vpl, t.waves>, "GLX_AX_LDS_PAD");
+    glx_launch((k_ax_lds<T, t.mt, NT, NSRC, t.pf, t.vpl, t.waves>), grid, dim3(64 * t.waves), pad, st, A, X[0],
+               X[1], X[2], P, p.m, p.n, chunks, S, gx, xmap, gate, epoch, pub, dv);
   }
-}
-
-// the planner's kind-5 tiles (lds_plan): 52228 (f64 batched / one RHS in the Infinity Cache),
-// 52224 (its 4-wave form for deep-split shards), 51328 (one 16-row tile per wave: the
-// one-RHS and shard tile at l = 32), 52324 (f32 batched)
-template <typename T, int NT, int NSRC>
-static void ax_lds_code(const GemmPlan& p, int code, int S, const T* A, const T* const* X, T* P,
-                        const int* gate, int epoch, hipStream_t st, Pub pub) {
-  if (dma_kind(code)) {
-    if (!launch_ax_dma<T>(p, code, NSRC, S, A, X, P, gate, epoch, st, pub))
-      throw Error{GLX_E_INVALID, "A@X: unknown LDS-DMA tile code"};
-    return;
-  }
-  switch (code) {
-    case 52228: ax_lds_go<T, NT, NSRC, 2, 2, 2, 8>(p, S, A, X, P, gate, epoch, st, pub); break;
-    case 51328: ax_lds_go<T, NT, NSRC, 1, 3, 2, 8>(p, S, A, X, P, gate, epoch, st, pub); break;
-    case 52324: ax_lds_go<T, NT, NSRC, 2, 3, 2, 4>(p, S, A, X, P, gate, epoch, st, pub); break;
-    case 52224: ax_lds_go<T, NT, NSRC, 2, 2, 2, 4>(p, S, A, X, P, gate, epoch, st, pub); break;
-    default: throw Error{GLX_E_INVALID, "A@X: unknown LDS tile code"};
-  }
-}
-
-// Direct-load tiles (kinds 1/2) only where no LDS tile fits the shape (lds_code_ok: l not 16/32
-// is VALU; n not a multiple of the LDS chunk): 21820 / 1820 (f64, or any n % 4E), 21410 (f32),
-// and for batched sources 1420 / 1220.
-template <typename T, int NT>
-static void ax_mfma_nt(const GemmPlan& p, int nsrc, const T* A, const T* const* X, T* P,
-                       const int* gate, int epoch, hipStream_t st, Pub pub) {
-  const int code = p.axb_code[nsrc];
-  if (lds_kind(code)) {
-    if (nsrc == 1) ax_lds_code<T, NT, 1>(p, code, p.axb_S[1], A, X, P, gate, epoch, st, pub);
-    else if (nsrc == 2) ax_lds_code<T, NT, 2>(p, code, p.axb_S[2], A, X, P, gate, epoch, st, pub);
-    else ax_lds_code<T, NT, 3>(p, code, p.axb_S[3], A, X, P, gate, epoch, st, pub);
-    return;
-  }
-  if (pub.host != nullptr) throw Error{GLX_E_INVALID, "A@X: this tile cannot carry the scalar packet"};
-  if (nsrc == 2) {
-    ax_mfma_go<T, NT, 2, 4, 2, false, false>(p, A, X, P, gate, epoch, st);
-    return;
-  }
-  if (nsrc == 3) {
-    ax_mfma_go<T, NT, 3, 2, 2, false, false>(p, A, X, P, gate, epoch, st);
-    return;
-  }
-  switch (p.ax_code) {
-    case 21820: ax_mfma_go<T, NT, 1, 8, 2, false, false, 2>(p, A, X, P, gate, epoch, st); break;
-    case 21410: ax_mfma_go<T, NT, 1, 4, 1, false, false, 2>(p, A, X, P, gate, epoch, st); break;
-    default: ax_mfma_go<T, NT, 1, 8, 2, false, false>(p, A, X, P, gate, epoch, st); break;   // 1820
-  }
-}
-
-bool ax_pub_ok(const GemmPlan& p, int nsrc) {
-  return p.ax_kind != 3 && (p.l == 16 || p.l == 32) && nsrc >= 1 && nsrc <= 3 &&
-         lds_kind(p.axb_code[nsrc]);
 }
 
 template <typename T>
@@ -1017,18 +679,36 @@ void launch_ax(const GemmPlan& p, int nsrc, const T* A, const T* const* X, T* P,
                int epoch, hipStream_t st, Pub pub) {
   if (pub.host != nullptr && !ax_pub_ok(p, nsrc))
     throw Error{GLX_E_INVALID, "A@X: this plan cannot carry the scalar packet"};
-  if (p.ax_kind == 3) {
-    if (nsrc == 1) ax_valu_src<T, 1>(p, A, X, P, gate, epoch, st);
-    else if (nsrc == 2) ax_valu_src<T, 2>(p, A, X, P, gate, epoch, st);
-    else ax_valu_src<T, 3>(p, A, X, P, gate, epoch, st);
+  const AxTile* tile = p.ax[nsrc];
+  if (tile->fam == Fam::Valu) {
+    with_const<1, 2, 3>(nsrc, [&](auto ns) {
+      with_const<1, 2, 4, 8>(p.ax_lb, [&](auto lb) {
+        ax_valu_lb<T, decltype(lb)::value, decltype(ns)::value>(p, A, X, P, gate, epoch, st);
+      });
+    });
     return;
   }
-  if (p.l == 16) ax_mfma_nt<T, 1>(p, nsrc, A, X, P, gate, epoch, st, pub);
-  else ax_mfma_nt<T, 2>(p, nsrc, A, X, P, gate, epoch, st, pub);
-}
-
-bool ax_derive_ok(const GemmPlan& p, int esize) {
-  return esize == 8 && p.ax_kind == 5 && p.axb_code[1] == 51328 && p.l == 32 && p.n % 16 == 0;
+  if (tile->fam == Fam::Dma) {
+    if (!launch_ax_dma<T>(p, tile, nsrc, p.axb_S[nsrc], A, X, P, gate, epoch, st, pub))
+      throw Error{GLX_E_INVALID, "A@X: unknown LDS-DMA tile code"};
+    return;
+  }
+  // Direct loads run only where no LDS tile fits the shape, and there is one such kernel per
+  // batched source count: a batch runs it whichever direct-load label its plan carries.
+  static constexpr const AxTile* kBatch[4] = {nullptr, nullptr, ax_tile(1420), ax_tile(1220)};
+  if (tile->fam == Fam::Mfma && nsrc > 1) tile = kBatch[nsrc];
+  with_const<1, 2>((int)(p.l / 16), [&](auto nt) {
+    visit_tile(kAxTiles, tile, [&](auto i) {
+      constexpr const AxTile& t = kAxTiles[decltype(i)::value];
+      if constexpr (t.fam == Fam::Mfma)
+        ax_mfma_go<T, decltype(nt)::value, decltype(i)::value>(p, A, X, P, gate, epoch, st);
+      else if constexpr (t.fam == Fam::Lds)
+        with_const<1, 2, 3>(nsrc, [&](auto ns) {
+          ax_lds_go<T, decltype(nt)::value, decltype(ns)::value, decltype(i)::value>(p, p.axb_S[nsrc], A, X, P,
+                                                                                     gate, epoch, st, pub);
+        });
+    });
+  });
 }
 
 template <typename T>
@@ -1045,7 +725,8 @@ bool launch_ax_derive(const GemmPlan& p, const T* A, const T* Xp, T* P, hipStrea
     dd.sp.pub = pub;
     dd.nd = kDrvThrBlocks;
     const T* xs[3] = {Xp, nullptr, nullptr};
-    ax_lds_go<T, 2, 1, 1, 3, 2, 8, 1>(p, p.axb_S[1], A, xs, P, nullptr, 0, st, pub, dd);
+    constexpr std::size_t kShard = ax_tile(51328) - kAxTiles;   // ax_derive_ok: the plan's tile, l = 32
+    ax_lds_go<T, 2, 1, kShard, 1>(p, p.axb_S[1], A, xs, P, nullptr, 0, st, pub, dd);
     return true;
   }
 }

@@ -269,51 +269,6 @@ static bool egat_mode(const glx_problem& P, const GemmPlan& plan, int smode) {
   return ax_egat_ok(plan, 8);
 }
 
-static GemmPlan session_plan(const glx_problem& P, const glx_opts& O) {
-  const int es = P.dtype == GLX_F64 ? 8 : 4;
-  GemmPlan p = make_plan(es, P.m, P.n, P.l, O.ax_variant);
-  const bool trial_method = (P.method == GLX_PROXGD || P.method == GLX_FPROXGD) &&
-                            (O.step_type == GLX_STEP_LINE_SEARCH || O.step_type == GLX_STEP_FIXED);
-  if (es == 4 && P.comm == nullptr && trial_method && p.atr_kind == 1 &&
-      (P.l == 16 || P.l == 32) && P.n % 64 == 0 && P.m >= 128 && (P.n / 64) * 2 < kMaxBlocks &&
-      !std::getenv("GLX_ATR_VARIANT") && !std::getenv("GLX_ATR_S") &&
-      !std::getenv("GLX_FUSED_TRIAL")) {
-    GemmPlan f = p;
-    f.atr_wl = 0;
-    f.atr_ntl = 1;
-    f.atr_pf = 8;   // round 3: the PF 8 ring (1008), see above
-    f.atr_S = 2;
-    // Round 4: with at least one panel per CU, the eight-wave panel (WL 2: two waves per SIMD)
-    // with one K split, no slab combine: C3 FProxGD A^T R + trial 101.2-101.4 us against
-    // 107.4-107.6, 3815-3825 against 3741-3748 it/s over 200 steps (profiles/r4_c3atr/; with
-    // two K splits it measured 119 us, with the PF 4 ring 104 us)
-    if (P.n / 64 >= 256) {
-      f.atr_wl = 2;
-      f.atr_S = 1;
-      // (round 6: a sixteen-step ring, twice the A bytes in flight per wave, measured slower:
-      // A^T R + trial 120.9 against 101.3 us at C3, 3 628 against 3 862 it/s, profiles/r6_egat/)
-    }
-    if (atr_prox_ok(f)) return f;   // only where the trial actually fuses (GLX_ATR_FUSE_SPLIT)
-  }
-  // Round 5: fp64 with fewer than 256 64-column panels (C2: 128, planned as 2 K splits) takes
-  // the 32-column panel without K splits (WL 3): 256+ workgroups and no slab combine in front of
-  // the fused trial. GLX_ATR_NARROW=0: off. (Its eight-wave form, WL 4, measured slower and is no
-  // longer built, round 6.)
-  if (es == 8 && P.comm == nullptr && trial_method && p.atr_kind == 1 && (P.l == 16 || P.l == 32) &&
-      P.n % 32 == 0 && P.n / 64 < 256 && P.n / 32 >= 256 && !std::getenv("GLX_ATR_VARIANT") &&
-      !std::getenv("GLX_ATR_S") && !std::getenv("GLX_FUSED_TRIAL")) {
-    const char* nw = std::getenv("GLX_ATR_NARROW");
-    if (!(nw && std::strcmp(nw, "0") == 0)) {
-      GemmPlan f = p;
-      f.atr_wl = 3;
-      f.atr_pf = 8;
-      f.atr_S = 1;
-      if (atr_prox_ok(f)) return f;
-    }
-  }
-  return p;
-}
-
 class SessionBase {
  public:
   virtual ~SessionBase() {}

@@ -217,3 +217,34 @@ def test_gradient_atr_codes(monkeypatch, shape, dtype, code):
     gmag = A.double().abs().T @ R.double().abs()
     tolg = 1e-13 if dtype == "f64" else 2e-6 * (m ** 0.5)
     assert _rel_err(G, gref, gmag) < tolg
+
+
+def test_session_plan_matches_recorded_planner():
+    """A session's method-level A^T R choice (planner.cpp session_plan) is what the commit before
+    the tile-table refactor chose: Session.describe() of sessions that are created and never run,
+    at the smallest shapes where each branch fires, equals the strings recorded from that commit
+    (tests/golden/make_plan_golden.py --sessions). Nothing in describe() varies from run to run, so
+    the whole string is compared."""
+    import json
+    import os
+    import sys
+    from conftest import ROOT
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    try:
+        import make_plan_golden as gen
+    finally:
+        sys.path.pop(0)
+    rows = json.load(open(os.path.join(ROOT, "tests", "golden", "plan_sessions.json")))["sessions"]
+    assert len(rows) == len(gen.SESSIONS)
+    saved = {k: os.environ.get(k) for k in gen.PLANNER_ENV}
+    try:
+        got = [gen.record_session(*r[:6]) for r in rows]
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    for g, r in zip(got, rows):
+        print(r[:6], g)
+        assert g == r[6], r[:6]

@@ -166,6 +166,33 @@ def test_plan_describe_picks_tiles_by_shape():
         _lib.plan_describe(_lib.GLX_F64, 0, 16, 16)
 
 
+def test_plan_matches_recorded_planner():
+    """The planner decides what the commit before the tile-table refactor decided: for every
+    recorded (dtype, shape, override) the describe string is byte-identical and the kernel and
+    session workspace sizes and error codes are equal (tests/golden/make_plan_golden.py; the
+    fixture was recorded from that commit's build and is never regenerated from this code)."""
+    import json
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    try:
+        import make_plan_golden as gen
+    finally:
+        sys.path.pop(0)
+    cases = json.load(open(os.path.join(ROOT, "tests", "golden", "plan_golden.json")))["cases"]
+    assert len(cases) >= 300
+    saved = {k: os.environ.get(k) for k in gen.PLANNER_ENV}
+    try:
+        got = [gen.record_case(*c[:5]) for c in cases]
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    bad = [(g, c) for g, c in zip(got, cases) if g != c]
+    assert not bad, "%d of %d differ, first: got %r, recorded %r" % (len(bad), len(cases), bad[0][0], bad[0][1])
+
+
 def test_kernel_workspace_covers_every_planned_split():
     """glx_kernel_workspace_bytes must hold the partial slabs of the largest K split any tile
     (single or batched, register or LDS) plans, else the single-kernel calls refuse to run."""
