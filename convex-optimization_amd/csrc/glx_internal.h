@@ -7,6 +7,7 @@
 #include <stddef.h>
 
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <tuple>
 #include <utility>
@@ -141,7 +142,7 @@ struct Pub {
   // Round 5, deferred reductions: workgroup partials (Red::parts_only layout: dnv values per
   // slot, dnp slots) that the publishing workgroup reduces (dmax bit j: max) into dout[0, dnv)
   // before it copies the packet, so the kernels that produced them skip their grid reduction's
-  // serial tail (solver.cpp defer_)
+  // serial tail (SessionMode::defer)
   const double* dpart[2] = {nullptr, nullptr};
   int dnp[2] = {0, 0}, dnv[2] = {0, 0};
   unsigned dmax[2] = {0u, 0u};
@@ -179,6 +180,19 @@ inline int env_int(const char* name, int dflt) {
   const char* v = std::getenv(name);
   return (v && *v) ? std::atoi(v) : dflt;
 }
+// One knob of the planner (planner.cpp Knobs) or of a session's mode (SessionKnobs). set(): the
+// variable is present, which makes it an override: the shape-dependent choices stand back.
+struct EnvInt {
+  const char* s;
+  explicit EnvInt(const char* name) : s(std::getenv(name)) {}
+  bool set() const { return s != nullptr; }
+  int or_(int dflt) const { return (s && *s) ? std::atoi(s) : dflt; }
+  bool on() const { return or_(1) != 0; }   // a switch that defaults to on
+  bool is(const char* v) const { return s != nullptr && std::strcmp(s, v) == 0; }   // exactly this text
+  // present: its number (an empty value reads 0), else dflt
+  int num(int dflt) const { return s ? std::atoi(s) : dflt; }
+  double real(double dflt) const { return s ? std::atof(s) : dflt; }
+};
 // ax_variant: a tile code of glx_tiles.h, or 0 (GLX_AX_VARIANT, else the planner's choice)
 GemmPlan make_plan(int esize, int64_t m, int64_t n, int64_t l, int ax_variant);
 // make_plan, then the method-level A^T R choice of a session (the fused trial's tiles)
@@ -201,6 +215,67 @@ bool ax_egat_ok(const GemmPlan& p, int esize);
 bool ax_derive_ok(const GemmPlan& p, int esize);
 bool atr_prox_ok(const GemmPlan& p);
 int atr_prox_slots(const GemmPlan& p, bool pub);
+
+// ---- a session's mode (session_mode.cpp, host only) ----
+// Every environment variable a session's mode depends on, read once per session_mode call and
+// never cached (tests change the environment between calls in one process). The planner's knobs
+// are the planner's (planner.cpp Knobs: GLX_FUSED_TRIAL's presence is an override there, its
+// value a switch here); the launch knobs stay with their kernels (kernels_*.hip).
+struct SessionKnobs {
+  EnvInt dc_batch{"GLX_DC_BATCH"}, shard_rows{"GLX_SHARD_ROWS"}, split_f32{"GLX_SPLIT_F32"},
+      split_cand{"GLX_SPLIT_CAND"}, split_fista{"GLX_SPLIT_FISTA"}, split_nnz{"GLX_SPLIT_NNZ"},
+      ae_fused{"GLX_AE_FUSED"}, ae_hyb_rows{"GLX_AE_HYB_ROWS"}, gemv_fused{"GLX_GEMV_FUSED"},
+      unfused_spec{"GLX_UNFUSED_SPEC"}, fused_trial{"GLX_FUSED_TRIAL"}, readback{"GLX_READBACK"},
+      attach_pub{"GLX_ATTACH_PUB"}, spec_grad{"GLX_SPEC_GRAD"}, spec_ax_pub{"GLX_SPEC_AX_PUB"},
+      shard_derive{"GLX_SHARD_DERIVE"}, defer_red{"GLX_DEFER_RED"}, ax_keep_mib{"GLX_AX_KEEP_MIB"},
+      atr_keep_mib{"GLX_ATR_KEEP_MIB"};
+};
+constexpr int kMaxShardRanks = 64;   // ranks (or modelled ranks) of the row-sharded schedules
+// The row-sharded schedule of ProxGD (solver.cpp iter_proxgd_shard) / FProxGD (iter_fista_shard):
+// this rank's rows [row0, row0 + rows) of n, `ranks` row blocks (cranks communicator ranks; they
+// differ only in the timing model)
+struct ShardMode {
+  bool on = false, fista = false, model = false;
+  int ranks = 1, rank = 0, cranks = 1;
+  int64_t rows = 0, row0 = 0;
+  int nbp = 0, nbf = 0;   // k_prox_pgd's workgroups on `rows` rows, the trial finalize's
+  int stv = 6;            // values per trial workgroup partial in the chunk (FProxGD: 4)
+  int chunk = 0;          // doubles per rank's chunk
+  bool zskip = false;     // the gathered p serves as e (bitmap / list gathers)
+  bool derive = false;    // round 6: the speculative derive inside the dense pass (AxDerive)
+  int64_t moff = 0;       // doubles into a rank's chunk: its row masks + column bitmaps (derive)
+};
+// What a session launches, resolved once from the problem, the options and the environment;
+// Session<T> (solver.cpp) lays out its workspace from it and iterates by it.
+struct SessionMode {
+  int method = 0, esize = 8;
+  int64_t m = 0, n = 0, l = 0;
+  bool comm = false;              // the problem has a communicator
+  GemmPlan plan{};                // session_plan with the two keep_mib values
+  int64_t fh_cap = 0;             // objective history entries
+  int smode = 0;                  // split-candidate trial: 0 off, 1 A e from the transposed copy of A
+  int gform = 0;                  // A e: 0 bitmap gather, 1 k_at_rows, 2 lists + gather (gather_form)
+  bool rows_form = false;         // gform == 1: A e by k_at_rows (round 5), gsplit slabs
+  int gsplit = 1;
+  bool egat = false;              // round 6: A e inside the dense pass (launch_ax_egat), gsplit = its S
+  double hyb_rows = 0.0;          // round 6: > 0: the fused form per trial from this many flagged rows
+  double nnz_budget = 0.0;        // nnz(e_c) above which the dense batch is cheaper
+  bool emode = false;             // split-candidate ProxGD: trials write e = p - p_thr, not z
+  bool fsplit = false;            // split-candidate FProxGD
+  bool spin_readback = true, attach_ok = true;
+  bool spec_off = false;          // GLX_SPEC_GRAD=0
+  bool spec_ax_pub = true;        // GLX_SPEC_AX_PUB=0: the packet rides k_prox_pgd instead
+  bool unfused_spec = false;      // one GPU, a plan without the fused trial: the communicator form
+  bool fused_ok = false, fused_fista_ok = false;   // the trial is queued speculatively (ProxGD / FProxGD)
+  int dc_window = 0;              // device-controlled iterations in flight (0: the host decides)
+  int nsets = 2;                  // gradient sets
+  bool defer = false;             // deferred reductions (single GPU)
+  int gemv_blocks = 0;            // SGD / GD, l = 1: workgroups of the one-pass form (0: two passes)
+  ShardMode sh;
+};
+SessionMode session_mode(const glx_problem& P, const glx_opts& O);
+// the kernels the session launches (glx_session_describe, glx_mode_describe)
+std::string describe_mode(const SessionMode& md);
 
 // ---- dense products (kernels_gemm.hip) ----
 // A @ [X[0] | .. | X[nsrc-1]] (nsrc <= 3, each n x l) in one pass over A: partial slabs

@@ -9,15 +9,6 @@
 namespace glx {
 namespace {
 
-// One planner knob. set(): the variable is present, which makes it an override: the
-// shape-dependent choices stand back.
-struct EnvInt {
-  const char* s;
-  explicit EnvInt(const char* name) : s(std::getenv(name)) {}
-  bool set() const { return s != nullptr; }
-  int or_(int dflt) const { return (s && *s) ? std::atoi(s) : dflt; }
-  bool on() const { return or_(1) != 0; }   // a switch that defaults to on
-};
 // Read once per planning call and never cached: tests change the environment between calls in
 // one process. (GLX_FUSED_TRIAL is the session's knob; its presence is an override here.)
 struct Knobs {

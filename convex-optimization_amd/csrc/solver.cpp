@@ -87,8 +87,6 @@ static int method_bufs(int method) {
 constexpr int kBufs = 9;
 constexpr int kTailBytes = 64;   // behind each gradient set: scalars that ride its all-reduce
 constexpr int kRes = 4;
-constexpr int kDcWindow = 8;     // device-controlled line search: iterations in flight (GLX_DC_BATCH)
-constexpr int kKeepMiB = 192;    // Infinity-Cache hand-off between the non-temporal passes
 // gradient sets: 2 (current, speculative); with a communicator and device control a ring of
 // window + 2, so that the all-reduces queued behind a cancelling decision (they cannot be
 // gated) never land in the set the host resumes from
@@ -97,38 +95,10 @@ constexpr int kMaxGSets = kCtlMaxBatch / 2 + 2;
 // (the finalize's at [6, 10), the trial's workgroup partials from kShardPartOff, ShardPub), for
 // up to kMaxShardRanks ranks
 constexpr int kShardChunkMax = kShardPartOff + (6 + 4) * kMaxBlocks;
-constexpr int kMaxShardRanks = 64;
-// round 6: flagged rows from which ProxGD's split-candidate A e takes the fused form (GLX_AE_HYB_ROWS)
-constexpr double kHybRows = 2000.0;
-// the chunks' doubles: the sums of up to kMaxShardRanks ranks, plus (round 6, sderive_) every rank's
+// the chunks' doubles: the sums of up to kMaxShardRanks ranks, plus (round 6, ShardMode::derive) every rank's
 // row masks and column bitmaps of e for its rows (n / 2 + l n / 64 doubles over all ranks)
 static int64_t shard_blk_doubles(int64_t n, int64_t l) {
   return (int64_t)kShardChunkMax * kMaxShardRanks + n / 2 + l * n / 64 + 64;
-}
-
-// device-controlled batches' window: opts.dc_window (> 0: that window, < 0: off), else
-// GLX_DC_BATCH, else the measured default (0 = the host decides every iteration): kDcWindow for
-// FProxGD with a communicator, off elsewhere. Same box, 200-step windows, host control against
-// window 8 (profiles/r3_dc/): ProxGD NS 2374-2382 vs 2344-2354 it/s, C2 9003-9010 vs 8894-8910,
-// the comm-path shards 6922-11023 vs 6735-10612 (its speculative A@X already hides the host's
-// turn); FProxGD NS 2454-2478 vs 2456-2465 (whole solve 2058-2060 vs 2036-2038), C3 3702 vs
-// 3687-3703, C5's shard 1227-1231 vs 1230-1234, the 1024-row comm shard 9802-9829 vs 10517-10587
-// (+7.5 %: the host path leaves the GPU idle while it decides behind the short speculative trial).
-// Round 5: also kDcWindow for ProxGD on the unfused speculative form (unfused: Session's
-// dc_unfused_ok) when A is at most kDcSmallBytes — launch-bound shapes, where the host's turn per
-// iteration is a large share: C1 (512, 1024, 2) 200-step windows 24 250 / 24 253 it/s with host
-// control against 25 477 / 25 591 with window 8 (and 22 079 / 21 752 on the rounds-1-4 form;
-// profiles/r5_unfused/).
-static constexpr double kDcSmallBytes = 64.0 * 1024 * 1024;
-static int dc_window_opt(const glx_problem& P, const glx_opts& O, bool unfused = false) {
-  int w = (P.method == GLX_FPROXGD && P.comm != nullptr) ? kDcWindow : 0;
-  if (unfused && (double)P.m * (double)P.n * 8.0 <= kDcSmallBytes) w = kDcWindow;
-  if (O.dc_window != 0) {
-    w = O.dc_window;
-  } else if (const char* dc = std::getenv("GLX_DC_BATCH")) {
-    w = std::atoi(dc);
-  }
-  return std::max(0, std::min(w, kCtlMaxBatch / 2));
 }
 
 static void validate(const glx_problem* P, const glx_opts* O) {
@@ -146,127 +116,6 @@ static void validate(const glx_problem* P, const glx_opts* O) {
   if ((reinterpret_cast<uintptr_t>(P->A) | reinterpret_cast<uintptr_t>(P->b) |
        reinterpret_cast<uintptr_t>(P->x)) & 15)
     throw Error{GLX_E_INVALID, "A, b, x must be 16-byte aligned"};
-}
-
-// ------------------------------------------------------------------------------------------
-// The solver's plan: the shape's GEMM plan, plus one method-level choice. fp32 ProxGD/FProxGD
-// on one GPU take the 4-wave panel AᵀR with 2 K splits (code 1008) instead of the 4-panel
-// tile (1114), so that the line-search trial fuses into it (atr_split_combine): the AᵀR pass
-// is ≈13 µs slower but the trial launch and its boundary go. Same box: C3 (8192,16384,32)
-// FProxGD 3669–3691 → 3743–3749 it/s, ProxGD 3654–3657 → 3744–3752, FProxGD at (4096,8192,16)
-// 11 362–11 366 → 13 200–13 215 (profiles/r1_tuning/small_kernels/atr_f32_fused.log).
-// Round 3: with the PF 8 ring (1008) instead of PF 4 the C3 pass reads 5.0 instead of 4.7 TB/s
-// (A^T R 106.6–107.1 vs 113–114.5 us), FProxGD 3627–3680 → 3725–3763 it/s over 200 steps;
-// S = 1 / 4 and the default load policy measured level or slower (profiles/r3_c3atr/sweep.txt).
-// Split-candidate ProxGD (the fast objective mode, see iter_proxgd): 0 = off (exact mode, other
-// methods, shapes the gather does not cover, or GLX_SPLIT_CAND=0 / glx_opts.split_cand = 0: the
-// dense [z | p_thr] batch of round 1); 1 = A e from the transposed copy of A (kernels_gather.hip;
-// costs an extra m x n copy of A in the workspace, glx_session_workspace_bytes).
-// ProxGD: fp64 only. In fp32 its regrouped sum (A p_thr - b) + A e IS the recorded objective
-// and moves f by ~1e-6 relative on short unconverged runs (measured 1.5e-6 on mid_384x640x16
-// against the 1e-6 fp32 bar); no fp32 ProxGD configuration is on the benchmark path.
-// FProxGD in fp32 (C3): the objective is A xc computed directly; only A y_next is regrouped.
-// Round 4 kept it opt-in because one whole C3 solve ended 3.4e-5 from the reference's fp32 run
-// against 3.4e-7 for the dense batch. Round 5 measured the band (scripts/c3_band.py,
-// profiles/r5_d/c3_band.jsonl): eleven summation orders of the two forms (K splits, tiles, A e
-// forms) end 3.4e-7 .. 8.7e-5 (dense) and 1.6e-5 .. 8.9e-5 (split) from the reference's fp32
-// objective, all 7.0e-3 .. 7.1e-3 from its fp64 one (the reference's own fp32 run: 7.0e-3).
-// Round 6: the dense batch is the fp32 default again — its default order ends
-// 3.4e-7 from the reference's fp32 run, inside the 1e-6 fp32 bar, the split form's 1.6e-5 does
-// not, and whole solves run level (3897 it/s both: late in a solve e_c fills and the budget runs
-// dense batches; only 200-step windows gain, +17 %). GLX_SPLIT_F32=1: the split form (opt-in).
-// (The size gate counts elements as fp64.)
-// FProxGD with line search takes the gather form too (iter_fista: A y_next by linearity from
-// A xc, A e_c and the kept A thr(x_k)); GLX_SPLIT_FISTA=0 keeps its dense [xc | y_next] batch.
-// Only for A of at least kSplitMinBytes (this rank's rows): the column lists and the gather
-// carry a fixed ~70 + 50 us that a short dense pass cannot hide. Measured against the dense
-// batch (profiles/r2_splitgate/): NS (1 GiB) 2295 vs 2080 it/s, (4096,16384,32) 3894 vs 3832,
-// but C2 (4096,8192,16) 7329 vs 8948 and the comm-path shards of 4096 / 2048 / 1024 rows
-// 3543 / 6756 / 9748 vs 3623 / 6884 / 11162. GLX_SPLIT_CAND=1 forces it at any size (tests).
-// Round 5 (the bitmap gather: no lists kernel, ~5 us fixed): ProxGD at l = 32 takes it from
-// 64 MiB of A on this rank. Measured against the dense batch (profiles/r5_e/, profiles/r5_f/;
-// 200-step windows / whole solves): (4096, 16384, 32) 4844 / 4894 vs 3987 / 4069 it/s; the
-// communicator-path shards of 1024 / 2048 / 4096 rows 12114 / 8016 / 4759 vs 11122 / 6931 / 3915
-// (whole solves at 1024 / 4096 rows 12082 / 4848 vs 11226 / 4015). C2 (l = 16, A in the Infinity
-// Cache, where At would evict it) stays dense: 8411 / 8205 vs 9127 / 9151; FProxGD's shards too
-// (whole solves 10480 / 3943 vs 10847 / 4000: e_c fills late in a solve).
-static constexpr double kSplitMinBytesL32 = 64.0 * 1024 * 1024;
-static constexpr double kSplitMinBytes = 768.0 * 1024 * 1024;
-// Round 6: row-sharded FProxGD (iter_fista_shard) — the gradient
-// reduce-scattered, k_fista_trial on this rank's n / G rows, xc's rows all-gathered and v_next,
-// y_next re-derived from it on every rank (k_fista_split). Returns G where it applies, else 0.
-// opts.shard_rows (GLX_SHARD_ROWS): 1 on (needs n % G == 0), 2 off, 0 auto: on where this rank's
-// A is below kFistaShardMaxBytes and no device-control window is asked for. Host control only:
-// the device-controlled FISTA batch (fista_dc_run) decides from all-reduced gradient tails; the
-// sharded form would need its decision behind the all-gather, one more collective per queued
-// iteration, so big shards (C5: 2 GiB per rank, where the replicated row work is ~2 % of an
-// iteration) keep the all-reduce schedule with device control.
-static constexpr double kFistaShardMaxBytes = 768.0 * 1024 * 1024;
-static int shard_rows_opt(const glx_opts& O) {
-  int want = O.shard_rows;
-  if (const char* e = std::getenv("GLX_SHARD_ROWS")) {
-    want = std::atoi(e);
-    if (want < 0 || want > 2) throw Error{GLX_E_INVALID, "GLX_SHARD_ROWS must be 0 (auto), 1 (on) or 2 (off)"};
-  }
-  return want;
-}
-static int fista_shard_ranks(const glx_problem& P, const glx_opts& O) {
-  if (P.comm == nullptr || P.method != GLX_FPROXGD) return 0;
-  if (O.step_type != GLX_STEP_LINE_SEARCH && O.step_type != GLX_STEP_FIXED) return 0;
-  const int want = shard_rows_opt(O);
-  if (want == 2) return 0;
-  const glx_comm* c = static_cast<const glx_comm*>(P.comm);
-  const int vr = comm_size(c) == 1 ? std::max(1, O.shard_model) : comm_size(c);
-  if (vr <= 1) return 0;
-  const bool fits = vr <= 64 && P.n % vr == 0;
-  if (want == 1 && !fits)
-    throw Error{GLX_E_INVALID, "row-sharded FProxGD needs n % ranks == 0 and at most 64 ranks "
-                               "(opts.shard_rows = 0 / 2: the all-reduce schedule)"};
-  if (!fits) return 0;
-  if (want == 0 && ((double)P.m * (double)P.n * 8.0 >= kFistaShardMaxBytes || O.dc_window > 0)) return 0;
-  return vr;
-}
-
-static int split_mode(const glx_problem& P, const glx_opts& O) {
-  if (O.exact_objective != 0) return 0;
-  if (P.method != GLX_PROXGD && P.method != GLX_FPROXGD) return 0;
-  if (P.dtype != GLX_F64) {   // fp32: FProxGD only, opt-in (GLX_SPLIT_F32=1, above)
-    const char* f = std::getenv("GLX_SPLIT_F32");
-    if (P.method != GLX_FPROXGD || !(f && std::strcmp(f, "1") == 0)) return 0;
-  }
-  if (O.split_cand == 2) return 0;
-  const char* sc = O.split_cand == 0 ? std::getenv("GLX_SPLIT_CAND") : nullptr;
-  if (sc && std::strcmp(sc, "0") == 0) return 0;
-  const bool force = O.split_cand == 1 || (sc && std::strcmp(sc, "1") == 0);
-  const double gate = (P.method == GLX_PROXGD && P.l == 32) ? kSplitMinBytesL32 : kSplitMinBytes;
-  if (!force && (double)P.m * (double)P.n * 8.0 < gate) return 0;
-  if (P.method == GLX_FPROXGD) {
-    if (fista_shard_ranks(P, O) > 0) return 0;   // the row-sharded FISTA runs the dense batch
-    const char* sf = std::getenv("GLX_SPLIT_FISTA");
-    if (sf && std::strcmp(sf, "0") == 0) return 0;
-    const bool ls = O.step_type == GLX_STEP_LINE_SEARCH && O.ls_maxit > 0;
-    return (ls && gather_ok(P.n, P.l)) ? 1 : 0;
-  }
-  return gather_ok(P.n, P.l) ? 1 : 0;
-}
-
-// Round 6: ProxGD's split-candidate trial with A e fused into the dense pass (launch_ax_egat,
-// kernels_axdma.hip: A p on MFMA, A e on VALU from the same LDS chunks; no transposed copy of A,
-// no gather launch) where the session's one-source pass is the f64 LDS-DMA tile 92278 (NS).
-// Opt-in (GLX_AE_FUSED=1): same box, 200-step windows / whole solves (profiles/r6_egat/): NS
-// 2 452-2 467 / 2 461-2 467 it/s fused against 2 454-2 470 / 2 427-2 434 with the gather — level
-// in the window, +1.5 % over a solve (the gather grows late in a solve), but the fused pass runs
-// 210-218 µs against 174-176 µs: its A e (VALU, after the chunk's MFMAs) leaves the MFMA pipe of
-// both waves of a SIMD idle. Interleaving it into the MFMA stream (straight-line, or on opposite
-// sides of the two waves' MFMAs) spilled 16-208 VGPRs at 256. Throughout a solve it stays opt-in
-// (it also halves the session's workspace: no m x n copy of A); by default the session takes it
-// per trial once many rows are flagged (hyb_rows_, below).
-static bool egat_mode(const glx_problem& P, const GemmPlan& plan, int smode) {
-  if (smode != 1 || P.method != GLX_PROXGD || P.dtype != GLX_F64) return false;
-  if (gather_form() >= 0) return false;
-  const char* e = std::getenv("GLX_AE_FUSED");
-  if (!(e && std::strcmp(e, "1") == 0)) return false;
-  return ax_egat_ok(plan, 8);
 }
 
 class SessionBase {
@@ -287,18 +136,19 @@ template <typename T>
 class Session : public SessionBase {
  public:
   // workspace layout; with ws == nullptr only computes the size
-  static size_t carve(const glx_problem& P, const glx_opts& O, const GemmPlan& plan, int64_t fh_cap,
-                      int smode, void* ws, Session* s) {
+  static size_t carve(const SessionMode& md, void* ws, Session* s) {
     Carver c(ws);
-    const int64_t nl = P.n * P.l, ml = P.m * P.l;
-    const int nb = method_bufs(P.method);
-    T* bufs[kBufs] = {static_cast<T*>(P.x)};
+    const GemmPlan& plan = md.plan;
+    const int smode = md.smode;
+    const int64_t nl = md.n * md.l, ml = md.m * md.l;
+    const int nb = method_bufs(md.method);
+    T* bufs[kBufs] = {s ? static_cast<T*>(s->P_.x) : nullptr};
     for (int i = 1; i < nb; ++i) bufs[i] = static_cast<T*>(c.take(sizeof(T) * nl));
     T* res[kRes];
     for (int i = 0; i < kRes; ++i) res[i] = static_cast<T*>(c.take(sizeof(T) * ml));
     // gradient sets (G, its split-K slabs): the current one and the speculative one (a ring with
-    // a communicator and device control, gsets_for)
-    const int ngs = gsets_for(P, O, plan);
+    // a communicator and device control, SessionMode::nsets)
+    const int ngs = md.nsets;
     T* g[kMaxGSets];
     T* gp[kMaxGSets];
     for (int k = 0; k < ngs; ++k) {
@@ -307,14 +157,13 @@ class Session : public SessionBase {
     }
     // A@X slabs of up to 3 batched sources; split-candidate gather: the A e slabs + A p_thr's
     const int64_t pslabs = std::max<int64_t>((int64_t)ax_split_max(plan) * 3,
-                                             smode == 1 ? gather_split(P.m, P.n) + ax_split(plan, 1) : 0);
+                                             smode == 1 ? gather_split(md.m, md.n) + ax_split(plan, 1) : 0);
     T* pp = static_cast<T*>(c.take(sizeof(T) * ml * pslabs));
-    const bool eg = egat_mode(P, plan, smode);
-    T* at = (smode == 1 && !eg) ? static_cast<T*>(c.take(sizeof(T) * P.m * P.n)) : nullptr;   // A^T
-    void* glists = smode == 1 ? c.take(gather_lists_bytes(P.n)) : nullptr;
+    T* at = (smode == 1 && !md.egat) ? static_cast<T*>(c.take(sizeof(T) * md.m * md.n)) : nullptr;   // A^T
+    void* glists = smode == 1 ? c.take(gather_lists_bytes(md.n)) : nullptr;
     // split-candidate FISTA: e_c and a ring of three A thr(x) (x_k's, the trial's, the
     // speculated next trial's)
-    const bool fsp = smode == 1 && P.method == GLX_FPROXGD;
+    const bool fsp = md.fsplit;
     T* ec = fsp ? static_cast<T*>(c.take(sizeof(T) * nl)) : nullptr;
     T* sxo[3] = {nullptr, nullptr, nullptr};
     for (int k = 0; k < 3 && fsp; ++k) sxo[k] = static_cast<T*>(c.take(sizeof(T) * ml));
@@ -322,29 +171,28 @@ class Session : public SessionBase {
     double* part = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals * kMaxBlocks));
     unsigned* ticket = static_cast<unsigned*>(c.take(kTicketBytes));
     // per-panel arrival counters of the fused A^T R with K splits (atr_split_combine)
-    unsigned* pcnt = static_cast<unsigned*>(c.take(sizeof(unsigned) * (P.n / 64 + 64)));
+    unsigned* pcnt = static_cast<unsigned*>(c.take(sizeof(unsigned) * (md.n / 64 + 64)));
     int* flag = static_cast<int*>(c.take(256));
     // device-controlled batches: Ctl::state (4 doubles) and the abort word; decision records
     double* dcs = static_cast<double*>(c.take(256));
     double* dcr = static_cast<double*>(c.take(sizeof(double) * kCtlRec * kCtlMaxBatch));
     // split-candidate mode: per-row column masks of e = p - p_thr (z's buffer; bit c = e[k][c] != 0)
-    unsigned* zf = static_cast<unsigned*>(c.take(zf_bytes(P.n)));   // + the column bitmaps
-    // deferred reductions (defer_): two trial partial buffers (the kernel that reduces one may run
+    unsigned* zf = static_cast<unsigned*>(c.take(zf_bytes(md.n)));   // + the column bitmaps
+    // deferred reductions (md_.defer): two trial partial buffers (the kernel that reduces one may run
     // beside the next trial writing the other) and the finalize's
     double* tpart = static_cast<double*>(c.take(sizeof(double) * 2 * 6 * kMaxBlocks));
     double* fpart = static_cast<double*>(c.take(sizeof(double) * 4 * kMaxBlocks));
-    double* sblk = P.comm != nullptr && (P.method == GLX_PROXGD || P.method == GLX_FPROXGD)
-                       ? static_cast<double*>(c.take(sizeof(double) * shard_blk_doubles(P.n, P.l)))
+    double* sblk = md.comm && (md.method == GLX_PROXGD || md.method == GLX_FPROXGD)
+                       ? static_cast<double*>(c.take(sizeof(double) * shard_blk_doubles(md.n, md.l)))
                        : nullptr;
-    double* fh = static_cast<double*>(c.take(sizeof(double) * (fh_cap + 1)));
-    double* sp100 = static_cast<double*>(c.take(sizeof(double) * (fh_cap / 100 + 2)));
-    const int gb = gemv_blocks_for(P);
+    double* fh = static_cast<double*>(c.take(sizeof(double) * (md.fh_cap + 1)));
+    double* sp100 = static_cast<double*>(c.take(sizeof(double) * (md.fh_cap / 100 + 2)));
+    const int gb = md.gemv_blocks;
     T* gs = gb > 0 ? static_cast<T*>(c.take(sizeof(T) * nl * gb)) : nullptr;   // fused l = 1 slabs
     if (s) {
       for (int i = 0; i < kBufs; ++i) s->X_[i] = bufs[i];
       for (int i = 0; i < kRes; ++i) s->R_[i] = res[i];
       for (int k = 0; k < ngs; ++k) { s->Gs_[k] = g[k]; s->Gps_[k] = gp[k]; }
-      s->nsets_ = ngs;
       s->G_ = g[0]; s->Gp_ = gp[0]; s->Pp_ = pp; s->At_ = at; s->glists_ = glists;
       s->scal_ = scal; s->part_ = part; s->ticket_ = ticket; s->flag_ = flag; s->fh_dev_ = fh;
       s->pcnt_ = pcnt;
@@ -360,101 +208,19 @@ class Session : public SessionBase {
       for (int k = 0; k < 3; ++k) s->SXO_[k] = sxo[k];
       s->sp100_ = sp100;
       s->gemv_slabs_ = gs;
-      s->gemv_blocks_ = gb;
     }
     return c.off + 256;
   }
 
-  // SGD / GD with l = 1: the descent pass reads A once (kernels_gemv.hip); GLX_GEMV_FUSED=0
-  // selects the two-pass path (A @ [x | thr(x)], then A^T r)
-  static int gemv_blocks_for(const glx_problem& P) {
-    if (P.method != GLX_SGD && P.method != GLX_GD) return 0;
-    const char* e = std::getenv("GLX_GEMV_FUSED");
-    if (e && std::strcmp(e, "0") == 0) return 0;
-    return gemv_fused_blocks((int)sizeof(T), P.m, P.n, P.l);
-  }
-
-  // Round 5: ProxGD on one GPU whose plan cannot fuse the trial into A^T r (l not in {16, 32},
-  // n % 64 != 0, ...; C1's (512, 1024, 2)) runs the communicator path's form instead: A^T r, then
-  // k_prox_pgd from its slabs, queued speculatively the same way (the packet riding k_prox_pgd),
-  // so device control (dc_queue_comm) applies to these shapes too. GLX_UNFUSED_SPEC=0: off (the
-  // gradient and the trial as separate host-driven steps, rounds 1-4).
-  static bool unfused_spec_ok(const glx_problem& P, const glx_opts& O, const GemmPlan& plan) {
-    const char* e = std::getenv("GLX_UNFUSED_SPEC");
-    const char* fz = std::getenv("GLX_FUSED_TRIAL");
-    return P.comm == nullptr && P.method == GLX_PROXGD && !atr_prox_ok(plan) &&
-           (O.step_type == GLX_STEP_LINE_SEARCH || O.step_type == GLX_STEP_FIXED) &&
-           !(e && std::strcmp(e, "0") == 0) && !(fz && std::strcmp(fz, "0") == 0);
-  }
-  // device control on that form: as with a communicator (fp64: the finalize's sums go to the
-  // gradient set's tail, read as doubles), line search, fast objective mode
-  static bool dc_unfused_ok(const glx_problem& P, const glx_opts& O, const GemmPlan& plan) {
-    return unfused_spec_ok(P, O, plan) && P.dtype == GLX_F64 && O.step_type == GLX_STEP_LINE_SEARCH &&
-           O.ls_maxit > 0 && O.exact_objective == 0;
-  }
-  // device control with a communicator: ProxGD, fp64 (the trial sums ride the gradient
-  // all-reduce), line search, fast objective mode
-  static bool dc_comm_ok(const glx_problem& P, const glx_opts& O) {
-    return P.comm != nullptr && (P.method == GLX_PROXGD || P.method == GLX_FPROXGD) && P.dtype == GLX_F64 &&
-           O.step_type == GLX_STEP_LINE_SEARCH && O.ls_maxit > 0 && O.exact_objective == 0;
-  }
-  static bool env_is(const char* name, const char* v) {
-    const char* e = std::getenv(name);
-    return e && std::strcmp(e, v) == 0;
-  }
-  // the device-control window that takes effect for this plan: the requested one
-  // (dc_window_opt) where the fused speculative path, the spinning readback and, with a
-  // communicator, the attached packet are all on; else 0 (the host decides)
-  static int dc_window_eff(const glx_problem& P, const glx_opts& O, const GemmPlan& plan) {
-    if (fista_shard_ranks(P, O) > 0) return 0;   // row-sharded FProxGD: host control
-    const bool ls = O.step_type == GLX_STEP_LINE_SEARCH && O.ls_maxit > 0;
-    const bool spin = !env_is("GLX_READBACK", "sync");
-    const bool attach = spin && !env_is("GLX_ATTACH_PUB", "0");
-    const bool fuse_any = (P.comm != nullptr || atr_prox_ok(plan)) &&
-                          (O.step_type == GLX_STEP_LINE_SEARCH || O.step_type == GLX_STEP_FIXED) &&
-                          !env_is("GLX_FUSED_TRIAL", "0");
-    const bool method = P.method == GLX_PROXGD || P.method == GLX_FPROXGD;
-    const bool unf = dc_unfused_ok(P, O, plan) && attach;
-    if (!((fuse_any || unf) && method && spin && O.exact_objective == 0 && ls &&
-          (P.comm == nullptr || (dc_comm_ok(P, O) && attach))))
-      return 0;
-    return dc_window_opt(P, O, unf && P.comm == nullptr);
-  }
-  // a ring of window + 2 gradient sets only where device control with a communicator actually
-  // runs (it was sized on the request, not on the window that takes effect)
-  static int gsets_for(const glx_problem& P, const glx_opts& O, const GemmPlan& plan) {
-    const int w = dc_window_eff(P, O, plan);
-    return (w > 0 && (dc_comm_ok(P, O) || dc_unfused_ok(P, O, plan))) ? w + 2 : 2;
-  }
-
-  static int64_t fh_capacity(const glx_problem& P, const glx_opts& O) {
-    int64_t cap = 3 * (int64_t)O.maxit;
-    if (O.max_total_iters > 0) cap = std::min<int64_t>(cap, O.max_total_iters);
-    return cap;
-  }
-
+  // the mode is resolved once (session_mode.cpp); what follows is resource setup
   Session(const glx_problem& P, const glx_opts& O, void* ws, size_t ws_bytes, hipStream_t st)
-      : P_(P), O_(O), st_(st) {
+      : P_(P), O_(O), st_(st), md_(session_mode(P, O)), comm_(static_cast<glx_comm*>(P.comm)) {
     m_ = P.m; n_ = P.n; l_ = P.l;
     nl_ = n_ * l_; ml_ = m_ * l_;
-    plan_ = session_plan(P, O);
-    {   // Infinity-Cache hand-off between the two non-temporal passes: the last ~192 MiB each
-        // pass reads stay in the 256 MiB Infinity Cache for the other pass. NS, same box, two
-        // interleaved rounds: 2307 / 2318 it/s against 2252 / 2272 with both off, either alone
-        // in between (profiles/r3_keep/). GLX_AX_KEEP_MIB / GLX_ATR_KEEP_MIB = 0: off. Kernel
-        // arguments through the plan, so every session and device has its own value.
-      const char* ka = std::getenv("GLX_AX_KEEP_MIB");
-      const char* kr = std::getenv("GLX_ATR_KEEP_MIB");
-      plan_.ax_keep_mib = std::max(0, ka ? std::atoi(ka) : kKeepMiB);
-      plan_.atr_keep_mib = std::max(0, kr ? std::atoi(kr) : kKeepMiB);
-    }
-    comm_ = static_cast<glx_comm*>(P.comm);
-    fh_cap_ = fh_capacity(P, O);
-    smode_ = split_mode(P, O);
-    const size_t need = carve(P, O, plan_, fh_cap_, smode_, nullptr, nullptr);
+    const size_t need = carve(md_, nullptr, nullptr);
     if (!ws || ws_bytes < need) throw Error{GLX_E_WORKSPACE, "workspace too small: need " + std::to_string(need) + " bytes"};
     if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_WORKSPACE, "workspace must be 256-byte aligned"};
-    carve(P, O, plan_, fh_cap_, smode_, ws, this);
+    carve(md_, ws, this);
     A_ = static_cast<const T*>(P.A);
     B_ = static_cast<const T*>(P.b);
     // scalar packet: host-mapped, coherent memory the GPU writes directly (k_publish)
@@ -464,160 +230,15 @@ class Session : public SessionBase {
     *hseq_ = 0;
     GLX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&hs_dev_), hs_, 0));
     hseq_dev_ = reinterpret_cast<unsigned*>(hs_dev_ + NSCAL + 2);
-    const char* rb = std::getenv("GLX_READBACK");
-    spin_readback_ = !(rb && std::strcmp(rb, "sync") == 0);
-    // the scalar packet rides the speculative kernel queued right behind it (one extra
-    // workgroup, publisher_first) instead of a k_publish launch in front of it
-    const char* ap = std::getenv("GLX_ATTACH_PUB");
-    attach_ok_ = spin_readback_ && !(ap && std::strcmp(ap, "0") == 0);
-    const char* sp = std::getenv("GLX_SPEC_GRAD");
-    spec_off_env_ = (sp && std::strcmp(sp, "0") == 0);
-    const char* sa = std::getenv("GLX_SPEC_AX_PUB");
-    spec_ax_pub_ = !(sa && std::strcmp(sa, "0") == 0);
-    const char* fz = std::getenv("GLX_FUSED_TRIAL");
-    // With a communicator the trial cannot live in the A^T r epilogue (the gradient is summed
-    // over ranks first): it runs as A^T r, all-reduce, then k_prox_pgd / k_fista_trial, and is
-    // queued speculatively the same way (see atr_prox).
-    const bool fuse_any = (comm_ != nullptr || atr_prox_ok(plan_)) &&
-                          (O.step_type == GLX_STEP_LINE_SEARCH || O.step_type == GLX_STEP_FIXED) &&
-                          !(fz && std::strcmp(fz, "0") == 0);
-    unfused_spec_ = unfused_spec_ok(P, O, plan_);
-    fused_ok_ = (fuse_any || unfused_spec_) && P.method == GLX_PROXGD;
-    // ProxGD's fast objective mode evaluates the candidate as A p = A p_thr + A e, e = p - p_thr
-    // nonzero only where the hard threshold zeroed p (see iter_proxgd, split_mode)
-    emode_ = smode_ != 0 && P.method == GLX_PROXGD;
-    fsplit_ = smode_ == 1 && P.method == GLX_FPROXGD;
-    // A e form (round 5, scripts/ec_distribution.py over whole NS solves, profiles/r5_c/): ProxGD's
-    // e has ~1.1 nonzeros per flagged row (27 % of the rows), so the VALU bitmap gather does 1/30
-    // of the row form's MFMA work (whole solve 2206 against 2128 it/s for the row form, 2185 for
-    // the round-4 lists); FProxGD's e_c reaches 96 % of the rows with ~7.5 nonzeros each late in
-    // a solve, where the row form reads every flagged At row once (whole solves 2131-2143 against
-    // 2114-2121 bitmap, 2122-2124 lists).
-    gform_ = gather_form();
-    if (gform_ < 0) gform_ = P.method == GLX_FPROXGD ? 1 : 0;
-    if (gform_ == 1 && !gather_rows_ok(m_, n_)) gform_ = 0;
-    rows_form_ = gform_ == 1;
-    gsplit_ = rows_form_ ? gather_split(m_, n_) : 1;
-    egat_ = egat_mode(P, plan_, smode_);
-    if (egat_) gsplit_ = ax_split(plan_, 1);   // the A e slabs: one per K split of the dense pass
-    {   // the VALU gather's budget counts nonzeros of e_c, the row form's flagged rows (round 5)
-      const char* nb = std::getenv("GLX_SPLIT_NNZ");
-      nnz_budget_ = (nb ? std::atof(nb) : (rows_form_ ? kRowsBudget : 0.35)) * (double)n_;
-    }
-    if (smode_ == 1 && !egat_) {
+    if (md_.smode == 1 && !md_.egat) {
       launch_transpose<T>(static_cast<const T*>(P.A), At_, m_, n_, st_);   // once
     }
-    fused_fista_ok_ = fuse_any && P.method == GLX_FPROXGD;
-    // (Round 5's folded finalize — the split-candidate trial's finalize inside its dense pass,
-    // GLX_AX_FIN=1 — measured slower, 2376 against 2537-2543 it/s at NS, and was removed in round 6;
-    // DESIGN.md keeps the numbers.)
-    // device-controlled batches (dc_run / fista_dc_run): ProxGD / FProxGD with line search on
-    // the fused speculative path; GLX_DC_BATCH = iterations in flight (0: the host decides every
-    // iteration). With a communicator fp64 only (the trial sums ride the gradient all-reduce).
-    dc_window_ = dc_window_eff(P, O, plan_);
-    if (dc_window_ > 0 && !((fused_ok_ || fused_fista_ok_) && spin_readback_ && (comm_ == nullptr || attach_ok_)))
-      throw Error{GLX_E_STATE, "device-control window and the session's fused path disagree"};
-    if (dc_window_ > 0) {
+    if (md_.dc_window > 0) {
       GLX_HIP(hipHostMalloc(reinterpret_cast<void**>(&dc_ring_), sizeof(double) * kCtlRec * kCtlMaxBatch,
                             hipHostMallocMapped | hipHostMallocCoherent));
       std::memset(dc_ring_, 0, sizeof(double) * kCtlRec * kCtlMaxBatch);   // tags start at 1
       GLX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&dc_ring_dev_), dc_ring_, 0));
     }
-    // Row-sharded ProxGD (round 5, iter_proxgd_shard): with a communicator of G > 1 ranks the
-    // gradient is reduce-scattered, the trial runs on this rank's n / G rows and p's rows are
-    // all-gathered (opts.shard_rows: 0 auto = on where n % G == 0, 1 on, 2 off; GLX_SHARD_ROWS,
-    // same codes, overrides). Host control only (a device-control window keeps the all-reduce
-    // schedule). opts.shard_model = G at world size 1 (bench.py --shard-model, with --force-comm):
-    // the per-rank timing model of G ranks — the trial on n / G rows, every line-search test
-    // accepted — whose iterates are NOT a solve (glx_solve refuses it; ADVICE round 5: no
-    // environment variable turns it on inside the library).
-    if (comm_ != nullptr && P.method == GLX_FPROXGD) {
-      const int fr = fista_shard_ranks(P, O);
-      cranks_ = comm_size(comm_);
-      if (fr > 0) {
-        shard_ = true;
-        fshard_ = true;
-        shard_model_ = cranks_ == 1;
-        sranks_ = fr;
-        srank_ = shard_model_ ? 0 : comm_rank(comm_);
-        srows_ = n_ / fr;
-        srow0_ = (int64_t)srank_ * srows_;
-        nbp_ = prox_blocks(srows_, l_);   // k_fista_trial's grid is k_prox_pgd's
-        nbf_ = finalize_blocks(ml_, ax_split(plan_, 2), 0, srows_ * l_);
-        stv_ = 4;
-        schunk_ = kShardPartOff + stv_ * nbp_ + 4 * nbf_;
-      }
-    }
-    if (comm_ != nullptr && P.method == GLX_PROXGD && dc_window_ == 0) {
-      const int want = shard_rows_opt(O);
-      cranks_ = comm_size(comm_);
-      int vr = cranks_;
-      if (cranks_ == 1) {
-        vr = std::max(1, O.shard_model);
-        shard_model_ = vr > 1;
-      }
-      const bool fits = vr <= kMaxShardRanks && n_ % vr == 0;
-      if (want == 1 && vr > 1 && !fits)
-        throw Error{GLX_E_INVALID, "row-sharded ProxGD needs n % ranks == 0 and at most 64 ranks "
-                                   "(opts.shard_rows = 0 / 2: the all-reduce schedule)"};
-      if (want != 2 && vr > 1 && fits) {   // auto: the all-reduce schedule where it does not fit
-        shard_ = true;
-        sranks_ = vr;
-        srank_ = shard_model_ ? 0 : comm_rank(comm_);
-        srows_ = n_ / vr;
-        srow0_ = (int64_t)srank_ * srows_;
-        nbp_ = prox_blocks(srows_, l_);
-        // the trial finalize's workgroups (its sources: 2 in the split / dense modes, 3 exact)
-        const int fsrc = O.exact_objective != 0 ? 3 : 2;
-        nbf_ = finalize_blocks(ml_, emode_ && smode_ == 1 ? ax_split(plan_, 1) : ax_split(plan_, fsrc),
-                               emode_ && smode_ == 1 ? gsplit_ : 0, srows_ * l_);
-        schunk_ = kShardPartOff + stv_ * nbp_ + 4 * nbf_;
-        // A e from the bitmap / list gathers reads e only where its masks are set, where e = p:
-        // the gathered p serves as e and z is not re-derived (the row form reads whole rows)
-        zskip_ = emode_ && gform_ != 1;
-        // Round 6: that derive (k_trial_split) fused into the next trial's dense pass where the
-        // plan's one-source tile takes it (k_ax_lds DRV: the 8-wave shard tile, f64, l = 32) and
-        // the packet rides the pass (iter_proxgd_shard's speculative step). GLX_SHARD_DERIVE=0: off.
-        // With it the A e gather (AxDerive: extra workgroups of that pass): k_prox_pgd writes the
-        // masks and bitmaps of its rows into the rank's sums chunk (behind the partials, moff_),
-        // all-gathered with them, so the gather needs nothing the pass writes.
-        sderive_ = zskip_ && smode_ == 1 && !egat_ && gform_ == 0 && ax_derive_ok(plan_, (int)sizeof(T)) &&
-                   n_ % 64 == 0 && srows_ % 64 == 0 && n_ <= 65536 && !env_is("GLX_SHARD_DERIVE", "0");
-        moff_ = schunk_;
-        if (sderive_) schunk_ += srows_ / 2 + l_ * srows_ / 64;
-      } else {
-        shard_model_ = false;
-      }
-    }
-    // Round 5, deferred reductions (single GPU, host control, ProxGD): the fused trial (k_atr_prox)
-    // and the residual finalize leave their sums as workgroup partials (Red::parts_only) instead
-    // of running the grid reduction's serial tail (two arrival counters, the last workgroup's
-    // loads: ~3 us at the end of each kernel); the workgroup that publishes the next packet
-    // reduces them first (Pub::dpart, defer_reduce), and the finalize takes max |p| from the
-    // trial's partials itself. GLX_DEFER_RED=0: off.
-    // Only where the packet that follows is carried by the next speculative kernel (carry_): a
-    // standalone k_publish_pub that reduces them and then writes the packet measured 17-19 us
-    // against 4 us for k_publish (profiles/r5_probe/), so the non-speculative paths keep the
-    // in-kernel reduction.
-    // ProxGD only: FProxGD's k_atr_fista measured no gain (NS FProxGD 2583 / 2582, C3 4527 / 4535
-    // it/s over 200 steps, profiles/r5_defer3/) and lost 8 % on the rejection-heavy probe
-    // (its publisher's reduction stretched the 33 us fused kernel by ~4 us); that opt-in form
-    // (GLX_DEFER_RED=2) was removed in round 6.
-    const bool dmeth = P.method == GLX_PROXGD;
-    // Round 6: ProxGD's split-candidate A e chosen per trial on one GPU under host control: the
-    // bitmap gather while few rows are flagged (its cost grows with them: 12 us at ~570 rows,
-    // ~50 us averaged over a solve), A e fused into the dense pass (launch_ax_egat, a near-constant
-    // extra) once the last accepted trial flagged at least hyb_rows_ rows. NS whole solves 2 538-
-    // 2 541 it/s at 1 500-2 500 rows against 2 463-2 465 with the gather throughout, the 20-step
-    // window unchanged (profiles/r6_hyb/). GLX_AE_HYB_ROWS: the threshold, 0 = off (the gather
-    // throughout); GLX_AE_FUSED=1 keeps the fused form throughout.
-    if (smode_ == 1 && !egat_ && gform_ == 0 && comm_ == nullptr && dc_window_ == 0 &&
-        P.method == GLX_PROXGD && P.dtype == GLX_F64 && ax_egat_ok(plan_, 8)) {
-      const char* e = std::getenv("GLX_AE_HYB_ROWS");
-      hyb_rows_ = e ? std::atof(e) : kHybRows;
-    }
-    defer_ = comm_ == nullptr && dc_window_ == 0 && dmeth && spin_readback_ && attach_ok_ &&
-             !env_is("GLX_DEFER_RED", "0");
     GLX_HIP(hipMemsetAsync(ticket_, 0, kTicketBytes, st_));
     GLX_HIP(hipMemsetAsync(pcnt_, 0, sizeof(unsigned) * (P.n / 64 + 64), st_));
     GLX_HIP(hipMemsetAsync(flag_, 0, 256, st_));
@@ -754,31 +375,7 @@ class Session : public SessionBase {
     return (int64_t)split_hist_.size();
   }
 
-  // the kernels this session actually launches (bench.py re-derived the plan)
-  std::string describe() const override {
-    std::string s = describe_plan(plan_);
-    if (comm_ == nullptr && fused_ok_) s += unfused_spec_ ? " +trial (k_prox_pgd behind A^T r)" : " +trial (k_atr_prox)";
-    if (comm_ == nullptr && fused_fista_ok_) s += " +trial (k_atr_fista)";
-    s += "; split=";
-    if (smode_ == 0) s += "dense";
-    else if (egat_) s += "A e fused into the dense pass (k_ax_dma EG), S0=" + std::to_string(gsplit_);
-    else if (hyb_rows_ > 0.0)
-      s += "gather k_at_gather_bm, A e fused into the dense pass (k_ax_dma EG) from " +
-           std::to_string((int64_t)hyb_rows_) + " flagged rows";
-    else if (rows_form_) s += "rows k_at_rows S0=" + std::to_string(gsplit_);
-    else if (gform_ == 2) s += "gather k_e_lists+k_at_gather";
-    else s += "gather k_at_gather_bm";
-    if (shard_ && fshard_)
-      s += "; rows=sharded x" + std::to_string(sranks_) + (shard_model_ ? " (timing model)" : "") +
-           " (reduce-scatter of A^T r, k_fista_trial on n/" + std::to_string(sranks_) +
-           " rows, all-gather of xc, k_fista_split)";
-    else if (shard_)
-      s += "; rows=sharded x" + std::to_string(sranks_) + (shard_model_ ? " (timing model)" : "") +
-           " (reduce-scatter of A^T r, k_prox_pgd on n/" + std::to_string(sranks_) +
-           " rows, all-gather of p, " + (sderive_ ? "derive and A e in the dense pass" : "k_trial_split") + ")";
-    s += "; dc_window=" + std::to_string(dc_window_);
-    return s;
-  }
+  std::string describe() const override { return describe_mode(md_); }
 
   void progress(int64_t out[4]) const override {
     out[0] = prog_k_.load(std::memory_order_relaxed);
@@ -916,18 +513,18 @@ class Session : public SessionBase {
                  const double* cmax = nullptr, double* fh = nullptr, double fh_mu = 0.0,
                  unsigned* pub_seq = nullptr, double* defer = nullptr, bool skip_ax = false,
                  bool snap_trial = false, bool chain = false) {
-    const bool gat = chain && smode_ == 1;
+    const bool gat = chain && md_.smode == 1;
     if (!skip_ax) {
       if (gat) cand_ax(xs);
       else spec_ax(nsrc, xs);
     }
     T* rsc[3] = {chain ? nullptr : rs[0], rs[1], rs[2]};
     Red rd = defer ? red_to(defer) : red(slot);
-    const bool dfin = defer_ && carry_ && pub_seq == nullptr && defer == nullptr && !snap_trial &&
+    const bool dfin = md_.defer && carry_ && pub_seq == nullptr && defer == nullptr && !snap_trial &&
                       (comm_ ? nullptr : fh) == nullptr && dc_ctl_.rec == nullptr;
     // max |p| of a trial whose sums are still partials
     const bool dmax = cx != nullptr && ptr_.part != nullptr && cmax == ptr_.out + 3;
-    const int S = gat ? ax_split(plan_, 1) : ax_split(plan_, nsrc);
+    const int S = gat ? ax_split(md_.plan, 1) : ax_split(md_.plan, nsrc);
     if (dfin) {
       flush_fin_pending();
       rd.part = fpart_;
@@ -960,7 +557,7 @@ class Session : public SessionBase {
   // window - 1 dense passes per cancellation).
   void spec_ax(int nsrc, const T* const* xs, Pub pb = Pub{}) {
     hipEvent_t e0 = prof_begin(0);
-    launch_ax<T>(plan_, nsrc, A_, xs, Pp_, dc_gate_, 0, st_, pb);
+    launch_ax<T>(md_.plan, nsrc, A_, xs, Pp_, dc_gate_, 0, st_, pb);
     check_launch();
     prof_end(0, e0);
     ++ax_calls_;
@@ -973,9 +570,9 @@ class Session : public SessionBase {
   // and the cross-stream wait left the queue idle, see kernels_gather.hip). The dense pass and the
   // gather are timed apart (kinds 0 and 2), so each event pair brackets one kernel of the trace.
   // pb: the dense launch carries that scalar packet.
-  // Round 5 (rows_form_): A e is the A^T R panel over the flagged rows of At (k_at_rows: gsplit_
+  // Round 5 (md_.rows_form): A e is the A^T R panel over the flagged rows of At (k_at_rows: md_.gsplit
   // slabs, each workgroup compacts its K range's row flags itself), so no column lists.
-  // dv (row-sharded ProxGD, sderive_): the dense pass reads p (xs[2]) and derives p_thr into xs[1]
+  // dv (row-sharded ProxGD, md_.sh.derive): the dense pass reads p (xs[2]) and derives p_thr into xs[1]
   // itself, with the masks and bitmaps the gather reads (k_ax_lds DRV)
   void cand_ax(const T* const* xs, Pub pb = Pub{}, const AxDerive* dv = nullptr) {
     const T* xd[3] = {xs[1], nullptr, nullptr};
@@ -988,7 +585,7 @@ class Session : public SessionBase {
       eg.bstride = npad / 16;
       eg.Pe = Pp_;
       hipEvent_t e0 = prof_begin(0);
-      if (!launch_ax_egat<T>(plan_, A_, xs[2], Pp_ + (size_t)gs_of(true) * ml_, dc_gate_, 0, st_, pb, eg))
+      if (!launch_ax_egat<T>(md_.plan, A_, xs[2], Pp_ + (size_t)gs_of(true) * ml_, dc_gate_, 0, st_, pb, eg))
         throw Error{GLX_E_STATE, "fused A e: the plan does not take it"};
       check_launch();
       prof_end(0, e0);
@@ -996,17 +593,17 @@ class Session : public SessionBase {
       ax_cols_ += 1;
       return;
     }
-    if (gform_ == 2) {
+    if (md_.gform == 2) {
       launch_e_lists(zf_, n_, l_, glists_, st_, dc_gate_);
       check_launch();
     }
     hipEvent_t e0 = prof_begin(0);
     if (dv != nullptr) {
       if (pb.s2 != nullptr || pb.dpart[0] != nullptr || pb.dpart[1] != nullptr || dc_gate_ != nullptr ||
-          !launch_ax_derive<T>(plan_, A_, xs[2], Pp_ + (size_t)gsplit_ * ml_, st_, pb, *dv))
+          !launch_ax_derive<T>(md_.plan, A_, xs[2], Pp_ + (size_t)md_.gsplit * ml_, st_, pb, *dv))
         throw Error{GLX_E_STATE, "row-sharded derive: the dense pass does not take it"};
     } else {
-      launch_ax<T>(plan_, 1, A_, xd, Pp_ + (size_t)gsplit_ * ml_, dc_gate_, 0, st_, pb);
+      launch_ax<T>(md_.plan, 1, A_, xd, Pp_ + (size_t)md_.gsplit * ml_, dc_gate_, 0, st_, pb);
     }
     check_launch();
     prof_end(0, e0);
@@ -1016,8 +613,8 @@ class Session : public SessionBase {
       return;
     }
     hipEvent_t e2 = prof_begin(2);
-    if (gform_ == 1) launch_at_rows<T>(At_, xs[0], zf_, m_, n_, l_, Pp_, glists_, st_, dc_gate_);
-    else if (gform_ == 2) launch_at_gather<T>(At_, xs[0], m_, n_, l_, Pp_, glists_, st_, dc_gate_);
+    if (md_.gform == 1) launch_at_rows<T>(At_, xs[0], zf_, m_, n_, l_, Pp_, glists_, st_, dc_gate_);
+    else if (md_.gform == 2) launch_at_gather<T>(At_, xs[0], m_, n_, l_, Pp_, glists_, st_, dc_gate_);
     else launch_at_gather_bm<T>(At_, xs[0], zf_, m_, n_, l_, Pp_, glists_, st_, dc_gate_);
     check_launch();
     prof_end(2, e2);
@@ -1040,20 +637,20 @@ class Session : public SessionBase {
     T* G = Gs_[set];
     T* Gp = Gps_[set];
     hipEvent_t e0 = prof_begin(1);
-    launch_atr<T>(plan_, A_, r, Gp, st_);
+    launch_atr<T>(md_.plan, A_, r, Gp, st_);
     check_launch();
     prof_end(1, e0);
     ++atr_calls_;
-    if (!comm_) return {Gp, plan_.atr_S};
-    if (plan_.atr_S > 1) {
-      launch_sum_partials<T>(Gp, plan_.atr_S, G, nl_, st_);
+    if (!comm_) return {Gp, md_.plan.atr_S};
+    if (md_.plan.atr_S > 1) {
+      launch_sum_partials<T>(Gp, md_.plan.atr_S, G, nl_, st_);
       check_launch();
     }
     comm_allreduce(comm_, G, nl_ + tail_n, P_.dtype, st_);
     return {G, 1};
   }
   void use_gset(int set) { gset_ = set; G_ = Gs_[set]; Gp_ = Gps_[set]; }
-  int nset(int set) const { return set + 1 == nsets_ ? 0 : set + 1; }   // the next set of the ring
+  int nset(int set) const { return set + 1 == md_.nsets ? 0 : set + 1; }   // the next set of the ring
   double* tail(int set) { return reinterpret_cast<double*>(Gs_[set] + nl_); }
   // merge a speculated trial's residual sums into the next gradient all-reduce
   bool merge_tail() const { return comm_ != nullptr && sizeof(T) == 8; }
@@ -1073,7 +670,7 @@ class Session : public SessionBase {
     return gradient(r);
   }
   bool want_spec(int trial_it) const {
-    return spec_on_ && trial_it == 0 && O_.step_type == GLX_STEP_LINE_SEARCH && !spec_off_env_;
+    return spec_on_ && trial_it == 0 && O_.step_type == GLX_STEP_LINE_SEARCH && !md_.spec_off;
   }
 
   // Scalar readback in two halves so that work can be queued between them (the speculative
@@ -1090,16 +687,16 @@ class Session : public SessionBase {
       pb.off2 = S_RT;
       pb.n2 = extra ? 4 : 0;
       attach_pending(pb);
-      if (spin_readback_) {
+      if (md_.spin_readback) {
         pb.host = hs_dev_;
         pb.host_seq = hseq_dev_;
         pb.seq = ++seq_;
       }
       launch_publish_pub(pb, st_);
       check_launch();
-      if (spin_readback_) return pb.seq;
+      if (md_.spin_readback) return pb.seq;
     }
-    if (!spin_readback_) {   // GLX_READBACK=sync: stream-ordered copies, then an event wait
+    if (!md_.spin_readback) {   // GLX_READBACK=sync: stream-ordered copies, then an event wait
       GLX_HIP(hipMemcpyAsync(hs_, scal_, sizeof(double) * NSCAL, hipMemcpyDeviceToHost, st_));
       if (extra) GLX_HIP(hipMemcpyAsync(hs_ + S_RT, extra, 4 * sizeof(double), hipMemcpyDeviceToHost, st_));
       if (!rb_event_) GLX_HIP(hipEventCreateWithFlags(&rb_event_, hipEventDisableTiming));
@@ -1111,7 +708,7 @@ class Session : public SessionBase {
     check_launch();
     return seq;
   }
-  // The packet as a Pub for the next launch to carry (attach_ok_); *seq_out = its number.
+  // The packet as a Pub for the next launch to carry (md_.attach_ok); *seq_out = its number.
   Pub make_pub(const double* extra, unsigned* seq_out) {
     ++syncs_;
     Pub pb;
@@ -1127,7 +724,7 @@ class Session : public SessionBase {
     *seq_out = pb.seq;
     return pb;
   }
-  // deferred reductions (defer_): partials not yet reduced into their scalar slots
+  // deferred reductions (md_.defer): partials not yet reduced into their scalar slots
   struct Pend {
     const double* part = nullptr;
     int np = 0, nv = 0;
@@ -1164,7 +761,7 @@ class Session : public SessionBase {
     }
   }
   void wait_readback(unsigned seq) {
-    if (!spin_readback_) {
+    if (!md_.spin_readback) {
       GLX_HIP(hipEventSynchronize(rb_event_));
       return;
     }
@@ -1306,7 +903,7 @@ class Session : public SessionBase {
   // this trial ready (same mu and t); (2) otherwise A^T r with the trial fused into it
   // (launch_atr_prox); (3) otherwise the gradient (speculative or not) and k_prox_pgd.
   void iter_proxgd() {
-    if (shard_) { iter_proxgd_shard(); return; }
+    if (md_.sh.on) { iter_proxgd_shard(); return; }
     if (!state_valid_) proxgd_prologue(thr_from_trial_);
     record(f_cur_, s_cur_);
     if (stop_rule()) { end_phase(true); return; }
@@ -1321,7 +918,7 @@ class Session : public SessionBase {
       g = {G_, 1};
       first_done = (spec_trial_mu_ == mu_ && spec_trial_t_ == t0);   // else: a phase change
       if (!first_done) ax_queued_ = false;
-    } else if (fused_ok_) {
+    } else if (md_.fused_ok) {
       carry_ = want_spec(0);   // the batch's packet will ride the speculative kernel
       atr_prox(R_[irg_], gset_, X_[ixt_], ip_, ipt_, iz_, t0);
       carry_ = false;
@@ -1355,7 +952,7 @@ class Session : public SessionBase {
       for (int it = it0; it < O_.ls_maxit; ++it) {
         if (!(it == 0 && first_done)) trial(t, it == 0);
         // one pass: the candidate's g for the test (:91) + the next iteration's residual
-        // A p_thr (exact mode: g(z) and A p as a third source). Split-candidate mode (emode_,
+        // A p_thr (exact mode: g(z) and A p as a third source). Split-candidate mode (md_.emode,
         // the default fast mode): the batch is [e | p_thr], e = p - p_thr, and the test and the
         // next objective use g(p) = 1/2 ||(A p_thr - b) + A e||^2. z = x - t G_t equals p up to
         // the rounding of x - t((x - p)/t), the same order as the GEMMs' own summation-order
@@ -1366,22 +963,22 @@ class Session : public SessionBase {
         const int nsrc = exact ? 3 : 2;
         unsigned seq = 0;
         const bool spec = want_spec(it);
-        const bool merge = spec && fused_ok_ && merge_tail();
+        const bool merge = spec && md_.fused_ok && merge_tail();
         // the packet rides the speculative kernel (no communicator; with one only when merged)
-        const bool late_pub = merge || (spec && fused_ok_ && attach_ok_ && comm_ == nullptr);
+        const bool late_pub = merge || (spec && md_.fused_ok && md_.attach_ok && comm_ == nullptr);
         const bool skip_ax = it == 0 && first_done && ax_queued_;   // queued with the trial
         ax_queued_ = false;
         // with a communicator the speculative next trial is a short k_prox_pgd: its A@X is
         // queued right behind it and carries this trial's packet, whose trial sums (which
         // that k_prox_pgd overwrites) come from a snapshot this finalize takes
-        const bool axp = spec && fused_ok_ && comm_ != nullptr && late_pub && attach_ok_ &&
-                         spec_ax_pub_ && ax_pub_ok(plan_, smode_ == 1 ? 1 : nsrc);
+        const bool axp = spec && md_.fused_ok && comm_ != nullptr && late_pub && md_.attach_ok &&
+                         md_.spec_ax_pub && ax_pub_ok(md_.plan, md_.smode == 1 ? 1 : nsrc);
         carry_ = late_pub;
         residuals(nsrc, xs, rs, S_RT, X_[ip_], scal_ + S_TR + 3, nullptr, 0.0,
-                  late_pub ? nullptr : &seq, merge ? tail(nset(gset_)) : nullptr, skip_ax, axp, emode_);
+                  late_pub ? nullptr : &seq, merge ? tail(nset(gset_)) : nullptr, skip_ax, axp, md_.emode);
         carry_ = false;
         std::pair<const T*, int> sg;
-        if (spec && fused_ok_) {
+        if (spec && md_.fused_ok) {
           // the next iteration's A^T r and first trial at the candidate p_thr, into the other
           // gradient set and the spare buffers (z is free once this trial's A@X has read it)
           Pub pbx;
@@ -1393,7 +990,7 @@ class Session : public SessionBase {
             pbx.off3 = S_TR;
             pbx.n3 = 6;
             const T* sx[3] = {X_[iz_], X_[if2_], X_[if1_]};   // [z | p_thr | p] of that trial
-            if (smode_ == 1) cand_ax(sx, pbx);
+            if (md_.smode == 1) cand_ax(sx, pbx);
             else spec_ax(nsrc, sx, pbx);
             ax_queued_ = true;
           }
@@ -1448,7 +1045,7 @@ class Session : public SessionBase {
     // batch (GLX_SPLIT_CAND=0): A z - b (z = x - t G_t is ulp-close to p) unless the
     // threshold changed nothing, in which case A p_thr - b == A p - b exactly
     const double sq_x = exact ? hs_[S_RT + 2]
-                              : ((emode_ || hs_[trs + 4] != 0) ? hs_[S_RT] : hs_[S_RT + 1]);
+                              : ((md_.emode || hs_[trs + 4] != 0) ? hs_[S_RT] : hs_[S_RT + 1]);
     f_cur_ = 0.5 * sq_x + P_.mu0 * hs_[trs + 2];
     s_cur_ = hs_[S_RT + 3] / (double)nl_;
     state_valid_ = true;
@@ -1477,42 +1074,42 @@ class Session : public SessionBase {
   // of iter_proxgd). The all-gathered blocks replace the 8-byte all-reduces of the residual sums.
   // Bytes per iteration and rank: reduce-scatter + all-gather of n x l, the same as one ring
   // all-reduce of the gradient; the row-wise work (k_prox_pgd, the count) is divided by G.
-  double* blk_own() { return blk_ + (int64_t)(shard_model_ ? 0 : srank_) * schunk_; }
+  double* blk_own() { return blk_ + (int64_t)(md_.sh.model ? 0 : md_.sh.rank) * md_.sh.chunk; }
   // the speculated next trial's sums: ProxGD S_TRN; FProxGD S_RO (S_TRN = S_RG holds g(y) of a
   // prologue until the host has read it; S_RO is read right behind its own objective)
-  int tr_other() const { return tr_slot_ == S_TR ? (fshard_ ? S_RO : S_TRN) : S_TR; }
+  int tr_other() const { return tr_slot_ == S_TR ? (md_.sh.fista ? S_RO : S_TRN) : S_TR; }
   void shard_gradient(const T* r, int set) {
     T* G = Gs_[set];
     T* Gp = Gps_[set];
     hipEvent_t e0 = prof_begin(1);
-    launch_atr<T>(plan_, A_, r, Gp, st_);
+    launch_atr<T>(md_.plan, A_, r, Gp, st_);
     check_launch();
     prof_end(1, e0);
     ++atr_calls_;
-    if (plan_.atr_S > 1) {
-      launch_sum_partials<T>(Gp, plan_.atr_S, G, nl_, st_);
+    if (md_.plan.atr_S > 1) {
+      launch_sum_partials<T>(Gp, md_.plan.atr_S, G, nl_, st_);
       check_launch();
     }
-    comm_reduce_scatter(comm_, G, srows_ * l_, P_.dtype, st_);
+    comm_reduce_scatter(comm_, G, md_.sh.rows * l_, P_.dtype, st_);
   }
   // the trial on this rank's rows: p, p_thr, z rows into X_[op], X_[opt], X_[oz]; its workgroup
   // partials into this rank's chunk (Red::parts_only)
   void shard_prox(const T* xt, const T* G, int op, int opt, int oz, double t) {
-    const int64_t o = srow0_ * l_;
+    const int64_t o = md_.sh.row0 * l_;
     Red rd = red_to(scal_ + S_TR);
     rd.part = blk_own() + kShardPartOff;
     rd.parts_only = 1;
-    // sderive_: the masks and bitmaps of e for these rows into the chunk (the third output is then e)
-    unsigned* czf = sderive_ ? reinterpret_cast<unsigned*>(blk_own() + moff_) : nullptr;
-    launch_prox_pgd<T>(xt + o, G + o, 1, nullptr, X_[op] + o, X_[opt] + o, X_[oz] + o, srows_, l_, t,
+    // md_.sh.derive: the masks and bitmaps of e for these rows into the chunk (the third output is then e)
+    unsigned* czf = md_.sh.derive ? reinterpret_cast<unsigned*>(blk_own() + md_.sh.moff) : nullptr;
+    launch_prox_pgd<T>(xt + o, G + o, 1, nullptr, X_[op] + o, X_[opt] + o, X_[oz] + o, md_.sh.rows, l_, t,
                        mu_, O_.thres, rd, st_, Pub{}, czf);
     check_launch();
   }
   // one RCCL group: p's rows (op >= 0) and every rank's chunk of sums
   void shard_exchange(int op) {
     comm_group_begin(comm_);
-    if (op >= 0) comm_all_gather(comm_, X_[op], srows_ * l_, P_.dtype, st_);
-    comm_all_gather(comm_, blk_, schunk_, GLX_F64, st_);
+    if (op >= 0) comm_all_gather(comm_, X_[op], md_.sh.rows * l_, P_.dtype, st_);
+    comm_all_gather(comm_, blk_, md_.sh.chunk, GLX_F64, st_);
     comm_group_end(comm_);
   }
   // mask & 1: the trial's sums -> scal_[tr_dst], mask & 2: the finalize's -> scal_[S_RT];
@@ -1520,12 +1117,12 @@ class Session : public SessionBase {
   ShardPub shard_pub(int mask, int tr_dst, unsigned* seq) {
     ShardPub sp;
     sp.blk = blk_;
-    sp.nranks = cranks_;
-    sp.chunk = schunk_;
-    sp.nbp = nbp_;
-    sp.nbf = nbf_;
+    sp.nranks = md_.sh.cranks;
+    sp.chunk = md_.sh.chunk;
+    sp.nbp = md_.sh.nbp;
+    sp.nbf = md_.sh.nbf;
     sp.mask = mask;
-    sp.tv = stv_;
+    sp.tv = md_.sh.stv;
     sp.tr = scal_ + tr_dst;
     sp.rt = scal_ + S_RT;
     sp.tr_off = tr_dst;
@@ -1533,28 +1130,28 @@ class Session : public SessionBase {
     if (seq != nullptr) sp.pub = make_pub(nullptr, seq);
     return sp;
   }
-  // p_thr, z (unless zskip_) and e's masks from the gathered p, the sums combined beside the rows
+  // p_thr, z (unless md_.sh.zskip) and e's masks from the gathered p, the sums combined beside the rows
   void shard_derive(int ixt, int op, int opt, int oz, double t, const ShardPub& sp) {
-    launch_trial_split<T>(X_[op], X_[ixt], X_[opt], zskip_ ? nullptr : X_[oz], ezf(), n_, l_, t,
-                          O_.thres, emode_, sp, st_);
+    launch_trial_split<T>(X_[op], X_[ixt], X_[opt], md_.sh.zskip ? nullptr : X_[oz], ezf(), n_, l_, t,
+                          O_.thres, md_.emode, sp, st_);
     check_launch();
   }
   // the trial's pass over this rank's rows of A and its finalize: sums -> the chunk's [6, 10), the
   // count over this rank's rows of cx against the combined max at cmax
   void shard_fin(int nsrc, const T* const* xs, T* const* rs, const T* cx, const double* cmax, bool skip_ax) {
-    const bool chain = emode_;
-    const bool gat = chain && smode_ == 1;
+    const bool chain = md_.emode;
+    const bool gat = chain && md_.smode == 1;
     if (!skip_ax) {
       if (gat) cand_ax(xs);
       else spec_ax(nsrc, xs);
     }
     T* rsc[3] = {chain ? nullptr : rs[0], rs[1], rs[2]};
-    const int64_t o = srow0_ * l_;
+    const int64_t o = md_.sh.row0 * l_;
     Red rd = red_to(scal_ + S_RT);   // its workgroup partials ride the all-gather too
-    rd.part = blk_own() + kShardPartOff + stv_ * nbp_;
+    rd.part = blk_own() + kShardPartOff + md_.sh.stv * md_.sh.nbp;
     rd.parts_only = 1;
-    launch_finalize_residual<T>(Pp_, gat ? ax_split(plan_, 1) : ax_split(plan_, nsrc), B_, nsrc, rsc,
-                                ml_, nullptr, 0, 1, cx + o, srows_ * l_, cmax, nullptr, 0.0,
+    launch_finalize_residual<T>(Pp_, gat ? ax_split(md_.plan, 1) : ax_split(md_.plan, nsrc), B_, nsrc, rsc,
+                                ml_, nullptr, 0, 1, cx + o, md_.sh.rows * l_, cmax, nullptr, 0.0,
                                 scal_ + S_DRN, rd, st_, nullptr, nullptr, 0,
                                 chain ? (qeg_ ? 2 : 1) : 0, gat ? gs_of(qeg_) : 0, Ctl{});
     check_launch();
@@ -1587,7 +1184,7 @@ class Session : public SessionBase {
     if (ls) {
       for (int it = 0; it < O_.ls_maxit; ++it) {
         if (!(it == 0 && first_done)) trial(t);
-        const T* xs[3] = {zskip_ ? X_[ip_] : X_[iz_], X_[ipt_], X_[ip_]};
+        const T* xs[3] = {md_.sh.zskip ? X_[ip_] : X_[iz_], X_[ipt_], X_[ip_]};
         T* rs[3] = {R_[rz], R_[rpt], R_[rp]};
         const bool skip_ax = it == 0 && first_done && ax_queued_;
         ax_queued_ = false;
@@ -1606,10 +1203,10 @@ class Session : public SessionBase {
           // dense pass as its publisher workgroup: a workgroup of the 8 MiB-writing k_trial_split
           // that stores to host memory stretched that kernel from 5.6 to 17.8 us (its end-of-
           // kernel release), a separate k_publish costs ~4.5 us (profiles/r5_shard/)
-          const bool carry = spin_readback_ && attach_ok_ && ax_pub_ok(plan_, smode_ == 1 ? 1 : nsrc);
-          const bool fused = carry && sderive_;   // round 6: the derive inside the dense pass
+          const bool carry = md_.spin_readback && md_.attach_ok && ax_pub_ok(md_.plan, md_.smode == 1 ? 1 : nsrc);
+          const bool fused = carry && md_.sh.derive;   // round 6: the derive inside the dense pass
           if (!fused) shard_derive(ipt_, if1_, if2_, iz_, O_.alpha0, shard_pub(3, ot, nullptr));
-          const T* sx[3] = {zskip_ ? X_[if1_] : X_[iz_], X_[if2_], X_[if1_]};
+          const T* sx[3] = {md_.sh.zskip ? X_[if1_] : X_[iz_], X_[if2_], X_[if1_]};
           Pub pb;
           if (carry) pb = make_pub(nullptr, &seq);
           else seq = post_readback();
@@ -1623,11 +1220,11 @@ class Session : public SessionBase {
             dv.E = sx[0];
             dv.Pe = Pp_;
             dv.blk = blk_;
-            dv.bstride = shard_model_ ? 0 : schunk_;
-            dv.moff = moff_;
-            dv.srows = srows_;
+            dv.bstride = md_.sh.model ? 0 : md_.sh.chunk;
+            dv.moff = md_.sh.moff;
+            dv.srows = md_.sh.rows;
             cand_ax(sx, pb, &dv);
-          } else if (smode_ == 1) {
+          } else if (md_.smode == 1) {
             cand_ax(sx, pb);
           } else {
             spec_ax(nsrc, sx, pb);
@@ -1644,7 +1241,7 @@ class Session : public SessionBase {
         }
         wait_readback(seq);
         const double gz = 0.5 * hs_[S_RT];
-        if (shard_model_ || gz <= gx_ - t * hs_[tr_slot_ + 0] + 0.5 * t * hs_[tr_slot_ + 1]) {
+        if (md_.sh.model || gz <= gx_ - t * hs_[tr_slot_ + 0] + 0.5 * t * hs_[tr_slot_ + 1]) {
           accepted = true;
           spec_on_ = (it == 0);
           break;
@@ -1677,7 +1274,7 @@ class Session : public SessionBase {
   // SURVEY 8f row 2. In the speculative steady state (the previous first trial was accepted and
   // its fused kernel left G and this iteration's first trial ready) every iteration launches the
   // same kernels on buffer roles that rotate the same way: A@[e | p_thr] (+ the A e gather),
-  // its finalize, and the fused A^T r + next trial. So up to dc_window_ iterations are queued
+  // its finalize, and the fused A^T r + next trial. So up to md_.dc_window iterations are queued
   // ahead of the host. The Armijo test (gl_ProxGD_primal.py:89-92), the next record and the stop
   // rule (:118-125) run in the finalize's last block (ctl_decide, kernels_elem.hip), which writes
   // a decision record to host-mapped memory and an abort word every later launch of the batch
@@ -1689,8 +1286,8 @@ class Session : public SessionBase {
   struct Roles { int ix, ixt, ip, ipt, if1, if2, iz, irg, gset; };
   bool dc_ready() const {
     // (with a communicator the first trial's A@X is normally already queued: the batch uses it)
-    return dc_window_ > 0 && spec_trial_ready_ && spec_trial_mu_ == mu_ &&
-           spec_trial_t_ == O_.alpha0 && want_spec(0) && (comm_ != nullptr || unfused_spec_ || !ax_queued_);
+    return md_.dc_window > 0 && spec_trial_ready_ && spec_trial_mu_ == mu_ &&
+           spec_trial_t_ == O_.alpha0 && want_spec(0) && (comm_ != nullptr || md_.unfused_spec || !ax_queued_);
   }
   // Gated (cancellable) launches: the finalize (it would overwrite the decision state and the
   // gradient residual of the iteration the host resumes) and the speculative fused kernel (the
@@ -1710,7 +1307,7 @@ class Session : public SessionBase {
     c.nl = (double)nl_;
     c.stable_thr = O_.stable_len_threshold;
     c.use_sp = use_sparsity_ ? 1 : 0;
-    c.emode = emode_ ? 1 : 0;
+    c.emode = md_.emode ? 1 : 0;
     c.pass = 1 + (int)(tag % 0x3FFFFFFF);
     return c;
   }
@@ -1726,13 +1323,13 @@ class Session : public SessionBase {
     const T* xs[3] = {X_[q.iz], X_[q.ipt], X_[q.ip]};
     T* rs[3] = {R_[rz], R_[rpt], R_[rp]};
     if (first && !ax_queued_) {
-      if (smode_ == 1) cand_ax(xs);
+      if (md_.smode == 1) cand_ax(xs);
       else spec_ax(2, xs);
     }
     dc_gate_ = dc_abort_;
     const int ns = nset(q.gset);
     residuals(2, xs, rs, S_RT, X_[q.ip], scal_ + S_TR + 3, nullptr, 0.0, nullptr, tail(ns), true,
-              false, emode_);
+              false, md_.emode);
     const std::pair<const T*, int> g = gradient(R_[rpt], ns, 2);   // (one GPU: A^T r's slabs)
     const int64_t slot = (tag % kCtlMaxBatch) * kCtlRec;
     launch_ctl_decide(dc_make_ctl(tag), tail(ns), dc_ring_dev_ + slot,
@@ -1742,7 +1339,7 @@ class Session : public SessionBase {
                        X_[q.if2], X_[q.iz], n_, l_, O_.alpha0, mu_, O_.thres, red(S_TR), st_, Pub{}, ezf());
     check_launch();
     const T* sx[3] = {X_[q.iz], X_[q.if2], X_[q.if1]};   // [z | p_thr | p] of that trial
-    if (smode_ == 1) cand_ax(sx);
+    if (md_.smode == 1) cand_ax(sx);
     else spec_ax(2, sx);
     dc_gate_ = nullptr;
     q.irg = rpt;
@@ -1759,7 +1356,7 @@ class Session : public SessionBase {
     dc_ctl_ = dc_make_ctl(tag);
     const int64_t slot = (tag % kCtlMaxBatch) * kCtlRec;
     residuals(2, xs, rs, S_RT, X_[q.ip], scal_ + S_TR + 3, nullptr, 0.0, nullptr, nullptr, false,
-              false, emode_);
+              false, md_.emode);
     dc_ctl_ = Ctl{};
     dc_pass_ = 1 + (int)(tag % 0x3FFFFFFF);
     dc_pub_ = Pub{};
@@ -1809,10 +1406,10 @@ class Session : public SessionBase {
     Roles q{ix_, ixt_, ip_, ipt_, if1_, if2_, iz_, irg_, spec_set_};
     const int64_t tag0 = dc_tag_;
     int64_t queued = 0;
-    const int64_t w = std::min<int64_t>(dc_window_, budget);
+    const int64_t w = std::min<int64_t>(md_.dc_window, budget);
     auto push = [&]() {   // tags are never reused: dc_tag_ = the last one queued
       dc_tag_ = tag0 + 1 + queued++;
-      if (comm_ || unfused_spec_) dc_queue_comm(q, dc_tag_, queued == 1);
+      if (comm_ || md_.unfused_spec) dc_queue_comm(q, dc_tag_, queued == 1);
       else dc_queue(q, dc_tag_);
     };
     while (queued < w) push();
@@ -1828,7 +1425,7 @@ class Session : public SessionBase {
           // k_prox_pgd and everything behind it), which proxgd_spec_rotate declared ready: keep
           // its gradient set (the all-reduce in front of the decision completed) but never its
           // trial, even where the next phase's mu equals this one's (mu0 = 0).
-          if (comm_ || unfused_spec_) {
+          if (comm_ || md_.unfused_spec) {
             spec_trial_mu_ = NAN;
             ax_queued_ = false;
           }
@@ -1865,7 +1462,7 @@ class Session : public SessionBase {
       prev = code;
     }
     // with a communicator the last segment queued the next trial's A@X
-    ax_queued_ = comm_ != nullptr || unfused_spec_;
+    ax_queued_ = comm_ != nullptr || md_.unfused_spec;
   }
 
   // A^T r fused with a ProxGD trial at x (gradient set `set`, outputs X_[op], X_[opt], X_[oz]).
@@ -1877,11 +1474,11 @@ class Session : public SessionBase {
   void atr_prox(const T* r, int set, const T* x, int op, int opt, int oz, double t, int tail_n = 0,
                 unsigned* pub_seq = nullptr, Pub* pub_out = nullptr) {
     const double* extra = tail_n ? tail(set) : nullptr;
-    if (comm_ || unfused_spec_) {
+    if (comm_ || md_.unfused_spec) {
       const std::pair<const T*, int> g = gradient(r, set, tail_n);
       Pub pb;
       if (pub_seq && pub_out) *pub_out = make_pub(extra, pub_seq);
-      else if (pub_seq && attach_ok_) pb = make_pub(extra, pub_seq);
+      else if (pub_seq && md_.attach_ok) pb = make_pub(extra, pub_seq);
       else if (pub_seq) *pub_seq = post_readback(extra);
       // (one GPU: g is A^T r's slabs; the trial stores their sum as the set's G for retrials)
       launch_prox_pgd<T>(x, g.first, g.second, g.first != Gs_[set] ? Gs_[set] : nullptr, X_[op], X_[opt],
@@ -1900,16 +1497,16 @@ class Session : public SessionBase {
     // its trial sums stay partials (the other buffer than the one pb may reduce) when the packet
     // that needs them is carried by a later speculative kernel: this one's own trial is the next
     // iteration's (pub_seq), or the caller's batch is carried (carry_)
-    const bool dtr = defer_ && (pub_seq != nullptr || carry_);
+    const bool dtr = md_.defer && (pub_seq != nullptr || carry_);
     if (dtr) {
       tb_ ^= 1;
       rd.part = tpart_[tb_];
       rd.parts_only = 1;
     }
-    launch_atr_prox<T>(plan_, A_, r, Gs_[set], x, X_[op], X_[opt], X_[oz], t, mu_, O_.thres,
+    launch_atr_prox<T>(md_.plan, A_, r, Gs_[set], x, X_[op], X_[opt], X_[oz], t, mu_, O_.thres,
                        rd, st_, pb, Gps_[set], pcnt_, ezf());
     check_launch();
-    ptr_ = dtr ? Pend{tpart_[tb_], atr_prox_slots(plan_, pb.host != nullptr), 6, 0x8u, scal_ + S_TR} : Pend{};
+    ptr_ = dtr ? Pend{tpart_[tb_], atr_prox_slots(md_.plan, pb.host != nullptr), 6, 0x8u, scal_ + S_TR} : Pend{};
     prof_end(1, e0);
     ++atr_calls_;
   }
@@ -1930,9 +1527,9 @@ class Session : public SessionBase {
     const double theta_next = 2.0 / (double)(inner_ + 2);
     const bool ls = O_.step_type == GLX_STEP_LINE_SEARCH && O_.ls_maxit > 0;
     const double t0 = ls ? tk_ : schedule(inner_);
-    if (fshard_) { iter_fista_shard(theta, theta_next); return; }
-    const bool fuse = fused_fista_ok_ && !smooth;
-    if (fsplit_ && ls && kslot_ < 0 && dense_left_ == 0) fista_split_prologue();
+    if (md_.sh.fista) { iter_fista_shard(theta, theta_next); return; }
+    const bool fuse = md_.fused_fista_ok && !smooth;
+    if (md_.fsplit && ls && kslot_ < 0 && dense_left_ == 0) fista_split_prologue();
     if (!smooth && fista_dc_ready(t0, theta)) { fista_dc_run(); return; }
     // first trial: from the previous iteration's speculative fused kernel, fused into this
     // iteration's A^T r, or (FGD / unfusable plans) the gradient and k_fista_trial
@@ -1969,7 +1566,7 @@ class Session : public SessionBase {
   void fista_trials(std::pair<const T*, int> g, bool first_done, double t0, int it0, double theta,
                     double theta_next, bool smooth) {
     const bool ls = O_.step_type == GLX_STEP_LINE_SEARCH && O_.ls_maxit > 0;
-    const bool fuse = fused_fista_ok_ && !smooth;
+    const bool fuse = md_.fused_fista_ok && !smooth;
     const T* y = X_[iy_];
     if (smooth) {                                         // G = A^T r + mu y / sqrt(|y_i|^2 + d^2)
       launch_fgd_grad<T>(y, g.first, g.second, G_, n_, l_, mu_, O_.delta, red(S_REGY), st_);
@@ -1998,8 +1595,8 @@ class Session : public SessionBase {
         unsigned seq = 0;
         const bool spec = want_spec(it);
         const bool merge = spec && fuse && merge_tail();
-        const bool late_pub = merge || (spec && fuse && attach_ok_ && comm_ == nullptr);
-        fs_batch = fsplit_ && kslot_ >= 0 && dense_left_ == 0;
+        const bool late_pub = merge || (spec && fuse && md_.attach_ok && comm_ == nullptr);
+        fs_batch = md_.fsplit && kslot_ >= 0 && dense_left_ == 0;
         carry_ = late_pub;
         if (fs_batch) {   // A xc dense, A e_c gathered, A y_next by linearity
           fista_split_batch(R_[ryn], theta, theta_next, S_RT, X_[ic_], scal_ + S_TR + i_max,
@@ -2065,12 +1662,12 @@ class Session : public SessionBase {
     }
     tk_ = t;
     kslot_ = (accepted && fs_batch) ? (kslot_ + 1) % 3 : -1;
-    if (fsplit_ && ls) {
+    if (md_.fsplit && ls) {
       split_hist_.push_back(fs_batch ? hs_[S_RT + 2] : -1.0);
       if (fs_batch) {
         stats_[3] += 1;
         stats_[5] += hs_[S_RT + 2];
-        if (accepted && hs_[S_RT + 2] > nnz_budget_) dense_left_ = kFistaDenseRun;
+        if (accepted && hs_[S_RT + 2] > md_.nnz_budget) dense_left_ = kFistaDenseRun;
       } else {
         stats_[4] += 1;
         if (dense_left_ > 0) --dense_left_;
@@ -2098,15 +1695,15 @@ class Session : public SessionBase {
   // order; A @ [xc | y_next] over this rank's rows of A and its finalize (sums into the chunk, the
   // count over this rank's rows of xc). As iter_proxgd_shard, the next gradient and first trial
   // are queued speculatively behind the trial (their exchange carries its residual sums) and the
-  // packet rides the next trial's dense pass. Host control only (see fista_shard_ranks).
+  // packet rides the next trial's dense pass. Host control only (session_mode.cpp shard_ranks).
   void fshard_trial(int ix, int iy, const T* G, int oc, int ovn, int oyn, double t, double theta,
                     double theta_next) {
-    const int64_t o = srow0_ * l_;
+    const int64_t o = md_.sh.row0 * l_;
     Red rd = red_to(scal_ + S_TR);
     rd.part = blk_own() + kShardPartOff;
     rd.parts_only = 1;
     launch_fista_trial<T>(true, X_[iy] + o, G + o, 1, nullptr, X_[ix] + o, X_[oc] + o, X_[ovn] + o,
-                          X_[oyn] + o, srows_, l_, t, mu_, O_.thres, theta, theta_next, O_.delta, rd, st_,
+                          X_[oyn] + o, md_.sh.rows, l_, t, mu_, O_.thres, theta, theta_next, O_.delta, rd, st_,
                           Pub{}, nullptr, nullptr);
     check_launch();
   }
@@ -2160,7 +1757,7 @@ class Session : public SessionBase {
           shard_exchange(ff1_);
           fshard_derive(ic_, ff1_, ff2_, ff3_, theta_next, thnn, shard_pub(3, ot, nullptr));
           const T* sx[3] = {X_[ff1_], X_[ff3_], nullptr};
-          const bool carry = spin_readback_ && attach_ok_ && ax_pub_ok(plan_, 2);
+          const bool carry = md_.spin_readback && md_.attach_ok && ax_pub_ok(md_.plan, 2);
           Pub pb;
           if (carry) pb = make_pub(nullptr, &seq);
           else seq = post_readback();
@@ -2176,7 +1773,7 @@ class Session : public SessionBase {
         wait_readback(seq);
         if (gy_pending_) { gy_sq_ = hs_[S_RG]; gy_pending_ = false; }
         const double gy = 0.5 * gy_sq_, gxc = 0.5 * hs_[S_RT];
-        if (shard_model_ || gxc <= gy + hs_[tr_slot_ + 0] + hs_[tr_slot_ + 1] / (2 * t)) {
+        if (md_.sh.model || gxc <= gy + hs_[tr_slot_ + 0] + hs_[tr_slot_ + 1] / (2 * t)) {
           accepted = true;
           spec_on_ = (it == 0);
           break;
@@ -2209,9 +1806,9 @@ class Session : public SessionBase {
   // and checks it; results are bit-identical to host control.
   struct FRoles { int ix, iv, iy, ic, ivn, iyn, f1, f2, f3, iry, gset, ks; };
   bool fista_dc_ready(double t0, double theta) const {
-    return dc_window_ > 0 && method_ == GLX_FPROXGD && fused_fista_ok_ && spec_trial_ready_ &&
+    return md_.dc_window > 0 && method_ == GLX_FPROXGD && md_.fused_fista_ok && spec_trial_ready_ &&
            y_ready_ && !gy_pending_ && spec_trial_mu_ == mu_ && spec_trial_t_ == t0 &&
-           spec_trial_theta_ == theta && want_spec(0) && !(fsplit_ && kslot_ < 0 && dense_left_ == 0);
+           spec_trial_theta_ == theta && want_spec(0) && !(md_.fsplit && kslot_ < 0 && dense_left_ == 0);
   }
   // one segment of a device-controlled FISTA batch; th = theta of the iteration, thn / thnn the
   // next two (the speculative trial's theta and theta_next)
@@ -2221,14 +1818,14 @@ class Session : public SessionBase {
     Ctl c = dc_make_ctl(tag);
     c.mode = 1;
     c.t = t;
-    c.nnz_budget = split ? nnz_budget_ : -1.0;
+    c.nnz_budget = split ? md_.nnz_budget : -1.0;
     dc_gate_ = dc_abort_;
     const int ns = nset(q.gset);
     double* defer = comm_ ? tail(ns) : nullptr;
     if (split) {
       const T* xs[3] = {E_, X_[q.ic], nullptr};
       cand_ax(xs);
-      launch_finalize_fista<T>(Pp_ + (size_t)gsplit_ * ml_, ax_split(plan_, 1), Pp_, gsplit_, B_,
+      launch_finalize_fista<T>(Pp_ + (size_t)md_.gsplit * ml_, ax_split(md_.plan, 1), Pp_, md_.gsplit, B_,
                                R_[ryn], SXO_[q.ks], SXO_[(q.ks + 1) % 3], ml_, 1.0 - thn, thn, th,
                                X_[q.ic], nl_, scal_ + S_TR + 3, gather_counts(glists_, n_), gcount_n(),
                                defer ? red_to(defer) : red(S_RT), st_, comm_ ? Ctl{} : c);
@@ -2277,9 +1874,9 @@ class Session : public SessionBase {
     int64_t budget = O_.maxit - inner_ + 1;
     if (O_.max_total_iters > 0) budget = std::min<int64_t>(budget, O_.max_total_iters - k_ + 1);
     budget = std::max<int64_t>(1, std::min<int64_t>(budget, step_room_));
-    const bool split = fsplit_ && kslot_ >= 0 && dense_left_ == 0;
+    const bool split = md_.fsplit && kslot_ >= 0 && dense_left_ == 0;
     // dense batches: at most until the A thr(x_k) restore the host path runs after the last one
-    if (fsplit_ && dense_left_ > 0) budget = std::min<int64_t>(budget, dense_left_);
+    if (md_.fsplit && dense_left_ > 0) budget = std::min<int64_t>(budget, dense_left_);
     ++syncs_;   // the host's one drain point per batch (its records are read while it runs)
     launch_ctl_seed(dc_state_, dc_abort_, gy_sq_, f_cur_, s_cur_, (double)stable_, st_);
     check_launch();
@@ -2287,7 +1884,7 @@ class Session : public SessionBase {
     const int64_t tag0 = dc_tag_, in0 = inner_;
     const double t = tk_;
     int64_t queued = 0;
-    const int64_t w = std::min<int64_t>(dc_window_, budget);
+    const int64_t w = std::min<int64_t>(md_.dc_window, budget);
     auto push = [&]() {
       const int64_t d = queued;
       dc_tag_ = tag0 + 1 + queued++;
@@ -2329,7 +1926,7 @@ class Session : public SessionBase {
         return;
       }
       spec_on_ = true;
-      const bool trip = split && hs_[S_RT + 2] > nnz_budget_;
+      const bool trip = split && hs_[S_RT + 2] > md_.nnz_budget;
       if ((code == 3) != (trip && code != 1))
         throw Error{GLX_E_STATE, "device-controlled batch: nnz budget decision differs from the host's"};
       fista_update(true, true, t, split, theta_next, (iry_ + 2) % kRes, 2);
@@ -2360,16 +1957,13 @@ class Session : public SessionBase {
   // kFistaDenseRun batches are the dense [xc | y_next] pair, then A thr(x_k) is restored and
   // the gather form tried again.
   static constexpr int kFistaDenseRun = 128;
-  // the row form reads one At row per flagged row: its cost passes the dense second source's
-  // (~0.7 of a pass at NS) near 0.65 n flagged rows
-  static constexpr double kRowsBudget = 0.6;
   void fista_split_prologue() {
     T* scratch = X_[ff1_];   // free between iterations (the speculation's spare)
     launch_threshold<T>(X_[ix_], scratch, nl_, O_.thres, flag_, ++epoch_, st_);
     check_launch();
     const T* xs[3] = {scratch, nullptr, nullptr};
     spec_ax(1, xs);
-    launch_sum_partials<T>(Pp_, ax_split(plan_, 1), SXO_[0], ml_, st_);
+    launch_sum_partials<T>(Pp_, ax_split(md_.plan, 1), SXO_[0], ml_, st_);
     check_launch();
     kslot_ = 0;
     stats_[6] += 1;
@@ -2379,21 +1973,21 @@ class Session : public SessionBase {
     const T* xs[3] = {E_, X_[ic_], nullptr};
     cand_ax(xs);
     Red rd = defer ? Red{part_, ticket_, defer} : red(slot);
-    const bool dfin = defer_ && carry_ && pub_seq == nullptr && defer == nullptr;
+    const bool dfin = md_.defer && carry_ && pub_seq == nullptr && defer == nullptr;
     const bool dmax = cx != nullptr && ptr_.part != nullptr && cmax == ptr_.out + 3;
     if (dfin) {
       flush_fin_pending();
       rd.part = fpart_;
       rd.parts_only = 1;
     }
-    launch_finalize_fista<T>(Pp_ + (size_t)gsplit_ * ml_, ax_split(plan_, 1), Pp_, gsplit_, B_, ry,
+    launch_finalize_fista<T>(Pp_ + (size_t)md_.gsplit * ml_, ax_split(md_.plan, 1), Pp_, md_.gsplit, B_, ry,
                              SXO_[kslot_], SXO_[(kslot_ + 1) % 3], ml_, 1.0 - theta_next,
                              theta_next, theta, cx, nl_, cmax, gather_counts(glists_, n_), gcount_n(),
                              rd, st_, Ctl{}, dmax ? ptr_.part : nullptr, dmax ? ptr_.np : 0,
                              dmax ? ptr_.nv : 4);
     check_launch();
     if (dfin)
-      pfin_ = Pend{fpart_, finalize_fista_blocks(ml_, ax_split(plan_, 1), gsplit_, cx ? nl_ : 0), 4, 0u,
+      pfin_ = Pend{fpart_, finalize_fista_blocks(ml_, ax_split(md_.plan, 1), md_.gsplit, cx ? nl_ : 0), 4, 0u,
                    scal_ + slot};
     if (defer) return;
     if (comm_) comm_allreduce(comm_, scal_ + slot, 2, GLX_F64, st_);
@@ -2409,7 +2003,7 @@ class Session : public SessionBase {
     if (comm_) {
       const std::pair<const T*, int> g = gradient(r, set, tail_n);
       Pub pb;
-      if (pub_seq && attach_ok_) pb = make_pub(extra, pub_seq);
+      if (pub_seq && md_.attach_ok) pb = make_pub(extra, pub_seq);
       else if (pub_seq) *pub_seq = post_readback(extra);
       launch_fista_trial<T>(true, yv, g.first, g.second, nullptr, xk, X_[oc], X_[ov], X_[oy], n_,
                             l_, t, mu_, O_.thres, theta, theta_next, O_.delta, red(S_TR), st_, pb,
@@ -2421,16 +2015,16 @@ class Session : public SessionBase {
     if (pub_seq) pb = make_pub(extra, pub_seq);
     hipEvent_t e0 = prof_begin(1);
     Red rd = red(S_TR, dc_pass_);
-    const bool dtr = defer_ && (pub_seq != nullptr || carry_);   // (as atr_prox)
+    const bool dtr = md_.defer && (pub_seq != nullptr || carry_);   // (as atr_prox)
     if (dtr) {
       tb_ ^= 1;
       rd.part = tpart_[tb_];
       rd.parts_only = 1;
     }
-    launch_atr_fista<T>(plan_, A_, r, Gs_[set], yv, xk, X_[oc], X_[ov], X_[oy], t, mu_, O_.thres,
+    launch_atr_fista<T>(md_.plan, A_, r, Gs_[set], yv, xk, X_[oc], X_[ov], X_[oy], t, mu_, O_.thres,
                         theta, theta_next, rd, st_, pb, Gps_[set], pcnt_, fec(), fzf());
     check_launch();
-    ptr_ = dtr ? Pend{tpart_[tb_], atr_prox_slots(plan_, pb.host != nullptr), 4, 0x8u, scal_ + S_TR} : Pend{};
+    ptr_ = dtr ? Pend{tpart_[tb_], atr_prox_slots(md_.plan, pb.host != nullptr), 4, 0x8u, scal_ + S_TR} : Pend{};
     prof_end(1, e0);
     ++atr_calls_;
   }
@@ -2450,7 +2044,7 @@ class Session : public SessionBase {
   // gradient A^T (A thr(x) - b) (kernels_gemv.hip)
   void descent_pass(int64_t phase) {
     hipEvent_t e0 = prof_begin(0);
-    launch_gemv_fused<T>(gemv_blocks_, A_, X_[0], X_[1], B_, gemv_slabs_, m_, n_,
+    launch_gemv_fused<T>(md_.gemv_blocks, A_, X_[0], X_[1], B_, gemv_slabs_, m_, n_,
                          comm_ ? nullptr : fh_dev_ + k_, descent_mu_obj(phase), scal_ + S_DRN,
                          red(S_RO), st_);
     check_launch();
@@ -2464,8 +2058,8 @@ class Session : public SessionBase {
     }
   }
   std::pair<const T*, int> descent_gradient() {
-    if (gemv_blocks_ == 0) return gradient(R_[1]);
-    launch_sum_cols<T>(gemv_slabs_, gemv_blocks_, G_, n_, st_);   // l = 1: n x l = n
+    if (md_.gemv_blocks == 0) return gradient(R_[1]);
+    launch_sum_cols<T>(gemv_slabs_, md_.gemv_blocks, G_, n_, st_);   // l = 1: n x l = n
     check_launch();
     if (comm_) comm_allreduce(comm_, G_, nl_, P_.dtype, st_);
     return {G_, 1};
@@ -2477,7 +2071,7 @@ class Session : public SessionBase {
       check_launch();
       launch_threshold<T>(X_[0], X_[1], nl_, O_.thres, flag_, ++epoch_, st_);
       check_launch();
-      if (gemv_blocks_) descent_pass(phase_);
+      if (md_.gemv_blocks) descent_pass(phase_);
       else descent_residuals(phase_);
       state_valid_ = true;
     }
@@ -2488,7 +2082,7 @@ class Session : public SessionBase {
     launch_descent<T>(X_[0], X_[1], g.first, g.second, n_, l_, alpha, mu_, O_.thres, O_.delta,
                       gd ? 1 : 0, red(S_DRN), st_);
     check_launch();
-    if (k_ % 100 == 0 && k_ / 100 <= fh_cap_ / 100 + 1) {   // sparsity_func(x) of the debug line (:99)
+    if (k_ % 100 == 0 && k_ / 100 <= md_.fh_cap / 100 + 1) {   // sparsity_func(x) of the debug line (:99)
       launch_rownorm_max<T>(X_[0], n_, l_, red(S_SPX), st_);
       check_launch();
       launch_count_above<T>(X_[0], nl_, scal_ + S_SPX + 1, Red{part_, ticket_, sp100_ + k_ / 100}, st_);
@@ -2496,7 +2090,7 @@ class Session : public SessionBase {
     }
     // next iteration's objective residual and gradient residual, one pass
     const int64_t next_phase = (inner_ >= O_.maxit) ? phase_ + 1 : phase_;
-    if (gemv_blocks_) descent_pass(next_phase);
+    if (md_.gemv_blocks) descent_pass(next_phase);
     else descent_residuals(next_phase);
   }
 
@@ -2505,10 +2099,9 @@ class Session : public SessionBase {
   glx_problem P_;
   glx_opts O_;
   hipStream_t st_;
-  GemmPlan plan_{};
+  const SessionMode md_;   // what this session launches, resolved once (session_mode.cpp)
   glx_comm* comm_ = nullptr;
   bool ax_queued_ = false;     // the pending first trial's A@X is already queued (spec_ax)
-  bool spec_ax_pub_ = true;    // GLX_SPEC_AX_PUB=0: the packet rides k_prox_pgd instead
   int64_t m_ = 0, n_ = 0, l_ = 0, nl_ = 0, ml_ = 0;
   const T* A_ = nullptr;
   const T* B_ = nullptr;
@@ -2517,62 +2110,40 @@ class Session : public SessionBase {
   T *G_ = nullptr, *Gp_ = nullptr, *Pp_ = nullptr;
   T* Gs_[kMaxGSets] = {};
   T* Gps_[kMaxGSets] = {};
-  int nsets_ = 2;
   double *scal_ = nullptr, *part_ = nullptr, *fh_dev_ = nullptr;
   double *hs_ = nullptr, *hs_dev_ = nullptr;
   unsigned *hseq_ = nullptr, *hseq_dev_ = nullptr;
   unsigned* ticket_ = nullptr;
   unsigned* pcnt_ = nullptr;   // per-panel counters (fused A^T R with K splits)
   unsigned* zf_ = nullptr;     // per-row column masks of e (split-candidate mode)
-  // row-sharded ProxGD (iter_proxgd_shard): this rank's rows [srow0_, srow0_ + srows_) of n,
-  // sranks_ row blocks (cranks_ communicator ranks; they differ only in the timing model)
-  bool shard_ = false, shard_model_ = false;
-  bool fshard_ = false;        // round 6: row-sharded FProxGD (iter_fista_shard)
-  int stv_ = 6;                // values per trial workgroup partial in the chunk (FProxGD: 4)
-  int srank_ = 0, sranks_ = 1, cranks_ = 1;
-  int64_t srow0_ = 0, srows_ = 0;
-  int nbp_ = 0, nbf_ = 0;      // k_prox_pgd's workgroups on srows_ rows, the trial finalize's
-  int schunk_ = 0;             // doubles per rank's chunk
-  bool zskip_ = false;         // the gathered p serves as e (bitmap / list gathers)
-  bool sderive_ = false;       // round 6: the speculative derive inside the dense pass (AxDerive)
-  int64_t moff_ = 0;           // doubles into a rank's chunk: its row masks + column bitmaps (sderive_)
-  double* blk_ = nullptr;      // kMaxShardRanks chunks of sums (kShardChunkMax doubles each)
-  // deferred reductions (defer_, single GPU): the trial's and the finalize's pending partials
-  bool defer_ = false;
+  // row-sharded ProxGD / FProxGD (md_.sh): kMaxShardRanks chunks of sums (kShardChunkMax doubles each)
+  double* blk_ = nullptr;
+  // deferred reductions (md_.defer, single GPU): the trial's and the finalize's pending partials
   double* tpart_[2] = {nullptr, nullptr};
   double* fpart_ = nullptr;
   int tb_ = 0;
   Pend ptr_, pfin_;
-  bool unfused_spec_ = false;  // one GPU, a plan without the fused trial: the communicator form
   bool carry_ = false;         // while queuing: the next packet rides the speculative kernel
   int tr_slot_ = S_TR;         // the packet slots of the current trial's sums
   T* At_ = nullptr;            // A^T (split-candidate gather form)
   void* glists_ = nullptr;     // the gather's per-column index lists of e
-  int smode_ = 0, gsplit_ = 1;
-  int gform_ = 0;              // A e: 0 bitmap gather, 1 k_at_rows, 2 lists + gather (gather_form)
-  bool rows_form_ = false;     // gform_ == 1: A e by k_at_rows (round 5), gsplit_ slabs
-  bool egat_ = false;          // round 6: A e inside the dense pass (launch_ax_egat), gsplit_ = its S
-  double hyb_rows_ = 0.0;      // round 6: > 0: the fused form per trial from this many flagged rows
   double last_rows_ = 0.0;     // flagged rows of the last accepted trial
   bool qeg_ = false;           // the queued split-candidate A@X is the fused form (its finalize reads it)
   // the fused A e form for the next trial; its A e slabs (one per K split) in front of A p
-  bool egat_now() const { return egat_ || (hyb_rows_ > 0.0 && last_rows_ >= hyb_rows_); }
-  int gs_of(bool eg) const { return eg ? ax_split(plan_, 1) : gsplit_; }
+  bool egat_now() const { return md_.egat || (md_.hyb_rows > 0.0 && last_rows_ >= md_.hyb_rows); }
+  int gs_of(bool eg) const { return eg ? ax_split(md_.plan, 1) : md_.gsplit; }
   // entries of the gather counts the FISTA finalize sums: flagged rows per K range (row form) or
   // nonzeros per column (VALU gather)
-  int gcount_n() const { return rows_form_ ? gsplit_ : (int)l_; }
-  bool emode_ = false;         // split-candidate ProxGD: trials write e = p - p_thr, not z
-  unsigned* ezf() const { return emode_ ? zf_ : nullptr; }
+  int gcount_n() const { return md_.rows_form ? md_.gsplit : (int)l_; }
+  unsigned* ezf() const { return md_.emode ? zf_ : nullptr; }
   // split-candidate FProxGD (iter_fista): trials also write e_c = xc - thr(xc) to E_ and its
   // row flags to zf_; SXO_[kslot_] = A thr(x_k) (kslot_ < 0: not known)
-  bool fsplit_ = false;
   T* E_ = nullptr;
   T* SXO_[3] = {nullptr, nullptr, nullptr};
   int kslot_ = -1;
-  double nnz_budget_ = 0;      // nnz(e_c) above which the dense batch is cheaper
   int dense_left_ = 0;         // dense batches before the gather form is tried again
-  T* fec() const { return fsplit_ ? E_ : nullptr; }
-  unsigned* fzf() const { return fsplit_ ? zf_ : nullptr; }
+  T* fec() const { return md_.fsplit ? E_ : nullptr; }
+  unsigned* fzf() const { return md_.fsplit ? zf_ : nullptr; }
   int* flag_ = nullptr;
   // device-controlled ProxGD batches (dc_run)
   double* dc_state_ = nullptr;    // Ctl::state
@@ -2582,25 +2153,21 @@ class Session : public SessionBase {
   Pub dc_pub_{};                  // while queuing: the record's hand-off, carried by atr_prox
   double* dc_ring_ = nullptr;     // host-mapped decision records
   double* dc_ring_dev_ = nullptr;
-  int dc_window_ = 0;             // iterations in flight (0: off)
   int64_t dc_tag_ = 0;            // decision records issued
   int64_t step_room_ = INT64_MAX;
   const int* dc_gate_ = nullptr;  // while queuing a batch: the abort word the launches test
   Ctl dc_ctl_{};                  // while queuing a batch: the finalize's decision epilogue
-  int64_t fh_cap_ = 0;
   // progress record for glx_session_progress (read by other threads): iterations, phase, what
   // the host is waiting on (0 nothing, 1 a scalar packet, 2 a decision record)
   std::atomic<int64_t> prog_k_{0};
   std::atomic<int> prog_phase_{0}, prog_wait_{0};
   double* sp100_ = nullptr;   // SGD/GD: count(|x| > 1e-6 max|x|) after every 100th iteration
   T* gemv_slabs_ = nullptr;
-  int gemv_blocks_ = 0;
 
  private:
   int method_ = 0;
-  bool use_sparsity_ = true, device_hist_ = false, spin_readback_ = true;
+  bool use_sparsity_ = true, device_hist_ = false;
   unsigned seq_ = 0;
-  bool attach_ok_ = true;
   hipEvent_t rb_event_ = nullptr;
   int epoch_ = 0;
   // buffer roles
@@ -2611,10 +2178,10 @@ class Session : public SessionBase {
   bool state_valid_ = false, thr_from_trial_ = false, y_ready_ = false, gy_pending_ = false;
   // speculative gradient (take_gradient)
   int gset_ = 0, spec_set_ = 1;
-  bool spec_on_ = true, spec_ready_ = false, spec_off_env_ = false;
-  // ProxGD trial fused into A^T r (launch_atr_prox): fused_ok_ = the plan allows it; a
-  // speculative fused kernel leaves G and the next iteration's first trial (t, mu) ready
-  bool fused_ok_ = false, fused_fista_ok_ = false, spec_trial_ready_ = false;
+  bool spec_on_ = true, spec_ready_ = false;
+  // ProxGD trial fused into A^T r (launch_atr_prox, where md_.fused_ok): a speculative fused
+  // kernel leaves G and the next iteration's first trial (t, mu) ready
+  bool spec_trial_ready_ = false;
   double spec_trial_mu_ = 0, spec_trial_t_ = 0, spec_trial_theta_ = 0;
   std::pair<const T*, int> spec_g_{nullptr, 0};
   double gx_ = 0, gy_sq_ = 0;
@@ -2642,11 +2209,8 @@ class Session : public SessionBase {
 };
 
 static size_t session_bytes(const glx_problem& P, const glx_opts& O) {
-  const GemmPlan plan = session_plan(P, O);
-  const int sm = split_mode(P, O);
-  if (P.dtype == GLX_F64)
-    return Session<double>::carve(P, O, plan, Session<double>::fh_capacity(P, O), sm, nullptr, nullptr);
-  return Session<float>::carve(P, O, plan, Session<float>::fh_capacity(P, O), sm, nullptr, nullptr);
+  const SessionMode md = session_mode(P, O);
+  return P.dtype == GLX_F64 ? Session<double>::carve(md, nullptr, nullptr) : Session<float>::carve(md, nullptr, nullptr);
 }
 
 template <typename F>
@@ -2766,6 +2330,14 @@ int glx_workspace_bytes(const glx_problem* prob, const glx_opts* opts, size_t* b
     validate(prob, opts);
     if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
     *bytes = session_bytes(*prob, *opts);
+  });
+}
+
+int glx_mode_describe(const glx_problem* prob, const glx_opts* opts, char* out, size_t cap) {
+  return guarded([&] {
+    validate(prob, opts);
+    if (!out || cap == 0) throw Error{GLX_E_INVALID, "null out"};
+    std::snprintf(out, cap, "%s", describe_mode(session_mode(*prob, *opts)).c_str());
   });
 }
 

@@ -72,6 +72,7 @@ _SIGS = {
     "glx_session_trace": (c_int, [c_void_p, POINTER(c_double), c_int64, POINTER(c_int64),
                                   POINTER(c_int64)]),
     "glx_session_describe": (c_int, [c_void_p, c_char_p, c_size_t]),
+    "glx_mode_describe": (c_int, [POINTER(GlxProblem), POINTER(GlxOpts), c_char_p, c_size_t]),
     "glx_session_split_trace": (c_int, [c_void_p, POINTER(c_double), c_int64, POINTER(c_int64)]),
     "glx_session_destroy": (None, [c_void_p]),
     "glx_solve": (c_int, [POINTER(GlxProblem), POINTER(GlxOpts), c_void_p, c_size_t,
@@ -141,6 +142,14 @@ def plan_describe(dtype: int, m: int, n: int, l: int) -> str:
     """The kernels and K splits libglx plans for this shape (see glx_plan_describe)."""
     buf = ctypes.create_string_buffer(512)
     check(lib().glx_plan_describe(dtype, m, n, l, buf, len(buf)))
+    return buf.value.decode()
+
+
+def mode_describe(problem: GlxProblem, opts: GlxOpts) -> str:
+    """What a session of this problem and these options would describe (glx_mode_describe: resolved
+    on the host, no device)."""
+    buf = ctypes.create_string_buffer(1024)
+    check(lib().glx_mode_describe(ctypes.byref(problem), ctypes.byref(opts), buf, len(buf)))
     return buf.value.decode()
 
 

@@ -139,7 +139,9 @@ int         glx_default_opts(int method, glx_opts* out);
 /* Workspace (device bytes) a session needs for this problem and these options (includes the
  * transposed copy of A of the split-candidate trial, opts.split_cand, and the gradient-set ring
  * of device control with a communicator, opts.dc_window). Environment overrides (GLX_*) are read
- * here and at create: keep them unchanged in between. */
+ * here and at create: keep them unchanged in between. The session's whole mode is resolved here
+ * as it is at create, so an option the mode refuses (opts.shard_rows = 1 with n % ranks != 0)
+ * is refused here with the code and message glx_session_create gives. */
 int glx_workspace_bytes(const glx_problem* prob, const glx_opts* opts, size_t* bytes);
 
 /* Session API: the reference loop split so that a caller can time exactly K iterations.
@@ -179,6 +181,10 @@ int  glx_session_trace(glx_session* s, double* sparsity_after, int64_t cap, int6
  * after the session's own choices: the fused trial, the split-candidate form, the device-control
  * window), NUL-terminated, truncated to cap. */
 int  glx_session_describe(glx_session* s, char* out, size_t cap);
+/* The same string without a session, a device or a workspace: what a session created from this
+ * problem, these options and the current environment would describe (the mode is resolved on the
+ * host; A, b and x are validated as by glx_workspace_bytes and never read). */
+int  glx_mode_describe(const glx_problem* prob, const glx_opts* opts, char* out, size_t cap);
 /* The split-candidate trials' sparsity, one value per trial batch so far (diagnostic): ProxGD the
  * rows of e = p - p_thr (accepted trials), FProxGD nnz(e_c) of a gathered batch (flagged rows in
  * the row form) or -1 for a dense batch. *n = the count; up to cap values copied to out. */

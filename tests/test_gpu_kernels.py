@@ -248,3 +248,44 @@ def test_session_plan_matches_recorded_planner():
     for g, r in zip(got, rows):
         print(r[:6], g)
         assert g == r[6], r[:6]
+
+
+def test_session_mode_matches_recorded_sessions():
+    """Sessions take the mode the commit before csrc/session_mode.cpp took and compute the same
+    bits: for every recorded session (tests/golden/make_mode_golden.py --gpu, recorded from that
+    commit's build) Session.describe() equals the recording and what glx_mode_describe resolves
+    on the host for the same problem; for the recorded 30-step runs f_hist is bit-identical and
+    the counters are equal (a counter that did not repeat in that commit is listed in the row's
+    "skip"; none is)."""
+    import json
+    import os
+    import sys
+    from conftest import ROOT
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    try:
+        import make_mode_golden as gen
+    finally:
+        sys.path.pop(0)
+    fix = json.load(open(os.path.join(ROOT, "tests", "golden", "mode_golden.json")))
+    assert len(fix["sessions"]) >= 40 and len(fix["runs"]) >= 30
+    saved = {k: os.environ.get(k) for k in gen.MODE_ENV}
+    try:
+        for r in fix["sessions"]:
+            d = gen.record_session(r)
+            print(r["name"], d)
+            assert d == r["describe"], r["name"]
+            assert gen.mode_describe(r) == d, r["name"]
+        for r in fix["runs"]:
+            d, fh, cnt = gen.record_run(r)
+            print(r["name"], fh[-1], cnt)
+            assert d == r["describe"] and gen.mode_describe(r) == d, r["name"]
+            assert fh == r["f_hist"], r["name"]
+            assert not r["skip"] or "dc_window=0" not in d, r["name"]
+            assert {k: v for k, v in cnt.items() if k not in r["skip"]} == \
+                {k: v for k, v in r["counters"].items() if k not in r["skip"]}, r["name"]
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v

@@ -203,3 +203,55 @@ def test_kernel_workspace_covers_every_planned_split():
         splits = [int(s) for s in re.findall(r"S=(\d+)", _lib.plan_describe(_lib.GLX_F64, *shp))]
         m, n, l = shp
         assert nb.value >= 8 * m * l * max(splits) * 3, (shp, nb.value, splits)
+
+
+def _mode_fixture():
+    """(tests/golden/make_mode_golden.py as a module, the recorded tests/golden/mode_golden.json)"""
+    import json
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    try:
+        import make_mode_golden as gen
+    finally:
+        sys.path.pop(0)
+    return gen, json.load(open(os.path.join(ROOT, "tests", "golden", "mode_golden.json")))
+
+
+def test_mode_matches_recorded_sessions():
+    """A session's mode (csrc/session_mode.cpp) is what the commit before it resolved inside
+    Session<T>: glx_workspace_bytes returns the recorded byte count or error code for every
+    recorded (method, dtype, shape, options, environment, communicator), and glx_mode_describe
+    returns, without a device, the string (or the error) glx_session_create gave on the GPU for
+    every recorded session. The fixture was recorded from that commit's build
+    (tests/golden/make_mode_golden.py) and is never regenerated from this code. The rows marked
+    `differs` are the one deliberate difference: ProxGD's "row-sharded ProxGD needs n % ranks == 0"
+    error, which only glx_session_create raised; glx_workspace_bytes now raises it too, with the
+    recorded code and text."""
+    gen, fix = _mode_fixture()
+    cases, sessions = fix["cases"], fix["sessions"]
+    assert len(cases) >= 300
+    misfit = next(r["describe"] for r in sessions if r["name"] == "comm_misfit_p")
+    assert misfit["rc"] != 0 and "row-sharded ProxGD needs n % ranks == 0" in misfit["msg"]
+    saved = {k: os.environ.get(k) for k in gen.MODE_ENV}
+    try:
+        got = [gen.record_case(*c[:8]) for c in cases]
+        described = [gen.mode_describe(r) for r in sessions]
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    assert sum(c[9] for c in cases) >= 4
+    bad = []
+    for (g, msg), c in zip(got, cases):
+        if c[9]:   # recorded: the byte count of a session whose creation then failed
+            assert not isinstance(c[8], dict), c
+            ok = g[:8] == c[:8] and g[8] == {"rc": misfit["rc"]} and msg == misfit["msg"]
+        else:
+            ok = g == c
+        if not ok:
+            bad.append((g, msg, c))
+    assert not bad, "%d of %d differ, first: got %r (%s), recorded %r" % ((len(bad), len(cases)) + bad[0])
+    for d, r in zip(described, sessions):
+        assert d == r["describe"], (r["name"], d, r["describe"])
