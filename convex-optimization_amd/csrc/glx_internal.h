@@ -426,7 +426,8 @@ void launch_ctl_seed(double* state, int* abort, double s0, double s1, double s2,
 template <typename T>
 void launch_sum_partials(const T* Gp, int S, T* G, int64_t nl, hipStream_t st);
 // ProxGD trial: p = prox(x - t g, t), G_t = (x - p)/t, z = x - t G_t, pthr = p thresholded.
-// out: [sum g*G_t, sum G_t^2, sum_i ||p_i||, max |p|, #changed by the threshold]
+// out: [sum g*G_t, sum G_t^2, sum_i ||p_i||, max |p|, #{entries of p changed by the threshold},
+//       #{rows of p changed by the threshold}]
 // zf != NULL (split-candidate mode): z receives e = p - p_thr instead and zf[i] = the column mask
 // of row i of e (bit c = e[i][c] != 0).
 template <typename T>

@@ -2236,8 +2236,11 @@ struct KernelWs {
   void* rg_ws; double* rg_s; double* rg_g; int* rg_err;   // fused residual-gradient pass
   void* rg2_ws; double* rg2_g;                              // its l = 16 two-source form
   void* fr_slabs; void* fr_lists; void* fr_zf;              // glx_flagged_rows_product
+  unsigned* pcnt;   // per-panel counters of a fused A^T R with K splits (glx_trial_*, form 1)
 };
-static size_t kernel_ws(int es, const GemmPlan& p, void* base, KernelWs* out) {
+// trial: with the per-panel counters of glx_trial_* (glx_trial_workspace_bytes); without, the
+// layout and size glx_kernel_workspace_bytes has always reported
+static size_t kernel_ws(int es, const GemmPlan& p, void* base, KernelWs* out, bool trial = false) {
   Carver c(base);
   // room for the largest split any variant of this shape plans (MFMA tiles, VALU)
   int64_t s_ax = 1, s_atr = 1;
@@ -2274,9 +2277,10 @@ static size_t kernel_ws(int es, const GemmPlan& p, void* base, KernelWs* out) {
     fr_lists = c.take(gather_lists_bytes(p.n));
     fr_zf = c.take(zf_bytes(p.n));
   }
+  unsigned* pcnt = trial ? static_cast<unsigned*>(c.take(sizeof(unsigned) * (p.n / 64 + 64))) : nullptr;
   if (out)
     *out = KernelWs{pp, gp, part, ticket, scal, rg_ws, rg_s, rg_g, rg_err, rg2_ws, rg2_g, fr_slabs, fr_lists,
-                    fr_zf};
+                    fr_zf, pcnt};
   return c.off + 256;
 }
 
@@ -2452,15 +2456,15 @@ int glx_plan_describe(int dtype, int64_t m, int64_t n, int64_t l, char* out, siz
 }
 
 static KernelWs kernel_setup(int dtype, int64_t m, int64_t n, int64_t l, void* ws, size_t wsb,
-                             int variant, hipStream_t st, GemmPlan* plan) {
+                             int variant, hipStream_t st, GemmPlan* plan, bool trial = false) {
   if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "bad dtype"};
   if (m <= 0 || n <= 0 || l <= 0 || l > kMaxL) throw Error{GLX_E_INVALID, "bad shape"};
   const int es = dtype == GLX_F64 ? 8 : 4;
   *plan = make_plan(es, m, n, l, variant);
-  if (!ws || wsb < kernel_ws(es, *plan, nullptr, nullptr)) throw Error{GLX_E_WORKSPACE, "workspace too small"};
+  if (!ws || wsb < kernel_ws(es, *plan, nullptr, nullptr, trial)) throw Error{GLX_E_WORKSPACE, "workspace too small"};
   if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_WORKSPACE, "workspace must be 256-byte aligned"};
   KernelWs k;
-  kernel_ws(es, *plan, ws, &k);
+  kernel_ws(es, *plan, ws, &k, trial);
   GLX_HIP(hipMemsetAsync(k.ticket, 0, kTicketBytes, st));
   return k;
 }
@@ -2570,6 +2574,107 @@ int glx_flagged_rows_product(int dtype, int64_t m, int64_t n, int64_t l, const v
                                k.fr_lists, st);
       }
       launch_sum_partials<T>(slabs, S0, static_cast<T*>(Y), m * l, st);
+    };
+    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
+    else go(static_cast<float*>(nullptr));
+    check_launch();
+  });
+}
+
+int glx_trial_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes) {
+  return guarded([&] {
+    if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "bad dtype"};
+    if (m <= 0 || n <= 0 || l <= 0 || l > kMaxL || !bytes) throw Error{GLX_E_INVALID, "bad shape"};
+    const int es = dtype == GLX_F64 ? 8 : 4;
+    *bytes = kernel_ws(es, make_plan(es, m, n, l, 0), nullptr, nullptr, true);
+  });
+}
+
+int glx_trial_mask_bytes(int64_t n, size_t* bytes) {
+  return guarded([&] {
+    if (n <= 0 || !bytes) throw Error{GLX_E_INVALID, "bad arguments"};
+    *bytes = zf_bytes(n);
+  });
+}
+
+// the plan and workspace of a trial entry: form 1 plans the shape's A^T R (and refuses a plan that
+// takes no fused trial), the row forms need no product (m = 1, as glx_prox); zeroes the per-panel
+// counters a fused pass with K splits counts on, as Session's constructor does
+static KernelWs trial_setup(int dtype, int64_t m, int64_t n, int64_t l, int form, const void* A,
+                            const void* R, const uint32_t* zf, void* ws, size_t wsb, hipStream_t st,
+                            GemmPlan* p) {
+  if (form < 0 || form > 2) throw Error{GLX_E_INVALID, "form must be 0 (row kernel), 1 (A^T R epilogue), 2 (replicated half)"};
+  if (zf != nullptr && !gather_ok(n, l)) throw Error{GLX_E_INVALID, "zf needs l in {16, 32}, n < 65536"};
+  KernelWs k = kernel_setup(dtype, form == 1 ? m : 1, n, l, ws, wsb, 0, st, p, true);
+  if (form == 1) {
+    if (!A || !R) throw Error{GLX_E_INVALID, "form 1 needs A and R"};
+    if (!atr_prox_ok(*p)) throw Error{GLX_E_INVALID, "form 1: this shape's A^T R plan takes no fused trial (" + describe_plan(*p) + ")"};
+    GLX_HIP(hipMemsetAsync(k.pcnt, 0, sizeof(unsigned) * (n / 64 + 64), st));
+  }
+  return k;
+}
+
+int glx_trial_proxgd(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* R,
+                     void* G, const void* x, double t, double mu, double thres, int form, int emode,
+                     void* p, void* pthr, void* z, void* sums_dev, uint32_t* zf, void* ws, size_t wsb,
+                     void* stream) {
+  return guarded([&] {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GemmPlan plan;
+    KernelWs k = trial_setup(dtype, m, n, l, form, A, R, zf, ws, wsb, st, &plan);
+    if (!x || !p || !pthr) throw Error{GLX_E_INVALID, "null argument"};
+    if (form != 2 && (!G || !z || !sums_dev)) throw Error{GLX_E_INVALID, "null argument"};
+    if (emode != 0 && zf == nullptr) throw Error{GLX_E_INVALID, "emode needs zf"};
+    if (emode != 0 && form == 2 && z == nullptr) throw Error{GLX_E_INVALID, "emode needs z"};
+    if (emode == 0 && zf != nullptr && form != 2)
+      throw Error{GLX_E_INVALID, "forms 0 and 1 write zf only with emode"};
+    Red red{k.part, k.ticket, static_cast<double*>(sums_dev)};
+    auto go = [&](auto* tag) {
+      typedef std::remove_pointer_t<decltype(tag)> T;
+      if (form == 0)
+        launch_prox_pgd<T>((const T*)x, (const T*)G, 1, nullptr, (T*)p, (T*)pthr, (T*)z, n, l, t, mu, thres,
+                           red, st, Pub{}, zf);
+      else if (form == 1)
+        launch_atr_prox<T>(plan, (const T*)A, (const T*)R, (T*)G, (const T*)x, (T*)p, (T*)pthr, (T*)z, t, mu,
+                           thres, red, st, Pub{}, plan.atr_S > 1 ? (T*)k.gp : nullptr, k.pcnt, zf);
+      else
+        launch_trial_split<T>((const T*)p, (const T*)x, (T*)pthr, (T*)z, zf, n, l, t, thres, emode != 0,
+                              ShardPub{}, st);
+    };
+    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
+    else go(static_cast<float*>(nullptr));
+    check_launch();
+  });
+}
+
+int glx_trial_fista(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* R,
+                    void* G, const void* y, const void* xk, double t, double mu, double thres,
+                    double theta, double theta_next, double delta, int form, int prox, void* xc,
+                    void* vnext, void* ynext, void* ec, void* sums_dev, uint32_t* zf, void* ws,
+                    size_t wsb, void* stream) {
+  return guarded([&] {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GemmPlan plan;
+    KernelWs k = trial_setup(dtype, m, n, l, form, A, R, zf, ws, wsb, st, &plan);
+    if (!xk || !xc || !vnext || !ynext) throw Error{GLX_E_INVALID, "null argument"};
+    if (form != 2 && (!G || !y || !sums_dev)) throw Error{GLX_E_INVALID, "null argument"};
+    if ((ec != nullptr) != (zf != nullptr)) throw Error{GLX_E_INVALID, "ec and zf go together"};
+    if (ec != nullptr && (prox == 0 || form == 2)) throw Error{GLX_E_INVALID, "ec and zf need prox = 1 in form 0 or 1"};
+    if (form == 1 && prox == 0) throw Error{GLX_E_INVALID, "form 1 is the prox form"};
+    Red red{k.part, k.ticket, static_cast<double*>(sums_dev)};
+    auto go = [&](auto* tag) {
+      typedef std::remove_pointer_t<decltype(tag)> T;
+      if (form == 0)
+        launch_fista_trial<T>(prox != 0, (const T*)y, (const T*)G, 1, nullptr, (const T*)xk, (T*)xc, (T*)vnext,
+                              (T*)ynext, n, l, t, mu, thres, theta, theta_next, delta, red, st, Pub{}, (T*)ec,
+                              zf);
+      else if (form == 1)
+        launch_atr_fista<T>(plan, (const T*)A, (const T*)R, (T*)G, (const T*)y, (const T*)xk, (T*)xc, (T*)vnext,
+                            (T*)ynext, t, mu, thres, theta, theta_next, red, st, Pub{},
+                            plan.atr_S > 1 ? (T*)k.gp : nullptr, k.pcnt, (T*)ec, zf);
+      else
+        launch_fista_split<T>((const T*)xc, (const T*)xk, (T*)vnext, (T*)ynext, n * l, thres, theta, theta_next,
+                              ShardPub{}, st);
     };
     if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
     else go(static_cast<float*>(nullptr));

@@ -94,6 +94,16 @@ _SIGS = {
                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "glx_flagged_rows_product": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "glx_trial_mask_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
+    "glx_trial_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "glx_trial_proxgd": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_double, c_double, c_double, c_int, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                 c_void_p]),
+    "glx_trial_fista": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_double, c_double, c_double, c_double,
+                                c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "glx_kernel_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
     "glx_plan_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_char_p, c_size_t]),
     "glx_comm_unique_id": (c_int, [POINTER(c_uint8)]),

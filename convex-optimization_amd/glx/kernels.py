@@ -3,13 +3,15 @@
 
 These are the dense products and the group prox of the reference iteration exposed one at a
 time — ``A @ x - b`` (gl_ProxGD_primal.py:25,61), ``A.T @ r`` (:129) and ``prox_th``
-(:65-71) — used by the kernel-level tests and available for composition. All tensors are
-contiguous device tensors of one dtype (float32 / float64).
+(:65-71) — used by the kernel-level tests and available for composition, and one line-search
+trial at a time (``glx_trial_proxgd`` / ``glx_trial_fista``: the row kernels, the A^T R epilogues
+and the replicated halves of the row-sharded schedules). All tensors are contiguous device
+tensors of one dtype (float32 / float64).
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
 
@@ -28,6 +30,12 @@ def _dt(t: torch.Tensor) -> int:
 def _ws(dtype: int, m: int, n: int, l: int, device) -> torch.Tensor:
     nb = ctypes.c_size_t(0)
     check(lib().glx_kernel_workspace_bytes(dtype, m, n, l, ctypes.byref(nb)))
+    return torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+
+
+def _trial_ws(dtype: int, m: int, n: int, l: int, device) -> torch.Tensor:
+    nb = ctypes.c_size_t(0)
+    check(lib().glx_trial_workspace_bytes(dtype, m, n, l, ctypes.byref(nb)))
     return torch.empty(int(nb.value), dtype=torch.uint8, device=device)
 
 
@@ -133,6 +141,92 @@ def flagged_rows_product(At: torch.Tensor, E: torch.Tensor, row_masks: torch.Ten
                                          row_masks.data_ptr(), Y.data_ptr(), int(form),
                                          ws.data_ptr(), ws.numel(), _stream(At.device)))
     return Y
+
+
+def trial_mask_words(n: int) -> int:
+    """uint32 words of a trial's zf buffer for n rows (glx_trial_mask_bytes): the padded row masks,
+    then the column bitmaps (layout in include/glx.h)."""
+    nb = ctypes.c_size_t(0)
+    check(lib().glx_trial_mask_bytes(int(n), ctypes.byref(nb)))
+    return int(nb.value) // 4
+
+
+def _zf_arg(zf: Optional[torch.Tensor], want: bool, n: int, device) -> Optional[torch.Tensor]:
+    if zf is None and want:
+        zf = torch.zeros(trial_mask_words(n), dtype=torch.int32, device=device)
+    if zf is not None and (zf.dtype != torch.int32 or zf.numel() < trial_mask_words(n)):
+        raise ValueError("zf must be an int32 tensor of trial_mask_words(n) words")
+    return zf
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def trial_proxgd(x: torch.Tensor, G: Optional[torch.Tensor], t: float, mu: float,
+                 thres: float = 1e-3, form: int = 0, emode: bool = False,
+                 A: Optional[torch.Tensor] = None, R: Optional[torch.Tensor] = None,
+                 p: Optional[torch.Tensor] = None, zf: Optional[torch.Tensor] = None
+                 ) -> Dict[str, Optional[torch.Tensor]]:
+    """One ProxGD line-search trial (glx_trial_proxgd). form 0: the row kernel on the given G;
+    form 1: the epilogue of G = A^T R (A, R given, G returned); form 2: the replicated half of the
+    row-sharded schedule from a given p (x = the thresholded iterate). emode: z holds
+    e = p - pthr and zf (int32 words, bit patterns of uint32; allocated zeroed unless passed in:
+    the kernels do not clear it) the masks and column bitmaps of e. Returns a dict with G, p,
+    pthr, z, sums (6 float64; None in form 2) and zf (None where not written)."""
+    n, l = x.shape
+    dt = _dt(x)
+    dev = x.device
+    m = A.shape[0] if form == 1 else 1
+    new = lambda: torch.empty((n, l), dtype=x.dtype, device=dev)  # noqa: E731
+    if form == 1:
+        G = new()
+    if form != 2:
+        p = new()
+    pthr, z = new(), new()
+    sums = None if form == 2 else torch.full((6,), float("nan"), dtype=torch.float64, device=dev)
+    zf = _zf_arg(zf, bool(emode), n, dev)
+    ws = _trial_ws(dt, m, n, l, dev)
+    check(lib().glx_trial_proxgd(dt, m, n, l, _ptr(A), _ptr(R), _ptr(G), x.data_ptr(), float(t),
+                                 float(mu), float(thres), int(form), 1 if emode else 0,
+                                 p.data_ptr(), pthr.data_ptr(), z.data_ptr(), _ptr(sums), _ptr(zf),
+                                 ws.data_ptr(), ws.numel(), _stream(dev)))
+    return {"G": G, "p": p, "pthr": pthr, "z": z, "sums": sums, "zf": zf}
+
+
+def trial_fista(y: Optional[torch.Tensor], G: Optional[torch.Tensor], xk: torch.Tensor, t: float,
+                mu: float, theta: float, theta_next: float, thres: float = 1e-3,
+                delta: float = 0.0, form: int = 0, prox: bool = True, split: bool = False,
+                A: Optional[torch.Tensor] = None, R: Optional[torch.Tensor] = None,
+                xc: Optional[torch.Tensor] = None, zf: Optional[torch.Tensor] = None
+                ) -> Dict[str, Optional[torch.Tensor]]:
+    """One FProxGD (prox) / FGD trial with the next combine (glx_trial_fista). form 0: the row
+    kernel on the given G; form 1: the epilogue of G = A^T R; form 2: the replicated half from a
+    given xc (y, G unused). split: also ec = xc - thr(xc) and zf, its masks and column bitmaps (as
+    trial_proxgd). Returns a dict with G, xc, vnext, ynext, ec, sums (4 float64, FGD 5; None in
+    form 2) and zf."""
+    n, l = xk.shape
+    dt = _dt(xk)
+    dev = xk.device
+    m = A.shape[0] if form == 1 else 1
+    new = lambda: torch.empty((n, l), dtype=xk.dtype, device=dev)  # noqa: E731
+    if form == 1:
+        G = new()
+    if form != 2:
+        xc = new()
+    vnext, ynext = new(), new()
+    ec = new() if split else None
+    sums = None if form == 2 else torch.full((6,), float("nan"), dtype=torch.float64, device=dev)
+    zf = _zf_arg(zf, bool(split), n, dev)
+    ws = _trial_ws(dt, m, n, l, dev)
+    check(lib().glx_trial_fista(dt, m, n, l, _ptr(A), _ptr(R), _ptr(G), _ptr(y), xk.data_ptr(),
+                                float(t), float(mu), float(thres), float(theta), float(theta_next),
+                                float(delta), int(form), 1 if prox else 0, xc.data_ptr(),
+                                vnext.data_ptr(), ynext.data_ptr(), _ptr(ec), _ptr(sums), _ptr(zf),
+                                ws.data_ptr(), ws.numel(), _stream(dev)))
+    if sums is not None:
+        sums = sums[:4 if prox else 5]
+    return {"G": G, "xc": xc, "vnext": vnext, "ynext": ynext, "ec": ec, "sums": sums, "zf": zf}
 
 
 def prox(W: torch.Tensor, t: float, mu: float, thres: float = 1e-3

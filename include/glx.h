@@ -250,6 +250,57 @@ int glx_residual_gradient2(int dtype, int64_t m, int64_t n, int64_t l, const voi
 int glx_flagged_rows_product(int dtype, int64_t m, int64_t n, int64_t l, const void* At,
                              const void* E, const uint32_t* row_masks, void* Y, int form,
                              void* workspace, size_t workspace_bytes, void* stream);
+/* ---- the line-search trial, one kernel at a time (test surface) ----
+ * The other half of an iteration: prox, hard threshold, the Armijo / backtracking sums, and in
+ * the split-candidate form the masks of e and the column bitmaps the A e gather walks. Both
+ * entries wrap the launchers a session uses and add no arithmetic of their own. Outputs are
+ * caller-owned device buffers of n x l values of dtype; sums_dev is 6 device doubles.
+ *
+ * zf (may be NULL) is a caller-owned, caller-zeroed device buffer of the bytes
+ * glx_trial_mask_bytes(n) gives, read as uint32 words. Layout, with npad = n rounded up to a
+ * multiple of 64:
+ *   words [0, npad):  the row masks, zf[k] bit c = e[k][c] != 0 (rows >= n stay as passed in);
+ *   behind them, as uint16 words, the column bitmaps: word g of column c, at index
+ *   c * (npad / 16) + g, holds rows 16 g .. 16 g + 15 (bit j = row 16 g + j has bit c), for
+ *   c < l and the npad / 16 row groups.
+ * An entry does not clear zf: a trial rewrites the words of the row groups it visits (the 16-row
+ * groups below n rounded up to 16, or whole 64 / 32-row panels in the fused forms) and leaves
+ * the others as they are, as in a session, which clears the buffer once at creation. zf needs
+ * l in {16, 32} and n < 65536.
+ *
+ * The workspace of the two entries is glx_trial_workspace_bytes (glx_kernel_workspace_bytes plus
+ * the per-panel counters a fused A^T R with K splits counts on); forms 0 and 2 take m = 1. */
+int glx_trial_mask_bytes(int64_t n, size_t* bytes);
+int glx_trial_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes);
+/* ProxGD's trial (gl_ProxGD_primal.py:65-74, 89-92): p = prox_{t mu}(x - t G), G_t = (x - p) / t,
+ * z = x - t G_t, pthr = p with |p| < thres zeroed; sums_dev = [sum G * G_t, sum G_t^2,
+ * sum_i ||p_i||, max |p| (NaN-propagating), #{entries the threshold changed}, #{rows it changed}].
+ *   form 0: the row kernel (k_prox_pgd) on the given G; A, R and m are unused.
+ *   form 1: the trial in the epilogue of G = A^T R (k_atr_prox): G is written. The tile and K
+ *           splits are the planner's for this shape under GLX_ATR_VARIANT / GLX_ATR_S /
+ *           GLX_ATR_FUSE_SPLIT; GLX_E_INVALID where that plan does not take a fused trial.
+ *   form 2: the replicated half of the row-sharded schedule (k_trial_split): p is an INPUT and
+ *           x the thresholded iterate; writes pthr, z (may be NULL) and zf; no sums.
+ * emode != 0 (needs zf): z receives e = p - pthr instead, zf the masks and bitmaps of e. In
+ * forms 0 and 1 zf must be NULL when emode == 0; form 2 writes zf, when given, for either. */
+int glx_trial_proxgd(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* R,
+                     void* G, const void* x, double t, double mu, double thres, int form, int emode,
+                     void* p, void* pthr, void* z, void* sums_dev, uint32_t* zf, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* FProxGD's / FGD's trial with the next combine (gl_FProxGD_primal.py:92-102, 136-145):
+ * xc = prox_{t mu}(y - t G) (prox = 1) or y - t G (prox = 0, FGD),
+ * vnext = thr(xk) + (xc - thr(xk)) / theta, ynext = (1 - theta_next) thr(xc) + theta_next vnext.
+ * sums_dev: prox = 1: [sum G * (xc - y), sum (xc - y)^2, sum_i ||xc_i||, max |xc|];
+ *           prox = 0: [.., .., sum_i (sqrt(||xc_i||^2 + delta^2) - delta), sum_i ||xc_i||, max |xc|].
+ *   form 0: the row kernel (k_fista_trial). ec and zf (both or neither, prox = 1 only):
+ *           ec = xc - thr(xc) and zf its masks and bitmaps.
+ *   form 1: the trial in the epilogue of G = A^T R (k_atr_fista), prox = 1 only; plan as above.
+ *   form 2: the replicated half (k_fista_split): xc is an INPUT; writes vnext and ynext. */
+int glx_trial_fista(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* R,
+                    void* G, const void* y, const void* xk, double t, double mu, double thres,
+                    double theta, double theta_next, double delta, int form, int prox, void* xc,
+                    void* vnext, void* ynext, void* ec, void* sums_dev, uint32_t* zf,
+                    void* workspace, size_t workspace_bytes, void* stream);
 /* Workspace bytes for the single-kernel entry points above. */
 int glx_kernel_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes);
 /* One-line description of the kernels (tile, split) the planner picks for this shape, for
