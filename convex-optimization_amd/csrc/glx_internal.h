@@ -538,9 +538,6 @@ void launch_threshold(const T* x, T* xo, int64_t nl, double thres, int* flag, in
 template <typename T>
 void launch_thr_axpby(T* xk, const T* vk, T* y, int64_t nl, double thres, double a, double b,
                       hipStream_t st);
-// v = xk + (x - xk)/theta
-template <typename T>
-void launch_fista_v(const T* xk, const T* x, T* v, int64_t nl, double theta, hipStream_t st);
 // SGD (mode 0) / GD (mode 1) step from the thresholded iterate xt: x = xt - alpha (g + mu xt/d),
 // xt = thr(x). out: [sum ||x_new_i||]
 template <typename T>
@@ -560,11 +557,12 @@ void launch_record_f(const double* s, int i_sumsq, int i_reg, double mu, double*
 // l = 1 descent pass in one sweep of A (kernels_gemv.hip): Gp[blocks][n] = per-workgroup
 // A^T (A xt - b) slabs, red.out[0..1] = sum (A x - b)^2, sum (A xt - b)^2, fh[0] (if non-null)
 // = 0.5 out[0] + fh_mu * rn[0]. gemv_fused_blocks() = workgroups to launch, 0 = not applicable.
+// nt: 0 / 1 = A read with the default / the non-temporal policy, -1 = GLX_GEMV_NT, else by size.
 int gemv_fused_blocks(int esize, int64_t m, int64_t n, int64_t l);
 template <typename T>
 void launch_gemv_fused(int blocks, const T* A, const T* x, const T* xt, const T* b, T* Gp, int64_t m,
                        int64_t n, double* fh, double fh_mu, const double* rn, Red red,
-                       hipStream_t st);
+                       hipStream_t st, int nt = -1);
 // G[j] = sum_{s<S} Gp[s][j] (slab order, deterministic)
 template <typename T>
 void launch_sum_cols(const T* Gp, int S, T* G, int64_t n, hipStream_t st);

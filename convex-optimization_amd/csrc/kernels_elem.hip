@@ -704,17 +704,6 @@ __global__ void k_publish(const double* __restrict__ s, int ns, double* host, un
   if (threadIdx.x == 0) publish_packet(s, ns, host, host_seq, seq, s2, off2, n2);
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_fista_v(const T* __restrict__ xk, const T* __restrict__ x,
-                                                 T* __restrict__ v, int64_t nl, double theta_) {
-  const T theta = (T)theta_;
-  const int64_t stride = (int64_t)gridDim.x * 256;
-  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < nl; idx += stride) {
-    const T xo = xk[idx];
-    v[idx] = xo + (x[idx] - xo) / theta;
-  }
-}
-
 __global__ void k_record_f(const double* __restrict__ s, int i_sumsq, int i_reg, double mu,
                            double* __restrict__ fh, int64_t idx) {
   if (threadIdx.x == 0) fh[idx] = 0.5 * s[i_sumsq] + mu * s[i_reg];
@@ -954,10 +943,6 @@ void launch_thr_axpby(T* xk, const T* vk, T* y, int64_t nl, double thres, double
   hipLaunchKernelGGL(k_thr_axpby<T>, dim3(grid_for(nl, 256 * 4)), dim3(256), 0, st, xk, vk, y, nl, thres,
                      a, b);
 }
-template <typename T>
-void launch_fista_v(const T* xk, const T* x, T* v, int64_t nl, double theta, hipStream_t st) {
-  hipLaunchKernelGGL(k_fista_v<T>, dim3(grid_for(nl, 256 * 4)), dim3(256), 0, st, xk, x, v, nl, theta);
-}
 void launch_record_f(const double* s, int i_sumsq, int i_reg, double mu, double* fh, int64_t idx,
                      hipStream_t st) {
   hipLaunchKernelGGL(k_record_f, dim3(1), dim3(64), 0, st, s, i_sumsq, i_reg, mu, fh, idx);
@@ -1010,8 +995,7 @@ void launch_publish(const double* s, int ns, double* host, unsigned* host_seq, u
                                    Red, hipStream_t);                                               \
   template void launch_count_above<T>(const T*, int64_t, const double*, Red, hipStream_t);          \
   template void launch_threshold<T>(const T*, T*, int64_t, double, int*, int, hipStream_t);        \
-  template void launch_thr_axpby<T>(T*, const T*, T*, int64_t, double, double, double, hipStream_t);\
-  template void launch_fista_v<T>(const T*, const T*, T*, int64_t, double, hipStream_t);
+  template void launch_thr_axpby<T>(T*, const T*, T*, int64_t, double, double, double, hipStream_t);
 
 GLX_INST(double)
 GLX_INST(float)

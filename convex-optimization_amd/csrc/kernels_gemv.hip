@@ -198,12 +198,14 @@ int gemv_fused_blocks(int esize, int64_t m, int64_t n, int64_t l) {
 constexpr double kGemvNtBytes = 384.0 * 1024 * 1024;
 template <typename T, int VPT, int RB>
 static void gemv_go(int blocks, const T* A, const T* x, const T* xt, const T* b, T* Gp, int64_t m,
-                    int64_t n, double* fh, double fh_mu, const double* rn, Red red, hipStream_t st) {
+                    int64_t n, double* fh, double fh_mu, const double* rn, Red red, hipStream_t st,
+                    int nt_arg) {
   static const int nt_env = [] {
     const char* e = std::getenv("GLX_GEMV_NT");
     return e ? std::atoi(e) : -1;
   }();
-  const bool nt = nt_env >= 0 ? nt_env != 0 : (double)m * n * sizeof(T) > kGemvNtBytes;
+  const int nt_on = nt_arg >= 0 ? nt_arg : nt_env;   // the caller's choice, then GLX_GEMV_NT
+  const bool nt = nt_on >= 0 ? nt_on != 0 : (double)m * n * sizeof(T) > kGemvNtBytes;
   if (nt)
     glx_launch((k_gemv_pair_fused<T, VPT, RB, true>), dim3((unsigned)blocks),
                        dim3(kGemvThreads), 0, st, A, x, xt, b, Gp, m, n, fh, fh_mu, rn, red);
@@ -215,13 +217,13 @@ static void gemv_go(int blocks, const T* A, const T* x, const T* xt, const T* b,
 template <typename T>
 void launch_gemv_fused(int blocks, const T* A, const T* x, const T* xt, const T* b, T* Gp, int64_t m,
                        int64_t n, double* fh, double fh_mu, const double* rn, Red red,
-                       hipStream_t st) {
+                       hipStream_t st, int nt) {
   constexpr int E = 16 / sizeof(T);
   const int64_t vpt = (n / E + kGemvThreads - 1) / kGemvThreads;
-  if (vpt <= 1) gemv_go<T, 1, 2>(blocks, A, x, xt, b, Gp, m, n, fh, fh_mu, rn, red, st);
-  else if (vpt <= 2) gemv_go<T, 2, 2>(blocks, A, x, xt, b, Gp, m, n, fh, fh_mu, rn, red, st);
-  else if (vpt <= 4) gemv_go<T, 4, 2>(blocks, A, x, xt, b, Gp, m, n, fh, fh_mu, rn, red, st);
-  else gemv_go<T, 8, 1>(blocks, A, x, xt, b, Gp, m, n, fh, fh_mu, rn, red, st);
+  if (vpt <= 1) gemv_go<T, 1, 2>(blocks, A, x, xt, b, Gp, m, n, fh, fh_mu, rn, red, st, nt);
+  else if (vpt <= 2) gemv_go<T, 2, 2>(blocks, A, x, xt, b, Gp, m, n, fh, fh_mu, rn, red, st, nt);
+  else if (vpt <= 4) gemv_go<T, 4, 2>(blocks, A, x, xt, b, Gp, m, n, fh, fh_mu, rn, red, st, nt);
+  else gemv_go<T, 8, 1>(blocks, A, x, xt, b, Gp, m, n, fh, fh_mu, rn, red, st, nt);
 }
 
 template <typename T>
@@ -231,7 +233,8 @@ void launch_sum_cols(const T* Gp, int S, T* G, int64_t n, hipStream_t st) {
 
 #define GLX_GEMV_INST(T)                                                                           \
   template void launch_gemv_fused<T>(int, const T*, const T*, const T*, const T*, T*, int64_t,     \
-                                     int64_t, double*, double, const double*, Red, hipStream_t); \
+                                     int64_t, double*, double, const double*, Red, hipStream_t, \
+                                     int);                                                         \
   template void launch_sum_cols<T>(const T*, int, T*, int64_t, hipStream_t);
 GLX_GEMV_INST(double)
 GLX_GEMV_INST(float)

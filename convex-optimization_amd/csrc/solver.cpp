@@ -2800,4 +2800,138 @@ int glx_prox(int dtype, int64_t n, int64_t l, const void* W, double t, double mu
   });
 }
 
+// ---- the descent-method kernels, one launch at a time (test surface) ----
+// workspace of the descent entries: the single-kernel workspace (layout and size unchanged), then
+// the blocks x n gradient slabs of the one-pass kernel where it applies
+static size_t descent_ws(int es, int64_t m, int64_t n, int64_t l, size_t* slabs_off) {
+  const size_t kb = kernel_ws(es, make_plan(es, m, n, l, 0), nullptr, nullptr);
+  const int blocks = gemv_fused_blocks(es, m, n, l);
+  if (blocks == 0) return kb;
+  const size_t off = (kb + 255) & ~size_t(255);
+  if (slabs_off) *slabs_off = off;
+  return off + (size_t)blocks * (size_t)n * es;
+}
+
+int glx_descent_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes) {
+  return guarded([&] {
+    if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "bad dtype"};
+    if (m <= 0 || n <= 0 || l <= 0 || l > kMaxL || !bytes) throw Error{GLX_E_INVALID, "bad shape"};
+    *bytes = descent_ws(dtype == GLX_F64 ? 8 : 4, m, n, l, nullptr);
+  });
+}
+
+int glx_descent_step(int dtype, int64_t n, int64_t l, int mode, const void* g, int S, double alpha,
+                     double mu, double thres, double delta, void* x, void* xt, void* sum_dev,
+                     void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (mode != 0 && mode != 1) throw Error{GLX_E_INVALID, "mode must be 0 (SGD) or 1 (GD)"};
+    if (!g || S < 1 || !x || !xt || x == xt || !sum_dev) throw Error{GLX_E_INVALID, "bad argument"};
+    GemmPlan p;
+    KernelWs k = kernel_setup(dtype, 1, n, l, ws, wsb, 0, st, &p);
+    Red r{k.part, k.ticket, static_cast<double*>(sum_dev)};
+    if (dtype == GLX_F64)
+      launch_descent<double>((double*)x, (double*)xt, (const double*)g, S, n, l, alpha, mu, thres, delta, mode, r, st);
+    else
+      launch_descent<float>((float*)x, (float*)xt, (const float*)g, S, n, l, alpha, mu, thres, delta, mode, r, st);
+    check_launch();
+  });
+}
+
+int glx_fgd_gradient(int dtype, int64_t n, int64_t l, const void* y, const void* gp, int S, double mu,
+                     double delta, void* g, void* sum_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!y || !gp || S < 1 || !g || !sum_dev) throw Error{GLX_E_INVALID, "bad argument"};
+    GemmPlan p;
+    KernelWs k = kernel_setup(dtype, 1, n, l, ws, wsb, 0, st, &p);
+    Red r{k.part, k.ticket, static_cast<double*>(sum_dev)};
+    if (dtype == GLX_F64)
+      launch_fgd_grad<double>((const double*)y, (const double*)gp, S, (double*)g, n, l, mu, delta, r, st);
+    else
+      launch_fgd_grad<float>((const float*)y, (const float*)gp, S, (float*)g, n, l, mu, delta, r, st);
+    check_launch();
+  });
+}
+
+int glx_row_stats(int dtype, int64_t n, int64_t l, const void* x, void* stats_dev, void* ws, size_t wsb,
+                  void* stream) {
+  return guarded([&] {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!x || !stats_dev) throw Error{GLX_E_INVALID, "null argument"};
+    GemmPlan p;
+    KernelWs k = kernel_setup(dtype, 1, n, l, ws, wsb, 0, st, &p);
+    double* s = static_cast<double*>(stats_dev);
+    auto go = [&](auto* tag) {
+      typedef std::remove_pointer_t<decltype(tag)> T;
+      launch_rownorm_max<T>((const T*)x, n, l, Red{k.part, k.ticket, s}, st);
+      check_launch();
+      launch_count_above<T>((const T*)x, n * l, s + 1, Red{k.part, k.ticket, s + 2}, st);
+    };
+    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
+    else go(static_cast<float*>(nullptr));
+    check_launch();
+  });
+}
+
+int glx_threshold(int dtype, int64_t count, const void* x, void* xo, double thres, int* flag_dev,
+                  int epoch, void* stream) {
+  return guarded([&] {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "bad dtype"};
+    if (count <= 0 || !x || !xo || !flag_dev) throw Error{GLX_E_INVALID, "bad argument"};
+    if (dtype == GLX_F64) launch_threshold<double>((const double*)x, (double*)xo, count, thres, flag_dev, epoch, st);
+    else launch_threshold<float>((const float*)x, (float*)xo, count, thres, flag_dev, epoch, st);
+    check_launch();
+  });
+}
+
+int glx_thr_combine(int dtype, int64_t count, void* xk, const void* vk, void* y, double thres, double a,
+                    double b, void* stream) {
+  return guarded([&] {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "bad dtype"};
+    if (count <= 0 || !xk || !vk || !y) throw Error{GLX_E_INVALID, "bad argument"};
+    if (dtype == GLX_F64) launch_thr_axpby<double>((double*)xk, (const double*)vk, (double*)y, count, thres, a, b, st);
+    else launch_thr_axpby<float>((float*)xk, (const float*)vk, (float*)y, count, thres, a, b, st);
+    check_launch();
+  });
+}
+
+int glx_descent_pass(int dtype, int64_t m, int64_t n, const void* A, const void* x, const void* xt,
+                     const void* b, void* G, void* sums_dev, void* fh_dev, double fh_mu,
+                     const void* rn_dev, int nt, int* blocks, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "bad dtype"};
+    if (m <= 0 || n <= 0) throw Error{GLX_E_INVALID, "bad shape"};
+    if (!A || !x || !xt || !b || !G || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
+    if (fh_dev != nullptr && rn_dev == nullptr) throw Error{GLX_E_INVALID, "fh_dev needs rn_dev"};
+    if (nt < -1 || nt > 1) throw Error{GLX_E_INVALID, "nt must be -1 (as a session decides), 0 or 1"};
+    const int es = dtype == GLX_F64 ? 8 : 4;
+    const int nb = gemv_fused_blocks(es, m, n, 1);
+    if (nb == 0)
+      throw Error{GLX_E_INVALID, "the one-pass kernel needs n a multiple of " + std::to_string(16 / es) +
+                                     " and at most " + std::to_string(8 * 512 * (16 / es)) + " (n = " +
+                                     std::to_string(n) + ")"};
+    size_t off = 0;
+    if (!ws || wsb < descent_ws(es, m, n, 1, &off)) throw Error{GLX_E_WORKSPACE, "workspace too small"};
+    GemmPlan p;
+    KernelWs k = kernel_setup(dtype, m, n, 1, ws, wsb, 0, st, &p);
+    void* slabs = static_cast<char*>(ws) + off;
+    Red r{k.part, k.ticket, static_cast<double*>(sums_dev)};
+    auto go = [&](auto* tag) {
+      typedef std::remove_pointer_t<decltype(tag)> T;
+      launch_gemv_fused<T>(nb, (const T*)A, (const T*)x, (const T*)xt, (const T*)b, (T*)slabs, m, n,
+                           static_cast<double*>(fh_dev), fh_mu, static_cast<const double*>(rn_dev), r, st, nt);
+      check_launch();
+      launch_sum_cols<T>((const T*)slabs, nb, (T*)G, n, st);
+    };
+    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
+    else go(static_cast<float*>(nullptr));
+    check_launch();
+    if (blocks) *blocks = nb;
+  });
+}
+
 }  // extern "C"

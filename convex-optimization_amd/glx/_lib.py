@@ -104,6 +104,21 @@ _SIGS = {
                                 c_void_p, c_void_p, c_double, c_double, c_double, c_double,
                                 c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_descent_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "glx_descent_step": (c_int, [c_int, c_int64, c_int64, c_int, c_void_p, c_int, c_double,
+                                 c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_size_t, c_void_p]),
+    "glx_fgd_gradient": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_double,
+                                 c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_row_stats": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
+                              c_void_p]),
+    "glx_threshold": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_double, c_void_p, c_int,
+                              c_void_p]),
+    "glx_thr_combine": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_double,
+                                c_double, c_void_p]),
+    "glx_descent_pass": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_int,
+                                 POINTER(c_int), c_void_p, c_size_t, c_void_p]),
     "glx_kernel_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
     "glx_plan_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_char_p, c_size_t]),
     "glx_comm_unique_id": (c_int, [POINTER(c_uint8)]),

@@ -5,7 +5,9 @@ These are the dense products and the group prox of the reference iteration expos
 time — ``A @ x - b`` (gl_ProxGD_primal.py:25,61), ``A.T @ r`` (:129) and ``prox_th``
 (:65-71) — used by the kernel-level tests and available for composition, and one line-search
 trial at a time (``glx_trial_proxgd`` / ``glx_trial_fista``: the row kernels, the A^T R epilogues
-and the replicated halves of the row-sharded schedules). All tensors are contiguous device
+and the replicated halves of the row-sharded schedules), and the descent-method kernels one
+launch at a time (``glx_descent_step``, ``glx_fgd_gradient``, ``glx_row_stats``,
+``glx_threshold``, ``glx_thr_combine``, ``glx_descent_pass``). All tensors are contiguous device
 tensors of one dtype (float32 / float64).
 """
 from __future__ import annotations
@@ -227,6 +229,132 @@ def trial_fista(y: Optional[torch.Tensor], G: Optional[torch.Tensor], xk: torch.
     if sums is not None:
         sums = sums[:4 if prox else 5]
     return {"G": G, "xc": xc, "vnext": vnext, "ynext": ynext, "ec": ec, "sums": sums, "zf": zf}
+
+
+def _descent_ws(dtype: int, m: int, n: int, l: int, device) -> torch.Tensor:
+    nb = ctypes.c_size_t(0)
+    check(lib().glx_descent_workspace_bytes(dtype, m, n, l, ctypes.byref(nb)))
+    return torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+
+
+def _nan_sums(k: int, device) -> torch.Tensor:
+    return torch.full((k,), float("nan"), dtype=torch.float64, device=device)
+
+
+def _slabs(g: torch.Tensor, n: int, l: int) -> int:
+    if g.dim() == 2:
+        if tuple(g.shape) != (n, l):
+            raise ValueError("g must be (n, l) or (S, n, l)")
+        return 1
+    if g.dim() != 3 or tuple(g.shape[1:]) != (n, l) or g.shape[0] < 1:
+        raise ValueError("g must be (n, l) or (S, n, l)")
+    return int(g.shape[0])
+
+
+def descent_step(xt: torch.Tensor, g: torch.Tensor, alpha: float, mu: float, thres: float = 1e-3,
+                 delta: float = 0.0, mode: int = 0) -> Dict[str, torch.Tensor]:
+    """One SGD (mode 0) / GD (mode 1) step (glx_descent_step) from the thresholded iterate xt
+    (n x l, left unchanged: the kernel works on a copy) and the gradient g, (n, l) or S slabs
+    (S, n, l) summed in slab order. Returns a dict with x = xt - alpha (g + mu xt / d),
+    xt = thr(x) and sum (1 float64: sum_i ||x_i||)."""
+    n, l = xt.shape
+    dt = _dt(xt)
+    dev = xt.device
+    S = _slabs(g, n, l)
+    x = torch.empty_like(xt)
+    xt_io = xt.clone()
+    s = _nan_sums(1, dev)
+    ws = _descent_ws(dt, 1, n, l, dev)
+    check(lib().glx_descent_step(dt, n, l, int(mode), g.data_ptr(), S, float(alpha), float(mu),
+                                 float(thres), float(delta), x.data_ptr(), xt_io.data_ptr(),
+                                 s.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return {"x": x, "xt": xt_io, "sum": s}
+
+
+def fgd_gradient(y: torch.Tensor, gp: torch.Tensor, mu: float, delta: float
+                 ) -> Dict[str, torch.Tensor]:
+    """FGD's smoothed gradient (glx_fgd_gradient): g = sum of gp's slabs + mu y / sqrt(||y_i||^2 +
+    delta^2), gp (n, l) or (S, n, l). Returns a dict with g and sum (1 float64: the smoothed
+    norm sum_i (sqrt(||y_i||^2 + delta^2) - delta))."""
+    n, l = y.shape
+    dt = _dt(y)
+    dev = y.device
+    S = _slabs(gp, n, l)
+    g = torch.empty_like(y)
+    s = _nan_sums(1, dev)
+    ws = _descent_ws(dt, 1, n, l, dev)
+    check(lib().glx_fgd_gradient(dt, n, l, y.data_ptr(), gp.data_ptr(), S, float(mu), float(delta),
+                                 g.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(),
+                                 _stream(dev)))
+    return {"g": g, "sum": s}
+
+
+def row_stats(x: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """glx_row_stats: a dict with stats = [sum_i ||x_i||, max |x|, #{|x| > 1e-6 max |x|}]
+    (3 float64)."""
+    n, l = x.shape
+    dt = _dt(x)
+    s = _nan_sums(3, x.device)
+    ws = _descent_ws(dt, 1, n, l, x.device)
+    check(lib().glx_row_stats(dt, n, l, x.data_ptr(), s.data_ptr(), ws.data_ptr(), ws.numel(),
+                              _stream(x.device)))
+    return {"stats": s}
+
+
+def threshold(x: torch.Tensor, thres: float, flag: Optional[torch.Tensor] = None, epoch: int = 1,
+              inplace: bool = False) -> Dict[str, torch.Tensor]:
+    """glx_threshold on the x.numel() values of x: xo = x with |x| < thres zeroed (inplace: x
+    itself), flag (1 int32, -1 unless passed in) = epoch when a nonzero value was zeroed."""
+    dt = _dt(x)
+    xo = x if inplace else torch.empty_like(x)
+    if flag is None:
+        flag = torch.full((1,), -1, dtype=torch.int32, device=x.device)
+    if flag.dtype != torch.int32:
+        raise ValueError("flag must be an int32 tensor")
+    check(lib().glx_threshold(dt, x.numel(), x.data_ptr(), xo.data_ptr(), float(thres),
+                              flag.data_ptr(), int(epoch), _stream(x.device)))
+    return {"xo": xo, "flag": flag}
+
+
+def thr_combine(xk: torch.Tensor, vk: torch.Tensor, thres: float, a: float, b: float
+                ) -> Dict[str, torch.Tensor]:
+    """glx_thr_combine: a dict with xk = thr(xk) (a copy; the kernel's in-place output) and
+    y = a thr(xk) + b vk."""
+    dt = _dt(xk)
+    xo = xk.clone()
+    y = torch.empty_like(xk)
+    check(lib().glx_thr_combine(dt, xk.numel(), xo.data_ptr(), vk.data_ptr(), y.data_ptr(),
+                                float(thres), float(a), float(b), _stream(xk.device)))
+    return {"xk": xo, "y": y}
+
+
+def descent_pass(A: torch.Tensor, x: torch.Tensor, xt: torch.Tensor, b: torch.Tensor,
+                 fh_mu: Optional[float] = None, rn: Optional[torch.Tensor] = None, nt: int = -1,
+                 G: Optional[torch.Tensor] = None, sums: Optional[torch.Tensor] = None
+                 ) -> Dict[str, object]:
+    """One pass over A of an l = 1 descent iteration (glx_descent_pass): G = A^T (A xt - b),
+    sums = [sum (A x - b)^2, sum (A xt - b)^2] (2 float64) and, with fh_mu and rn (1 float64
+    device value) given, fh = 0.5 sums[0] + fh_mu rn. x, xt of n values, b of m. G and sums are
+    allocated (sums filled with NaN) unless passed in. Returns a dict with G, sums, fh (None
+    without fh_mu) and blocks, the workgroup count. GlxError (GLX_E_INVALID) where the kernel
+    does not apply."""
+    m, n = A.shape
+    dt = _dt(A)
+    dev = A.device
+    if x.numel() != n or xt.numel() != n or b.numel() != m:
+        raise ValueError("x, xt of n values and b of m")
+    if G is None:
+        G = torch.empty(n, dtype=A.dtype, device=dev)
+    if sums is None:
+        sums = _nan_sums(2, dev)
+    fh = _nan_sums(1, dev) if fh_mu is not None else None
+    nb = ctypes.c_int(0)
+    ws = _descent_ws(dt, m, n, 1, dev)
+    check(lib().glx_descent_pass(dt, m, n, A.data_ptr(), x.data_ptr(), xt.data_ptr(), b.data_ptr(),
+                                 G.data_ptr(), sums.data_ptr(), _ptr(fh),
+                                 float(fh_mu) if fh_mu is not None else 0.0, _ptr(rn), int(nt),
+                                 ctypes.byref(nb), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return {"G": G, "sums": sums, "fh": fh, "blocks": int(nb.value)}
 
 
 def prox(W: torch.Tensor, t: float, mu: float, thres: float = 1e-3

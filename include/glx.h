@@ -301,6 +301,52 @@ int glx_trial_fista(int dtype, int64_t m, int64_t n, int64_t l, const void* A, c
                     double theta, double theta_next, double delta, int form, int prox, void* xc,
                     void* vnext, void* ynext, void* ec, void* sums_dev, uint32_t* zf,
                     void* workspace, size_t workspace_bytes, void* stream);
+/* ---- the descent-method kernels, one launch at a time (test surface) ----
+ * What SGD, GD and FGD run between the dense products, and the one-pass kernel of an l = 1
+ * descent iteration. Each entry wraps the launcher a session uses and adds no arithmetic of its
+ * own; buffers are caller-owned device memory of dtype, sums are device doubles. The workspace of
+ * the entries that take one is glx_descent_workspace_bytes: glx_kernel_workspace_bytes plus, where
+ * the one-pass kernel applies to (m, n, l), its per-workgroup gradient slabs. The row entries
+ * take any m there (1 will do). */
+int glx_descent_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes);
+/* The SGD (mode 0, gl_SGD_primal.py:56-61, 93-96) / GD (mode 1, gl_GD_primal.py:59-63, 95-98)
+ * step from the thresholded iterate xt (in / out) and the gradient g = the sum, in slab order, of
+ * S >= 1 slabs of n * l values:
+ *   d = (||xt_i|| < thres) + ||xt_i||  (mode 0)  or  sqrt(||xt_i||^2 + delta^2)  (mode 1),
+ *   x = xt - alpha (g + mu xt / d)  (out),  xt = x with |x| < thres zeroed,
+ *   sum_dev[0] = sum_i ||x_i||. x and xt must not alias. */
+int glx_descent_step(int dtype, int64_t n, int64_t l, int mode, const void* g, int S, double alpha,
+                     double mu, double thres, double delta, void* x, void* xt, void* sum_dev,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* FGD's smoothed gradient (gl_FGD_primal.py:64-72): g = sum of the S slabs of gp
+ * + mu y / sqrt(||y_i||^2 + delta^2); sum_dev[0] = sum_i (sqrt(||y_i||^2 + delta^2) - delta). */
+int glx_fgd_gradient(int dtype, int64_t n, int64_t l, const void* y, const void* gp, int S, double mu,
+                     double delta, void* g, void* sum_dev, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* stats_dev = [sum_i ||x_i||, max |x| (NaN-propagating), #{|x| > 1e-6 max |x|}]: the row-norm
+ * kernel, then the count reading the maximum the first just wrote, on the same partials and
+ * ticket (sparsity_func of the SGD / GD log line). */
+int glx_row_stats(int dtype, int64_t n, int64_t l, const void* x, void* stats_dev, void* workspace,
+                  size_t workspace_bytes, void* stream);
+/* xo = x with |x| < thres zeroed (count values; xo may equal x). *flag_dev = epoch when a nonzero
+ * value was zeroed, else left as it is. */
+int glx_threshold(int dtype, int64_t count, const void* x, void* xo, double thres, int* flag_dev,
+                  int epoch, void* stream);
+/* FISTA / FGD's threshold and combine (gl_FGD_primal.py:139-142): xk[|xk| < thres] = 0 in place,
+ * y = a xk + b vk. */
+int glx_thr_combine(int dtype, int64_t count, void* xk, const void* vk, void* y, double thres, double a,
+                    double b, void* stream);
+/* One pass over A (m x n) of an l = 1 descent iteration, then the column sum of its slabs:
+ * G = A^T (A xt - b), sums_dev = [sum (A x - b)^2, sum (A xt - b)^2], and, when fh_dev is given
+ * (it needs rn_dev), fh_dev[0] = 0.5 sums_dev[0] + fh_mu * rn_dev[0]. nt: 0 / 1 = A read with the
+ * default / the non-temporal policy, -1 = as a session decides. *blocks (may be NULL) receives
+ * the workgroup count. GLX_E_INVALID, with nothing written, where the kernel does not apply:
+ * n no multiple of 16 / sizeof(dtype), or more than 8 vectors of 16 bytes per thread
+ * (n > 4096 * 16 / sizeof(dtype)). */
+int glx_descent_pass(int dtype, int64_t m, int64_t n, const void* A, const void* x, const void* xt,
+                     const void* b, void* G, void* sums_dev, void* fh_dev, double fh_mu,
+                     const void* rn_dev, int nt, int* blocks, void* workspace, size_t workspace_bytes,
+                     void* stream);
 /* Workspace bytes for the single-kernel entry points above. */
 int glx_kernel_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes);
 /* One-line description of the kernels (tile, split) the planner picks for this shape, for

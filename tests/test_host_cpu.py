@@ -205,6 +205,35 @@ def test_kernel_workspace_covers_every_planned_split():
         assert nb.value >= 8 * m * l * max(splits) * 3, (shp, nb.value, splits)
 
 
+def test_descent_workspace_adds_the_gradient_slabs():
+    """glx_descent_workspace_bytes holds the single-kernel workspace plus, where the one-pass kernel
+    applies, its blocks x n gradient slabs (blocks = ceil(m / 8), at most 256); where it does not
+    (l != 1, n no multiple of 16 / esize, more than 8 vectors per thread) it equals
+    glx_kernel_workspace_bytes, whose own sizes the recorded plan fixture pins."""
+    from glx import _lib
+
+    def sizes(dt, m, n, l):
+        a, b = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        _lib.check(_lib.lib().glx_kernel_workspace_bytes(dt, m, n, l, ctypes.byref(a)))
+        _lib.check(_lib.lib().glx_descent_workspace_bytes(dt, m, n, l, ctypes.byref(b)))
+        return a.value, b.value
+
+    f64 = [(m, 64) for m in range(1, 10)] + [(m, 4098) for m in range(1, 10)] + \
+        [(7, 2), (9, 1024), (13, 1026), (37, 2050), (17, 8192), (33, 512), (2049, 64), (3001, 1030)]
+    f32 = [(7, 4), (9, 2048), (13, 2052), (21, 8196), (5, 16384), (3001, 1028)]
+    for dt, es, shapes in ((_lib.GLX_F64, 8, f64), (_lib.GLX_F32, 4, f32)):
+        for m, n in shapes:
+            blocks = max(1, min(256, (m + 7) // 8))
+            kernel, descent = sizes(dt, m, n, 1)
+            assert kernel + blocks * n * es <= descent < kernel + blocks * n * es + 512, (dt, m, n)
+    for dt, m, n, l in [(_lib.GLX_F64, 9, 1031, 1), (_lib.GLX_F64, 9, 8194, 1), (_lib.GLX_F32, 9, 16388, 1),
+                        (_lib.GLX_F64, 9, 1024, 2), (_lib.GLX_F32, 1, 1000, 17), (_lib.GLX_F64, 1, 17, 128)]:
+        kernel, descent = sizes(dt, m, n, l)
+        assert descent == kernel, (dt, m, n, l)
+    nb = ctypes.c_size_t(0)
+    assert _lib.lib().glx_descent_workspace_bytes(_lib.GLX_F64, 0, 64, 1, ctypes.byref(nb)) == 1   # GLX_E_INVALID
+
+
 def _mode_fixture():
     """(tests/golden/make_mode_golden.py as a module, the recorded tests/golden/mode_golden.json)"""
     import json
