@@ -589,5 +589,42 @@ __device__ inline unsigned fista_row(const T (&yv)[EPL], const T (&gv)[EPL], con
   return ecv != nullptr ? row_or<LPR>(mk) : 0u;
 }
 
+// ------------------------------------------------------------------------------------------
+// Dual ADMM's row step (gl_ADMM_dual.py:44-46, 64-67) for a lane that holds EPL elements of the
+// row (as prox_pgd_row), with g = A^T z, in the reference's evaluation order:
+//   w = x / rho - g,  u+ = (mu w) / max(||w||, mu)  (np.clip(., a_min=mu): NaN stays NaN),
+//   r = u+ + g,       x+ = x - (tau rho) r.
+// acc (per thread, reduced over the grid by the caller): [sum_i ||x+_i||, max |x+|].
+// Shared by the row kernel (k_admm_dual) and the A^T z epilogue that fuses it (k_atr_admm), so
+// both write the same bits.
+// ------------------------------------------------------------------------------------------
+template <typename T, int LPR, int EPL>
+__device__ inline void admm_dual_row(const T (&xv)[EPL], const T (&gv)[EPL], const bool (&ok)[EPL],
+                                     bool rv, int sub, T rho, T taurho, T mu, T (&uv)[EPL],
+                                     T (&xn)[EPL], T (&rr)[EPL], double (&acc)[2]) {
+  T w[EPL];
+  T sq = T(0);
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) {
+    w[e] = xv[e] / rho - gv[e];
+    sq = sq + w[e] * w[e];
+  }
+  const T nrm = __builtin_sqrt(row_allsum<LPR>(sq));
+  const T d = (nrm < mu) ? mu : nrm;   // NaN compares false and stays
+  T xsq = T(0);
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) {
+    uv[e] = (mu * w[e]) / d;
+    rr[e] = uv[e] + gv[e];
+    xn[e] = xv[e] - taurho * rr[e];
+    if (ok[e]) {
+      acc[1] = nan_max(acc[1], (double)tabs(xn[e]));
+      xsq = xsq + xn[e] * xn[e];
+    }
+  }
+  const T xnorm = __builtin_sqrt(row_allsum<LPR>(xsq));
+  if (rv && sub == 0) acc[0] += (double)xnorm;
+}
+
 }  // namespace glx
 #endif  // GLX_DEVICE_H_

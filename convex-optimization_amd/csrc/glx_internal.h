@@ -327,6 +327,45 @@ void launch_atr_fista(const GemmPlan& p, const T* A, const T* R, T* G, const T* 
                       T* Gp = nullptr, unsigned* pcnt = nullptr, T* ec = nullptr,
                       unsigned* zf = nullptr);
 
+// Dual ADMM's row step fused into g = A^T z (same plan condition as launch_atr_prox, and the
+// plan's tile built `fused` for T): G = A^T Z, then u+, x+, r of launch_admm_dual and its two sums
+// into red. Gp / pcnt: the slabs and per-panel counters of K splits, as launch_atr_prox.
+template <typename T>
+void launch_atr_admm(const GemmPlan& p, const T* A, const T* Z, T* G, const T* x, T* un, T* xn, T* rn,
+                     double rho, double taurho, double mu, Red red, hipStream_t st, T* Gp = nullptr,
+                     unsigned* pcnt = nullptr);
+
+// The unfused row step on the same plan's panel layout (one workgroup per panel, the lanes
+// holding the rows the epilogue's lanes hold): g = S slabs of launch_atr under plan p, summed in
+// slab order. Every bit it writes, the two sums included, equals launch_atr_admm's. Needs the
+// plan condition of launch_atr_admm. gout (may be NULL) receives g.
+template <typename T>
+void launch_admm_dual_panel(const GemmPlan& p, const T* x, const T* g, int S, T* gout, T* un, T* xn,
+                            T* rn, double rho, double taurho, double mu, Red red, hipStream_t st);
+
+// ---- the dual ADMM solver's own kernels (kernels_admm.hip; gl_ADMM_dual.py:61-93) ----
+// v = (Ax - rho Au) - b over ml values (the right-hand side of the K product, :63)
+template <typename T>
+void launch_admm_v(const T* Ax, const T* Au, const T* b, T* v, int64_t ml, double rho, hipStream_t st);
+// The row step (:64-67) on g = the sum, in slab order, of S slabs of n * l values (gout, when
+// non-null, receives it): w = x / rho - g, u+ = (mu w) / max(||w_i||, mu), r = u+ + g,
+// x+ = x - (tau rho) r. out: [sum_i ||x+_i||, max |x+| (NaN-propagating)]
+template <typename T>
+void launch_admm_dual(const T* x, const T* g, int S, T* gout, T* un, T* xn, T* rn, int64_t n, int64_t l,
+                      double rho, double taurho, double mu, Red red, hipStream_t st);
+// The batched pass's finalize: P = S slabs of A x+ then S slabs of A u+ (ml values each), summed
+// in slab order into Ax and Au; s = Au_old - Au_new (:68) where s != NULL (Au is read first);
+// out: [sum (Ax - b)^2]
+template <typename T>
+void launch_admm_fin(const T* P, int S, const T* b, T* Ax, T* Au, T* s, int64_t ml, Red red,
+                     hipStream_t st);
+// gram (l x l doubles, row-major) = R^T R for R of rows x l (l <= 32), accumulated in double:
+// gram_blocks(rows) workgroups each reduce a contiguous slab of rows, in row order, into a partial
+// at part[block * l * l]; a second launch adds the partials in slab order (bit-reproducible)
+int gram_blocks(int64_t rows);
+template <typename T>
+void launch_gram(const T* R, int64_t rows, int64_t l, double* part, double* gram, hipStream_t st);
+
 // ---- split-candidate A e from a transposed copy of A (kernels_gather.hip) ----
 // gather_ok: the shape supports it (l in {16, 32}, n < 65536); gather_split: K splits of the
 // flagged-row list for m output rows (slabs P[S][m][l]).

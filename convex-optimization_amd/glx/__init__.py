@@ -5,6 +5,7 @@ Public surface:
     (also re-exported as the drop-in modules ``gl_ProxGD_primal`` etc. next to this package);
   * ``Session`` — the same solver split into steps (benchmarks);
   * ``kernels`` — single HIP kernels (residual, gradient, prox);
+  * ``admm`` — the dual ADMM solver ``gl_Admm_dual`` (``admm.solve``; drop-in module ``gl_ADMM_dual``);
   * ``dist`` — row sharding + RCCL communicator.
 """
 from ._lib import LIB_PATH, GlxError, lib  # noqa: F401

@@ -47,6 +47,13 @@ class GlxResult(ctypes.Structure):
                 ("stats", c_double * 8), ("record_waits", c_int64)]
 
 
+class GlxAdmmOpts(ctypes.Structure):
+    """glx_admm_opts (include/glx.h): the options of the dual ADMM solver."""
+    _fields_ = [("maxit", c_int32), ("converge_len", c_int32), ("thres", c_double),
+                ("tau", c_double), ("rho", c_double), ("fused", c_int32),
+                ("max_total_iters", c_int64), ("reserved", c_int32 * 4)]
+
+
 class GlxError(RuntimeError):
     """Error returned by libglx (message from glx_last_error())."""
 
@@ -121,6 +128,19 @@ _SIGS = {
                                  POINTER(c_int), c_void_p, c_size_t, c_void_p]),
     "glx_kernel_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
     "glx_plan_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_char_p, c_size_t]),
+    "glx_admm_default_opts": (c_int, [POINTER(GlxAdmmOpts)]),
+    "glx_admm_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(GlxAdmmOpts),
+                                         POINTER(c_size_t)]),
+    "glx_admm_dual_solve": (c_int, [POINTER(GlxProblem), c_void_p, POINTER(GlxAdmmOpts), c_void_p,
+                                    c_size_t, POINTER(GlxResult), c_void_p]),
+    "glx_admm_trace": (c_int, [POINTER(c_double), c_int64, POINTER(c_int64)]),
+    "glx_admm_describe": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(GlxAdmmOpts), c_char_p,
+                                  c_size_t]),
+    "glx_admm_dual_step": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_double, c_double, c_double, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_gram": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_sym_lambda_max": (c_int, [POINTER(c_double), c_int, POINTER(c_double)]),
     "glx_comm_unique_id": (c_int, [POINTER(c_uint8)]),
     "glx_comm_create": (c_int, [POINTER(c_void_p), POINTER(c_uint8), c_int, c_int]),
     "glx_comm_create_host": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
@@ -182,3 +202,18 @@ def default_opts(method: int) -> GlxOpts:
     o = GlxOpts()
     check(lib().glx_default_opts(method, ctypes.byref(o)))
     return o
+
+
+def admm_default_opts() -> GlxAdmmOpts:
+    o = GlxAdmmOpts()
+    check(lib().glx_admm_default_opts(ctypes.byref(o)))
+    return o
+
+
+def admm_describe(dtype: int, m: int, n: int, l: int, opts: "GlxAdmmOpts | None" = None) -> str:
+    """The tiles of the dual ADMM solver's three passes and whether its row step is fused
+    (glx_admm_describe: resolved on the host, no device)."""
+    buf = ctypes.create_string_buffer(2048)
+    check(lib().glx_admm_describe(dtype, m, n, l, ctypes.byref(opts) if opts is not None else None,
+                                  buf, len(buf)))
+    return buf.value.decode()

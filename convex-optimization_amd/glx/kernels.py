@@ -7,7 +7,9 @@ time — ``A @ x - b`` (gl_ProxGD_primal.py:25,61), ``A.T @ r`` (:129) and ``pro
 trial at a time (``glx_trial_proxgd`` / ``glx_trial_fista``: the row kernels, the A^T R epilogues
 and the replicated halves of the row-sharded schedules), and the descent-method kernels one
 launch at a time (``glx_descent_step``, ``glx_fgd_gradient``, ``glx_row_stats``,
-``glx_threshold``, ``glx_thr_combine``, ``glx_descent_pass``). All tensors are contiguous device
+``glx_threshold``, ``glx_thr_combine``, ``glx_descent_pass``), and the dual ADMM solver's row step,
+Gram kernel and host eigenvalue sweep (``glx_admm_dual_step``, ``glx_gram``,
+``glx_sym_lambda_max``). All tensors are contiguous device
 tensors of one dtype (float32 / float64).
 """
 from __future__ import annotations
@@ -368,3 +370,61 @@ def prox(W: torch.Tensor, t: float, mu: float, thres: float = 1e-3
     check(lib().glx_prox(dt, n, l, W.data_ptr(), float(t), float(mu), float(thres), X.data_ptr(),
                          sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream(W.device)))
     return X, sums
+
+
+def _admm_ws(dtype: int, m: int, n: int, l: int, device) -> torch.Tensor:
+    nb = ctypes.c_size_t(0)
+    check(lib().glx_admm_workspace_bytes(dtype, m, n, l, None, ctypes.byref(nb)))
+    return torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+
+
+def admm_dual_step(x: torch.Tensor, rho: float, tau: float, mu: float, G: Optional[torch.Tensor] = None,
+                   A: Optional[torch.Tensor] = None, Z: Optional[torch.Tensor] = None, form: int = 0,
+                   m: int = 1) -> Dict[str, torch.Tensor]:
+    """The dual ADMM row step (gl_ADMM_dual.py:64-67, glx_admm_dual_step): w = x / rho - g,
+    u = (mu w) / max(||w_i||, mu), r = u + g, x_new = x - (tau rho) r. form 0: the row kernel on
+    the given G (with ``m`` the rows of A: on the panel layout a solve's unfused arm takes at
+    (m, n, l), bit-identical to form 1; m = 1: the generic row layout); form 1: the epilogue of
+    G = A^T Z (G is computed and returned). Returns
+    {"G", "u", "x", "r", "sums"} with sums = [sum_i ||x_new_i||, max |x_new|] (float64)."""
+    n, l = x.shape
+    dt = _dt(x)
+    dev = x.device
+    if form == 1:
+        if A is None or Z is None:
+            raise ValueError("form 1 needs A and Z")
+        m = A.shape[0]
+        G = torch.full((n, l), float("nan"), dtype=x.dtype, device=dev)
+    else:
+        if G is None:
+            raise ValueError("form 0 needs G")
+    u = torch.full_like(x, float("nan"))
+    xn = torch.full_like(x, float("nan"))
+    r = torch.full_like(x, float("nan"))
+    sums = _nan_sums(2, dev)
+    ws = _admm_ws(dt, m, n, l, dev)
+    check(lib().glx_admm_dual_step(dt, m, n, l, _ptr(A), _ptr(Z), G.data_ptr(), x.data_ptr(), float(rho),
+                                   float(tau), float(mu), int(form), u.data_ptr(), xn.data_ptr(),
+                                   r.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return {"G": G, "u": u, "x": xn, "r": r, "sums": sums}
+
+
+def gram(R: torch.Tensor) -> torch.Tensor:
+    """R^T R (l x l, float64) accumulated in double over fixed row slabs (glx_gram)."""
+    rows, l = R.shape
+    out = torch.full((l, l), float("nan"), dtype=torch.float64, device=R.device)
+    ws = torch.empty(8 * 256 * l * l, dtype=torch.uint8, device=R.device)
+    check(lib().glx_gram(_dt(R), rows, l, R.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                         _stream(R.device)))
+    return out
+
+
+def sym_lambda_max(G) -> float:
+    """Largest eigenvalue of a symmetric l x l matrix (l <= 32) by the library's host Jacobi sweep
+    (glx_sym_lambda_max); needs no device."""
+    import numpy as np
+    g = np.ascontiguousarray(np.asarray(G, dtype=np.float64))
+    out = ctypes.c_double(0.0)
+    check(lib().glx_sym_lambda_max(g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(g.shape[0]),
+                                   ctypes.byref(out)))
+    return float(out.value)

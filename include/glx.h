@@ -12,7 +12,11 @@
  *   GLX_GD      <- code/gl_GD_primal.py:9-112       (gradient on the smoothed problem)
  *   GLX_FGD     <- code/gl_FGD_primal.py:9-163      (Nesterov on the smoothed problem)
  * and the dense products inside them (A @ x at gl_ProxGD_primal.py:25,61,129 and
- * A.T @ r at :129), which NumPy sends to host BLAS.
+ * A.T @ r at :129), which NumPy sends to host BLAS. A sixth solver has entries of its own
+ * (glx_admm_*, below; it is not a glx_method and takes no session):
+ *   dual ADMM   <- code/gl_ADMM_dual.py:10-103      (gl_Admm_dual; the Cholesky solves replaced by
+ *                  one product with the explicit inverse K = (I + rho A A^T)^-1, caller-computed)
+ * The reference's ALM dual and ADMM primal solvers are out of scope.
  *
  * Conventions
  *   - Every pointer named "device" is HBM memory on the current HIP device; the library never
@@ -352,6 +356,73 @@ int glx_kernel_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_
 /* One-line description of the kernels (tile, split) the planner picks for this shape, for
  * A @ X with 1, 2, 3 right-hand sides and for A^T R (NUL-terminated, truncated to cap). */
 int glx_plan_describe(int dtype, int64_t m, int64_t n, int64_t l, char* out, size_t cap);
+
+/* ---- the dual ADMM solver (additive entries; the ABI version stays 2) ----
+ * GLX dual ADMM <- code/gl_ADMM_dual.py:10-103, gl_Admm_dual(x0, A, b, mu, opts). Of the
+ * reference's three factorising solvers this is the one built; ALM dual and ADMM primal remain
+ * out of scope. The reference solves with the Cholesky factor of I + rho A A^T at every iteration
+ * (:57, :63); here the caller computes the explicit inverse K = (I + rho A A^T)^-1 once per solve
+ * (m x m, always in fp64, then cast to dtype; plumbing, like alpha0 = 1 / lambda_max above) and
+ * hands it in as a device pointer, so z = K v is one more dense product. Per iteration: one pass
+ * over K, two over A (A^T z, A @ [x+ | u+]), small kernels, and one readback of a small record
+ * (the objective's sums and the l x l Gram matrices of r and s, whose largest eigenvalues give the
+ * spectral norms of the stop rule, :85-93). l <= 32. Single GPU. */
+typedef struct glx_admm_opts {
+  int32_t maxit;            /* gl_ADMM_dual.py:12 (100)                                       */
+  int32_t converge_len;     /* :16 (20): stop after this many consecutive small iterations    */
+  double  thres;            /* :13 (1e-3): both spectral norms below it count as small        */
+  double  tau;              /* :14 ((1 + sqrt 5) / 2)                                         */
+  double  rho;              /* :15 (1e2); K must have been built with the same value          */
+  int32_t fused;            /* the row step in the epilogue of A^T z: 0 auto, 1 on (where the
+                               plan's A^T R tile is built fused for dtype), 2 off (row kernel) */
+  int64_t max_total_iters;  /* stop after this many iterations (0 = off)                      */
+  int32_t reserved[4];
+} glx_admm_opts;
+int glx_admm_default_opts(glx_admm_opts* out);
+/* Device bytes glx_admm_dual_solve needs (opts may be NULL: the defaults). Also enough for
+ * glx_admm_dual_step at the same (dtype, m, n, l). */
+int glx_admm_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, const glx_admm_opts* opts,
+                             size_t* bytes);
+/* The whole solve. prob->x holds x0 on entry and the iterate on return; prob->method is ignored;
+ * prob->comm must be NULL (GLX_E_INVALID otherwise, as for l = 0 or l > 32, a NULL K and a
+ * workspace smaller than glx_admm_workspace_bytes). Fills res->iters, fval, tt (the loop, stream-
+ * synchronised; the caller adds its K setup), f_hist, f_hist_best, n_fhist, ax_calls (passes over
+ * A by A @ [x | u]), ax_sources, atr_calls, syncs (one per iteration); stats[0] = passes over K,
+ * stats[1] = 1 when the row step ran fused. */
+int glx_admm_dual_solve(const glx_problem* prob, const void* K_device, const glx_admm_opts* opts,
+                        void* workspace, size_t workspace_bytes, glx_result* res, void* stream);
+/* After glx_admm_dual_solve, on the same thread: the sparsity of the iterate after each iteration
+ * (sparsity_func, :22-23, for the replayed debug line :83); *n = entries written (with
+ * sparsity_after == NULL: entries available). */
+int glx_admm_trace(double* sparsity_after, int64_t cap, int64_t* n);
+/* One line: the tiles of the three passes (K v; A @ [x | u] and A^T z) and whether the row step is
+ * fused. Resolved on the host; needs no device. opts may be NULL. */
+int glx_admm_describe(int dtype, int64_t m, int64_t n, int64_t l, const glx_admm_opts* opts, char* out,
+                      size_t cap);
+/* ---- the dual ADMM kernels, one launch at a time (test surface) ----
+ * The row step (:64-67) through the launchers the driver uses: w = x / rho - g,
+ * u_out = (mu w) / max(||w_i||, mu), r_out = u_out + g, x_out = x - (tau rho) r_out;
+ * sums_dev = [sum_i ||x_out_i||, max |x_out| (NaN-propagating)] (device doubles).
+ *   form 0: the row kernel on the given G; A and Z are unused. Where the plan of (m, n, l) takes
+ *           a fused epilogue the rows run on that epilogue's panel layout (k_admm_dual_panel, what
+ *           a solve with fused = 2 launches there) and every bit, the two sums included, equals
+ *           form 1's; elsewhere (any l <= 32, any n; m = 1 will do) the generic row layout
+ *           (k_admm_dual).
+ *   form 1: the epilogue of G = A^T Z (k_atr_admm): G is written. GLX_E_INVALID where the plan of
+ *           this shape takes no fused epilogue (glx_admm_describe).
+ * Workspace: glx_admm_workspace_bytes(dtype, m, n, l). */
+int glx_admm_dual_step(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* Z, void* G,
+                       const void* x, double rho, double tau, double mu, int form, void* u_out,
+                       void* x_out, void* r_out, void* sums_dev, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* gram_dev (l x l device doubles, row-major) = R^T R for R of rows x l values of dtype (l <= 32),
+ * accumulated in double over fixed row slabs in a fixed order (bit-reproducible).
+ * Workspace: 8 * 256 * l * l bytes. */
+int glx_gram(int dtype, int64_t rows, int64_t l, const void* R, void* gram_dev, void* workspace,
+             size_t workspace_bytes, void* stream);
+/* Host only: *out = the largest eigenvalue of the symmetric l x l matrix G (row-major, l <= 32) by
+ * cyclic Jacobi sweeps; NaN where G holds one. */
+int glx_sym_lambda_max(const double* G, int l, double* out);
 
 /* ---- multi-GPU (row-sharded A; A^T r all-reduced, or reduce-scattered with the row-sharded step) ---- */
 #define GLX_COMM_ID_BYTES 128
