@@ -56,20 +56,10 @@ int guarded(F&& f) {
   }
 }
 
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-  void* take(size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    void* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  }
-};
-
-constexpr int kAdmmMaxL = 32;   // the Gram kernel and the host Jacobi sweep
-constexpr int kRecHead = 4;     // record: [||Ax - b||^2, sum_i ||x_i||, max |x|, count] + 2 Grams
+// the carver, the pinned record, the Jacobi sweep and the trace are shared with admm_primal.cpp
+// (glx_internal.h, namespace admm; defined at the end of this file)
+using namespace admm;
+constexpr int kAdmmMaxL = admm::kMaxL;
 
 // The launch plans of a solve: A's is the session plan of a one-GPU line-search ProxGD at this
 // shape, i.e. the A^T R tile and split measured best for a fused epilogue where one fuses (both
@@ -86,17 +76,7 @@ AdmmPlan admm_plan(int dtype, int64_t m, int64_t n, int64_t l, bool with_k = tru
   if (l > kAdmmMaxL) throw Error{GLX_E_INVALID, "the dual ADMM solver takes l <= 32"};
   AdmmPlan p;
   p.es = dtype == GLX_F64 ? 8 : 4;
-  glx_problem P;
-  glx_opts O;
-  std::memset(&P, 0, sizeof P);
-  std::memset(&O, 0, sizeof O);
-  P.dtype = dtype;
-  P.method = GLX_PROXGD;
-  P.m = m;
-  P.n = n;
-  P.l = l;
-  O.step_type = GLX_STEP_LINE_SEARCH;
-  p.a = session_plan(P, O);
+  p.a = admm::a_plan(dtype, m, n, l);
   p.k = with_k ? make_plan(p.es, m, m, l, 0) : p.a;   // (the row step alone plans no K product
   if (!with_k) p.k.ax_S = 1;                            //  and carves one slab for it)
   p.fuse_ok = atr_prox_ok(p.a) && (p.a.atr->fused & dtype_bit(p.es)) != 0;
@@ -106,17 +86,6 @@ AdmmPlan admm_plan(int dtype, int64_t m, int64_t n, int64_t l, bool with_k = tru
 // measured the fused epilogue not slower than the row kernel ("Dual ADMM").
 bool use_fused(const AdmmPlan& p, int fused) { return p.fuse_ok && fused != 2; }
 
-// field `idx` of describe_plan's "ax1=..; ax2=..; ax3=..; atr=.." line, without its label
-std::string plan_field(const GemmPlan& p, int idx) {
-  std::string d = describe_plan(p);
-  for (int i = 0; i < idx; ++i) {
-    const size_t at = d.find("; ");
-    d = at == std::string::npos ? std::string() : d.substr(at + 2);
-  }
-  d = d.substr(0, d.find("; "));
-  const size_t eq = d.find('=');
-  return eq == std::string::npos ? d : d.substr(eq + 1);
-}
 std::string describe_admm(const AdmmPlan& p, int fused) {
   std::string s = "K v=" + plan_field(p.k, 0) + "; A [x|u]=" + plan_field(p.a, 1) + "; A^T z=" +
                   plan_field(p.a, 3) + "; projection=";
@@ -162,63 +131,6 @@ void check_opts(const glx_admm_opts* o) {
   if (!(o->rho > 0.0)) throw Error{GLX_E_INVALID, "rho must be positive"};
 }
 
-// Largest eigenvalue of the symmetric l x l matrix G (row-major) by cyclic Jacobi sweeps
-// (Golub & Van Loan, Alg. 8.5.3); NaN where G holds one. The Gram matrices of the stop rule are
-// at most 32 x 32, so a sweep is a few thousand flops on the host.
-double sym_lambda_max(const double* G, int l) {
-  double a[kAdmmMaxL][kAdmmMaxL];
-  double tr = 0.0;
-  for (int i = 0; i < l; ++i)
-    for (int j = 0; j < l; ++j) {
-      const double v = G[i * l + j];
-      if (v != v) return std::numeric_limits<double>::quiet_NaN();
-      a[i][j] = v;
-      if (i == j) tr += std::fabs(v);
-    }
-  for (int sweep = 0; sweep < 64; ++sweep) {
-    double off = 0.0;
-    for (int p = 0; p < l; ++p)
-      for (int q = p + 1; q < l; ++q) off += a[p][q] * a[p][q];
-    if (!(std::sqrt(off) > 1e-18 * tr)) break;
-    for (int p = 0; p < l; ++p)
-      for (int q = p + 1; q < l; ++q) {
-        const double apq = a[p][q];
-        if (apq == 0.0) continue;
-        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-        const double cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
-        for (int k = 0; k < l; ++k) {
-          if (k == p || k == q) continue;
-          const double akp = a[k][p], akq = a[k][q];
-          a[k][p] = a[p][k] = cs * akp - sn * akq;
-          a[k][q] = a[q][k] = sn * akp + cs * akq;
-        }
-        a[p][p] -= t * apq;
-        a[q][q] += t * apq;
-        a[p][q] = a[q][p] = 0.0;
-      }
-  }
-  double mx = a[0][0];
-  for (int i = 1; i < l; ++i) mx = a[i][i] > mx ? a[i][i] : mx;
-  return mx;
-}
-// the spectral norm of R from R^T R (a tiny negative eigenvalue of a rounded Gram matrix is 0)
-double spectral_norm(const double* gram, int l) {
-  const double lm = sym_lambda_max(gram, l);
-  return lm != lm ? lm : std::sqrt(lm > 0.0 ? lm : 0.0);
-}
-
-// sparsity of the iterate after each iteration of this thread's last solve (glx_admm_trace)
-thread_local std::vector<double> g_admm_sparsity;
-
-struct HostRec {
-  double* p = nullptr;
-  explicit HostRec(size_t n) { GLX_HIP(hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(double) * n, hipHostMallocDefault)); }
-  ~HostRec() { if (p) (void)hipHostFree(p); }
-  HostRec(const HostRec&) = delete;
-  HostRec& operator=(const HostRec&) = delete;
-};
-
 template <typename T>
 void admm_solve(const glx_problem& P, const T* K, const glx_admm_opts& O, void* ws, size_t wsb,
                 glx_result* res, hipStream_t st) {
@@ -262,7 +174,7 @@ void admm_solve(const glx_problem& P, const T* K, const glx_admm_opts& O, void* 
   int64_t k = 0, length = 0;
   int cur = 0;
   double f_best = std::numeric_limits<double>::infinity(), f_now = 0.0;
-  g_admm_sparsity.clear();
+  admm::trace().clear();
   res->n_fhist = 0;
   while (k < maxit) {
     ++k;
@@ -305,7 +217,7 @@ void admm_solve(const glx_problem& P, const T* K, const glx_admm_opts& O, void* 
       if (res->f_hist_best) res->f_hist_best[res->n_fhist] = f_best;
       ++res->n_fhist;
     }
-    g_admm_sparsity.push_back(h[3] / (double)nl);
+    admm::trace().push_back(h[3] / (double)nl);
     const double rn = spectral_norm(h + kRecHead, (int)l), sn = spectral_norm(h + kRecHead + ll, (int)l);
     if (rn < O.thres && sn < O.thres) ++length;
     else length = 0;
@@ -333,6 +245,91 @@ void admm_solve(const glx_problem& P, const T* K, const glx_admm_opts& O, void* 
 }
 
 }  // namespace
+
+// ---- shared with admm_primal.cpp (glx_internal.h, namespace admm) ----
+namespace admm {
+
+// Largest eigenvalue of the symmetric l x l matrix G (row-major) by cyclic Jacobi sweeps
+// (Golub & Van Loan, Alg. 8.5.3); NaN where G holds one. The Gram matrices of the stop rule are
+// at most 32 x 32, so a sweep is a few thousand flops on the host.
+double sym_lambda_max(const double* G, int l) {
+  double a[kMaxL][kMaxL];
+  double tr = 0.0;
+  for (int i = 0; i < l; ++i)
+    for (int j = 0; j < l; ++j) {
+      const double v = G[i * l + j];
+      if (v != v) return std::numeric_limits<double>::quiet_NaN();
+      a[i][j] = v;
+      if (i == j) tr += std::fabs(v);
+    }
+  for (int sweep = 0; sweep < 64; ++sweep) {
+    double off = 0.0;
+    for (int p = 0; p < l; ++p)
+      for (int q = p + 1; q < l; ++q) off += a[p][q] * a[p][q];
+    if (!(std::sqrt(off) > 1e-18 * tr)) break;
+    for (int p = 0; p < l; ++p)
+      for (int q = p + 1; q < l; ++q) {
+        const double apq = a[p][q];
+        if (apq == 0.0) continue;
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
+        for (int k = 0; k < l; ++k) {
+          if (k == p || k == q) continue;
+          const double akp = a[k][p], akq = a[k][q];
+          a[k][p] = a[p][k] = cs * akp - sn * akq;
+          a[k][q] = a[q][k] = sn * akp + cs * akq;
+        }
+        a[p][p] -= t * apq;
+        a[q][q] += t * apq;
+        a[p][q] = a[q][p] = 0.0;
+      }
+  }
+  double mx = a[0][0];
+  for (int i = 1; i < l; ++i) mx = a[i][i] > mx ? a[i][i] : mx;
+  return mx;
+}
+// the spectral norm of R from R^T R (a tiny negative eigenvalue of a rounded Gram matrix is 0)
+double spectral_norm(const double* gram, int l) {
+  const double lm = sym_lambda_max(gram, l);
+  return lm != lm ? lm : std::sqrt(lm > 0.0 ? lm : 0.0);
+}
+
+std::vector<double>& trace() {
+  thread_local std::vector<double> sparsity;
+  return sparsity;
+}
+
+HostRec::HostRec(size_t n) { GLX_HIP(hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(double) * n, hipHostMallocDefault)); }
+HostRec::~HostRec() { if (p) (void)hipHostFree(p); }
+
+GemmPlan a_plan(int dtype, int64_t m, int64_t n, int64_t l) {
+  glx_problem P;
+  glx_opts O;
+  std::memset(&P, 0, sizeof P);
+  std::memset(&O, 0, sizeof O);
+  P.dtype = dtype;
+  P.method = GLX_PROXGD;
+  P.m = m;
+  P.n = n;
+  P.l = l;
+  O.step_type = GLX_STEP_LINE_SEARCH;
+  return session_plan(P, O);
+}
+
+std::string plan_field(const GemmPlan& p, int idx) {
+  std::string d = describe_plan(p);
+  for (int i = 0; i < idx; ++i) {
+    const size_t at = d.find("; ");
+    d = at == std::string::npos ? std::string() : d.substr(at + 2);
+  }
+  d = d.substr(0, d.find("; "));
+  const size_t eq = d.find('=');
+  return eq == std::string::npos ? d : d.substr(eq + 1);
+}
+
+}  // namespace admm
+
 }  // namespace glx
 
 using namespace glx;
@@ -391,9 +388,9 @@ int glx_admm_dual_solve(const glx_problem* prob, const void* K_device, const glx
 
 int glx_admm_trace(double* sparsity_after, int64_t cap, int64_t* n) {
   return guarded([&] {
-    const int64_t have = (int64_t)g_admm_sparsity.size();
+    const int64_t have = (int64_t)admm::trace().size();
     const int64_t k = sparsity_after ? std::min(cap, have) : have;
-    for (int64_t i = 0; sparsity_after && i < k; ++i) sparsity_after[i] = g_admm_sparsity[(size_t)i];
+    for (int64_t i = 0; sparsity_after && i < k; ++i) sparsity_after[i] = admm::trace()[(size_t)i];
     if (n) *n = k;
   });
 }

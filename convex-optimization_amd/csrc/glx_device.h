@@ -626,5 +626,53 @@ __device__ inline void admm_dual_row(const T (&xv)[EPL], const T (&gv)[EPL], con
   if (rv && sub == 0) acc[0] += (double)xnorm;
 }
 
+// ------------------------------------------------------------------------------------------
+// Primal ADMM's row step (gl_ADMM_primal.py:47-51, 78-84) for a lane that holds EPL elements of
+// the row, on pv = the product of the inverse's pass: y+ = pv (direct: Kn w) or (w - pv) / rho
+// (WOODBURY: pv = A^T K (A w)). Then, in the reference's evaluation order,
+//   p  = x - (eta rho)((x - y+) - z / rho),  nr = ||p||,
+//   x+ = (p max(nr - eta mu, 0)) / ((nr < thres) + nr)   (np.clip(., a_min=0): NaN stays NaN),
+//   z+ = z - (tau rho)(x+ - y+),  r = x+ - y+,  s = y+ - y,
+// and the next iteration's right-hand side w+ = (ATb - z+) + rho x+.
+// acc (per thread, reduced over the grid by the caller): [sum_i ||x+_i||, max |x+|].
+// ------------------------------------------------------------------------------------------
+template <typename T, int EPL>
+struct AdmmPrimalRow {
+  T x[EPL], y[EPL], z[EPL], r[EPL], s[EPL], w[EPL];
+};
+template <typename T, int LPR, int EPL, bool WOODBURY>
+__device__ inline void admm_primal_row(const T (&pv)[EPL], const T (&xv)[EPL], const T (&yv)[EPL],
+                                       const T (&zv)[EPL], const T (&wv)[EPL], const T (&av)[EPL],
+                                       const bool (&ok)[EPL], bool rv, int sub, T rho, T etarho, T etamu,
+                                       T taurho, T thres, AdmmPrimalRow<T, EPL>& o, double (&acc)[2]) {
+  T p[EPL];
+  T sq = T(0);
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) {
+    o.y[e] = WOODBURY ? (wv[e] - pv[e]) / rho : pv[e];
+    p[e] = xv[e] - etarho * ((xv[e] - o.y[e]) - zv[e] / rho);
+    sq = sq + p[e] * p[e];
+  }
+  const T nr = __builtin_sqrt(row_allsum<LPR>(sq));
+  T c = nr - etamu;
+  c = (c < T(0)) ? T(0) : c;   // NaN compares false and stays
+  const T d = ((nr < thres) ? T(1) : T(0)) + nr;
+  T xsq = T(0);
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) {
+    o.x[e] = (p[e] * c) / d;
+    o.r[e] = o.x[e] - o.y[e];
+    o.z[e] = zv[e] - taurho * o.r[e];
+    o.s[e] = o.y[e] - yv[e];
+    o.w[e] = (av[e] - o.z[e]) + rho * o.x[e];
+    if (ok[e]) {
+      acc[1] = nan_max(acc[1], (double)tabs(o.x[e]));
+      xsq = xsq + o.x[e] * o.x[e];
+    }
+  }
+  const T xnorm = __builtin_sqrt(row_allsum<LPR>(xsq));
+  if (rv && sub == 0) acc[0] += (double)xnorm;
+}
+
 }  // namespace glx
 #endif  // GLX_DEVICE_H_

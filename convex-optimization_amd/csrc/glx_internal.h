@@ -11,6 +11,7 @@
 #include <string>
 #include <tuple>
 #include <utility>
+#include <vector>
 
 #include "glx.h"
 #include "glx_tiles.h"
@@ -365,6 +366,64 @@ void launch_admm_fin(const T* P, int S, const T* b, T* Ax, T* Au, T* s, int64_t 
 int gram_blocks(int64_t rows);
 template <typename T>
 void launch_gram(const T* R, int64_t rows, int64_t l, double* part, double* gram, hipStream_t st);
+
+// ---- the primal ADMM solver's own kernels (kernels_admm_primal.hip; gl_ADMM_primal.py:47-51, 78-84) ----
+// w = (ATb - z) + rho x over nl values: the first iteration's right-hand side (later ones come
+// from the row step)
+template <typename T>
+void launch_admm_primal_w(const T* ATb, const T* x, const T* z, T* w, int64_t nl, double rho, hipStream_t st);
+// The row step on prod = the sum, in slab order, of S slabs of n * l values: y+ = prod (direct) or
+// (w - prod) / rho (woodbury: prod = A^T K (A w)); p = x - (eta rho)((x - y+) - z / rho),
+// x+ = (p max(||p_i|| - eta mu, 0)) / ((||p_i|| < thres) + ||p_i||), z+ = z - (tau rho)(x+ - y+),
+// r = x+ - y+, s = y+ - y, w+ = (ATb - z+) + rho x+. Row-local: xn, yn, zn, wn may alias x, y, z, w.
+// w is read by the Woodbury form only. out: [sum_i ||x+_i||, max |x+| (NaN-propagating)]
+struct AdmmPrimalScalars {
+  double rho, etarho, etamu, taurho, thres;
+};
+template <typename T>
+void launch_admm_primal(bool woodbury, const T* prod, int S, const T* x, const T* y, const T* z, const T* w,
+                        const T* ATb, T* xn, T* yn, T* zn, T* rn, T* sn, T* wn, int64_t n, int64_t l,
+                        const AdmmPrimalScalars& sc, Red red, hipStream_t st);
+// The finish of the pass over A. P = S slabs of A x+ (ml values each), summed in slab order into
+// Ax; out: [sum (Ax - b)^2]. AATb != NULL (Woodbury): S slabs of A z+ follow, summed into Az, and
+// v = (AATb - Az) + rho Ax, the right-hand side of the next K product.
+template <typename T>
+void launch_admm_primal_fin(const T* P, int S, const T* b, const T* AATb, T* Ax, T* Az, T* v, int64_t ml,
+                            double rho, Red red, hipStream_t st);
+
+// ---- shared by the two ADMM drivers (defined in admm.cpp) ----
+namespace admm {
+constexpr int kMaxL = 32;    // the Gram kernel and the host Jacobi sweep
+constexpr int kRecHead = 4;  // record: [||Ax - b||^2, sum_i ||x_i||, max |x|, count] + 2 Grams
+struct Carver {   // 256-byte aligned pieces of a workspace (base == NULL: sizes only)
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* b) : base(static_cast<char*>(b)) {}
+  void* take(size_t bytes) {
+    off = (off + 255) & ~size_t(255);
+    void* p = base ? base + off : nullptr;
+    off += bytes;
+    return p;
+  }
+};
+struct HostRec {   // n pinned doubles for the per-iteration readback
+  double* p = nullptr;
+  explicit HostRec(size_t n);
+  ~HostRec();
+  HostRec(const HostRec&) = delete;
+  HostRec& operator=(const HostRec&) = delete;
+};
+// largest eigenvalue of the symmetric l x l matrix G (row-major, l <= kMaxL) by cyclic Jacobi
+// sweeps, NaN where G holds one; the spectral norm of R from gram = R^T R
+double sym_lambda_max(const double* G, int l);
+double spectral_norm(const double* gram, int l);
+// sparsity of the iterate after each iteration of this thread's last solve (glx_admm_trace)
+std::vector<double>& trace();
+// A's plan of an ADMM solve: the session plan of a one-GPU line-search ProxGD at this shape
+GemmPlan a_plan(int dtype, int64_t m, int64_t n, int64_t l);
+// field `idx` of describe_plan's "ax1=..; ax2=..; ax3=..; atr=.." line, without its label
+std::string plan_field(const GemmPlan& p, int idx);
+}  // namespace admm
 
 // ---- split-candidate A e from a transposed copy of A (kernels_gather.hip) ----
 // gather_ok: the shape supports it (l in {16, 32}, n < 65536); gather_split: K splits of the

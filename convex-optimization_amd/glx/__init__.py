@@ -6,6 +6,8 @@ Public surface:
   * ``Session`` — the same solver split into steps (benchmarks);
   * ``kernels`` — single HIP kernels (residual, gradient, prox);
   * ``admm`` — the dual ADMM solver ``gl_Admm_dual`` (``admm.solve``; drop-in module ``gl_ADMM_dual``);
+  * ``admm_primal`` — the primal ADMM solver ``gl_Admm_primal`` (``admm_primal.solve``; drop-in module
+    ``gl_ADMM_primal``);
   * ``dist`` — row sharding + RCCL communicator.
 """
 from ._lib import LIB_PATH, GlxError, lib  # noqa: F401

@@ -54,6 +54,13 @@ class GlxAdmmOpts(ctypes.Structure):
                 ("max_total_iters", c_int64), ("reserved", c_int32 * 4)]
 
 
+class GlxAdmmPrimalOpts(ctypes.Structure):
+    """glx_admm_primal_opts (include/glx.h): the options of the primal ADMM solver."""
+    _fields_ = [("maxit", c_int32), ("converge_len", c_int32), ("thres", c_double),
+                ("tau", c_double), ("rho", c_double), ("eta_0", c_double), ("step_type", c_int32),
+                ("form", c_int32), ("max_total_iters", c_int64), ("reserved", c_int32 * 4)]
+
+
 class GlxError(RuntimeError):
     """Error returned by libglx (message from glx_last_error())."""
 
@@ -141,6 +148,18 @@ _SIGS = {
                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "glx_gram": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "glx_sym_lambda_max": (c_int, [POINTER(c_double), c_int, POINTER(c_double)]),
+    "glx_admm_primal_default_opts": (c_int, [POINTER(GlxAdmmPrimalOpts)]),
+    "glx_admm_primal_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64,
+                                                POINTER(GlxAdmmPrimalOpts), POINTER(c_size_t)]),
+    "glx_admm_primal_describe": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(GlxAdmmPrimalOpts),
+                                         c_char_p, c_size_t]),
+    "glx_admm_primal_solve": (c_int, [POINTER(GlxProblem), c_void_p, c_void_p, c_void_p,
+                                      POINTER(GlxAdmmPrimalOpts), c_void_p, c_size_t,
+                                      POINTER(GlxResult), c_void_p]),
+    "glx_admm_primal_step": (c_int, [c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_double, c_double, c_double,
+                                     c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "glx_comm_unique_id": (c_int, [POINTER(c_uint8)]),
     "glx_comm_create": (c_int, [POINTER(c_void_p), POINTER(c_uint8), c_int, c_int]),
     "glx_comm_create_host": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
@@ -216,4 +235,21 @@ def admm_describe(dtype: int, m: int, n: int, l: int, opts: "GlxAdmmOpts | None"
     buf = ctypes.create_string_buffer(2048)
     check(lib().glx_admm_describe(dtype, m, n, l, ctypes.byref(opts) if opts is not None else None,
                                   buf, len(buf)))
+    return buf.value.decode()
+
+
+def admm_primal_default_opts() -> GlxAdmmPrimalOpts:
+    o = GlxAdmmPrimalOpts()
+    check(lib().glx_admm_primal_default_opts(ctypes.byref(o)))
+    return o
+
+
+def admm_primal_describe(dtype: int, m: int, n: int, l: int,
+                         opts: "GlxAdmmPrimalOpts | None" = None) -> str:
+    """The resolved form ("form=direct" or "form=Woodbury") and the tiles of the primal ADMM solver's
+    passes (glx_admm_primal_describe: resolved on the host, no device). GlxError for what the solve
+    refuses, the fp32 rule included."""
+    buf = ctypes.create_string_buffer(2048)
+    check(lib().glx_admm_primal_describe(dtype, m, n, l, ctypes.byref(opts) if opts is not None else None,
+                                         buf, len(buf)))
     return buf.value.decode()

@@ -21,8 +21,9 @@ Differences, all forced by what the image lacks:
 - The svg plots (``main.py:200-235``) are replaced by ``f_hist.npz`` in ``--dest_dir``: the
   per-solver objective histories and f* = obj(u) those plots are drawn from. matplotlib is
   not installed.
-- Of the ALM/ADMM solvers only ADMM dual is built (``gl_ADMM_dual.gl_Admm_dual``, DESIGN.md
-  "Dual ADMM"); it is not registered here. ALM dual and ADMM primal are out of scope.
+- Of the ALM/ADMM solvers ADMM dual and ADMM primal are built (``gl_ADMM_dual.gl_Admm_dual``,
+  ``gl_ADMM_primal.gl_Admm_primal``, DESIGN.md "Dual ADMM" and "Primal ADMM"); they are not
+  registered here. ALM dual is out of scope.
 
 Every solver runs on the GPU through libglx (``glx.solver.solve``); there is no CPU path.
 

@@ -8,7 +8,7 @@ trial at a time (``glx_trial_proxgd`` / ``glx_trial_fista``: the row kernels, th
 and the replicated halves of the row-sharded schedules), and the descent-method kernels one
 launch at a time (``glx_descent_step``, ``glx_fgd_gradient``, ``glx_row_stats``,
 ``glx_threshold``, ``glx_thr_combine``, ``glx_descent_pass``), and the dual ADMM solver's row step,
-Gram kernel and host eigenvalue sweep (``glx_admm_dual_step``, ``glx_gram``,
+Gram kernel and host eigenvalue sweep (``glx_admm_dual_step``, ``glx_admm_primal_step``, ``glx_gram``,
 ``glx_sym_lambda_max``). All tensors are contiguous device
 tensors of one dtype (float32 / float64).
 """
@@ -407,6 +407,37 @@ def admm_dual_step(x: torch.Tensor, rho: float, tau: float, mu: float, G: Option
                                    float(tau), float(mu), int(form), u.data_ptr(), xn.data_ptr(),
                                    r.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
     return {"G": G, "u": u, "x": xn, "r": r, "sums": sums}
+
+
+def admm_primal_step(prod: torch.Tensor, x: torch.Tensor, y: torch.Tensor, z: torch.Tensor,
+                     ATb: torch.Tensor, rho: float, tau: float, eta: float, mu: float, thres: float = 1e-3,
+                     form: int = 1, w: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """The primal ADMM row step (gl_ADMM_primal.py:78-84, glx_admm_primal_step) in one launch.
+    ``prod`` is (n, l), or (S, n, l) slabs summed in slab order: Kn w (form 1, direct) or
+    g = A^T K (A w) (form 2, Woodbury, which also reads ``w``). With y+ = prod or (w - prod) / rho:
+    p = x - (eta rho)((x - y+) - z / rho), x+ = (p max(||p_i|| - eta mu, 0)) / ((||p_i|| < thres) +
+    ||p_i||), z+ = z - (tau rho)(x+ - y+), r = x+ - y+, s = y+ - y, w+ = (ATb - z+) + rho x+.
+    Returns {"x", "y", "z", "r", "s", "w", "sums"} with sums = [sum_i ||x+_i||, max |x+|] (float64)."""
+    n, l = x.shape
+    dt = _dt(x)
+    dev = x.device
+    prod = prod.contiguous()
+    S = 1 if prod.dim() == 2 else prod.shape[0]
+    if prod.numel() != S * n * l:
+        raise ValueError("prod must be (n, l) or (S, n, l)")
+    if form == 2 and w is None:
+        raise ValueError("form 2 reads w")
+    outs = {k: torch.full_like(x, float("nan")) for k in ("x", "y", "z", "r", "s", "w")}
+    sums = _nan_sums(2, dev)
+    ws = _ws(dt, 1, n, l, dev)
+    check(lib().glx_admm_primal_step(dt, n, l, int(form), int(S), prod.data_ptr(), x.data_ptr(), y.data_ptr(),
+                                     z.data_ptr(), _ptr(w), ATb.data_ptr(), float(rho), float(tau),
+                                     float(eta), float(mu), float(thres), outs["x"].data_ptr(),
+                                     outs["y"].data_ptr(), outs["z"].data_ptr(), outs["r"].data_ptr(),
+                                     outs["s"].data_ptr(), outs["w"].data_ptr(), sums.data_ptr(),
+                                     ws.data_ptr(), ws.numel(), _stream(dev)))
+    outs["sums"] = sums
+    return outs
 
 
 def gram(R: torch.Tensor) -> torch.Tensor:

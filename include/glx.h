@@ -16,7 +16,9 @@
  * (glx_admm_*, below; it is not a glx_method and takes no session):
  *   dual ADMM   <- code/gl_ADMM_dual.py:10-103      (gl_Admm_dual; the Cholesky solves replaced by
  *                  one product with the explicit inverse K = (I + rho A A^T)^-1, caller-computed)
- * The reference's ALM dual and ADMM primal solvers are out of scope.
+ *   primal ADMM <- code/gl_ADMM_primal.py:10-117    (gl_Admm_primal; glx_admm_primal_*, likewise with
+ *                  an explicit inverse of rho I + A^T A, directly or through the Woodbury identity)
+ * The reference's ALM dual solver is out of scope.
  *
  * Conventions
  *   - Every pointer named "device" is HBM memory on the current HIP device; the library never
@@ -359,8 +361,8 @@ int glx_plan_describe(int dtype, int64_t m, int64_t n, int64_t l, char* out, siz
 
 /* ---- the dual ADMM solver (additive entries; the ABI version stays 2) ----
  * GLX dual ADMM <- code/gl_ADMM_dual.py:10-103, gl_Admm_dual(x0, A, b, mu, opts). Of the
- * reference's three factorising solvers this is the one built; ALM dual and ADMM primal remain
- * out of scope. The reference solves with the Cholesky factor of I + rho A A^T at every iteration
+ * reference's three factorising solvers this was the first built (ADMM primal follows below); ALM
+ * dual remains out of scope. The reference solves with the Cholesky factor of I + rho A A^T at every iteration
  * (:57, :63); here the caller computes the explicit inverse K = (I + rho A A^T)^-1 once per solve
  * (m x m, always in fp64, then cast to dtype; plumbing, like alpha0 = 1 / lambda_max above) and
  * hands it in as a device pointer, so z = K v is one more dense product. Per iteration: one pass
@@ -423,6 +425,72 @@ int glx_gram(int dtype, int64_t rows, int64_t l, const void* R, void* gram_dev, 
 /* Host only: *out = the largest eigenvalue of the symmetric l x l matrix G (row-major, l <= 32) by
  * cyclic Jacobi sweeps; NaN where G holds one. */
 int glx_sym_lambda_max(const double* G, int l, double* out);
+
+/* ---- the primal ADMM solver (additive entries; the ABI version stays 2) ----
+ * GLX primal ADMM <- code/gl_ADMM_primal.py:10-117, gl_Admm_primal(x0, A, b, mu, opts). The
+ * reference solves with the Cholesky factor of rho I + A^T A (n x n) at every iteration (:62, :78);
+ * here the caller builds an explicit inverse once per solve (always in fp64, then cast to dtype)
+ * and hands it in, in one of two forms of y+ = (rho I + A^T A)^-1 w, w = A^T b - z + rho x:
+ *   direct   (form 1): y+ = Kn w with Kn = (rho I + A^T A)^-1 (n x n): one pass over Kn and one
+ *                      over A (A @ x+) per iteration;
+ *   Woodbury (form 2): y+ = (w - A^T K (A w)) / rho with K = (rho I + A A^T)^-1 (m x m) and
+ *                      A w = A A^T b - A z + rho A x from the batched pass A @ [x+ | z+]: one pass
+ *                      over K and two over A per iteration, the dual solver's schedule.
+ * form 0 (auto) resolves to Woodbury exactly when m^2 + m n < n^2 (the bytes an iteration streams:
+ * 2 m n + m^2 against n^2 + m n). Then the row step (:47-51, :80-84): p = x - (eta rho)(x - y+ -
+ * z / rho), x+ = p max(||p_i|| - eta mu, 0) / ((||p_i|| < thres) + ||p_i||), z+ = z - (tau rho)(x+
+ * - y+), r = x+ - y+, s = y+ - y, and one readback of a small record per iteration, as in the dual
+ * solver (both Gram matrices are of n x l iterates here). l <= 32. Single GPU.
+ * dtype: GLX_F64 always; GLX_F32 only where m >= n and the resolved form is direct: rho I + A^T A
+ * has condition number ||A||^2 / rho (1e5 .. 1e6 at the default rho) for m < n, and an fp32 inverse
+ * and fp32 iterates then never meet the stop rule. Anything else is GLX_E_INVALID. */
+typedef struct glx_admm_primal_opts {
+  int32_t maxit;            /* gl_ADMM_primal.py:12 (100)                                     */
+  int32_t converge_len;     /* :17 (10): stop after this many consecutive small iterations    */
+  double  thres;            /* :13 (1e-3): the stop rule's bound and the prox denominator's   */
+  double  tau;              /* :14 ((1 + sqrt 5) / 2)                                         */
+  double  rho;              /* :15 (1e-2); the inverse must have been built with this value   */
+  double  eta_0;            /* :16 (100)                                                      */
+  int32_t step_type;        /* :19 GLX_STEP_FIXED (eta_0), _DIMINISHING (eta_0 / sqrt k),
+                               _DIMINISHING2 (eta_0 / k)                                      */
+  int32_t form;             /* 0 auto, 1 direct, 2 Woodbury                                   */
+  int64_t max_total_iters;  /* stop after this many iterations (0 = off)                      */
+  int32_t reserved[4];
+} glx_admm_primal_opts;
+int glx_admm_primal_default_opts(glx_admm_primal_opts* out);
+/* Device bytes glx_admm_primal_solve needs (opts may be NULL: the defaults). */
+int glx_admm_primal_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l,
+                                    const glx_admm_primal_opts* opts, size_t* bytes);
+/* One line: "form=direct" or "form=Woodbury", then the tiles of the passes. Resolved on the host;
+ * needs no device. opts may be NULL. GLX_E_INVALID for what the solve would refuse (the fp32 rule
+ * included). */
+int glx_admm_primal_describe(int dtype, int64_t m, int64_t n, int64_t l,
+                             const glx_admm_primal_opts* opts, char* out, size_t cap);
+/* The whole solve. prob->x holds x0 on entry and the iterate on return (y and z start at x0 too,
+ * :53-55); prob->method is ignored; prob->comm must be NULL. K_device: Kn (n x n) for the direct
+ * form, K (m x m) for Woodbury; ATb_device = A^T b (n x l); AATb_device = A A^T b (m x l),
+ * required by Woodbury and unused (may be NULL) by direct. GLX_E_INVALID for a communicator,
+ * l > 32, rho <= 0, eta_0 <= 0, an unknown step_type or form, a NULL or not 16-byte aligned
+ * pointer, the fp32 rule above, Woodbury without AATb and a workspace smaller than
+ * glx_admm_primal_workspace_bytes. Fills res as glx_admm_dual_solve does: ax_calls = iters + 1
+ * (the first pass gives the objective of x0, returned when maxit = 0), atr_calls = iters
+ * (Woodbury) or 0 (direct), syncs = iters; stats[0] = passes over the inverse, stats[1] = the
+ * resolved form (1 direct, 2 Woodbury). glx_admm_trace serves this solver too. */
+int glx_admm_primal_solve(const glx_problem* prob, const void* K_device, const void* ATb_device,
+                          const void* AATb_device, const glx_admm_primal_opts* opts, void* workspace,
+                          size_t workspace_bytes, glx_result* res, void* stream);
+/* ---- the primal ADMM row kernel in one launch (test surface) ----
+ * prod = S >= 1 slabs of n * l values, summed in slab order: the product Kn w (form 1) or
+ * g = A^T K (A w) (form 2, which also reads w). With y+ = prod (form 1) or (w - prod) / rho
+ * (form 2), the step above with eta given: x_out, y_out, z_out, r_out, s_out and
+ * w_out = (ATb - z_out) + rho x_out, the next iteration's w;
+ * sums_dev = [sum_i ||x_out_i||, max |x_out| (NaN-propagating)] (device doubles). w may be NULL in
+ * form 1. Any n, l <= 32, both dtypes. Workspace: glx_kernel_workspace_bytes(dtype, 1, n, l). */
+int glx_admm_primal_step(int dtype, int64_t n, int64_t l, int form, int S, const void* prod,
+                         const void* x, const void* y, const void* z, const void* w, const void* ATb,
+                         double rho, double tau, double eta, double mu, double thres, void* x_out,
+                         void* y_out, void* z_out, void* r_out, void* s_out, void* w_out,
+                         void* sums_dev, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- multi-GPU (row-sharded A; A^T r all-reduced, or reduce-scattered with the row-sharded step) ---- */
 #define GLX_COMM_ID_BYTES 128
