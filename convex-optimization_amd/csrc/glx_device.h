@@ -674,5 +674,34 @@ __device__ inline void admm_primal_row(const T (&pv)[EPL], const T (&xv)[EPL], c
   if (rv && sub == 0) acc[0] += (double)xnorm;
 }
 
+// ------------------------------------------------------------------------------------------
+// One step of dual ALM's inner Nesterov loop (gl_ALM_dual.py:45-47, 56-61) for a lane that holds
+// EPL elements of the row, on pv = (Qn y) of that row, in the reference's evaluation order:
+//   w  = y - t (P + J),  u+ = (mu w) / max(||w||, mu)  (np.clip(., a_min=mu): NaN stays NaN),
+//   v+ = u + (u+ - u) / gamma,  y+ = a1 u+ + gn v+  with a1 = 1 - gamma+, gn = gamma+.
+// v+ stays in registers: the state between steps is (u, y). No sums. Shared by the fused epilogue
+// (k_atr_alm), the panel row kernel (k_alm_inner_panel) and the generic one (k_alm_inner).
+// ------------------------------------------------------------------------------------------
+template <typename T, int LPR, int EPL>
+__device__ inline void alm_inner_row(const T (&pv)[EPL], const T (&yv)[EPL], const T (&jv)[EPL],
+                                     const T (&uv)[EPL], T t, T mu, T gamma, T a1, T gn,
+                                     T (&un)[EPL], T (&yn)[EPL]) {
+  T w[EPL];
+  T sq = T(0);
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) {
+    w[e] = yv[e] - t * (pv[e] + jv[e]);
+    sq = sq + w[e] * w[e];
+  }
+  const T nrm = __builtin_sqrt(row_allsum<LPR>(sq));
+  const T d = (nrm < mu) ? mu : nrm;   // NaN compares false and stays
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) {
+    un[e] = (mu * w[e]) / d;
+    const T vn = uv[e] + (un[e] - uv[e]) / gamma;
+    yn[e] = a1 * un[e] + gn * vn;
+  }
+}
+
 }  // namespace glx
 #endif  // GLX_DEVICE_H_

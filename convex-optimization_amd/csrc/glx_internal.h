@@ -391,6 +391,35 @@ template <typename T>
 void launch_admm_primal_fin(const T* P, int S, const T* b, const T* AATb, T* Ax, T* Az, T* v, int64_t ml,
                             double rho, Red red, hipStream_t st);
 
+// ---- the dual ALM solver's kernels (kernels_alm.hip, kernels_atr.hip; gl_ALM_dual.py:45-61, 119-124) ----
+// One step of the inner Nesterov loop on P = Qn y (Qn = rho (I + rho A^T A)^-1, symmetric):
+// w = y - t (P + J), u+ = (mu w) / max(||w_i||, mu), v+ = u + (u+ - u) / gamma,
+// y+ = (1 - gamma_next) u+ + gamma_next v+. un may be u (rows are owned); yn == NULL (the last
+// step): y+ is not written; yn must not be y. fp64 only.
+//   launch_atr_alm:          the step in the epilogue of P = Qn^T y under the plan p of (n, n, l)
+//                            (plan condition of launch_atr_admm); Gp / pcnt as launch_atr_prox
+//   launch_alm_inner_panel:  on S slabs of P from launch_atr under p, the epilogue's lane-to-row
+//                            layout: every bit equals launch_atr_alm's
+//   launch_alm_inner:        on S slabs of P, any n and l <= 32 (kernels_elem.hip's row layout)
+template <typename T>
+void launch_atr_alm(const GemmPlan& p, const T* Qn, const T* y, const T* J, const T* u, T* un, T* yn,
+                    double t, double mu, double gamma, double gamma_next, hipStream_t st,
+                    T* Gp = nullptr, unsigned* pcnt = nullptr);
+template <typename T>
+void launch_alm_inner_panel(const GemmPlan& p, const T* P, int S, const T* y, const T* J, const T* u, T* un,
+                            T* yn, double t, double mu, double gamma, double gamma_next, hipStream_t st);
+template <typename T>
+void launch_alm_inner(const T* P, int S, const T* y, const T* J, const T* u, T* un, T* yn, int64_t n,
+                      int64_t l, double t, double mu, double gamma, double gamma_next, hipStream_t st);
+// J = rho (h - x / rho) over nl values, h = the sum in slab order of S slabs of A^T E
+template <typename T>
+void launch_alm_j(const T* h, int S, const T* x, T* J, int64_t nl, double rho, hipStream_t st);
+// r = u + g, x+ = x - (tau rho) r with g = the sum in slab order of S slabs of A^T z (xn may be x);
+// out: [sum_i ||x+_i||, max |x+| (NaN-propagating)]
+template <typename T>
+void launch_alm_x(const T* x, const T* u, const T* g, int S, T* xn, T* rn, int64_t n, int64_t l,
+                  double taurho, Red red, hipStream_t st);
+
 // ---- shared by the two ADMM drivers (defined in admm.cpp) ----
 namespace admm {
 constexpr int kMaxL = 32;    // the Gram kernel and the host Jacobi sweep

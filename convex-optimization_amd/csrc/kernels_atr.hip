@@ -605,6 +605,102 @@ __global__ __launch_bounds__(atr_waves<WL>() * 64) void k_admm_dual_panel(const 
                              (int)blockIdx.x, -1);
 }
 
+// One step of dual ALM's inner loop (gl_ALM_dual.py:56-61) on the panel layout of an A^T R
+// epilogue, A = Qn (n x n, symmetric) and R = y: ps = the wave's 16 complete rows of P = Qn y.
+// Runs alm_inner_row and stores u+ (un; may be u itself: a row's lanes read their own elements
+// before they write them) and, where yn != NULL, y+. yn is never the y the product reads: other
+// workgroups may still be streaming it. No sums, so no grid reduction; waves past NE have no rows.
+// Shared by k_atr_alm and k_alm_inner_panel, so both write the same bits.
+template <typename T>
+struct AlmScalars {
+  T t, mu, gamma, a1, gn;
+};
+template <typename T, int NT, int WL>
+__device__ inline void alm_panel_rows(const T (&ps)[4][NT], int64_t col0, const T* __restrict__ y,
+                                      const T* __restrict__ J, const T* u, T* un, T* __restrict__ yn,
+                                      const AlmScalars<T>& sc) {
+  typedef MF<T> M;
+  constexpr int L = 16 * NT;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int i = lane & 15;
+  if (wave >= atr_ne<WL>()) return;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
+    T yv[NT], jv[NT], uv[NT], uo[NT], yo[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      yv[nt] = y[row * L + nt * 16 + i];
+      jv[nt] = J[row * L + nt * 16 + i];
+      uv[nt] = u[row * L + nt * 16 + i];
+    }
+    alm_inner_row<T, 16, NT>(ps[r], yv, jv, uv, sc.t, sc.mu, sc.gamma, sc.a1, sc.gn, uo, yo);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+      un[row * L + nt * 16 + i] = uo[nt];
+      if (yn != nullptr) yn[row * L + nt * 16 + i] = yo[nt];
+    }
+  }
+}
+
+// The inner step fused into P = Qn^T y (= Qn y): once the block's reduction (and, with K splits,
+// the last arriver's slab combine) leaves each wave its 16 complete rows of P, alm_panel_rows runs
+// on them. One launch per inner step.
+template <typename T, int NT, int PF, bool NTL, bool SPLIT, int WL>
+__global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && sizeof(T) == 8) ? 2 : 1) void k_atr_alm(const T* __restrict__ Qn, const T* __restrict__ y,
+                                                  int64_t n, const T* __restrict__ J, const T* u, T* un,
+                                                  T* __restrict__ yn, AlmScalars<T> sc, int S,
+                                                  T* __restrict__ Gp, unsigned* __restrict__ pcnt,
+                                                  int keep_mib) {
+  typedef MF<T> M;
+  const int wave = threadIdx.x >> 6;
+  typename M::acc_t acc[4][NT];
+  const int64_t bid = (int64_t)blockIdx.x;
+  const int64_t panel = SPLIT ? bid / S : bid, split = SPLIT ? bid % S : 0;
+  const int64_t col0 = atr_panel<T, NT, PF, WL, NTL>(Qn, y, n, n, SPLIT ? S : 1, acc, panel, split, keep_mib);
+  if constexpr (SPLIT) {
+    int slot;
+    if (!atr_split_combine<T, NT>(acc, Gp, n, S, panel, split, pcnt, &slot)) return;
+  }
+  T ps[4][NT];
+#pragma unroll
+  for (int e = 0; e < atr_ne<WL>(); ++e) {
+    if (e != wave) continue;   // (static register index into acc)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) ps[r][nt] = acc[e][nt][r];
+  }
+  alm_panel_rows<T, NT, WL>(ps, col0, y, J, u, un, yn, sc);
+}
+
+// The unfused form on the same layout: P = the sum, in slab order (atr_split_combine's order), of
+// the S slabs launch_atr wrote; one workgroup per panel. Every bit equals k_atr_alm's.
+template <typename T, int NT, int WL>
+__global__ __launch_bounds__(atr_waves<WL>() * 64) void k_alm_inner_panel(const T* __restrict__ P, int S, int64_t n,
+                                                  const T* __restrict__ y, const T* __restrict__ J,
+                                                  const T* u, T* un, T* __restrict__ yn,
+                                                  AlmScalars<T> sc) {
+  typedef MF<T> M;
+  constexpr int L = 16 * NT;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int i = lane & 15;
+  const int64_t col0 = (int64_t)blockIdx.x * atr_pw<WL>();
+  const int64_t nl = n * L;
+  T ps[4][NT];
+  if (wave < atr_ne<WL>()) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) ps[r][nt] = slab_sum(P, S, nl, row * L + nt * 16 + i);
+    }
+  }
+  alm_panel_rows<T, NT, WL>(ps, col0, y, J, u, un, yn, sc);
+}
+
 // A^T R on VALU: a thread owns E consecutive columns of A over a row range; R[row][c0..c0+LB)
 // is wave-uniform (scalar loads). Gp[blockIdx.y][n][l].
 template <typename T, int LB, bool VEC>
@@ -813,6 +909,58 @@ void launch_admm_dual_panel(const GemmPlan& p, const T* x, const T* g, int S, T*
   });
 }
 
+template <typename T>
+static AlmScalars<T> alm_scalars(double t, double mu, double gamma, double gamma_next) {
+  return AlmScalars<T>{(T)t, (T)mu, (T)gamma, (T)(1.0 - gamma_next), (T)gamma_next};
+}
+template <typename T, int NT, int PF, bool NTL, int WL>
+static void atr_alm_go(const GemmPlan& p, const T* Qn, const T* y, const T* J, const T* u, T* un, T* yn,
+                       const AlmScalars<T>& sc, hipStream_t st, T* Gp, unsigned* pcnt) {
+  const dim3 grid((unsigned)(p.n / atr_pw<WL>() * p.atr_S));
+  const dim3 block(atr_waves<WL>() * 64);
+  if (WL != 3 && WL != 4 && p.atr_S > 1) {
+    glx_launch((k_atr_alm<T, NT, PF, NTL, true, WL>), grid, block, 0, st, Qn, y, p.n, J, u, un, yn, sc,
+               p.atr_S, Gp, pcnt, p.atr_keep_mib);
+    return;
+  }
+  static const size_t pad = lds_pad(k_atr_alm<T, NT, PF, NTL, false, WL>, "GLX_ATR_LDS_PAD");
+  glx_launch((k_atr_alm<T, NT, PF, NTL, false, WL>), grid, block, pad, st, Qn, y, p.n, J, u, un, yn, sc, 1,
+             Gp, pcnt, p.atr_keep_mib);
+}
+template <typename T>
+void launch_atr_alm(const GemmPlan& p, const T* Qn, const T* y, const T* J, const T* u, T* un, T* yn,
+                    double t, double mu, double gamma, double gamma_next, hipStream_t st, T* Gp,
+                    unsigned* pcnt) {
+  if (p.m != p.n) throw Error{GLX_E_INVALID, "fused Qn y: the plan must be of the square (n, n, l)"};
+  if (yn == y) throw Error{GLX_E_INVALID, "fused Qn y: y+ must not be written over the product's operand"};
+  if (p.atr_S > 1 && (Gp == nullptr || pcnt == nullptr))
+    throw Error{GLX_E_INVALID, "fused A^T R with K splits needs slab and counter buffers"};
+  const AlmScalars<T> sc = alm_scalars<T>(t, mu, gamma, gamma_next);
+  atr_visit<T, true>(p, "fused Qn y + ALM inner step", [&](auto i, auto nt) {
+    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
+    atr_alm_go<T, decltype(nt)::value, tile.pf, tile.ntl, tile.wl>(p, Qn, y, J, u, un, yn, sc, st, Gp, pcnt);
+  });
+}
+
+template <typename T>
+void launch_alm_inner_panel(const GemmPlan& p, const T* P, int S, const T* y, const T* J, const T* u, T* un,
+                            T* yn, double t, double mu, double gamma, double gamma_next, hipStream_t st) {
+  const AlmScalars<T> sc = alm_scalars<T>(t, mu, gamma, gamma_next);
+  atr_visit<T, true>(p, "ALM inner step on the panel layout", [&](auto i, auto nt) {
+    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
+    constexpr int WL = tile.wl, NT = decltype(nt)::value;
+    glx_launch((k_alm_inner_panel<T, NT, WL>), dim3((unsigned)(p.n / atr_pw<WL>())), dim3(atr_waves<WL>() * 64),
+               0, st, P, S, p.n, y, J, u, un, yn, sc);
+  });
+}
+
+// (dual ALM is fp64 only)
+template void launch_atr_alm<double>(const GemmPlan&, const double*, const double*, const double*,
+                                     const double*, double*, double*, double, double, double, double,
+                                     hipStream_t, double*, unsigned*);
+template void launch_alm_inner_panel<double>(const GemmPlan&, const double*, int, const double*,
+                                             const double*, const double*, double*, double*, double,
+                                             double, double, double, hipStream_t);
 template void launch_admm_dual_panel<double>(const GemmPlan&, const double*, const double*, int, double*,
                                              double*, double*, double*, double, double, double, Red,
                                              hipStream_t);

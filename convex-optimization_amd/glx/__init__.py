@@ -8,6 +8,7 @@ Public surface:
   * ``admm`` — the dual ADMM solver ``gl_Admm_dual`` (``admm.solve``; drop-in module ``gl_ADMM_dual``);
   * ``admm_primal`` — the primal ADMM solver ``gl_Admm_primal`` (``admm_primal.solve``; drop-in module
     ``gl_ADMM_primal``);
+  * ``alm`` — the dual ALM solver ``gl_Alm_dual`` (``alm.solve``; drop-in module ``gl_ALM_dual``);
   * ``dist`` — row sharding + RCCL communicator.
 """
 from ._lib import LIB_PATH, GlxError, lib  # noqa: F401

@@ -61,6 +61,14 @@ class GlxAdmmPrimalOpts(ctypes.Structure):
                 ("form", c_int32), ("max_total_iters", c_int64), ("reserved", c_int32 * 4)]
 
 
+class GlxAlmOpts(ctypes.Structure):
+    """glx_alm_opts (include/glx.h): the options of the dual ALM solver."""
+    _fields_ = [("maxit", c_int32), ("converge_len", c_int32), ("thres", c_double),
+                ("tau", c_double), ("rho", c_double), ("inner_iters", c_int32),
+                ("inner_step", c_double), ("fused", c_int32), ("max_total_iters", c_int64),
+                ("reserved", c_int32 * 4)]
+
+
 class GlxError(RuntimeError):
     """Error returned by libglx (message from glx_last_error())."""
 
@@ -160,6 +168,19 @@ _SIGS = {
                                      c_void_p, c_void_p, c_void_p, c_double, c_double, c_double,
                                      c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_alm_default_opts": (c_int, [POINTER(GlxAlmOpts)]),
+    "glx_alm_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(GlxAlmOpts),
+                                        POINTER(c_size_t)]),
+    "glx_alm_describe": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(GlxAlmOpts), c_char_p,
+                                 c_size_t]),
+    "glx_alm_dual_solve": (c_int, [POINTER(GlxProblem), c_void_p, c_void_p, POINTER(GlxAlmOpts), c_void_p,
+                                   c_size_t, POINTER(GlxResult), c_void_p]),
+    "glx_alm_inner_workspace_bytes": (c_int, [c_int, c_int64, c_int64, POINTER(c_size_t)]),
+    "glx_alm_inner_step": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_double, c_double, c_double, c_double, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_alm_inner_run": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_double, c_double,
+                                  c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "glx_comm_unique_id": (c_int, [POINTER(c_uint8)]),
     "glx_comm_create": (c_int, [POINTER(c_void_p), POINTER(c_uint8), c_int, c_int]),
     "glx_comm_create_host": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
@@ -235,6 +256,22 @@ def admm_describe(dtype: int, m: int, n: int, l: int, opts: "GlxAdmmOpts | None"
     buf = ctypes.create_string_buffer(2048)
     check(lib().glx_admm_describe(dtype, m, n, l, ctypes.byref(opts) if opts is not None else None,
                                   buf, len(buf)))
+    return buf.value.decode()
+
+
+def alm_default_opts() -> GlxAlmOpts:
+    o = GlxAlmOpts()
+    check(lib().glx_alm_default_opts(ctypes.byref(o)))
+    return o
+
+
+def alm_describe(dtype: int, m: int, n: int, l: int, opts: "GlxAlmOpts | None" = None) -> str:
+    """The tiles of the dual ALM solver's passes over K, A and Qn and whether its inner step is fused
+    (glx_alm_describe: resolved on the host, no device). GlxError for what the solve refuses, fp32
+    included."""
+    buf = ctypes.create_string_buffer(2048)
+    check(lib().glx_alm_describe(dtype, m, n, l, ctypes.byref(opts) if opts is not None else None,
+                                 buf, len(buf)))
     return buf.value.decode()
 
 

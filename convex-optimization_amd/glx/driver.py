@@ -21,9 +21,9 @@ Differences, all forced by what the image lacks:
 - The svg plots (``main.py:200-235``) are replaced by ``f_hist.npz`` in ``--dest_dir``: the
   per-solver objective histories and f* = obj(u) those plots are drawn from. matplotlib is
   not installed.
-- Of the ALM/ADMM solvers ADMM dual and ADMM primal are built (``gl_ADMM_dual.gl_Admm_dual``,
-  ``gl_ADMM_primal.gl_Admm_primal``, DESIGN.md "Dual ADMM" and "Primal ADMM"); they are not
-  registered here. ALM dual is out of scope.
+- The ALM/ADMM solvers ADMM dual, ADMM primal and ALM dual are built (``gl_ADMM_dual.gl_Admm_dual``,
+  ``gl_ADMM_primal.gl_Admm_primal``, ``gl_ALM_dual.gl_Alm_dual``, DESIGN.md "Dual ADMM", "Primal
+  ADMM" and "Dual ALM"); they are not registered here.
 
 Every solver runs on the GPU through libglx (``glx.solver.solve``); there is no CPU path.
 

@@ -9,7 +9,8 @@ and the replicated halves of the row-sharded schedules), and the descent-method 
 launch at a time (``glx_descent_step``, ``glx_fgd_gradient``, ``glx_row_stats``,
 ``glx_threshold``, ``glx_thr_combine``, ``glx_descent_pass``), and the dual ADMM solver's row step,
 Gram kernel and host eigenvalue sweep (``glx_admm_dual_step``, ``glx_admm_primal_step``, ``glx_gram``,
-``glx_sym_lambda_max``). All tensors are contiguous device
+``glx_sym_lambda_max``), and the dual ALM solver's inner step and inner loop (``glx_alm_inner_step``,
+``glx_alm_inner_run``). All tensors are contiguous device
 tensors of one dtype (float32 / float64).
 """
 from __future__ import annotations
@@ -438,6 +439,56 @@ def admm_primal_step(prod: torch.Tensor, x: torch.Tensor, y: torch.Tensor, z: to
                                      ws.data_ptr(), ws.numel(), _stream(dev)))
     outs["sums"] = sums
     return outs
+
+
+def _alm_inner_ws(dtype: int, n: int, l: int, device) -> torch.Tensor:
+    nb = ctypes.c_size_t(0)
+    check(lib().glx_alm_inner_workspace_bytes(dtype, n, l, ctypes.byref(nb)))
+    return torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+
+
+def alm_inner_step(y: torch.Tensor, u: torch.Tensor, J: torch.Tensor, gamma: float, gamma_next: float,
+                   t: float, mu: float, P: Optional[torch.Tensor] = None, Qn: Optional[torch.Tensor] = None,
+                   form: int = 0, y_out: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """One step of dual ALM's inner loop (gl_ALM_dual.py:56-61, glx_alm_inner_step): with P = Qn y,
+    w = y - t (P + J), u+ = (mu w) / max(||w_i||, mu), v = u + (u+ - u) / gamma,
+    y+ = (1 - gamma_next) u+ + gamma_next v. form 0: the row kernel on the given ``P``, (n, l) or
+    (S, n, l) slabs summed in slab order (the panel layout where the plan of (n, n, l) fuses, the
+    generic one elsewhere); form 1: the epilogue of Qn^T y (``Qn`` given). gamma_next = 0: y+ is not
+    written (``y_out``, NaN-filled unless passed in, stays as it was). float64 only.
+    Returns {"u", "y"}."""
+    n, l = y.shape
+    dt = _dt(y)
+    dev = y.device
+    S = 1
+    if form == 0:
+        if P is None:
+            raise ValueError("form 0 needs P")
+        P = P.contiguous()
+        S = _slabs(P, n, l)
+    elif Qn is None:
+        raise ValueError("form 1 needs Qn")
+    un = torch.full_like(y, float("nan"))
+    yn = torch.full_like(y, float("nan")) if y_out is None else y_out
+    ws = _alm_inner_ws(dt, n, l, dev)
+    check(lib().glx_alm_inner_step(dt, n, l, _ptr(Qn), _ptr(P), int(S), y.data_ptr(), u.data_ptr(), J.data_ptr(),
+                                   float(gamma), float(gamma_next), float(t), float(mu), int(form),
+                                   un.data_ptr(), yn.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return {"u": un, "y": yn}
+
+
+def alm_inner_run(Qn: torch.Tensor, J: torch.Tensor, iters: int, t: float, mu: float,
+                  fused: int = 0) -> torch.Tensor:
+    """The dual ALM driver's inner loop (glx_alm_inner_run): ``iters`` steps from u = y = 0 with
+    gamma = 2 / (i + 1), enqueued back to back; fused: 0 auto, 1 on, 2 off. Returns u."""
+    n, l = J.shape
+    dt = _dt(J)
+    dev = J.device
+    u = torch.full_like(J, float("nan"))
+    ws = _alm_inner_ws(dt, n, l, dev)
+    check(lib().glx_alm_inner_run(dt, n, l, Qn.data_ptr(), J.data_ptr(), int(iters), float(t), float(mu),
+                                  int(fused), u.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return u
 
 
 def gram(R: torch.Tensor) -> torch.Tensor:

@@ -18,7 +18,8 @@
  *                  one product with the explicit inverse K = (I + rho A A^T)^-1, caller-computed)
  *   primal ADMM <- code/gl_ADMM_primal.py:10-117    (gl_Admm_primal; glx_admm_primal_*, likewise with
  *                  an explicit inverse of rho I + A^T A, directly or through the Woodbury identity)
- * The reference's ALM dual solver is out of scope.
+ *   dual ALM    <- code/gl_ALM_dual.py:10-158       (gl_Alm_dual; glx_alm_*, with the explicit inverses
+ *                  K and Qn = rho (I + rho A^T A)^-1; the 500-step inner loop runs on the device)
  *
  * Conventions
  *   - Every pointer named "device" is HBM memory on the current HIP device; the library never
@@ -361,8 +362,8 @@ int glx_plan_describe(int dtype, int64_t m, int64_t n, int64_t l, char* out, siz
 
 /* ---- the dual ADMM solver (additive entries; the ABI version stays 2) ----
  * GLX dual ADMM <- code/gl_ADMM_dual.py:10-103, gl_Admm_dual(x0, A, b, mu, opts). Of the
- * reference's three factorising solvers this was the first built (ADMM primal follows below); ALM
- * dual remains out of scope. The reference solves with the Cholesky factor of I + rho A A^T at every iteration
+ * reference's three factorising solvers this was the first built (ADMM primal and ALM dual follow
+ * below). The reference solves with the Cholesky factor of I + rho A A^T at every iteration
  * (:57, :63); here the caller computes the explicit inverse K = (I + rho A A^T)^-1 once per solve
  * (m x m, always in fp64, then cast to dtype; plumbing, like alpha0 = 1 / lambda_max above) and
  * hands it in as a device pointer, so z = K v is one more dense product. Per iteration: one pass
@@ -491,6 +492,73 @@ int glx_admm_primal_step(int dtype, int64_t n, int64_t l, int form, int S, const
                          double rho, double tau, double eta, double mu, double thres, void* x_out,
                          void* y_out, void* z_out, void* r_out, void* s_out, void* w_out,
                          void* sums_dev, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- the dual ALM solver (additive entries; the ABI version stays 2) ----
+ * GLX dual ALM <- code/gl_ALM_dual.py:10-158, gl_Alm_dual(x0, A, b, mu, opts). At every outer
+ * iteration the reference rebuilds T = (I + rho A A^T)^-1, F = rho T A, G = I - A^T F,
+ * Q = F^T F + rho G^T G and J (:33-40) and runs 500 Nesterov steps on grad = Q u + J (:53-61). Two
+ * identities remove that: G = (I + rho A^T A)^-1, so Q = rho G =: Qn depends on A and rho alone, and
+ * J = rho H = rho (A^T K (A x - b) - x / rho). The caller builds K = (I + rho A A^T)^-1 (m x m) and
+ * Qn (n x n, symmetric) once per solve, in fp64, and hands both in. Per outer iteration: two passes
+ * over K (E = K (Ax - b); z = K v), two A^T passes (A^T E, A^T z), two passes over A (A u;
+ * A @ [x+ | u]), inner_iters inner steps with one pass over Qn each, enqueued back to back with no
+ * host synchronisation and no graph, and one readback of the small record of the ADMM solvers.
+ * l <= 32. Single GPU. GLX_F64 only: I + rho A^T A has condition number about rho ||A||^2 (1e5 ..
+ * 1e6 at the default rho for m < n) and the inner loop multiplies by its inverse 500 times per outer
+ * iteration; GLX_F32 is GLX_E_INVALID in every entry below. */
+typedef struct glx_alm_opts {
+  int32_t maxit;            /* gl_ALM_dual.py:68 (100)                                         */
+  int32_t converge_len;     /* :72 (20): stop after this many consecutive small iterations     */
+  double  thres;            /* :69 (1e-3): both spectral norms below it count as small         */
+  double  tau;              /* :70 ((1 + sqrt 5) / 2)                                          */
+  double  rho;              /* :71 (1e2); K and Qn must have been built with the same value    */
+  int32_t inner_iters;      /* :53 (500), the reference's hard-coded max_iteration; >= 1       */
+  double  inner_step;       /* :57 (1e-2), the reference's hard-coded t. As in the reference,
+                               nothing guards inner_step * rho > 1 (the step then exceeds
+                               1 / ||Qn|| and the inner loop may diverge)                      */
+  int32_t fused;            /* the inner step in the epilogue of Qn y: 0 auto (on where the plan
+                               of (n, n, l) admits it), 1 on (likewise), 2 off                 */
+  int64_t max_total_iters;  /* stop after this many outer iterations (0 = off)                 */
+  int32_t reserved[4];
+} glx_alm_opts;
+int glx_alm_default_opts(glx_alm_opts* out);
+/* Device bytes glx_alm_dual_solve needs (opts may be NULL: the defaults). */
+int glx_alm_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, const glx_alm_opts* opts,
+                            size_t* bytes);
+/* One line: the tiles of the passes over K, A and Qn and whether the inner step is fused ("inner
+ * step=fused ..." or "inner step=row kernel ..."). Resolved on the host; needs no device. */
+int glx_alm_describe(int dtype, int64_t m, int64_t n, int64_t l, const glx_alm_opts* opts, char* out,
+                     size_t cap);
+/* The whole solve. prob->x holds x0 on entry and the iterate on return; prob->method is ignored.
+ * GLX_E_INVALID for a communicator, l = 0 or l > 32, GLX_F32, rho <= 0, inner_iters < 1, fused
+ * outside 0..2, a NULL or not 16-byte aligned pointer and a workspace smaller than
+ * glx_alm_workspace_bytes. Fills res as glx_admm_dual_solve does: ax_calls = 2 iters + 1,
+ * atr_calls = 2 iters, syncs = iters; stats[0] = passes over K (2 iters), stats[1] = 1 when the
+ * inner step ran fused, stats[2] = inner steps run (iters * inner_iters). maxit = 0 returns x0 and
+ * its objective. glx_admm_trace serves this solver too. */
+int glx_alm_dual_solve(const glx_problem* prob, const void* K_device, const void* Qn_device,
+                       const glx_alm_opts* opts, void* workspace, size_t workspace_bytes, glx_result* res,
+                       void* stream);
+/* ---- the dual ALM inner loop, one launch or one loop at a time (test surface) ----
+ * Workspace of the two entries below for (n, l). */
+int glx_alm_inner_workspace_bytes(int dtype, int64_t n, int64_t l, size_t* bytes);
+/* One inner step: with P = Qn y, w = y - t (P + J), u_out = (mu w) / max(||w_i||, mu),
+ * v = u + (u_out - u) / gamma, y_out = (1 - gamma_next) u_out + gamma_next v.
+ *   form 0: the row kernel on the given P = S >= 1 slabs of n * l values summed in slab order (Qn is
+ *           unused): on the epilogue's panel layout where the plan of (n, n, l) fuses
+ *           (k_alm_inner_panel: every bit equals form 1's), on the generic row layout elsewhere.
+ *   form 1: the epilogue of P = Qn^T y (k_atr_alm; P and S are unused). GLX_E_INVALID where the plan
+ *           takes no fused epilogue (glx_alm_describe).
+ * gamma_next = 0: y_out is not written. u_out may be u; y_out must not be y. */
+int glx_alm_inner_step(int dtype, int64_t n, int64_t l, const void* Qn, const void* P, int S, const void* y,
+                       const void* u, const void* J, double gamma, double gamma_next, double t, double mu,
+                       int form, void* u_out, void* y_out, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/* The driver's inner loop from u = y = 0: `iters` steps with gamma = 2 / (i + 1), enqueued back to
+ * back; u_out (n x l) receives u. fused as in glx_alm_opts. */
+int glx_alm_inner_run(int dtype, int64_t n, int64_t l, const void* Qn, const void* J, int iters, double t,
+                      double mu, int fused, void* u_out, void* workspace, size_t workspace_bytes,
+                      void* stream);
 
 /* ---- multi-GPU (row-sharded A; A^T r all-reduced, or reduce-scattered with the row-sharded step) ---- */
 #define GLX_COMM_ID_BYTES 128
