@@ -1,0 +1,229 @@
+// certificate.cpp — the native driver of the optimality certificate (DESIGN.md "Certificate"): for
+// any iterate x of  P(x) = 1/2 ||A x - b||_F^2 + mu sum_i ||x_i||_2  one pass over A (r = A x - b
+// with ||r||^2 and <r, b>) and one over A^T (g = A^T r with the row terms of cert_row in its
+// epilogue where the plan fuses, a row kernel behind launch_atr elsewhere), then one readback of an
+// eight-value record from which the host composes the primal and dual objectives, the duality gap
+// of the rescaled residual theta = s r, s = min(1, mu / max_i ||g_i||), and the KKT violation.
+// Single GPU; beside the solvers' drivers and independent of Session<T>.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <type_traits>
+
+#include "glx.h"
+#include "glx_internal.h"
+
+namespace glx {
+namespace {
+
+#define GLX_HIP(expr)                                                                          \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess) throw Error{GLX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)}; \
+  } while (0)
+
+inline void check_launch() {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) throw Error{GLX_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)};
+}
+
+template <typename F>
+int guarded(F&& f) {
+  try {
+    f();
+    return GLX_OK;
+  } catch (const Error& e) {
+    g_last_error = e.msg;
+    return e.code;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return GLX_E_STATE;
+  } catch (...) {
+    g_last_error = "unknown error";
+    return GLX_E_STATE;
+  }
+}
+
+using admm::Carver;
+using admm::plan_field;
+
+constexpr int kCertRec = 8;   // the record: [||r||^2, <r, b>] (k_cert_fin), the five row sums, fused
+
+// A's plan is the ADMM solvers' (admm::a_plan), so the fuse condition is theirs: the plan takes a
+// fused epilogue and its tile is built for it.
+struct CertPlan {
+  int es = 8;
+  GemmPlan a{};
+  bool fuse_ok = false;
+};
+CertPlan cert_plan(int dtype, int64_t m, int64_t n, int64_t l) {
+  if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+  if (m <= 0 || n <= 0 || l <= 0) throw Error{GLX_E_INVALID, "m, n, l must be positive"};
+  if (l > kMaxL) throw Error{GLX_E_INVALID, "the certificate takes l <= 128"};
+  CertPlan p;
+  p.es = dtype == GLX_F64 ? 8 : 4;
+  p.a = admm::a_plan(dtype, m, n, l);
+  p.fuse_ok = atr_prox_ok(p.a) && (p.a.atr->fused & dtype_bit(p.es)) != 0;
+  return p;
+}
+void check_fused(int fused) {
+  if (fused < 0 || fused > 2) throw Error{GLX_E_INVALID, "fused must be 0 (auto), 1 (on) or 2 (off)"};
+}
+// fused: 0 auto, 1 on (where admitted), 2 off. Auto = on (DESIGN.md "Certificate": the A/B).
+bool use_fused(const CertPlan& p, int fused) { return p.fuse_ok && fused != 2; }
+
+std::string describe_cert(const CertPlan& p, int fused) {
+  std::string s = "A x=" + plan_field(p.a, 0) + "; A^T r=" + plan_field(p.a, 3) + "; rows=";
+  s += use_fused(p, fused) ? "fused (k_atr_cert, the A^T r epilogue)"
+                           : (p.fuse_ok ? "row kernel (k_cert_panel, the epilogue's layout)" : "row kernel (k_cert_row)");
+  return s;
+}
+
+struct CertWs {
+  double* part; unsigned* ticket; unsigned* pcnt; double* rec;
+  void *r, *pa, *gp;
+};
+size_t cert_carve(const CertPlan& p, int64_t m, int64_t n, int64_t l, void* base, CertWs* out) {
+  Carver c(base);
+  const size_t es = (size_t)p.es;
+  CertWs w;
+  w.part = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals * kMaxBlocks));
+  w.ticket = static_cast<unsigned*>(c.take(kTicketBytes));
+  w.pcnt = static_cast<unsigned*>(c.take(sizeof(unsigned) * (n / 64 + 64)));
+  w.rec = static_cast<double*>(c.take(sizeof(double) * kCertRec));
+  w.r = c.take(es * m * l);
+  w.pa = c.take(es * m * l * std::max(1, ax_split(p.a, 1)));
+  w.gp = c.take(es * n * l * std::max(1, p.a.atr_S));   // the K-split slabs of A^T r
+  if (out) *out = w;
+  return c.off + 256;
+}
+void check_ws(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const void* ws, size_t wsb) {
+  if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
+  if (wsb < cert_carve(pl, m, n, l, nullptr, nullptr))
+    throw Error{GLX_E_INVALID, "workspace too small (glx_certificate_workspace_bytes)"};
+  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
+}
+
+// the A^T pass and the row terms: g = A^T R, the five sums into red
+template <typename T>
+void cert_rows(const CertPlan& pl, bool fused, const T* A, const T* R, const T* x, double mu, T* G, double* rn,
+               const CertWs& w, Red red, hipStream_t st) {
+  const int SG = pl.a.atr_S;
+  T* gp = static_cast<T*>(w.gp);
+  if (fused) {
+    launch_atr_cert<T>(pl.a, A, R, G, x, rn, mu, red, st, SG > 1 ? gp : nullptr, w.pcnt);
+    return;
+  }
+  // the row kernel on the slabs: where the plan would fuse, on the epilogue's panel layout, so
+  // that fused = 1 and fused = 2 give the same bits (the sums' order included)
+  launch_atr<T>(pl.a, A, R, gp, st);
+  if (pl.fuse_ok) launch_cert_panel<T>(pl.a, x, gp, SG, G, rn, mu, red, st);
+  else launch_cert_row<T>(x, gp, SG, G, rn, pl.a.n, pl.a.l, mu, red, st);
+}
+
+template <typename T>
+void certificate(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const T* A, const T* X, const T* b,
+                 double mu, int fused_opt, T* G, double* rn, double* out, void* ws, hipStream_t st) {
+  CertWs w;
+  cert_carve(pl, m, n, l, ws, &w);
+  const bool fused = use_fused(pl, fused_opt);
+  const int64_t ml = m * l;
+  T *r = static_cast<T*>(w.r), *pa = static_cast<T*>(w.pa);
+  GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+  GLX_HIP(hipMemsetAsync(w.pcnt, 0, sizeof(unsigned) * (n / 64 + 64), st));
+  GLX_HIP(hipMemsetAsync(w.rec, 0, sizeof(double) * kCertRec, st));
+  const T* xs[3] = {X, nullptr, nullptr};
+  launch_ax<T>(pl.a, 1, A, xs, pa, nullptr, 0, st);
+  launch_cert_fin<T>(pa, ax_split(pl.a, 1), b, r, ml, Red{w.part, w.ticket, w.rec}, st);
+  cert_rows<T>(pl, fused, A, r, X, mu, G, rn, w, Red{w.part, w.ticket, w.rec + 2}, st);
+  check_launch();
+  GLX_HIP(hipMemcpyAsync(out, w.rec, sizeof(double) * kCertRec, hipMemcpyDeviceToHost, st));
+  GLX_HIP(hipStreamSynchronize(st));
+  out[7] = fused ? 1.0 : 0.0;
+}
+
+}  // namespace
+}  // namespace glx
+
+using namespace glx;
+
+extern "C" {
+
+int glx_certificate_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    *bytes = cert_carve(cert_plan(dtype, m, n, l), m, n, l, nullptr, nullptr);
+  });
+}
+
+int glx_certificate_describe(int dtype, int64_t m, int64_t n, int64_t l, int fused, char* out, size_t cap) {
+  return guarded([&] {
+    if (!out || cap == 0) throw Error{GLX_E_INVALID, "null out"};
+    check_fused(fused);
+    std::snprintf(out, cap, "%s", describe_cert(cert_plan(dtype, m, n, l), fused).c_str());
+  });
+}
+
+int glx_certificate(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                    double mu, int fused, void* G_out, double* rownorm_out, double* out, void* ws, size_t wsb,
+                    void* stream) {
+  return guarded([&] {
+    const CertPlan pl = cert_plan(dtype, m, n, l);
+    check_fused(fused);
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    if (!A || !X || !b) throw Error{GLX_E_INVALID, "A, X and b must be device pointers"};
+    if (!out) throw Error{GLX_E_INVALID, "null out"};
+    if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(b) |
+         reinterpret_cast<uintptr_t>(G_out)) & 15)
+      throw Error{GLX_E_INVALID, "A, X, b, G_out must be 16-byte aligned"};
+    check_ws(pl, m, n, l, ws, wsb);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == GLX_F64)
+      certificate<double>(pl, m, n, l, (const double*)A, (const double*)X, (const double*)b, mu, fused,
+                          (double*)G_out, rownorm_out, out, ws, st);
+    else
+      certificate<float>(pl, m, n, l, (const float*)A, (const float*)X, (const float*)b, mu, fused,
+                         (float*)G_out, rownorm_out, out, ws, st);
+  });
+}
+
+int glx_certificate_step(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* Z, void* G,
+                         const void* x, double mu, int form, double* rownorm_out, void* sums_dev, void* ws,
+                         size_t wsb, void* stream) {
+  return guarded([&] {
+    if (form != 0 && form != 1) throw Error{GLX_E_INVALID, "form must be 0 (row kernel) or 1 (A^T r epilogue)"};
+    const CertPlan pl = cert_plan(dtype, m, n, l);
+    if (!G || !x || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
+    if (form == 1) {
+      if (!A || !Z) throw Error{GLX_E_INVALID, "form 1 needs A and Z"};
+      if (!pl.fuse_ok)
+        throw Error{GLX_E_INVALID, "form 1: this shape's A^T R plan takes no fused epilogue (" + describe_plan(pl.a) + ")"};
+    }
+    check_ws(pl, m, n, l, ws, wsb);
+    CertWs w;
+    cert_carve(pl, m, n, l, ws, &w);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    GLX_HIP(hipMemsetAsync(w.pcnt, 0, sizeof(unsigned) * (n / 64 + 64), st));
+    Red red{w.part, w.ticket, static_cast<double*>(sums_dev)};
+    auto go = [&](auto* tag) {
+      typedef std::remove_pointer_t<decltype(tag)> T;
+      if (form == 0 && pl.fuse_ok)   // the layout the driver's unfused arm takes at this (m, n, l)
+        launch_cert_panel<T>(pl.a, (const T*)x, (const T*)G, 1, nullptr, rownorm_out, mu, red, st);
+      else if (form == 0)
+        launch_cert_row<T>((const T*)x, (const T*)G, 1, nullptr, rownorm_out, n, l, mu, red, st);
+      else
+        launch_atr_cert<T>(pl.a, (const T*)A, (const T*)Z, (T*)G, (const T*)x, rownorm_out, mu, red, st,
+                           pl.a.atr_S > 1 ? (T*)w.gp : nullptr, w.pcnt);
+    };
+    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
+    else go(static_cast<float*>(nullptr));
+    check_launch();
+  });
+}
+
+}  // extern "C"

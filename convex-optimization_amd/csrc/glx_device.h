@@ -627,6 +627,52 @@ __device__ inline void admm_dual_row(const T (&xv)[EPL], const T (&gv)[EPL], con
 }
 
 // ------------------------------------------------------------------------------------------
+// The optimality certificate's row terms (DESIGN.md "Certificate") for a lane that holds EPL
+// elements of the row (as admm_dual_row), with g = A^T (A x - b) and mu rounded to T:
+//   ||g_i||, ||x_i||, and the KKT violation of the row,
+//   kkt_i = ||g_i + (mu x_i) / ||x_i|| ||  where ||x_i|| != 0,   max(||g_i|| - mu, 0)  where it is 0
+// (a row counts as zero when its computed norm is; NaN compares false and stays NaN).
+// acc (per thread, reduced over the grid by the caller):
+//   [sum_i ||x_i||, max_i ||g_i||, max_i kkt_i, sum_i kkt_i^2, #{i : ||x_i|| != 0}]
+// with the two max entries NaN-propagating (nan_max) and the count NaN where a row's norm is.
+// Returns ||g_i|| (every lane of the row gets it). Shared by the A^T r epilogue (k_atr_cert), the
+// panel row kernel (k_cert_panel) and the generic one (k_cert_row), so the first two write the
+// same bits.
+// ------------------------------------------------------------------------------------------
+template <typename T, int LPR, int EPL>
+__device__ inline T cert_row(const T (&xv)[EPL], const T (&gv)[EPL], const bool (&ok)[EPL], bool rv,
+                             int sub, T mu, double (&acc)[5]) {
+  T gsq = T(0), xsq = T(0);
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) {
+    if (ok[e]) {
+      gsq = gsq + gv[e] * gv[e];
+      xsq = xsq + xv[e] * xv[e];
+    }
+  }
+  const T gn = __builtin_sqrt(row_allsum<LPR>(gsq));
+  const T xn = __builtin_sqrt(row_allsum<LPR>(xsq));
+  T ksq = T(0);
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) {
+    const T k = gv[e] + (mu * xv[e]) / xn;   // (0 / 0 in a zero row: not selected below)
+    if (ok[e]) ksq = ksq + k * k;
+  }
+  const T kn = __builtin_sqrt(row_allsum<LPR>(ksq));
+  T d = gn - mu;
+  d = (d < T(0)) ? T(0) : d;   // NaN compares false and stays
+  const T kkt = (xn == T(0)) ? d : kn;
+  if (rv && sub == 0) {
+    acc[0] += (double)xn;
+    acc[1] = nan_max(acc[1], (double)gn);
+    acc[2] = nan_max(acc[2], (double)kkt);
+    acc[3] += (double)kkt * (double)kkt;
+    acc[4] += (xn != xn) ? (double)xn : (xn != T(0) ? 1.0 : 0.0);
+  }
+  return gn;
+}
+
+// ------------------------------------------------------------------------------------------
 // Primal ADMM's row step (gl_ADMM_primal.py:47-51, 78-84) for a lane that holds EPL elements of
 // the row, on pv = the product of the inverse's pass: y+ = pv (direct: Kn w) or (w - pv) / rho
 // (WOODBURY: pv = A^T K (A w)). Then, in the reference's evaluation order,

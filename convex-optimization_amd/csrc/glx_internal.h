@@ -420,6 +420,29 @@ template <typename T>
 void launch_alm_x(const T* x, const T* u, const T* g, int S, T* xn, T* rn, int64_t n, int64_t l,
                   double taurho, Red red, hipStream_t st);
 
+// ---- the optimality certificate's kernels (kernels_cert.hip, kernels_atr.hip; DESIGN.md "Certificate") ----
+// The row terms of the certificate on g = A^T r and the iterate x (cert_row, glx_device.h). out:
+// [sum_i ||x_i||, max_i ||g_i||, max_i kkt_i, sum_i kkt_i^2, #{i : x_i != 0}], the max entries
+// NaN-propagating. gout / G (may be NULL) receives g, rn (may be NULL) ||g_i|| as n doubles.
+//   launch_atr_cert:    in the epilogue of G = A^T R under plan p (plan condition of
+//                       launch_atr_admm); Gp / pcnt as launch_atr_prox
+//   launch_cert_panel:  on S slabs of launch_atr under p, the epilogue's lane-to-row layout: every
+//                       bit, the five sums included, equals launch_atr_cert's
+//   launch_cert_row:    on S slabs of n * l values, any n and l <= kMaxL (kernels_elem.hip's layout)
+template <typename T>
+void launch_atr_cert(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, double* rn, double mu,
+                     Red red, hipStream_t st, T* Gp = nullptr, unsigned* pcnt = nullptr);
+template <typename T>
+void launch_cert_panel(const GemmPlan& p, const T* x, const T* g, int S, T* gout, double* rn, double mu,
+                       Red red, hipStream_t st);
+template <typename T>
+void launch_cert_row(const T* x, const T* g, int S, T* gout, double* rn, int64_t n, int64_t l, double mu,
+                     Red red, hipStream_t st);
+// r = (the sum, in slab order, of the S slabs of A x at P) - b over ml values; S = 0: r = 0 - b.
+// out: [sum r^2, sum r b] (accumulated in double)
+template <typename T>
+void launch_cert_fin(const T* P, int S, const T* b, T* r, int64_t ml, Red red, hipStream_t st);
+
 // ---- shared by the two ADMM drivers (defined in admm.cpp) ----
 namespace admm {
 constexpr int kMaxL = 32;    // the Gram kernel and the host Jacobi sweep

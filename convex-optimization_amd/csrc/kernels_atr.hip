@@ -605,6 +605,122 @@ __global__ __launch_bounds__(atr_waves<WL>() * 64) void k_admm_dual_panel(const 
                              (int)blockIdx.x, -1);
 }
 
+// The certificate's row terms on the panel layout an A^T R epilogue holds (as admm_panel_rows):
+// xa = the wave's values of the iterate, gs of g = A^T r. Runs cert_row, hands its five sums to
+// grid_reduce and then stores G (when non-null) and the rows' ||g_i|| as doubles (rn, when
+// non-null). Called by every thread of the workgroup (waves past NE reduce identities). Shared by
+// k_atr_cert and k_cert_panel, so the fused and the unfused form write the same bits, sums
+// included.
+template <typename T, int NT, int WL>
+__device__ inline void cert_panel_rows(const T (&xa)[4][NT], const T (&gs)[4][NT], int64_t col0,
+                                       T* __restrict__ G, double* __restrict__ rn, T mu,
+                                       const Red& red, int slot, int nparts) {
+  typedef MF<T> M;
+  constexpr int L = 16 * NT;
+  constexpr int NW = atr_waves<WL>();
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int i = lane & 15;
+  const bool mine = wave < atr_ne<WL>();
+  double accr[5] = {0.0, -__builtin_inf(), -__builtin_inf(), 0.0, 0.0};
+  T gn[4];
+  if (mine) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      bool ok[NT];
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) ok[nt] = true;
+      gn[r] = cert_row<T, 16, NT>(xa[r], gs[r], ok, true, i, mu, accr);
+    }
+  }
+  grid_reduce<5, 0x6u, NW>(accr, red, slot, nparts);
+  if (!mine) return;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
+    if (G != nullptr) {
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) G[row * L + nt * 16 + i] = gs[r][nt];
+    }
+    if (rn != nullptr && i == 0) rn[row] = (double)gn[r];
+  }
+}
+
+// The certificate's row terms fused into g = A^T r, assembled as k_atr_admm is: once the block's
+// reduction (and, with K splits, the last arriver's slab combine) leaves each wave its 16
+// complete rows of g, cert_panel_rows runs on them with x the iterate. G is written only where
+// the caller asks for it.
+template <typename T, int NT, int PF, bool NTL, bool SPLIT, int WL>
+__global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && sizeof(T) == 8) ? 2 : 1) void k_atr_cert(const T* __restrict__ A, const T* __restrict__ R,
+                                                  T* __restrict__ G, int64_t m, int64_t n,
+                                                  const T* __restrict__ x, double* __restrict__ rn,
+                                                  double mu_, Red red, int S, T* __restrict__ Gp,
+                                                  unsigned* __restrict__ pcnt, int keep_mib) {
+  const int nparts = SPLIT ? (int)(n / 64) : -1;   // with K splits only the panel owners reduce
+  typedef MF<T> M;
+  constexpr int L = 16 * NT;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int i = lane & 15;
+  typename M::acc_t acc[4][NT];
+  const int64_t bid = (int64_t)blockIdx.x;
+  const int64_t panel = SPLIT ? bid / S : bid, split = SPLIT ? bid % S : 0;
+  const int64_t col0 = atr_panel<T, NT, PF, WL, NTL>(A, R, m, n, SPLIT ? S : 1, acc, panel, split, keep_mib);
+  T xa[4][NT], gs[4][NT];
+#pragma unroll
+  for (int e = 0; e < atr_ne<WL>(); ++e) {
+    if (e != wave) continue;   // wave w owns the rows e == w (4 per lane group)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t row = col0 + atr_col<T>(M::row(lane, r), e);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) xa[r][nt] = x[row * L + nt * 16 + i];
+    }
+  }
+  int slot = (int)blockIdx.x;
+  if constexpr (SPLIT) {   // fixed reduction slots, see atr_split_combine
+    if (!atr_split_combine<T, NT>(acc, Gp, n, S, panel, split, pcnt, &slot)) return;
+  }
+#pragma unroll
+  for (int e = 0; e < atr_ne<WL>(); ++e) {
+    if (e != wave) continue;   // (static register index into acc)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) gs[r][nt] = acc[e][nt][r];
+  }
+  cert_panel_rows<T, NT, WL>(xa, gs, col0, G, rn, (T)mu_, red, slot, nparts);
+}
+
+// The unfused form on the same layout: g = the sum, in slab order (atr_split_combine's order), of
+// the S slabs launch_atr wrote under the same plan; one workgroup per panel, slot = panel. Every
+// bit it writes, the five sums included, equals k_atr_cert's.
+template <typename T, int NT, int WL>
+__global__ __launch_bounds__(atr_waves<WL>() * 64) void k_cert_panel(const T* __restrict__ x, const T* __restrict__ g, int S,
+                                                  T* __restrict__ gout, double* __restrict__ rn,
+                                                  int64_t n, double mu_, Red red) {
+  typedef MF<T> M;
+  constexpr int L = 16 * NT;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int i = lane & 15;
+  const int64_t col0 = (int64_t)blockIdx.x * atr_pw<WL>();
+  const int64_t nl = n * L;
+  T xa[4][NT], gs[4][NT];
+  if (wave < atr_ne<WL>()) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        xa[r][nt] = x[row * L + nt * 16 + i];
+        gs[r][nt] = slab_sum(g, S, nl, row * L + nt * 16 + i);
+      }
+    }
+  }
+  cert_panel_rows<T, NT, WL>(xa, gs, col0, gout, rn, (T)mu_, red, (int)blockIdx.x, -1);
+}
+
 // One step of dual ALM's inner loop (gl_ALM_dual.py:56-61) on the panel layout of an A^T R
 // epilogue, A = Qn (n x n, symmetric) and R = y: ps = the wave's 16 complete rows of P = Qn y.
 // Runs alm_inner_row and stores u+ (un; may be u itself: a row's lanes read their own elements
@@ -909,6 +1025,42 @@ void launch_admm_dual_panel(const GemmPlan& p, const T* x, const T* g, int S, T*
   });
 }
 
+template <typename T, int NT, int PF, bool NTL, int WL>
+static void atr_cert_go(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, double* rn, double mu,
+                        Red red, hipStream_t st, T* Gp, unsigned* pcnt) {
+  const dim3 grid((unsigned)(p.n / atr_pw<WL>() * p.atr_S));
+  const dim3 block(atr_waves<WL>() * 64);
+  if (WL != 3 && WL != 4 && p.atr_S > 1) {
+    glx_launch((k_atr_cert<T, NT, PF, NTL, true, WL>), grid, block, 0, st, A, R, G, p.m, p.n, x, rn, mu, red,
+               p.atr_S, Gp, pcnt, p.atr_keep_mib);
+    return;
+  }
+  static const size_t pad = lds_pad(k_atr_cert<T, NT, PF, NTL, false, WL>, "GLX_ATR_LDS_PAD");
+  glx_launch((k_atr_cert<T, NT, PF, NTL, false, WL>), grid, block, pad, st, A, R, G, p.m, p.n, x, rn, mu, red,
+             1, Gp, pcnt, p.atr_keep_mib);
+}
+template <typename T>
+void launch_atr_cert(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, double* rn, double mu,
+                     Red red, hipStream_t st, T* Gp, unsigned* pcnt) {
+  if (p.atr_S > 1 && (Gp == nullptr || pcnt == nullptr))
+    throw Error{GLX_E_INVALID, "fused A^T R with K splits needs slab and counter buffers"};
+  atr_visit<T, true>(p, "fused A^T r + certificate rows", [&](auto i, auto nt) {
+    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
+    atr_cert_go<T, decltype(nt)::value, tile.pf, tile.ntl, tile.wl>(p, A, R, G, x, rn, mu, red, st, Gp, pcnt);
+  });
+}
+
+template <typename T>
+void launch_cert_panel(const GemmPlan& p, const T* x, const T* g, int S, T* gout, double* rn, double mu,
+                       Red red, hipStream_t st) {
+  atr_visit<T, true>(p, "certificate rows on the panel layout", [&](auto i, auto nt) {
+    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
+    constexpr int WL = tile.wl, NT = decltype(nt)::value;
+    glx_launch((k_cert_panel<T, NT, WL>), dim3((unsigned)(p.n / atr_pw<WL>())), dim3(atr_waves<WL>() * 64),
+               0, st, x, g, S, gout, rn, p.n, mu, red);
+  });
+}
+
 template <typename T>
 static AlmScalars<T> alm_scalars(double t, double mu, double gamma, double gamma_next) {
   return AlmScalars<T>{(T)t, (T)mu, (T)gamma, (T)(1.0 - gamma_next), (T)gamma_next};
@@ -973,6 +1125,15 @@ template void launch_atr_admm<double>(const GemmPlan&, const double*, const doub
 template void launch_atr_admm<float>(const GemmPlan&, const float*, const float*, float*,
                                      const float*, float*, float*, float*, double, double, double,
                                      Red, hipStream_t, float*, unsigned*);
+template void launch_atr_cert<double>(const GemmPlan&, const double*, const double*, double*,
+                                      const double*, double*, double, Red, hipStream_t, double*,
+                                      unsigned*);
+template void launch_atr_cert<float>(const GemmPlan&, const float*, const float*, float*, const float*,
+                                     double*, double, Red, hipStream_t, float*, unsigned*);
+template void launch_cert_panel<double>(const GemmPlan&, const double*, const double*, int, double*,
+                                        double*, double, Red, hipStream_t);
+template void launch_cert_panel<float>(const GemmPlan&, const float*, const float*, int, float*, double*,
+                                       double, Red, hipStream_t);
 template void launch_atr<double>(const GemmPlan&, const double*, const double*, double*, hipStream_t);
 template void launch_atr_fista<double>(const GemmPlan&, const double*, const double*, double*,
                                        const double*, const double*, double*, double*, double*,

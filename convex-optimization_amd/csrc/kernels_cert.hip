@@ -1,0 +1,122 @@
+// kernels_cert.hip — the kernels of the optimality certificate (DESIGN.md "Certificate") around
+// its two dense products A x and g = A^T r:
+//   k_cert_fin  sums the slabs of A x in slab order into r = A x - b and reduces ||r||^2, <r, b>
+//   k_cert_row  the row terms (cert_row, glx_device.h) on a given g, any n and l <= kMaxL (their
+//               fused form is k_atr_cert and its panel counterpart k_cert_panel, kernels_atr.hip)
+// mu is rounded to T first, as in kernels_elem.hip; reductions are deterministic (grid_reduce,
+// fixed slabs) and accumulate in double.
+#include <cstdlib>
+#include <type_traits>
+
+#include "glx.h"
+#include "glx_device.h"
+
+namespace glx {
+
+static inline unsigned cert_grid_for(int64_t work, int per_block) {
+  int64_t g = (work + per_block - 1) / per_block;
+  if (g < 1) g = 1;
+  if (g > kMaxBlocks) g = kMaxBlocks;
+  return (unsigned)g;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_cert_fin(const T* __restrict__ P, int S, const T* __restrict__ b,
+                                                  T* __restrict__ r, int64_t ml, Red red) {
+  double v[2] = {0.0, 0.0};
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ml; idx += stride) {
+    const T ax = S > 0 ? slab_sum(P, S, ml, idx) : T(0);
+    const T bv = b[idx];
+    const T rv = ax - bv;
+    r[idx] = rv;
+    v[0] += (double)rv * (double)rv;
+    v[1] += (double)rv * (double)bv;
+  }
+  grid_reduce<2, 0u>(v, red);
+}
+
+// Rows of x are owned by LPR lanes holding EPL elements strided by LPR (kernels_elem.hip's layout)
+template <typename T, int LPR, int EPL>
+__global__ __launch_bounds__(256) void k_cert_row(const T* __restrict__ x, const T* __restrict__ g, int S,
+                                                  T* __restrict__ gout, double* __restrict__ rn, int64_t n,
+                                                  int64_t l, double mu_, Red red) {
+  const T mu = (T)mu_;
+  const int64_t nl = n * l;
+  double acc[5] = {0.0, -__builtin_inf(), -__builtin_inf(), 0.0, 0.0};
+  const int sub = threadIdx.x & (LPR - 1);
+  const int64_t rows_per_block = 256 / LPR;
+  const int64_t row_stride = (int64_t)gridDim.x * rows_per_block;
+  const int64_t n_trips = (n + row_stride - 1) / row_stride;
+  for (int64_t trip = 0; trip < n_trips; ++trip) {   // uniform trip count: every lane shuffles
+    const int64_t row = trip * row_stride + (int64_t)blockIdx.x * rows_per_block + (threadIdx.x / LPR);
+    const bool rv = row < n;
+    const int64_t base = (rv ? row : 0) * l;
+    T xv[EPL], gv[EPL];
+    bool ok[EPL];
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+      const int64_t j = sub + (int64_t)e * LPR;
+      ok[e] = rv && j < l;
+      xv[e] = ok[e] ? x[base + j] : T(0);
+      gv[e] = ok[e] ? slab_sum(g, S, nl, base + j) : T(0);
+      if (ok[e] && gout != nullptr) gout[base + j] = gv[e];
+    }
+    const T gn = cert_row<T, LPR, EPL>(xv, gv, ok, rv, sub, mu, acc);
+    if (rv && sub == 0 && rn != nullptr) rn[row] = (double)gn;
+  }
+  grid_reduce<5, 0x6u>(acc, red);
+}
+
+// ------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------
+template <typename T>
+void launch_cert_fin(const T* P, int S, const T* b, T* r, int64_t ml, Red red, hipStream_t st) {
+  hipLaunchKernelGGL(k_cert_fin<T>, dim3(cert_grid_for(ml, 256)), dim3(256), 0, st, P, S, b, r, ml, red);
+}
+
+template <typename T, int LPR, int EPL>
+static void cert_row_go(const T* x, const T* g, int S, T* gout, double* rn, int64_t n, int64_t l, double mu,
+                        Red red, hipStream_t st) {
+  unsigned grid = cert_grid_for(n, 256 / LPR);
+  if (grid > 512u) grid = 512u;   // two trips per workgroup at n = 16384 (kernels_elem.hip kRowBlocks)
+  hipLaunchKernelGGL((k_cert_row<T, LPR, EPL>), dim3(grid), dim3(256), 0, st, x, g, S, gout, rn, n, l, mu, red);
+}
+// F receives (lpr_constant, epl_constant): LPR = the power of two >= l up to 16, then EPL up to 8
+// at LPR 16 (kernels_elem.hip dispatch_row)
+template <typename F>
+static void cert_dispatch_row(int64_t l, F&& f) {
+#define GLX_CERT_LE(LPR, EPL) f(std::integral_constant<int, LPR>{}, std::integral_constant<int, EPL>{})
+  if (l <= 1) GLX_CERT_LE(1, 1);
+  else if (l <= 2) GLX_CERT_LE(2, 1);
+  else if (l <= 4) GLX_CERT_LE(4, 1);
+  else if (l <= 8) GLX_CERT_LE(8, 1);
+  else if (l <= 16) GLX_CERT_LE(16, 1);
+  else if (l <= 32) GLX_CERT_LE(16, 2);
+  else if (l <= 48) GLX_CERT_LE(16, 3);
+  else if (l <= 64) GLX_CERT_LE(16, 4);
+  else if (l <= 80) GLX_CERT_LE(16, 5);
+  else if (l <= 96) GLX_CERT_LE(16, 6);
+  else if (l <= 112) GLX_CERT_LE(16, 7);
+  else GLX_CERT_LE(16, 8);
+#undef GLX_CERT_LE
+}
+template <typename T>
+void launch_cert_row(const T* x, const T* g, int S, T* gout, double* rn, int64_t n, int64_t l, double mu,
+                     Red red, hipStream_t st) {
+  if (l < 1 || l > kMaxL) throw Error{GLX_E_INVALID, "the certificate's row kernel takes 1 <= l <= 128"};
+  cert_dispatch_row(l, [&](auto lpr, auto epl) {
+    cert_row_go<T, decltype(lpr)::value, decltype(epl)::value>(x, g, S, gout, rn, n, l, mu, red, st);
+  });
+}
+
+#define GLX_CERT_INST(T)                                                                              \
+  template void launch_cert_fin<T>(const T*, int, const T*, T*, int64_t, Red, hipStream_t);           \
+  template void launch_cert_row<T>(const T*, const T*, int, T*, double*, int64_t, int64_t, double, Red, \
+                                   hipStream_t);
+
+GLX_CERT_INST(double)
+GLX_CERT_INST(float)
+
+}  // namespace glx

@@ -9,9 +9,14 @@ Public surface:
   * ``admm_primal`` — the primal ADMM solver ``gl_Admm_primal`` (``admm_primal.solve``; drop-in module
     ``gl_ADMM_primal``);
   * ``alm`` — the dual ALM solver ``gl_Alm_dual`` (``alm.solve``; drop-in module ``gl_ALM_dual``);
+  * ``certificate(x, A, b, mu)`` — the duality gap and KKT violation of any iterate, and
+    ``mu_max(A, b)``, the smallest mu at which x = 0 is optimal (``glx/certificate.py``; the name
+    ``glx.certificate`` is the function, so its module's helpers are reached with
+    ``from glx.certificate import compose, record``);
   * ``dist`` — row sharding + RCCL communicator.
 """
 from ._lib import LIB_PATH, GlxError, lib  # noqa: F401
 from .solver import Session, solve  # noqa: F401
+from .certificate import certificate, mu_max  # noqa: F401
 
-__all__ = ["solve", "Session", "lib", "LIB_PATH", "GlxError"]
+__all__ = ["solve", "Session", "lib", "LIB_PATH", "GlxError", "certificate", "mu_max"]

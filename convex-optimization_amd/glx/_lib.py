@@ -181,6 +181,13 @@ _SIGS = {
                                    c_void_p, c_void_p, c_size_t, c_void_p]),
     "glx_alm_inner_run": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_double, c_double,
                                   c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_certificate_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "glx_certificate_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_char_p, c_size_t]),
+    "glx_certificate": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double,
+                                c_int, c_void_p, c_void_p, POINTER(c_double), c_void_p, c_size_t, c_void_p]),
+    "glx_certificate_step": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_double, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]),
     "glx_comm_unique_id": (c_int, [POINTER(c_uint8)]),
     "glx_comm_create": (c_int, [POINTER(c_void_p), POINTER(c_uint8), c_int, c_int]),
     "glx_comm_create_host": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
@@ -272,6 +279,14 @@ def alm_describe(dtype: int, m: int, n: int, l: int, opts: "GlxAlmOpts | None" =
     buf = ctypes.create_string_buffer(2048)
     check(lib().glx_alm_describe(dtype, m, n, l, ctypes.byref(opts) if opts is not None else None,
                                  buf, len(buf)))
+    return buf.value.decode()
+
+
+def certificate_describe(dtype: int, m: int, n: int, l: int, fused: int = 0) -> str:
+    """The tiles of the certificate's two passes and where its row terms run, "fused ..." or "row
+    kernel ..." (glx_certificate_describe: resolved on the host, no device)."""
+    buf = ctypes.create_string_buffer(2048)
+    check(lib().glx_certificate_describe(dtype, m, n, l, int(fused), buf, len(buf)))
     return buf.value.decode()
 
 

@@ -18,6 +18,9 @@ Differences, all forced by what the image lacks:
   (``tests/golden/default_xstar.npz`` for the default instance, made by
   ``tests/golden/make_xstar.py``). It reproduces the report's CVX-Mosek row. Without
   ``--xstar`` the column reads ``n/a``. cvxpy, Mosek and Gurobi are not installed.
+- For any ``--size``, ``--certify`` appends two columns that need no stored x*: ``gap``, the duality
+  gap of the returned x (an upper bound on f(x) - f*), and ``kkt``, its largest KKT violation
+  (``glx.certificate``, DESIGN.md "Certificate"). Without the flag the output is unchanged.
 - The svg plots (``main.py:200-235``) are replaced by ``f_hist.npz`` in ``--dest_dir``: the
   per-solver objective histories and f* = obj(u) those plots are drawn from. matplotlib is
   not installed.
@@ -95,8 +98,10 @@ def _glx_solvers() -> Dict[str, Callable]:
 
 
 def solve_routine(mode: str, func: Callable, x0, A, b, mu, opts, errfun, errfun_exact, sparsity,
-                  xstar: Optional[np.ndarray] = None):
-    """main.py:113-130. Returns (x, num_iters, out, log_dict) and logs one line."""
+                  xstar: Optional[np.ndarray] = None, certify: bool = False):
+    """main.py:113-130. Returns (x, num_iters, out, log_dict) and logs one line. ``certify``: two
+    more columns, the duality gap and the largest KKT violation of the returned x at mu
+    (``glx.certificate``, on the GPU)."""
     x, num_iters, out = func(x0, A, b, mu, opts)
     x = np.asarray(x.cpu().numpy() if hasattr(x, "cpu") else x)
     log_dict = {
@@ -107,6 +112,12 @@ def solve_routine(mode: str, func: Callable, x0, A, b, mu, opts, errfun, errfun_
         "err-to-exact": "%3.2E" % errfun_exact(x),
         "err-to-x*": "n/a" if xstar is None else "%3.2E" % errfun(xstar, x),
     }
+    if certify:
+        from glx.certificate import certificate
+        cert = certificate(x, A, b, mu)
+        out["certificate"] = cert
+        log_dict["gap"] = "%3.2E" % cert["gap"]
+        log_dict["kkt"] = "%3.2E" % cert["kkt_max"]
     line = ("[%-10s]: " % mode) + ", ".join(k + ": " + v for k, v in log_dict.items())
     logging.getLogger(LOGGER).info(line)
     return x, num_iters, out, log_dict
@@ -146,10 +157,12 @@ def setup_logger(log_file: Optional[str], level=logging.INFO) -> logging.Logger:
 
 def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Dict[str, dict]] = None,
         xstar: Optional[np.ndarray] = None, dest_dir: Optional[str] = None, seed: int = SEED,
-        size=(256, 512, 2), stream: TextIO = sys.stdout) -> Dict[str, Any]:
+        size=(256, 512, 2), stream: TextIO = sys.stdout, certify: bool = False) -> Dict[str, Any]:
     """The body of main.py's __main__ block (main.py:141-235) without the CVX solvers and plots.
 
     ``solvers`` defaults to the GPU solvers; tests pass other callables with the same signature.
+    ``certify`` appends the ``gap`` and ``kkt`` columns (solve_routine); without it the log lines,
+    the table and f_hist.npz are what they were before the flag existed.
     Returns {"log_dicts", "f_hists", "f_star", "xs"}.
     """
     m, n, l = size
@@ -161,7 +174,7 @@ def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Di
     log_dicts, f_hists, xs = {}, {}, {}
     for mode, solver in solvers.items():             # main.py:199-205
         x, _, out, log_dict = solve_routine(mode, solver, x0, A, b, mu, dict(solvers_opts.get(mode, {})),
-                                            errfun, errfun_exact, sparsity, xstar)
+                                            errfun, errfun_exact, sparsity, xstar, certify)
         if "f_hist" in out:
             f_hists[mode] = np.asarray(out["f_hist"], dtype=np.float64)
         log_dicts[mode] = log_dict
@@ -186,6 +199,8 @@ def main(argv=None) -> int:
     p.add_argument("--seed", type=int, default=SEED)
     p.add_argument("--size", default="256,512,2", help="m,n,l")
     p.add_argument("--solvers", default=None, help="comma-separated subset, e.g. 'ProxGD Primal'")
+    p.add_argument("--certify", action="store_true",
+                   help="Append the duality gap and the KKT violation of each result (gap, kkt columns).")
     a = p.parse_args(argv)
     setup_logger(a.log)
     size = tuple(int(v) for v in a.size.split(","))
@@ -197,7 +212,8 @@ def main(argv=None) -> int:
         if unknown:
             p.error(f"unknown solver(s) {unknown}; choose from {list(solvers)}")
         solvers = {k: solvers[k] for k in keep}
-    run(solvers, xstar=xstar, dest_dir=a.dest_dir, seed=a.seed, size=size)
+    run(solvers, xstar=xstar, dest_dir=a.dest_dir, seed=a.seed, size=size, stream=sys.stdout,
+        certify=a.certify)
     return 0
 
 

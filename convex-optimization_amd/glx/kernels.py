@@ -10,7 +10,8 @@ launch at a time (``glx_descent_step``, ``glx_fgd_gradient``, ``glx_row_stats``,
 ``glx_threshold``, ``glx_thr_combine``, ``glx_descent_pass``), and the dual ADMM solver's row step,
 Gram kernel and host eigenvalue sweep (``glx_admm_dual_step``, ``glx_admm_primal_step``, ``glx_gram``,
 ``glx_sym_lambda_max``), and the dual ALM solver's inner step and inner loop (``glx_alm_inner_step``,
-``glx_alm_inner_run``). All tensors are contiguous device
+``glx_alm_inner_run``), and the optimality certificate's row terms (``glx_certificate_step``). All
+tensors are contiguous device
 tensors of one dtype (float32 / float64).
 """
 from __future__ import annotations
@@ -408,6 +409,37 @@ def admm_dual_step(x: torch.Tensor, rho: float, tau: float, mu: float, G: Option
                                    float(tau), float(mu), int(form), u.data_ptr(), xn.data_ptr(),
                                    r.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
     return {"G": G, "u": u, "x": xn, "r": r, "sums": sums}
+
+
+def certificate_step(x: torch.Tensor, mu: float, G: Optional[torch.Tensor] = None, form: int = 0,
+                     A: Optional[torch.Tensor] = None, Z: Optional[torch.Tensor] = None,
+                     m: int = 1) -> Dict[str, torch.Tensor]:
+    """The certificate's row terms in one launch (glx_certificate_step; DESIGN.md "Certificate"). form
+    0: a row kernel on the given G (with ``m`` the rows of A: on the panel layout a certificate's
+    unfused arm takes at (m, n, l), bit-identical to form 1; m = 1: the generic row layout, any n,
+    l <= 128); form 1: the epilogue of G = A^T Z (G is computed and returned). Returns {"G", "sums",
+    "row_norms"} with sums = [sum_i ||x_i||, max_i ||g_i||, max_i kkt_i, sum_i kkt_i^2, nonzero rows]
+    and row_norms = ||g_i|| (both float64)."""
+    n, l = x.shape
+    dt = _dt(x)
+    dev = x.device
+    if form == 1:
+        if A is None or Z is None:
+            raise ValueError("form 1 needs A and Z")
+        m = A.shape[0]
+        G = torch.full((n, l), float("nan"), dtype=x.dtype, device=dev)
+    else:
+        if G is None:
+            raise ValueError("form 0 needs G")
+    sums = _nan_sums(6, dev)
+    rn = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    nb = ctypes.c_size_t(0)
+    check(lib().glx_certificate_workspace_bytes(dt, m, n, l, ctypes.byref(nb)))
+    ws = torch.empty(int(nb.value), dtype=torch.uint8, device=dev)
+    check(lib().glx_certificate_step(dt, m, n, l, _ptr(A), _ptr(Z), G.data_ptr(), x.data_ptr(), float(mu),
+                                     int(form), rn.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     _stream(dev)))
+    return {"G": G, "sums": sums[:5], "row_norms": rn}
 
 
 def admm_primal_step(prod: torch.Tensor, x: torch.Tensor, y: torch.Tensor, z: torch.Tensor,

@@ -560,6 +560,44 @@ int glx_alm_inner_run(int dtype, int64_t n, int64_t l, const void* Qn, const voi
                       double mu, int fused, void* u_out, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* ---- optimality certificate of any iterate (DESIGN.md "Certificate") ----
+ * For P(x) = 1/2 ||A x - b||_F^2 + mu sum_i ||x_i||_2 (x_i the rows of the n x l iterate) and its
+ * dual D(theta) = -1/2 ||theta||_F^2 - <theta, b> over ||(A^T theta)_i||_2 <= mu: with r = A x - b,
+ * g = A^T r, gmax = max_i ||g_i||_2 and s = 1 where gmax <= mu, mu / gmax elsewhere, theta = s r is
+ * dual feasible and gap = P(x) - D(s r) >= P(x) - min P >= 0. One pass over A and one over A^T,
+ * one readback, one stream synchronise. Single GPU: there is no communicator argument.
+ *   out = [||r||^2, <r, b>, sum_i ||x_i||, gmax, kkt_max, sum_i kkt_i^2, nonzero rows, fused was
+ *          used], host doubles, with kkt_i = ||g_i + mu x_i / ||x_i|| || where x_i != 0 and
+ *          max(||g_i|| - mu, 0) where x_i = 0. The caller composes, in double,
+ *          primal = out[0] / 2 + mu out[2], dual = -s^2 out[0] / 2 - s out[1], gap = primal - dual.
+ *          gmax and kkt_max are NaN where a row feeding them holds one (so is the row count).
+ *   fused: 0 auto, 1 on (the row terms in the epilogue of A^T r where the ADMM solvers' plan of
+ *          (dtype, m, n, l) is built fused), 2 off (a row kernel behind the plain product); the
+ *          record and rownorm_out are bit-identical between 1 and 2.
+ *   G_out (n x l of dtype) and rownorm_out (n doubles: ||g_i||_2) are device pointers, or NULL.
+ * GLX_E_INVALID, with a message, for a bad dtype, non-positive shapes, l > 128, fused outside 0..2,
+ * NULL A, X, b or workspace, a workspace that is too small or not 256-byte aligned, mu < 0 or NaN.
+ * mu = 0 is allowed. Inputs are not modified. */
+int glx_certificate_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes);
+/* One line: the tiles of the two passes and where the row terms run ("fused ..." or "row kernel
+ * ..."). Resolved on the host; needs no device. */
+int glx_certificate_describe(int dtype, int64_t m, int64_t n, int64_t l, int fused, char* out, size_t cap);
+int glx_certificate(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                    double mu, int fused, void* G_out, double* rownorm_out, double out[8], void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* The row terms one launch at a time (test surface), through the launchers the driver uses;
+ * sums_dev = out[2..6] above as 5 device doubles; rownorm_out may be NULL.
+ *   form 0: a row kernel on the given G; A and Z are unused. Where the plan of (m, n, l) takes a
+ *           fused epilogue the rows run on that epilogue's panel layout (k_cert_panel) and every
+ *           bit equals form 1's; elsewhere (any l <= 128, any n; m = 1 will do) the generic row
+ *           layout (k_cert_row).
+ *   form 1: the epilogue of G = A^T Z (k_atr_cert): G is written. GLX_E_INVALID where the plan of
+ *           this shape takes no fused epilogue.
+ * Workspace: glx_certificate_workspace_bytes at the same (dtype, m, n, l). */
+int glx_certificate_step(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* Z, void* G,
+                         const void* x, double mu, int form, double* rownorm_out, void* sums_dev,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- multi-GPU (row-sharded A; A^T r all-reduced, or reduce-scattered with the row-sharded step) ---- */
 #define GLX_COMM_ID_BYTES 128
 int  glx_comm_unique_id(uint8_t id[GLX_COMM_ID_BYTES]);
