@@ -246,18 +246,35 @@ __global__ __launch_bounds__(64 * WAVES) void k_ax_dma(const T* __restrict__ A,
 
   // ---- EG: the MFMA source X0 is the candidate p itself (A p: the objective and the Armijo test)
   // and A e, e = p where the hard threshold zeroes it, is accumulated on VALU from the staged
-  // chunks: lane (c, h) owns column c = lane % L of e and the RPL rows h RPL .. h RPL + RPL - 1 of
-  // the wave's 16 MT rows. Per chunk the lane reads the u32 of column c's bitmap that covers the
-  // chunk's 32 k (loaded one chunk ahead, like the DMA ring, so the barrier's wait covers it) and,
-  // for every set bit k (ascending), adds A[row][k] p[k][c] for its rows, A and p read from the
-  // chunk's LDS image. Order: per K split, the block's (rotated) chunk walk, ascending k within a
-  // chunk; the finalize sums the S slabs in order and forms A p_thr - b = (A p - b) - A e.
-  constexpr int RPL = EG ? (16 * MT * L) / 64 : 1;
-  T accE[RPL];
+  // chunks, by the block as a whole: after the barrier every wave's A chunk image is visible to
+  // every wave, and the images of the WAVES waves are contiguous ([16 MT WAVES][SLR] slots), so
+  // wave v owns the CPW = L / WAVES COLUMNS v CPW .. v CPW + CPW - 1 of e for all the block's
+  // rows, and lane i the RG = 16 MT WAVES / 64 rows i, i + 64, .. of them: accE[RG][CPW], every
+  // index static. The bitmap is tested on the scalar side: lane c < L loads the u32 of column c's
+  // bitmap that covers the chunk's 32 k (one chunk ahead, like the DMA ring, so the barrier's
+  // wait covers it); at the chunk the wave takes the words of its own CPW columns to SGPRs with
+  // readlane and skips the walk whole where they are all zero (with about one entry per flagged
+  // row and eight flagged rows per chunk late in a solve, a wave meets about one entry per
+  // chunk, where a wave that owned rows met all eight). Else its columns are visited in a
+  // statically unrolled loop and the set bits k of a word in a wave-uniform loop, ascending. Per
+  // entry (k, c) the wave issues one broadcast read of p[k][c] from the staged X chunk (source
+  // 0 = p), RG ds_read_b64 of A[i + 64 g][k] (the lane's row base plus the uniform k under dma_sw,
+  // the row groups 64 rows = an immediate offset apart: conflict-free over 16 rows, two-way over
+  // 32) and accE[g][c - v CPW] += A[i + 64 g][k] p[k][c] in all 64 lanes.
+  // Order of summation of every (row, column) accumulator: (1) per K split, the block's (rotated)
+  // chunk walk; (2) ascending k within a chunk; (3) one rounded multiply and one rounded add per
+  // entry (-ffp-contract=off). The finalize sums the S slabs in order and forms
+  // A p_thr - b = (A p - b) - A e.
+  static_assert(!EG || ((16 * MT * WAVES) % 64 == 0 && L % WAVES == 0 && AW == 16 * MT * SLR * 16),
+                "the fused A e: whole 64-row groups, whole columns per wave, contiguous images");
+  constexpr int RG = EG ? (16 * MT * WAVES) / 64 : 1;
+  constexpr int CPW = EG ? L / WAVES : 1;
+  T accE[RG][CPW];
 #pragma unroll
-  for (int r = 0; r < RPL; ++r) accE[r] = T(0);
+  for (int g = 0; g < RG; ++g)
+#pragma unroll
+    for (int j = 0; j < CPW; ++j) accE[g][j] = T(0);
   const int ecol_c = lane % L;
-  const int rb0 = (lane / L) * RPL;
   const unsigned short* ecol = EG ? eg.bm + (int64_t)ecol_c * eg.bstride : nullptr;
   auto ebits = [&](int64_t c) -> unsigned {   // bitmap word of walk step c (0 past the range)
     if constexpr (!EG) {
@@ -271,22 +288,33 @@ __global__ __launch_bounds__(64 * WAVES) void k_ax_dma(const T* __restrict__ A,
   };
   auto ework = [&](int slot, unsigned bits) {
     if constexpr (EG) {
+      unsigned wd[CPW], any = 0u;
+#pragma unroll
+      for (int j = 0; j < CPW; ++j) {
+        wd[j] = (unsigned)__builtin_amdgcn_readlane((int)bits, wave * CPW + j);
+        any |= wd[j];
+      }
+      if (any == 0u) return;   // wave-uniform, as every branch below
       const char* sb = lds + slot * SLOT;
-      while (bits != 0u) {
-        const int kk = __builtin_ctz(bits);
-        bits &= bits - 1u;
-        const int unit = (kk * NT + (ecol_c >> 4)) ^ ((kk / EV) & (EV - 1));
-        // e[k][c] = p[k][c] where the bitmap is set: read from the staged X chunk (source 0 = p)
-        const T ev = *reinterpret_cast<const T*>(sb + WAVES * AW + unit * UB + (ecol_c & 15) * ES);
-        T ar[RPL];
+      const char* arow = sb + lane * (SLR * 16);
+      const int esw = dma_sw<SLR>(lane & 15);
 #pragma unroll
-        for (int r = 0; r < RPL; ++r) {
-          const int w = rb0 + r, ri = w & 15;
-          ar[r] = *reinterpret_cast<const T*>(sb + wave * AW + w * (SLR * 16) + 16 * ((kk / EV) ^ dma_sw<SLR>(ri)) +
-                                              ES * (kk % EV));
+      for (int j = 0; j < CPW; ++j) {
+        const int c = wave * CPW + j;
+        unsigned w = wd[j];
+        while (w != 0u) {
+          const int kk = __builtin_ctz(w);
+          w &= w - 1u;
+          const int unit = (kk * NT + (c >> 4)) ^ ((kk / EV) & (EV - 1));
+          // e[k][c] = p[k][c] where the bitmap is set: one address for the whole wave
+          const T ev = *reinterpret_cast<const T*>(sb + WAVES * AW + unit * UB + (c & 15) * ES);
+          const int ao = 16 * ((kk / EV) ^ esw) + ES * (kk % EV);
+          T ar[RG];
+#pragma unroll
+          for (int g = 0; g < RG; ++g) ar[g] = *reinterpret_cast<const T*>(arow + g * 64 * (SLR * 16) + ao);
+#pragma unroll
+          for (int g = 0; g < RG; ++g) accE[g][j] = accE[g][j] + ar[g] * ev;
         }
-#pragma unroll
-        for (int r = 0; r < RPL; ++r) accE[r] = accE[r] + ar[r] * ev;
       }
     }
   };
@@ -416,12 +444,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_ax_dma(const T* __restrict__ A,
   }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the surplus re-issues, before exit
-  if constexpr (EG) {
+  if constexpr (EG) {   // wave v, lane i: its CPW contiguous columns of the block's rows i + 64 g
     T* pe = static_cast<T*>(eg.Pe) + (int64_t)by * m * L;
 #pragma unroll
-    for (int r = 0; r < RPL; ++r) {
-      const int64_t row = row0 + rb0 + r;
-      if (row < m) pe[row * L + ecol_c] = accE[r];
+    for (int g = 0; g < RG; ++g) {
+      const int64_t row = (int64_t)bx * (16 * MT * WAVES) + g * 64 + lane;
+      if (row < m) {
+#pragma unroll
+        for (int j = 0; j < CPW; ++j) pe[row * L + wave * CPW + j] = accE[g][j];
+      }
     }
   }
 

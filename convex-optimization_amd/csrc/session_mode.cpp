@@ -306,6 +306,14 @@ SessionMode session_mode(const glx_problem& P, const glx_opts& O) {
   // 2 541 it/s at 1 500-2 500 rows against 2 463-2 465 with the gather throughout, the 20-step
   // window unchanged (profiles/r6_hyb/). GLX_AE_HYB_ROWS: the threshold, 0 = off (the gather
   // throughout); GLX_AE_FUSED=1 keeps the fused form throughout.
+  // Round 7: the fused walk re-laid (a wave owns columns of e over the block's rows,
+  // kernels_axdma.hip): the fused pass costs 9 us over the plain pass instead of 19-26. The
+  // threshold swept again on one box, two interleaved rounds (profiles/r7_walk/hyb_sweep.json),
+  // whole solve / 200-step window in it/s: 0 (the gather throughout) 2 472-2 480 / 2 509-2 519,
+  // 250 2 621-2 629 / 2 610-2 611, 500 2 621-2 623 / 2 604-2 607, 1000 2 625-2 626 / 2 604-2 612,
+  // 2000 2 607-2 624 / 2 607-2 615, the fused form throughout 2 609-2 613 / 2 605-2 615. Every
+  // threshold from 250 to 2000 lies within the 0.1-1.2 % run-to-run spread of the others and the
+  // fused form throughout does not win both, so kHybRows stays 2000.
   if (egat_fits && !md.egat && md.gform == 0 && !md.comm && md.dc_window == 0)
     md.hyb_rows = k.ae_hyb_rows.real(kHybRows);
   // Round 5, deferred reductions (single GPU, host control, ProxGD): the fused trial (k_atr_prox)

@@ -125,6 +125,7 @@ class SessionBase {
   virtual void finish(glx_result* res) = 0;
   virtual void kernel_time(int kind, int64_t* launches, double* ms) = 0;
   virtual void counters(int64_t out[4]) const = 0;
+  virtual void ae_forms(int64_t out[2]) const = 0;
   // thread-safe progress record (a watchdog thread reads it while run() is in progress)
   virtual void progress(int64_t out[4]) const = 0;
   virtual void trace(double* sp_after, int64_t cap, int64_t* n, int64_t phase_info[6]) const = 0;
@@ -390,6 +391,10 @@ class Session : public SessionBase {
     out[2] = atr_calls_;
     out[3] = syncs_;
   }
+  void ae_forms(int64_t out[2]) const override {
+    out[0] = ae_gather_;
+    out[1] = ae_fused_;
+  }
 
   void kernel_time(int kind, int64_t* launches, double* ms) override {
     if (kind < 0 || kind > 2)
@@ -591,6 +596,7 @@ class Session : public SessionBase {
       prof_end(0, e0);
       ++ax_calls_;
       ax_cols_ += 1;
+      ++ae_fused_;
       return;
     }
     if (md_.gform == 2) {
@@ -620,6 +626,7 @@ class Session : public SessionBase {
     prof_end(2, e2);
     ++ax_calls_;
     ax_cols_ += 1;
+    ++ae_gather_;
   }
   void residual1(const T* x, T* r, int slot, const T* cx = nullptr, const double* cmax = nullptr,
                  unsigned* pub_seq = nullptr) {
@@ -2200,6 +2207,7 @@ class Session : public SessionBase {
   // per device-controlled batch); record_waits_: decision records read while the device keeps
   // later iterations queued (device-controlled batches)
   int64_t ax_calls_ = 0, ax_cols_ = 0, atr_calls_ = 0, syncs_ = 0, record_waits_ = 0;
+  int64_t ae_gather_ = 0, ae_fused_ = 0;   // split-candidate trials by the form their A e took (cand_ax)
   double stats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   std::vector<double> split_hist_;
   struct EvSample { hipEvent_t a, b; int64_t tag; };
@@ -2386,6 +2394,13 @@ int glx_session_counters(glx_session* s, int64_t out[4]) {
   return guarded([&] {
     if (!s || !s->impl || !out) throw Error{GLX_E_INVALID, "null session/out"};
     s->impl->counters(out);
+  });
+}
+
+int glx_session_ae_forms(glx_session* s, int64_t out[2]) {
+  return guarded([&] {
+    if (!s || !s->impl || !out) throw Error{GLX_E_INVALID, "null session/out"};
+    s->impl->ae_forms(out);
   });
 }
 
@@ -2577,6 +2592,31 @@ int glx_flagged_rows_product(int dtype, int64_t m, int64_t n, int64_t l, const v
     };
     if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
     else go(static_cast<float*>(nullptr));
+    check_launch();
+  });
+}
+
+int glx_fused_ae_pass(int64_t m, int64_t n, int64_t l, const void* A, const void* p, const uint32_t* zf,
+                      void* P, void* Pe, int* S_out, int* rotated, void* stream) {
+  return guarded([&] {
+    if (m <= 0 || n <= 0 || l <= 0 || l > kMaxL) throw Error{GLX_E_INVALID, "bad shape"};
+    const GemmPlan plan = make_plan(8, m, n, l, 0);
+    if (!ax_egat_ok(plan, 8))
+      throw Error{GLX_E_INVALID, "the fused A e pass needs the f64 LDS-DMA tile 92278 as this shape's one-source "
+                                 "plan (" + describe_plan(plan) + ")"};
+    if (S_out) *S_out = ax_split(plan, 1);
+    if (rotated) *rotated = (plan.ax_xmap & 2) != 0 ? 1 : 0;
+    if (P == nullptr && Pe == nullptr) return;   // the query
+    if (!A || !p || !zf || !P || !Pe) throw Error{GLX_E_INVALID, "null argument"};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    EGat eg;
+    const int64_t npad = (n + 63) / 64 * 64;   // glx_device.h zf_npad
+    eg.bm = reinterpret_cast<const unsigned short*>(zf + npad);
+    eg.bstride = npad / 16;
+    eg.Pe = Pe;
+    if (!launch_ax_egat<double>(plan, static_cast<const double*>(A), static_cast<const double*>(p),
+                                static_cast<double*>(P), nullptr, 0, st, Pub{}, eg))
+      throw Error{GLX_E_STATE, "fused A e: the plan does not take it"};
     check_launch();
   });
 }

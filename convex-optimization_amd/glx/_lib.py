@@ -90,6 +90,7 @@ _SIGS = {
     "glx_session_finish": (c_int, [c_void_p, POINTER(GlxResult)]),
     "glx_session_kernel_time": (c_int, [c_void_p, c_int, POINTER(c_int64), POINTER(c_double)]),
     "glx_session_counters": (c_int, [c_void_p, POINTER(c_int64)]),
+    "glx_session_ae_forms": (c_int, [c_void_p, POINTER(c_int64)]),
     "glx_session_progress": (c_int, [c_void_p, POINTER(c_int64)]),
     "glx_session_trace": (c_int, [c_void_p, POINTER(c_double), c_int64, POINTER(c_int64),
                                   POINTER(c_int64)]),
@@ -116,6 +117,8 @@ _SIGS = {
                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "glx_flagged_rows_product": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "glx_fused_ae_pass": (c_int, [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, POINTER(c_int), POINTER(c_int), c_void_p]),
     "glx_trial_mask_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
     "glx_trial_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
     "glx_trial_proxgd": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,

@@ -10,7 +10,8 @@ launch at a time (``glx_descent_step``, ``glx_fgd_gradient``, ``glx_row_stats``,
 ``glx_threshold``, ``glx_thr_combine``, ``glx_descent_pass``), and the dual ADMM solver's row step,
 Gram kernel and host eigenvalue sweep (``glx_admm_dual_step``, ``glx_admm_primal_step``, ``glx_gram``,
 ``glx_sym_lambda_max``), and the dual ALM solver's inner step and inner loop (``glx_alm_inner_step``,
-``glx_alm_inner_run``), and the optimality certificate's row terms (``glx_certificate_step``). All
+``glx_alm_inner_run``), and the optimality certificate's row terms (``glx_certificate_step``), and
+the split-candidate trial's dense pass with A e fused in, one launch (``glx_fused_ae_pass``). All
 tensors are contiguous device
 tensors of one dtype (float32 / float64).
 """
@@ -147,6 +148,30 @@ def flagged_rows_product(At: torch.Tensor, E: torch.Tensor, row_masks: torch.Ten
                                          row_masks.data_ptr(), Y.data_ptr(), int(form),
                                          ws.data_ptr(), ws.numel(), _stream(At.device)))
     return Y
+
+
+def fused_ae_pass(A: torch.Tensor, p: torch.Tensor, thres: float = 1e-3) -> Dict[str, object]:
+    """The split-candidate trial's dense pass with A e fused in, one launch (glx_fused_ae_pass;
+    float64, where the shape's one-source plan under GLX_AX_VARIANT / GLX_AX_S is the LDS-DMA tile
+    92278). e = p - thr(p); its row masks and column bitmaps come from the trial's own replicated
+    half (trial_proxgd form 2, emode), in the layout include/glx.h documents for zf. Returns a
+    dict with P (S, m, l: A p per K split), Pe (S, m, l: A e per K split), S, rotated (the chunk
+    rotation of GLX_AX_ROT is on), e and zf."""
+    m, n = A.shape
+    l = p.shape[1]
+    if A.dtype != torch.float64 or p.dtype != torch.float64:
+        raise ValueError("float64 required")
+    S, rot = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().glx_fused_ae_pass(m, n, l, None, None, None, None, None, ctypes.byref(S),
+                                  ctypes.byref(rot), None))
+    tr = trial_proxgd(p, None, 1.0, 0.0, thres=thres, form=2, emode=True, p=p)
+    P = torch.full((S.value, m, l), float("nan"), dtype=A.dtype, device=A.device)
+    Pe = torch.full((S.value, m, l), float("nan"), dtype=A.dtype, device=A.device)
+    check(lib().glx_fused_ae_pass(m, n, l, A.data_ptr(), p.data_ptr(), tr["zf"].data_ptr(),
+                                  P.data_ptr(), Pe.data_ptr(), ctypes.byref(S), ctypes.byref(rot),
+                                  _stream(A.device)))
+    return {"P": P, "Pe": Pe, "S": int(S.value), "rotated": bool(rot.value), "e": tr["z"],
+            "zf": tr["zf"]}
 
 
 def trial_mask_words(n: int) -> int:

@@ -225,6 +225,14 @@ class Session:
         check(lib().glx_session_counters(self.h, out))
         return {"ax_calls": out[0], "ax_sources": out[1], "atr_calls": out[2], "syncs": out[3]}
 
+    def ae_forms(self) -> Dict[str, int]:
+        """Split-candidate trials so far by the form their A e took (glx_session_ae_forms): the
+        gather from the transposed copy of A / the fused form inside the dense pass. Apart from
+        counters(), whose keys recorded runs compare as a whole."""
+        ae = (ctypes.c_int64 * 2)()
+        check(lib().glx_session_ae_forms(self.h, ae))
+        return {"ae_gather_trials": ae[0], "ae_fused_trials": ae[1]}
+
     def progress(self) -> Dict[str, int]:
         """Thread-safe progress record (glx_session_progress), for watchdogs: iterations so far,
         phase, what the host waits on (0 nothing, 1 packet, 2 decision record), collectives

@@ -169,6 +169,10 @@ int  glx_session_kernel_time(glx_session* s, int kind, int64_t* launches, double
  * passes, host readbacks (glx_result.syncs)} (cumulative; the caller differences them around a
  * timed region). */
 int  glx_session_counters(glx_session* s, int64_t out[4]);
+/* Split-candidate trials since create by the form their A e took: out = {the gather from the
+ * transposed copy of A (a launch of its own), the fused form inside the dense pass}. Both count
+ * in a hybrid run (GLX_AE_HYB_ROWS); a session without the split-candidate trial reports 0, 0. */
+int  glx_session_ae_forms(glx_session* s, int64_t out[2]);
 /* Progress record, safe to call from ANOTHER thread while glx_session_run() is in progress (a
  * watchdog's diagnostic, round 6): out = {iterations recorded so far (k), continuation phase
  * (0..2), what the host is waiting on (0 nothing, 1 a scalar packet, 2 a device decision record),
@@ -257,6 +261,19 @@ int glx_residual_gradient2(int dtype, int64_t m, int64_t n, int64_t l, const voi
 int glx_flagged_rows_product(int dtype, int64_t m, int64_t n, int64_t l, const void* At,
                              const void* E, const uint32_t* row_masks, void* Y, int form,
                              void* workspace, size_t workspace_bytes, void* stream);
+/* The split-candidate trial's dense pass with A e fused in, one launch (launch_ax_egat; fp64):
+ *   P  (S x m x l) = the K-split slabs of A p,
+ *   Pe (S x m x l) = the K-split slabs of A e, e[k][c] = p[k][c] where zf's column bitmaps flag
+ *                    (k, c) and 0 elsewhere (zf: the layout documented below, as a trial wrote it).
+ * Runs only where the shape's one-source plan under GLX_AX_VARIANT / GLX_AX_S is the LDS-DMA tile
+ * 92278 (l in {16, 32}, n % 32 == 0, n < 65536), else GLX_E_INVALID. *S = the K splits, *rotated =
+ * 1 when row block bx walks its split's chunks from chunk bx * nch / gx (GLX_AX_ROT). With P and
+ * Pe both NULL nothing is launched and only *S and *rotated are set (no device needed). Every
+ * accumulator of Pe receives its entries in this order: the block's (rotated) walk over the
+ * split's 32-column chunks, ascending k inside a chunk, one rounded multiply and one rounded add
+ * per entry. */
+int glx_fused_ae_pass(int64_t m, int64_t n, int64_t l, const void* A, const void* p,
+                      const uint32_t* zf, void* P, void* Pe, int* S, int* rotated, void* stream);
 /* ---- the line-search trial, one kernel at a time (test surface) ----
  * The other half of an iteration: prox, hard threshold, the Armijo / backtracking sums, and in
  * the split-candidate form the masks of e and the column bitmaps the A e gather walks. Both
