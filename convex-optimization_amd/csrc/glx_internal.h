@@ -443,6 +443,35 @@ void launch_cert_row(const T* x, const T* g, int S, T* gout, double* rn, int64_t
 template <typename T>
 void launch_cert_fin(const T* P, int S, const T* b, T* r, int64_t ml, Red red, hipStream_t st);
 
+// ---- gap-safe screening (kernels_screen.hip; DESIGN.md "Certified solve and screening") ----
+// norms[j] = ||A[:, j]||_2 (n doubles), accumulated in double over col_norm_slabs(m) fixed row slabs
+// and summed in slab order; red.out = [max_j norms[j] (NaN-propagating), sum_j norms[j]^2]. part:
+// col_norms_part_bytes; ccnt: col_norms_count_bytes, zero before the first launch (reset by the kernel).
+int col_norm_slabs(int64_t m);
+size_t col_norms_part_bytes(int64_t m, int64_t n);
+size_t col_norms_count_bytes(int64_t n);
+template <typename T>
+void launch_col_norms(const T* A, int64_t m, int64_t n, double* norms, double* part, unsigned* ccnt, Red red,
+                      hipStream_t st);
+// keep[i] = !(s rn[i] + cn[i] rho < mu_lo) (a NaN keeps the row); list = the kept rows, ascending,
+// then -1 up to cnt[1]; cnt = [kept, kept rounded up to 64]. mask (n bytes) may be NULL; list holds n
+// rounded up to 64 ints; bal: screen_words_bytes(n); ticket: one zeroed word (reset by the kernel).
+size_t screen_words_bytes(int64_t n);
+void launch_screen(const double* rn, const double* cn, int64_t n, double s, double rho, double mu_lo,
+                   unsigned char* mask, int* list, int* cnt, unsigned long long* bal, unsigned* ticket,
+                   hipStream_t st);
+// dst (m x wp, wp % 64 == 0) [r, j] = src (m x sw) [r, idx[j]], 0 where idx[j] is outside [0, sw)
+template <typename T>
+void launch_gather_cols(const T* src, int64_t m, int64_t sw, const int* idx, int64_t wp, T* dst, hipStream_t st);
+// rows of l values: dst[j, :] = src[idx[j], :] (0 where idx[j] < 0) / dst[idx[j], :] = src[j, :]
+// (where idx[j] >= 0; dst is cleared by the caller), j < wp
+template <typename T>
+void launch_gather_rows(const T* src, const int* idx, int64_t wp, int64_t l, T* dst, hipStream_t st);
+template <typename T>
+void launch_scatter_rows(const T* src, const int* idx, int64_t wp, int64_t l, T* dst, hipStream_t st);
+// out[j] = map[idx[j]] (idx[j] itself where map == NULL), -1 where idx[j] < 0
+void launch_compose_list(const int* map, const int* idx, int64_t wp, int* out, hipStream_t st);
+
 // ---- shared by the two ADMM drivers (defined in admm.cpp) ----
 namespace admm {
 constexpr int kMaxL = 32;    // the Gram kernel and the host Jacobi sweep

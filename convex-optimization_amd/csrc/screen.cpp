@@ -1,0 +1,570 @@
+// screen.cpp — the native driver of the certified solve (DESIGN.md "Certified solve and screening"):
+// FISTA with the exact group prox and a fixed step t <= 1 / lambda_max(A^T A) on
+//   P(x) = 1/2 ||A x - b||_F^2 + mu sum_i ||x_i||_2,
+// stopped on the certificate's relative duality gap, with gap-safe screening: every check_every
+// iterations the certificate of the current (reduced) problem gives a dual point theta = s r and
+// the radius rho = sqrt(2 gap) of a ball that holds the dual optimum; a row with
+// s ||g_i|| + ||a_i|| rho < mu is zero at the optimum, and its column leaves A. The radius carries a
+// rounding guard composed on the host in float64 (glx_screen_guard). Kept columns are gathered into
+// one of two workspace buffers, padded with zero columns to a multiple of 64 so that the reduced
+// problem keeps the MFMA A^T r panel. One iteration is launch_ax on y, the residual finalize, and
+// the FISTA epilogue of A^T r (launch_atr_fista) or, where the plan does not fuse, launch_atr and the
+// row kernel (launch_fista_trial); thres is the dtype's smallest normal number, with which
+// fista_row's denominator switch and hard threshold are no-ops. Single GPU; beside certificate.cpp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <type_traits>
+
+#include "glx.h"
+#include "glx_internal.h"
+
+namespace glx {
+namespace {
+
+#define GLX_HIP(expr)                                                                          \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess) throw Error{GLX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)}; \
+  } while (0)
+
+inline void check_launch() {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) throw Error{GLX_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)};
+}
+
+template <typename F>
+int guarded(F&& f) {
+  try {
+    f();
+    return GLX_OK;
+  } catch (const Error& e) {
+    g_last_error = e.msg;
+    return e.code;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return GLX_E_STATE;
+  } catch (...) {
+    g_last_error = "unknown error";
+    return GLX_E_STATE;
+  }
+}
+
+using admm::Carver;
+using admm::plan_field;
+
+inline int64_t pad64(int64_t v) { return (v + 63) / 64 * 64; }
+
+// gamma_k = k u / (1 - k u): the bar of a k-term dot product in unit roundoff u (infinite once
+// k u >= 1, which switches screening off)
+double gamma_k(double k, double u) {
+  const double ku = k * u;
+  return ku < 1.0 ? ku / (1.0 - ku) : std::numeric_limits<double>::infinity();
+}
+
+// The rounding guard (DESIGN.md "Certified solve and screening", "The guard, term by term").
+// rec: the certificate's record of the stored residual r^ and g^ = A^T r^ in dtype arithmetic.
+// out = [s_safe, gap+, rho+]. Every quantity below is an upper bound; NaN propagates (and then
+// keeps every row in k_screen).
+void screen_guard(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, double cmax,
+                  double csq, double bn, double* out) {
+  const double u = dtype == GLX_F64 ? DBL_EPSILON : (double)FLT_EPSILON;   // eps of A's dtype
+  const double u64 = DBL_EPSILON;
+  const double rr = rec[0], rb = rec[1], sx = rec[2], gmax = rec[3];
+  const double rn = std::sqrt(rr);
+  const double gm = gamma_k((double)m + 2.0, u), gn = gamma_k((double)n + 2.0, u);
+  // 1. dual feasibility: ||a_i^T r^|| <= ||g^_i|| + gm ||a_i|| ||r^||
+  const double den = gmax + gm * cmax * rn;
+  const double s = den > mu ? mu / den : (den <= mu ? 1.0 : den);   // (NaN den: NaN)
+  // 2. the primal value: ||r^ - (A x - b)|| <= dr
+  const double dr = gn * std::sqrt(csq) * sx + u * (rn + 2.0 * bn);
+  const double ml = (double)m * (double)l;
+  const double g_ml = gamma_k(ml + 2.0, u64);
+  const double bar_rr = g_ml * rr;                      // the fp64 sum ||r^||^2
+  const double bar_rb = g_ml * rn * bn;                 // the fp64 sum <r^, b> (Cauchy-Schwarz on sum |r b|)
+  const double bar_sx = (gamma_k((double)l + 2.0, u) + gamma_k((double)n + 2.0, u64)) * sx;   // sum_i ||x_i||
+  const double gap = 0.5 * (1.0 + s * s) * rr + s * rb + mu * sx;
+  const double bars = rn * dr + 0.5 * dr * dr + 0.5 * (1.0 + s * s) * bar_rr + s * bar_rb + mu * bar_sx;
+  const double gap_p = (gap > 0.0 ? gap : (gap <= 0.0 ? 0.0 : gap)) + bars;
+  // 3. the row's own value: s ||a_i^T r^|| <= s ||g^_i|| (1 + gl) + s gm ||a_i|| ||r^||, and
+  //    ||g^_i|| <= (1 + gm) ||a_i|| ||r^||, so both terms are ||a_i|| times a radius; the column
+  //    norms themselves are low by at most gamma64_{m+2}
+  const double gl = gamma_k((double)l + 2.0, u);
+  double rho = std::sqrt(2.0 * gap_p) + s * gm * rn + s * gl * (1.0 + gm) * rn;
+  rho *= 1.0 + gamma_k((double)m + 2.0, u64);
+  out[0] = s;
+  out[1] = gap_p;
+  out[2] = rho;
+}
+
+// the plan of a (reduced) problem: the certificate's (certificate.cpp cert_plan)
+struct CPlan {
+  int es = 8;
+  GemmPlan a{};
+  bool fuse = false;
+};
+CPlan cplan(int dtype, int64_t m, int64_t w, int64_t l) {
+  CPlan p;
+  p.es = dtype == GLX_F64 ? 8 : 4;
+  p.a = admm::a_plan(dtype, m, w, l);
+  p.fuse = atr_prox_ok(p.a) && (p.a.atr->fused & dtype_bit(p.es)) != 0;
+  return p;
+}
+void check_shape(int dtype, int64_t m, int64_t n, int64_t l) {
+  if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+  if (m <= 0 || n <= 0 || l <= 0) throw Error{GLX_E_INVALID, "m, n, l must be positive"};
+  if (l > kMaxL) throw Error{GLX_E_INVALID, "the certified solve takes l <= 128"};
+  if (n > (int64_t)0x7fffffc0) throw Error{GLX_E_INVALID, "the certified solve takes n < 2^31 - 64"};
+}
+
+// the largest padded widths the two compaction buffers can be asked to hold
+int64_t buf_width(int64_t w) { return (w * 9 / 10) / 64 * 64; }
+
+// What the reduced problems need at most: over n itself and every multiple of 64 a compaction can
+// reach (<= 0.9 n), the certificate's workspace and the K splits of the two products.
+struct Extent {
+  size_t cert = 0;
+  int ax_s = 1, atr_s = 1;
+};
+Extent extent(int dtype, int64_t m, int64_t n, int64_t l, bool screen) {
+  Extent e;
+  auto take = [&](int64_t w) {
+    size_t b = 0;
+    if (glx_certificate_workspace_bytes(dtype, m, w, l, &b) != GLX_OK) throw Error{GLX_E_INVALID, g_last_error};
+    e.cert = std::max(e.cert, b);
+    const CPlan p = cplan(dtype, m, w, l);
+    e.ax_s = std::max(e.ax_s, std::max(1, ax_split(p.a, 1)));
+    e.atr_s = std::max(e.atr_s, std::max(1, p.a.atr_S));
+  };
+  take(n);
+  if (screen)
+    for (int64_t w = 64; w <= buf_width(n); w += 64) take(w);
+  return e;
+}
+
+constexpr int kRedOut = 16;
+
+struct Ws {
+  double* part; unsigned* ticket; unsigned* pcnt; double* red;
+  void* cert;
+  void *r, *pa, *gp, *g, *x[5];
+  double *rn, *cn[2], *cpart;
+  unsigned* ccnt;
+  int *map[2], *list, *cnt;
+  unsigned long long* bal;
+  unsigned* sticket;
+  void* abuf[2];
+  size_t cert_bytes;
+  int64_t cap[2];
+};
+size_t carve(int dtype, int64_t m, int64_t n, int64_t l, bool screen, bool own_norms, void* base, Ws* out) {
+  const size_t es = dtype == GLX_F64 ? 8 : 4;
+  const Extent e = extent(dtype, m, n, l, screen);
+  const int64_t np = pad64(n);
+  Carver c(base);
+  Ws w;
+  w.part = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals * kMaxBlocks));
+  w.ticket = static_cast<unsigned*>(c.take(kTicketBytes));
+  w.pcnt = static_cast<unsigned*>(c.take(sizeof(unsigned) * (np / 64 + 64)));
+  w.red = static_cast<double*>(c.take(sizeof(double) * kRedOut));
+  w.cert_bytes = e.cert;
+  w.cert = c.take(e.cert);
+  w.r = c.take(es * m * l);
+  w.pa = c.take(es * m * l * e.ax_s);
+  w.gp = c.take(es * np * l * e.atr_s);
+  w.g = c.take(es * np * l);
+  for (int i = 0; i < 5; ++i) w.x[i] = c.take(es * np * l);
+  w.rn = static_cast<double*>(c.take(sizeof(double) * np));
+  for (int i = 0; i < 2; ++i) w.cn[i] = static_cast<double*>(c.take(sizeof(double) * np));
+  w.cpart = static_cast<double*>(c.take(own_norms ? col_norms_part_bytes(m, n) : 0));
+  w.ccnt = static_cast<unsigned*>(c.take(col_norms_count_bytes(n)));
+  for (int i = 0; i < 2; ++i) w.map[i] = static_cast<int*>(c.take(sizeof(int) * np));
+  w.list = static_cast<int*>(c.take(sizeof(int) * np));
+  w.cnt = static_cast<int*>(c.take(sizeof(int) * 4));
+  w.bal = static_cast<unsigned long long*>(c.take(screen_words_bytes(n)));
+  w.sticket = static_cast<unsigned*>(c.take(256));
+  w.cap[0] = screen ? buf_width(n) : 0;
+  w.cap[1] = screen ? buf_width(w.cap[0]) : 0;
+  for (int i = 0; i < 2; ++i) w.abuf[i] = c.take(es * (size_t)m * (size_t)w.cap[i]);
+  if (out) *out = w;
+  return c.off + 256;
+}
+
+std::string describe_certified(int dtype, int64_t m, int64_t n, int64_t l, bool screen) {
+  const CPlan p = cplan(dtype, m, n, l);
+  std::string s = "FISTA, fixed step, exact prox; A y=" + plan_field(p.a, 0) + "; A^T r=" + plan_field(p.a, 3) +
+                  "; step=";
+  s += p.fuse ? "fused (k_atr_fista, the A^T r epilogue)" : "row kernel (k_fista_trial)";
+  s += screen ? "; screening=gap-safe, compaction to multiples of 64 at <= 0.9 of the width" : "; screening=off";
+  return s;
+}
+
+struct Composed {
+  double primal, dual, gap, rel, scale;
+};
+// glx/certificate.py compose, in the same order of operations
+Composed compose(const double* rec, double mu) {
+  const double rr = rec[0], rb = rec[1], sx = rec[2], gmax = rec[3];
+  Composed c;
+  c.scale = gmax <= mu ? 1.0 : mu / gmax;
+  c.primal = 0.5 * rr + mu * sx;
+  c.dual = -0.5 * c.scale * c.scale * rr - c.scale * rb;
+  c.gap = c.primal - c.dual;
+  c.rel = c.gap / std::max(std::fabs(c.primal), DBL_MIN);
+  return c;
+}
+
+void cert_call(int dtype, int64_t m, int64_t w, int64_t l, const void* A, const void* x, const void* b, double mu,
+               double* rn, double* rec, const Ws& ws, hipStream_t st) {
+  const int rc = glx_certificate(dtype, m, w, l, A, x, b, mu, 0, nullptr, rn, rec, ws.cert, ws.cert_bytes, st);
+  if (rc != GLX_OK) throw Error{rc, "certified solve: " + g_last_error};
+}
+
+template <typename T>
+void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T* X, double mu, double t,
+           double tol, int64_t maxit, bool screen, int check_every, const double* cn_in, const double* cstats_in,
+           int32_t* kept_rows, void* wsp, glx_certified_info* info, hipStream_t st) {
+  Ws w;
+  carve(dtype, m, n, l, screen, cn_in == nullptr, wsp, &w);
+  const size_t es = sizeof(T);
+  const double thres = std::is_same<T, double>::value ? DBL_MIN : (double)FLT_MIN;
+  const int64_t ml = m * l;
+  std::memset(info, 0, sizeof *info);
+  const auto t_begin = std::chrono::steady_clock::now();
+
+  GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+  GLX_HIP(hipMemsetAsync(w.pcnt, 0, sizeof(unsigned) * (pad64(n) / 64 + 64), st));
+  GLX_HIP(hipMemsetAsync(w.ccnt, 0, col_norms_count_bytes(n), st));
+  GLX_HIP(hipMemsetAsync(w.sticket, 0, 256, st));
+  GLX_HIP(hipMemsetAsync(w.red, 0, sizeof(double) * kRedOut, st));
+  const Red red0{w.part, w.ticket, w.red}, red1{w.part, w.ticket, w.red + 4}, red2{w.part, w.ticket, w.red + 10};
+
+  // the column figures and ||b||_F (screening only)
+  double cmax = 0.0, csq = 0.0, bn = 0.0;
+  const double* cn = nullptr;
+  if (screen) {
+    if (cn_in != nullptr) {
+      cn = cn_in;
+      cmax = cstats_in[0];
+      csq = cstats_in[1];
+    } else {
+      launch_col_norms<T>(A, m, n, w.cn[1], w.cpart, w.ccnt, red2, st);
+      check_launch();
+      cn = w.cn[1];
+      info->passes += 1.0;
+    }
+    launch_cert_fin<T>(nullptr, 0, b, static_cast<T*>(w.r), ml, red0, st);   // r = -b: red0 = [||b||^2, .]
+    check_launch();
+    double h[4];
+    GLX_HIP(hipMemcpyAsync(h, w.red, sizeof(double), hipMemcpyDeviceToHost, st));
+    GLX_HIP(hipMemcpyAsync(h + 1, w.red + 10, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    GLX_HIP(hipStreamSynchronize(st));
+    bn = std::sqrt(h[0]);
+    if (cn_in == nullptr) {
+      cmax = h[1];
+      csq = h[2];
+    }
+  }
+
+  // the current (reduced) problem
+  const T* Ac = A;
+  int64_t wc = n;
+  CPlan pl = cplan(dtype, m, n, l);
+  int side = 0;              // the buffer the next compaction writes
+  const int* map = nullptr;  // reduced row -> full row (NULL: identity)
+  int mapi = 0;
+  T *x = static_cast<T*>(w.x[0]), *y = static_cast<T*>(w.x[1]), *xc = static_cast<T*>(w.x[2]),
+    *yn = static_cast<T*>(w.x[3]), *vn = static_cast<T*>(w.x[4]);
+  GLX_HIP(hipMemcpyAsync(x, X, es * n * l, hipMemcpyDeviceToDevice, st));
+  GLX_HIP(hipMemcpyAsync(y, X, es * n * l, hipMemcpyDeviceToDevice, st));
+  info->fused = pl.fuse ? 1 : 0;
+
+  double target = tol;
+  int64_t k = 1;       // momentum index: theta = 2 / (k + 1)
+  int64_t it = 0;
+  bool all_zero = false;
+  int64_t listed = -1;   // >= 0: entries of w.list from the last screen, valid for the current problem
+  double rec[8];
+
+  // x (reduced) -> X (n x l); then the certificate of the full problem on the caller's A
+  auto full_certificate = [&]() {
+    if (all_zero) {
+      GLX_HIP(hipMemsetAsync(X, 0, es * n * l, st));
+    } else if (map == nullptr) {
+      GLX_HIP(hipMemcpyAsync(X, x, es * n * l, hipMemcpyDeviceToDevice, st));
+    } else {
+      GLX_HIP(hipMemsetAsync(X, 0, es * n * l, st));
+      launch_scatter_rows<T>(x, map, wc, l, X, st);
+      check_launch();
+    }
+    cert_call(dtype, m, n, l, A, X, b, mu, nullptr, info->cert, w, st);
+    info->passes += 2.0;
+    return compose(info->cert, mu);
+  };
+
+  // one check of the reduced problem: its certificate, the stop rule, the guard, the screen and,
+  // where it pays, a compaction. Returns true when the reduced problem meets `target`.
+  auto check = [&]() -> bool {
+    ++info->checks;
+    cert_call(dtype, m, wc, l, Ac, x, b, mu, w.rn, rec, w, st);
+    info->passes += 2.0 * (double)wc / (double)n;
+    const Composed c = compose(rec, mu);
+    info->inner_rel_gap = c.rel;
+    const bool met = c.rel <= target;
+    if (!screen) return met;
+    double gd[3];
+    screen_guard(rec, mu, dtype, m, wc, l, cmax, csq, bn, gd);
+    const double mu_lo = mu * (1.0 - 4.0 * DBL_EPSILON);   // the test's own three roundings in fp64
+    launch_screen(w.rn, cn, wc, gd[0], gd[2], mu_lo, nullptr, w.list, w.cnt, w.bal, w.sticket, st);
+    check_launch();
+    int hc[2];
+    GLX_HIP(hipMemcpyAsync(hc, w.cnt, sizeof hc, hipMemcpyDeviceToHost, st));
+    GLX_HIP(hipStreamSynchronize(st));
+    const int64_t kept = hc[0], wp = hc[1];
+    info->kept = kept;
+    listed = wp;   // w.list names the rows of the current problem that are not proven zero
+    if (met || wp * 10 > wc * 9) return met;
+    if (kept == 0) {   // every row is zero at the optimum
+      all_zero = true;
+      wc = 0;
+      listed = -1;
+      if (info->compactions < GLX_CERTIFIED_MAX_HIST) info->kept_hist[info->compactions] = 0;
+      ++info->compactions;
+      return true;
+    }
+    if (wp > w.cap[side]) throw Error{GLX_E_STATE, "certified solve: a compaction exceeds its buffer"};
+    T* An = static_cast<T*>(w.abuf[side]);
+    launch_gather_cols<T>(Ac, m, wc, w.list, wp, An, st);
+    launch_gather_rows<T>(x, w.list, wp, l, xc, st);
+    double* cnn = w.cn[cn == w.cn[0] ? 1 : 0];
+    launch_gather_rows<double>(cn, w.list, wp, 1, cnn, st);
+    int* mapn = w.map[mapi ^ 1];
+    launch_compose_list(map, w.list, wp, mapn, st);
+    check_launch();
+    info->passes += (double)wc / (double)n;
+    std::swap(x, xc);
+    GLX_HIP(hipMemcpyAsync(y, x, es * wp * l, hipMemcpyDeviceToDevice, st));   // the momentum restarts
+    k = 1;
+    Ac = An;
+    cn = cnn;
+    map = mapn;
+    mapi ^= 1;
+    side ^= 1;
+    wc = wp;
+    pl = cplan(dtype, m, wc, l);
+    if (info->compactions < GLX_CERTIFIED_MAX_HIST) info->kept_hist[info->compactions] = kept;
+    ++info->compactions;
+    listed = -1;   // the composed list alone names them now
+    return false;
+  };
+
+  auto iterate = [&]() {
+    const double theta = 2.0 / (double)(k + 1), theta_next = 2.0 / (double)(k + 2);
+    const T* xs[3] = {y, nullptr, nullptr};
+    T* r = static_cast<T*>(w.r);
+    launch_ax<T>(pl.a, 1, Ac, xs, static_cast<T*>(w.pa), nullptr, 0, st);
+    launch_cert_fin<T>(static_cast<T*>(w.pa), ax_split(pl.a, 1), b, r, ml, red0, st);
+    T* gp = static_cast<T*>(w.gp);
+    if (pl.fuse) {
+      launch_atr_fista<T>(pl.a, Ac, r, static_cast<T*>(w.g), y, x, xc, vn, yn, t, mu, thres, theta, theta_next, red1,
+                          st, Pub{}, pl.a.atr_S > 1 ? gp : nullptr, w.pcnt);
+    } else {
+      launch_atr<T>(pl.a, Ac, r, gp, st);
+      launch_fista_trial<T>(true, y, gp, pl.a.atr_S, nullptr, x, xc, vn, yn, wc, l, t, mu, thres, theta, theta_next,
+                            0.0, red1, st);
+    }
+    check_launch();
+    std::swap(x, xc);
+    std::swap(y, yn);
+    ++k;
+    ++it;
+    info->passes += 2.0 * (double)wc / (double)n;
+  };
+
+  info->kept = n;
+  Composed full{};
+  for (int round = 0;; ++round) {
+    info->rounds = round + 1;
+    bool met = check();   // (the first: x0 may already do, and a warm start screens before it iterates)
+    while (!met && !all_zero && it < maxit) {
+      iterate();
+      if (it % check_every == 0 || it >= maxit) met = check();
+    }
+    full = full_certificate();
+    if (full.rel <= tol) {
+      info->converged = 1;
+      break;
+    }
+    if (it >= maxit || round + 1 >= 6 || all_zero) break;   // the first round and at most 5 resumed ones
+    target *= 0.5;
+  }
+  // the rows not proven zero: the last screen's list through the composed one, or the latter alone
+  if (kept_rows != nullptr && wc > 0 && listed > 0) {
+    launch_compose_list(map, w.list, listed, kept_rows, st);
+    check_launch();
+    info->listed = listed;
+  } else if (kept_rows != nullptr && wc > 0 && listed < 0 && map != nullptr) {
+    GLX_HIP(hipMemcpyAsync(kept_rows, map, sizeof(int) * wc, hipMemcpyDeviceToDevice, st));
+    info->listed = wc;
+  }
+  GLX_HIP(hipStreamSynchronize(st));
+  info->iters = it;
+  info->width = wc;
+  info->tt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+}
+
+void check_ws(size_t need, const void* ws, size_t wsb, const char* who) {
+  if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
+  if (wsb < need) throw Error{GLX_E_INVALID, std::string("workspace too small (") + who + ")"};
+  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
+}
+
+// the one-launch entries' workspace: [partials | ticket | out | column partials | column counters |
+// ballot words | screen ticket]
+struct StepWs {
+  double* part; unsigned* ticket; double* out; double* cpart; unsigned* ccnt; unsigned long long* bal;
+  unsigned* sticket;
+};
+size_t step_carve(int64_t m, int64_t n, void* base, StepWs* out) {
+  Carver c(base);
+  StepWs w;
+  w.part = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals * kMaxBlocks));
+  w.ticket = static_cast<unsigned*>(c.take(kTicketBytes));
+  w.out = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals));
+  w.cpart = static_cast<double*>(c.take(col_norms_part_bytes(m, n)));
+  w.ccnt = static_cast<unsigned*>(c.take(col_norms_count_bytes(n)));
+  w.bal = static_cast<unsigned long long*>(c.take(screen_words_bytes(n)));
+  w.sticket = static_cast<unsigned*>(c.take(256));
+  if (out) *out = w;
+  return c.off + 256;
+}
+
+}  // namespace
+}  // namespace glx
+
+using namespace glx;
+
+extern "C" {
+
+int glx_screen_guard(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, double col_max,
+                     double col_sumsq, double b_norm, double* out) {
+  return guarded([&] {
+    if (!rec || !out) throw Error{GLX_E_INVALID, "null argument"};
+    check_shape(dtype, m, n, l);
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    screen_guard(rec, mu, dtype, m, n, l, col_max, col_sumsq, b_norm, out);
+  });
+}
+
+int glx_screen_workspace_bytes(int64_t m, int64_t n, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    if (m <= 0 || n <= 0) throw Error{GLX_E_INVALID, "m, n must be positive"};
+    *bytes = step_carve(m, n, nullptr, nullptr);
+  });
+}
+
+int glx_col_norms(int dtype, int64_t m, int64_t n, const void* A, double* norms_dev, double* stats_dev, void* ws,
+                  size_t wsb, void* stream) {
+  return guarded([&] {
+    check_shape(dtype, m, n, 1);
+    if (!A || !norms_dev || !stats_dev) throw Error{GLX_E_INVALID, "null argument"};
+    check_ws(step_carve(m, n, nullptr, nullptr), ws, wsb, "glx_screen_workspace_bytes");
+    StepWs w;
+    step_carve(m, n, ws, &w);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    GLX_HIP(hipMemsetAsync(w.ccnt, 0, col_norms_count_bytes(n), st));
+    const Red red{w.part, w.ticket, stats_dev};
+    if (dtype == GLX_F64) launch_col_norms<double>((const double*)A, m, n, norms_dev, w.cpart, w.ccnt, red, st);
+    else launch_col_norms<float>((const float*)A, m, n, norms_dev, w.cpart, w.ccnt, red, st);
+    check_launch();
+  });
+}
+
+int glx_screen_step(int64_t n, const double* row_norms, const double* col_norms, double s, double rho, double mu,
+                    uint8_t* mask, int32_t* list, int32_t* count, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    if (n <= 0 || n > (int64_t)0x7fffffc0) throw Error{GLX_E_INVALID, "n must be in 1 .. 2^31 - 65"};
+    if (!row_norms || !col_norms || !list || !count) throw Error{GLX_E_INVALID, "null argument"};
+    check_ws(step_carve(1, n, nullptr, nullptr), ws, wsb, "glx_screen_workspace_bytes");
+    StepWs w;
+    step_carve(1, n, ws, &w);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GLX_HIP(hipMemsetAsync(w.sticket, 0, 256, st));
+    launch_screen(row_norms, col_norms, n, s, rho, mu, mask, list, count, w.bal, w.sticket, st);
+    check_launch();
+  });
+}
+
+int glx_gather_cols(int dtype, int64_t m, int64_t src_width, const void* src, const int32_t* idx, int64_t width,
+                    void* dst, void* stream) {
+  return guarded([&] {
+    if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+    if (m <= 0 || src_width <= 0 || width < 0) throw Error{GLX_E_INVALID, "bad shape"};
+    if (width % 64 != 0) throw Error{GLX_E_INVALID, "the destination width must be a multiple of 64"};
+    if (width == 0) return;
+    if (!src || !idx || !dst) throw Error{GLX_E_INVALID, "null argument"};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == GLX_F64) launch_gather_cols<double>((const double*)src, m, src_width, idx, width, (double*)dst, st);
+    else launch_gather_cols<float>((const float*)src, m, src_width, idx, width, (float*)dst, st);
+    check_launch();
+  });
+}
+
+int glx_certified_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int screen, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    check_shape(dtype, m, n, l);
+    *bytes = carve(dtype, m, n, l, screen != 0, true, nullptr, nullptr);
+  });
+}
+
+int glx_certified_describe(int dtype, int64_t m, int64_t n, int64_t l, int screen, char* out, size_t cap) {
+  return guarded([&] {
+    if (!out || cap == 0) throw Error{GLX_E_INVALID, "null out"};
+    check_shape(dtype, m, n, l);
+    std::snprintf(out, cap, "%s", describe_certified(dtype, m, n, l, screen != 0).c_str());
+  });
+}
+
+int glx_certified_solve(const glx_problem* prob, double t, double tol, int64_t maxit, int screen, int check_every,
+                        const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev,
+                        void* ws, size_t wsb, glx_certified_info* info, void* stream) {
+  return guarded([&] {
+    if (!prob || !info) throw Error{GLX_E_INVALID, "null problem/info"};
+    if (prob->comm != nullptr) throw Error{GLX_E_INVALID, "the certified solve is single-GPU: comm must be NULL"};
+    check_shape(prob->dtype, prob->m, prob->n, prob->l);
+    if (!(prob->mu0 >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    if (!(t > 0.0) || !std::isfinite(t)) throw Error{GLX_E_INVALID, "the step t must be positive and finite"};
+    if (!(tol > 0.0)) throw Error{GLX_E_INVALID, "tol must be positive"};
+    if (maxit < 0) throw Error{GLX_E_INVALID, "negative iteration limit"};
+    if (check_every < 1) throw Error{GLX_E_INVALID, "check_every must be >= 1"};
+    if (!prob->A || !prob->b || !prob->x) throw Error{GLX_E_INVALID, "A, b and x must be device pointers"};
+    if ((reinterpret_cast<uintptr_t>(prob->A) | reinterpret_cast<uintptr_t>(prob->b) |
+         reinterpret_cast<uintptr_t>(prob->x)) & 15)
+      throw Error{GLX_E_INVALID, "A, b, x must be 16-byte aligned"};
+    if ((col_norms_dev != nullptr) != (col_stats != nullptr))
+      throw Error{GLX_E_INVALID, "col_norms_dev and col_stats go together"};
+    check_ws(carve(prob->dtype, prob->m, prob->n, prob->l, screen != 0, true, nullptr, nullptr), ws, wsb,
+             "glx_certified_workspace_bytes");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (prob->dtype == GLX_F64)
+      solve<double>(prob->dtype, prob->m, prob->n, prob->l, (const double*)prob->A, (const double*)prob->b,
+                    (double*)prob->x, prob->mu0, t, tol, maxit, screen != 0, check_every, col_norms_dev, col_stats,
+                    kept_rows_dev, ws, info, st);
+    else
+      solve<float>(prob->dtype, prob->m, prob->n, prob->l, (const float*)prob->A, (const float*)prob->b,
+                   (float*)prob->x, prob->mu0, t, tol, maxit, screen != 0, check_every, col_norms_dev, col_stats,
+                   kept_rows_dev, ws, info, st);
+  });
+}
+
+}  // extern "C"

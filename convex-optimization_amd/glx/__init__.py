@@ -13,10 +13,14 @@ Public surface:
     ``mu_max(A, b)``, the smallest mu at which x = 0 is optimal (``glx/certificate.py``; the name
     ``glx.certificate`` is the function, so its module's helpers are reached with
     ``from glx.certificate import compose, record``);
+  * ``solve_certified(A, b, mu)`` — a solve to a stated relative duality gap with gap-safe screening,
+    and ``path(A, b)`` — the same over a decreasing sequence of mu, warm-started (``glx/screen.py``);
   * ``dist`` — row sharding + RCCL communicator.
 """
 from ._lib import LIB_PATH, GlxError, lib  # noqa: F401
 from .solver import Session, solve  # noqa: F401
 from .certificate import certificate, mu_max  # noqa: F401
+from .screen import path, solve_certified  # noqa: F401
 
-__all__ = ["solve", "Session", "lib", "LIB_PATH", "GlxError", "certificate", "mu_max"]
+__all__ = ["solve", "Session", "lib", "LIB_PATH", "GlxError", "certificate", "mu_max",
+           "solve_certified", "path"]

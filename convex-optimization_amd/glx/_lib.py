@@ -69,6 +69,14 @@ class GlxAlmOpts(ctypes.Structure):
                 ("reserved", c_int32 * 4)]
 
 
+class GlxCertifiedInfo(ctypes.Structure):
+    """glx_certified_info (include/glx.h): what glx_certified_solve reports."""
+    _fields_ = [("iters", c_int64), ("checks", c_int64), ("compactions", c_int64), ("kept", c_int64),
+                ("listed", c_int64), ("width", c_int64), ("rounds", c_int64), ("converged", c_int32), ("fused", c_int32),
+                ("passes", c_double), ("tt", c_double), ("inner_rel_gap", c_double),
+                ("cert", c_double * 8), ("kept_hist", c_int64 * 64)]
+
+
 class GlxError(RuntimeError):
     """Error returned by libglx (message from glx_last_error())."""
 
@@ -191,6 +199,19 @@ _SIGS = {
     "glx_certificate_step": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_double, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                      c_void_p]),
+    "glx_screen_guard": (c_int, [POINTER(c_double), c_double, c_int, c_int64, c_int64, c_int64, c_double,
+                                 c_double, c_double, POINTER(c_double)]),
+    "glx_screen_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
+    "glx_col_norms": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                              c_void_p]),
+    "glx_screen_step": (c_int, [c_int64, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_gather_cols": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "glx_certified_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, POINTER(c_size_t)]),
+    "glx_certified_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_char_p, c_size_t]),
+    "glx_certified_solve": (c_int, [POINTER(GlxProblem), c_double, c_double, c_int64, c_int, c_int,
+                                    c_void_p, POINTER(c_double), c_void_p, c_void_p, c_size_t,
+                                    POINTER(GlxCertifiedInfo), c_void_p]),
     "glx_comm_unique_id": (c_int, [POINTER(c_uint8)]),
     "glx_comm_create": (c_int, [POINTER(c_void_p), POINTER(c_uint8), c_int, c_int]),
     "glx_comm_create_host": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
@@ -290,6 +311,14 @@ def certificate_describe(dtype: int, m: int, n: int, l: int, fused: int = 0) -> 
     kernel ..." (glx_certificate_describe: resolved on the host, no device)."""
     buf = ctypes.create_string_buffer(2048)
     check(lib().glx_certificate_describe(dtype, m, n, l, int(fused), buf, len(buf)))
+    return buf.value.decode()
+
+
+def certified_describe(dtype: int, m: int, n: int, l: int, screen: bool = True) -> str:
+    """The tiles of the certified solve's two passes at the full width, where its step runs and
+    whether screening is on (glx_certified_describe: resolved on the host, no device)."""
+    buf = ctypes.create_string_buffer(2048)
+    check(lib().glx_certified_describe(dtype, m, n, l, int(bool(screen)), buf, len(buf)))
     return buf.value.decode()
 
 

@@ -21,6 +21,11 @@ Differences, all forced by what the image lacks:
 - For any ``--size``, ``--certify`` appends two columns that need no stored x*: ``gap``, the duality
   gap of the returned x (an upper bound on f(x) - f*), and ``kkt``, its largest KKT violation
   (``glx.certificate``, DESIGN.md "Certificate"). Without the flag the output is unchanged.
+- ``--certified`` appends, after the solvers' rows, one ``Certified`` row: ``glx.solve_certified`` at
+  the instance's mu, solved to a relative duality gap of 1e-6 with gap-safe screening (DESIGN.md
+  "Certified solve and screening"); ``--certified path`` appends the rows of ``glx.path`` instead,
+  one per mu of a ten-point grid below mu_max (their ``optval`` is at that row's mu). Without the
+  flag the output is unchanged.
 - The svg plots (``main.py:200-235``) are replaced by ``f_hist.npz`` in ``--dest_dir``: the
   per-solver objective histories and f* = obj(u) those plots are drawn from. matplotlib is
   not installed.
@@ -123,6 +128,37 @@ def solve_routine(mode: str, func: Callable, x0, A, b, mu, opts, errfun, errfun_
     return x, num_iters, out, log_dict
 
 
+def certified_rows(mode: str, x0, A, b, mu, errfun, errfun_exact, sparsity, xstar=None, certify=False,
+                   headers=None) -> Dict[str, Dict[str, str]]:
+    """The rows ``--certified`` appends: ``mode`` "solve" gives one row "Certified" (glx.solve_certified
+    at mu from x0), "path" one row per mu of glx.path's default grid. Same keys as solve_routine's."""
+    from glx.screen import path, solve_certified
+    if mode == "solve":
+        x, info = solve_certified(A, b, mu, x0=x0)
+        results = [("Certified", x, info)]
+    elif mode == "path":
+        results = [("Certified mu=%.3E" % m_, x, info) for m_, x, info in path(A, b)]
+    else:
+        raise ValueError("certified must be 'solve' or 'path'")
+    rows = {}
+    for name, x, info in results:
+        d = {
+            "cpu": "%5.2f" % info["tt"],
+            "iter": "%5d" % info["iterations"],
+            "optval": "%6.5E" % info["primal"],
+            "sparsity": "%6.4f" % (sparsity(x) if np.any(x) else 0.0),
+            "err-to-exact": "%3.2E" % errfun_exact(x),
+            "err-to-x*": "n/a" if xstar is None else "%3.2E" % errfun(xstar, x),
+        }
+        if certify:
+            d["gap"] = "%3.2E" % info["gap"]
+            d["kkt"] = "%3.2E" % info["kkt_max"]
+        logging.getLogger(LOGGER).info(("[%-10s]: " % name) + ", ".join(k + ": " + v for k, v in d.items())
+                                       + ", rel_gap: %3.2E, kept: %d" % (info["rel_gap"], info["kept"]))
+        rows[name] = d
+    return rows
+
+
 def write_to_table(log_dicts: Dict[str, Dict[str, str]], stream: TextIO = sys.stdout) -> str:
     """main.py:94-110: a Markdown table "Statistics", one row per solver, strings left-aligned."""
     headers = None
@@ -157,12 +193,14 @@ def setup_logger(log_file: Optional[str], level=logging.INFO) -> logging.Logger:
 
 def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Dict[str, dict]] = None,
         xstar: Optional[np.ndarray] = None, dest_dir: Optional[str] = None, seed: int = SEED,
-        size=(256, 512, 2), stream: TextIO = sys.stdout, certify: bool = False) -> Dict[str, Any]:
+        size=(256, 512, 2), stream: TextIO = sys.stdout, certify: bool = False,
+        certified: Optional[str] = None) -> Dict[str, Any]:
     """The body of main.py's __main__ block (main.py:141-235) without the CVX solvers and plots.
 
     ``solvers`` defaults to the GPU solvers; tests pass other callables with the same signature.
     ``certify`` appends the ``gap`` and ``kkt`` columns (solve_routine); without it the log lines,
-    the table and f_hist.npz are what they were before the flag existed.
+    the table and f_hist.npz are what they were before the flag existed. ``certified``: "solve" or
+    "path" appends certified_rows' rows to the table (they have no objective history).
     Returns {"log_dicts", "f_hists", "f_star", "xs"}.
     """
     m, n, l = size
@@ -179,6 +217,10 @@ def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Di
             f_hists[mode] = np.asarray(out["f_hist"], dtype=np.float64)
         log_dicts[mode] = log_dict
         xs[mode] = x
+    if certified:
+        for mode, d in certified_rows(certified, x0, A, b, mu, errfun, errfun_exact, sparsity, xstar,
+                                      certify).items():
+            log_dicts[mode] = d
     write_to_table(log_dicts, stream)
     f_star = obj_func(A, b, mu, u)
     if dest_dir:
@@ -201,6 +243,9 @@ def main(argv=None) -> int:
     p.add_argument("--solvers", default=None, help="comma-separated subset, e.g. 'ProxGD Primal'")
     p.add_argument("--certify", action="store_true",
                    help="Append the duality gap and the KKT violation of each result (gap, kkt columns).")
+    p.add_argument("--certified", nargs="?", const="solve", default=None, choices=["solve", "path"],
+                   help="Append a 'Certified' row (glx.solve_certified to rel. gap 1e-6 with gap-safe "
+                        "screening), or with 'path' the rows of glx.path over ten values of mu.")
     a = p.parse_args(argv)
     setup_logger(a.log)
     size = tuple(int(v) for v in a.size.split(","))
@@ -213,7 +258,7 @@ def main(argv=None) -> int:
             p.error(f"unknown solver(s) {unknown}; choose from {list(solvers)}")
         solvers = {k: solvers[k] for k in keep}
     run(solvers, xstar=xstar, dest_dir=a.dest_dir, seed=a.seed, size=size, stream=sys.stdout,
-        certify=a.certify)
+        certify=a.certify, certified=a.certified)
     return 0
 
 

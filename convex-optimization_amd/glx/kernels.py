@@ -11,7 +11,9 @@ launch at a time (``glx_descent_step``, ``glx_fgd_gradient``, ``glx_row_stats``,
 Gram kernel and host eigenvalue sweep (``glx_admm_dual_step``, ``glx_admm_primal_step``, ``glx_gram``,
 ``glx_sym_lambda_max``), and the dual ALM solver's inner step and inner loop (``glx_alm_inner_step``,
 ``glx_alm_inner_run``), and the optimality certificate's row terms (``glx_certificate_step``), and
-the split-candidate trial's dense pass with A e fused in, one launch (``glx_fused_ae_pass``). All
+the split-candidate trial's dense pass with A e fused in, one launch (``glx_fused_ae_pass``), and
+the pieces of gap-safe screening (``glx_col_norms``, ``glx_screen_step``, ``glx_gather_cols`` and the
+host-only ``glx_screen_guard``). All
 tensors are contiguous device
 tensors of one dtype (float32 / float64).
 """
@@ -567,3 +569,66 @@ def sym_lambda_max(G) -> float:
     check(lib().glx_sym_lambda_max(g.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(g.shape[0]),
                                    ctypes.byref(out)))
     return float(out.value)
+
+
+def _screen_ws(m: int, n: int, device) -> torch.Tensor:
+    nb = ctypes.c_size_t(0)
+    check(lib().glx_screen_workspace_bytes(int(m), int(n), ctypes.byref(nb)))
+    return torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+
+
+def col_norms(A: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """||a_i||_2 of every column of A in one pass (glx_col_norms): float64, accumulated in double over
+    fixed row slabs in slab order. Returns (norms (n,), stats = [max_i ||a_i||, sum_i ||a_i||^2]),
+    both float64 device tensors."""
+    m, n = A.shape
+    dev = A.device
+    norms = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    stats = torch.full((2,), float("nan"), dtype=torch.float64, device=dev)
+    ws = _screen_ws(m, n, dev)
+    check(lib().glx_col_norms(_dt(A), m, n, A.data_ptr(), norms.data_ptr(), stats.data_ptr(), ws.data_ptr(),
+                              ws.numel(), _stream(dev)))
+    return norms, stats
+
+
+def screen_step(row_norms: torch.Tensor, col_norms: torch.Tensor, s: float, rho: float,
+                mu: float) -> Dict[str, torch.Tensor]:
+    """The gap-safe test on n rows (glx_screen_step): row i is kept unless
+    s row_norms[i] + col_norms[i] rho < mu holds strictly (a NaN keeps it). Returns {"mask" (n,) uint8,
+    "list": int32, n rounded up to 64 entries: the kept rows ascending, then -1 up to count[1] (entries
+    past count[1] are left at -2), "count": int32 [kept, kept rounded up to 64]}."""
+    n = row_norms.shape[0]
+    dev = row_norms.device
+    assert row_norms.dtype == torch.float64 and col_norms.dtype == torch.float64
+    mask = torch.full((n,), 255, dtype=torch.uint8, device=dev)
+    lst = torch.full(((n + 63) // 64 * 64,), -2, dtype=torch.int32, device=dev)
+    cnt = torch.full((2,), -2, dtype=torch.int32, device=dev)
+    ws = _screen_ws(1, n, dev)
+    check(lib().glx_screen_step(n, row_norms.data_ptr(), col_norms.data_ptr(), float(s), float(rho), float(mu),
+                                mask.data_ptr(), lst.data_ptr(), cnt.data_ptr(), ws.data_ptr(), ws.numel(),
+                                _stream(dev)))
+    return {"mask": mask, "list": lst, "count": cnt}
+
+
+def gather_cols(src: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dst[r, j] = src[r, idx[j]], 0 where idx[j] is outside src's columns (glx_gather_cols). ``idx``:
+    int32, a multiple of 64 entries (the list of :func:`screen_step` up to count[1]). ``out``: a
+    contiguous (m, len(idx)) tensor to write (tests put canaries behind it)."""
+    m, sw = src.shape
+    wp = int(idx.shape[0])
+    assert idx.dtype == torch.int32
+    dst = torch.full((m, wp), float("nan"), dtype=src.dtype, device=src.device) if out is None else out
+    check(lib().glx_gather_cols(_dt(src), m, sw, src.data_ptr(), idx.data_ptr(), wp, dst.data_ptr(),
+                                _stream(src.device)))
+    return dst
+
+
+def screen_guard(rec, mu: float, dtype: int, m: int, n: int, l: int, col_max: float, col_sumsq: float,
+                 b_norm: float) -> Tuple[float, float, float]:
+    """The rounding guard of the screening test (glx_screen_guard, host only, needs no device): from
+    the certificate's record to (s_safe, gap+, rho+)."""
+    r = (ctypes.c_double * 8)(*[float(v) for v in rec])
+    out = (ctypes.c_double * 3)()
+    check(lib().glx_screen_guard(r, float(mu), int(dtype), int(m), int(n), int(l), float(col_max),
+                                 float(col_sumsq), float(b_norm), out))
+    return float(out[0]), float(out[1]), float(out[2])

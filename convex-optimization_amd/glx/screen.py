@@ -1,0 +1,190 @@
+"""A certified solve of the group-lasso problem with gap-safe screening, and a path over mu.
+
+``solve_certified`` runs libglx's ``glx_certified_solve`` (``csrc/screen.cpp``): FISTA with the exact
+group prox and the fixed step 1 / lambda_max(A^T A), stopped when the duality gap of
+:func:`glx.certificate` is at most ``tol`` of the primal objective. With ``screen=True`` the
+certificate's dual point and gap give, every ``check_every`` iterations, the gap-safe test
+
+    s ||g_i||_2 + ||a_i||_2 sqrt(2 gap) < mu   =>   x*_i = 0        (a_i = column i of A),
+
+under a rounding guard (``glx_screen_guard``); the columns of the rows it proves zero leave A, so the
+two passes over A of every later iteration stream a narrower matrix (DESIGN.md "Certified solve and
+screening"). ``path`` solves a decreasing sequence of mu, each warm-started from the one before,
+with the column norms and lambda_max computed once. Everything runs on the GPU; there is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import GlxCertifiedInfo, GlxProblem, check, lib
+from .certificate import _inputs, compose, mu_max
+
+DEFAULT_MAXIT = 100000
+
+
+def mu_grid(mu_top: float, n_mus: int = 10, mu_min_ratio: float = 1e-2) -> List[float]:
+    """The decreasing geometric grid of ``n_mus`` values from ``mu_top`` down to
+    ``mu_min_ratio * mu_top`` (a single value: ``mu_top``). Host only."""
+    mu_top = float(mu_top)
+    n_mus = int(n_mus)
+    if not (mu_top > 0.0 and math.isfinite(mu_top)):
+        raise ValueError("mu_max must be positive and finite (is A^T b zero?)")
+    if n_mus < 1:
+        raise ValueError("n_mus must be >= 1")
+    if not 0.0 < float(mu_min_ratio) < 1.0:
+        raise ValueError("mu_min_ratio must be in (0, 1)")
+    if n_mus == 1:
+        return [mu_top]
+    q = float(mu_min_ratio) ** (1.0 / (n_mus - 1))
+    return [mu_top * q ** i for i in range(n_mus)]
+
+
+def _check_mus(mus: Sequence[float]) -> List[float]:
+    out = [float(v) for v in mus]
+    if not out:
+        raise ValueError("mus is empty")
+    if any(not (v >= 0.0 and math.isfinite(v)) for v in out):
+        raise ValueError("every mu must be >= 0 and finite")
+    if any(b >= a for a, b in zip(out, out[1:])):
+        raise ValueError("mus must be strictly decreasing (each solve warm-starts the next)")
+    return out
+
+
+def _check_args(A, b, x0, tol, maxit, check_every):
+    """The argument checks that need no device (shapes from the arrays as they are)."""
+    sa, sb = tuple(np.shape(A)), tuple(np.shape(b))
+    if len(sa) != 2 or len(sb) != 2:
+        raise ValueError("A and b must be 2-D (group lasso with l columns)")
+    if sa[0] != sb[0]:
+        raise ValueError("shape mismatch: A %s, b %s" % (sa, sb))
+    if x0 is not None and tuple(np.shape(x0)) != (sa[1], sb[1]):
+        raise ValueError("shape mismatch: A %s, b %s, x0 %s" % (sa, sb, tuple(np.shape(x0))))
+    if not float(tol) > 0.0:
+        raise ValueError("tol must be positive")
+    if int(maxit) < 0:
+        raise ValueError("maxit must be >= 0")
+    if int(check_every) < 1:
+        raise ValueError("check_every must be >= 1")
+
+
+class _Prepared:
+    """What a sequence of solves on one (A, b) shares: the device copies, the step, the column norms
+    and the workspace."""
+
+    def __init__(self, A, b, screen: bool, comm=None):
+        from . import kernels
+        from .solver import _lambda_max
+        if comm is not None:
+            raise ValueError("the certified solve is single-GPU: it takes no communicator")
+        _, self.Ad, self.bd = _inputs(None, A, b)
+        self.numpy = not isinstance(A, torch.Tensor)
+        self.m, self.n = self.Ad.shape
+        self.l = self.bd.shape[1]
+        self.device = self.Ad.device
+        self.gdt = _lib.GLX_F64 if self.Ad.dtype == torch.float64 else _lib.GLX_F32
+        self.screen = bool(screen)
+        with torch.cuda.device(self.device):
+            nb = ctypes.c_size_t(0)   # (first: it refuses what the solve would, before any launch)
+            check(lib().glx_certified_workspace_bytes(self.gdt, self.m, self.n, self.l, int(self.screen),
+                                                      ctypes.byref(nb)))
+            self.lam = float(_lambda_max(self.Ad))
+            self.t = 1.0 / self.lam
+            self.cn = self.cstats = None
+            if self.screen:
+                self.cn, st = kernels.col_norms(self.Ad)
+                self.cstats = (ctypes.c_double * 2)(*st.cpu().tolist())
+            self.ws = torch.empty(int(nb.value), dtype=torch.uint8, device=self.device)
+
+    def solve(self, mu: float, x0, tol: float, maxit: int, check_every: int):
+        mu = float(mu)
+        if not mu >= 0.0:
+            raise ValueError("mu must be >= 0")
+        xd, _, _ = _inputs(x0, self.Ad, self.bd)
+        if x0 is not None:
+            xd = xd.clone()   # the solve works in place
+        p = GlxProblem(dtype=self.gdt, method=0, m=self.m, n=self.n, l=self.l, A=self.Ad.data_ptr(),
+                       b=self.bd.data_ptr(), x=xd.data_ptr(), mu0=mu, comm=None)
+        info = GlxCertifiedInfo()
+        rows = torch.full(((self.n + 63) // 64 * 64,), -1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().glx_certified_solve(ctypes.byref(p), self.t, float(tol), int(maxit), int(self.screen),
+                                            int(check_every), None if self.cn is None else self.cn.data_ptr(),
+                                            self.cstats, rows.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
+                                            ctypes.byref(info),
+                                            ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        out: Dict[str, Any] = compose(list(info.cert), mu)
+        out["plan"] = _lib.certified_describe(self.gdt, self.m, self.n, self.l, self.screen)
+        nc = int(info.compactions)
+        if int(info.listed) > 0:
+            kept_rows = rows[:int(info.listed)].cpu().numpy().astype(np.int64)
+            kept_rows = kept_rows[kept_rows >= 0]
+        elif self.screen and int(info.kept) == 0 and int(info.checks) > 0:
+            kept_rows = np.zeros(0, dtype=np.int64)
+        else:
+            kept_rows = np.arange(self.n, dtype=np.int64)
+        out.update(converged=bool(info.converged), iterations=int(info.iters), checks=int(info.checks),
+                   compactions=nc, kept_history=[int(info.kept_hist[i]) for i in range(min(nc, 64))],
+                   kept=int(info.kept), kept_rows=kept_rows, width=int(info.width), rounds=int(info.rounds),
+                   passes=float(info.passes), tt=float(info.tt), inner_rel_gap=float(info.inner_rel_gap),
+                   step_fused=bool(info.fused), screen=self.screen, tol=float(tol), step=self.t, mu=mu)
+        return xd, out
+
+    def result(self, xd: torch.Tensor):
+        return xd.cpu().numpy() if self.numpy else xd
+
+
+def solve_certified(A, b, mu, x0=None, tol: float = 1e-6, maxit: int = DEFAULT_MAXIT, screen: bool = True,
+                    check_every: int = 10, comm=None) -> Tuple[Any, Dict[str, Any]]:
+    """Solve min_x 1/2 ||A x - b||_F^2 + mu sum_i ||x_i||_2 until the duality gap is at most ``tol``
+    of the primal objective (or ``maxit`` iterations in total).
+
+    ``A`` (m x n), ``b`` (m x l) and ``x0`` (n x l, default 0) are NumPy arrays or torch tensors and
+    are not modified; the computation runs in A's dtype. Returns ``(x, info)``: x as A's kind of
+    array, and ``info`` with the keys of :func:`glx.certificate` for the returned x on the full
+    problem (``primal``, ``dual``, ``gap``, ``rel_gap``, ``scale``, ``gmax``, ``kkt_max``, ``kkt_fro``,
+    ``nonzero_rows``, ``fused``, ``plan``) plus ``converged`` (rel_gap <= tol), ``iterations``,
+    ``checks``, ``compactions``, ``kept_history`` (rows kept after each compaction), ``kept`` (rows the last screening test did not
+    prove zero), ``kept_rows`` (their indices, ascending: every other row is zero at the optimum),
+    ``width`` (columns of the last reduced problem), ``rounds``, ``passes`` (passes over A, each
+    weighted by its width / n), ``tt`` (seconds inside the native call) and ``step``. Single GPU: a
+    communicator is refused."""
+    _check_args(A, b, x0, tol, maxit, check_every)
+    if not float(mu) >= 0.0:
+        raise ValueError("mu must be >= 0")
+    prep = _Prepared(A, b, screen, comm)
+    xd, info = prep.solve(mu, x0, tol, maxit, check_every)
+    return prep.result(xd), info
+
+
+def path(A, b, mus: Optional[Sequence[float]] = None, n_mus: int = 10, mu_min_ratio: float = 1e-2,
+         **kw) -> List[Tuple[float, Any, Dict[str, Any]]]:
+    """Certified solves over a decreasing sequence of mu: ``mus``, or the geometric grid of ``n_mus``
+    values from ``glx.mu_max(A, b)`` down to ``mu_min_ratio`` of it (:func:`mu_grid`). Each solve is
+    warm-started from the one before; the column norms and lambda_max are computed once. ``kw``:
+    ``tol``, ``maxit``, ``screen``, ``check_every`` of :func:`solve_certified`. Returns the list of
+    ``(mu, x, info)``; at mu = mu_max the entry is x = 0 with gap 0 and no iterations."""
+    unknown = set(kw) - {"tol", "maxit", "screen", "check_every", "comm"}
+    if unknown:
+        raise TypeError("path() got unexpected keyword arguments %s" % sorted(unknown))
+    tol, maxit = kw.get("tol", 1e-6), kw.get("maxit", DEFAULT_MAXIT)
+    check_every = kw.get("check_every", 10)
+    _check_args(A, b, None, tol, maxit, check_every)
+    if mus is not None:
+        mus = _check_mus(mus)
+    else:
+        mu_grid(1.0, n_mus, mu_min_ratio)   # the grid's own checks, before any device work
+    prep = _Prepared(A, b, kw.get("screen", True), kw.get("comm"))
+    if mus is None:
+        mus = mu_grid(mu_max(prep.Ad, prep.bd), n_mus, mu_min_ratio)
+    out = []
+    xd = None
+    for mu in mus:
+        xd, info = prep.solve(mu, xd, tol, maxit, check_every)
+        out.append((mu, prep.result(xd.clone()), info))
+    return out

@@ -615,6 +615,91 @@ int glx_certificate_step(int dtype, int64_t m, int64_t n, int64_t l, const void*
                          const void* x, double mu, int form, double* rownorm_out, void* sums_dev,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- certified solve with gap-safe screening (DESIGN.md "Certified solve and screening"; additive
+ * entries, the ABI version stays 2) ----
+ * Solves P(x) to a stated relative duality gap: FISTA with the exact group prox and a fixed step
+ * t <= 1 / lambda_max(A^T A) (caller-computed, like alpha0), stopped on the certificate above. With
+ * screen != 0, every check_every iterations the certificate's dual point theta = s r and the radius
+ * rho = sqrt(2 gap) give the gap-safe test  s ||g_i|| + ||a_i|| rho < mu  =>  x*_i = 0  (a_i = column
+ * i of A); columns that pass leave A: the kept ones are gathered, padded with zero columns to a
+ * multiple of 64, into one of two workspace buffers whenever the padded width is at most 0.9 of the
+ * current one. s and rho carry a rounding guard composed on the host in float64.
+ *
+ * The guard (host only, needs no device): from the certificate's record of the current iterate
+ * (out[8] of glx_certificate at this dtype and shape; entries 0..3 are read), mu, max_i ||a_i||,
+ * sum_i ||a_i||^2 and ||b||_F to
+ *   out = [s_safe, gap+, rho+]:  s_safe <= s makes s_safe r dual feasible whatever the rounding of
+ *   g = A^T r; gap+ >= the true gap of (x, s_safe r); rho+ >= sqrt(2 gap+) plus the rounding of
+ *   the row's own norm, so that  s_safe ||g_i|| + ||a_i|| rho+ < mu  proves x*_i = 0 with the stored
+ *   row and column norms. A NaN in the record gives NaN outputs, which screen nothing. */
+int glx_screen_guard(const double rec[8], double mu, int dtype, int64_t m, int64_t n, int64_t l,
+                     double col_max, double col_sumsq, double b_norm, double out[3]);
+/* Workspace (device bytes, 256-byte aligned) of the two one-launch entries below. */
+int glx_screen_workspace_bytes(int64_t m, int64_t n, size_t* bytes);
+/* norms_dev[i] = ||a_i||_2 (n device doubles) of the row-major m x n matrix A of dtype, in one
+ * pass: squares accumulated in double over fixed row slabs (at most 64, a function of m) and the
+ * slabs summed in slab order; stats_dev = [max_i ||a_i|| (NaN-propagating), sum_i ||a_i||^2] (device
+ * doubles). Bit-reproducible. */
+int glx_col_norms(int dtype, int64_t m, int64_t n, const void* A, double* norms_dev, double* stats_dev,
+                  void* workspace, size_t workspace_bytes, void* stream);
+/* The screening test on n rows: row i is kept unless  s row_norms[i] + col_norms[i] rho < mu  holds
+ * strictly in double (one rounded product each, one rounded sum; a NaN keeps the row).
+ *   mask (n bytes, may be NULL): 1 = kept;  list: the kept rows, ascending, then -1 up to
+ *   count[1] (room for n rounded up to 64 entries);  count = [kept, kept rounded up to 64].
+ * The list comes from an ordered scan (wave ballots, popcounts, block offsets) and is identical
+ * from run to run. All pointers are device memory. */
+int glx_screen_step(int64_t n, const double* row_norms, const double* col_norms, double s, double rho,
+                    double mu, uint8_t* mask, int32_t* list, int32_t* count, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* dst (m x width, width a multiple of 64) [r, j] = src (m x src_width) [r, idx[j]], and 0 where
+ * idx[j] is outside 0 .. src_width - 1 (the list's -1 tail); idx holds width device ints. src and dst
+ * must not overlap. 16-byte stores where dst is 16-byte aligned. */
+int glx_gather_cols(int dtype, int64_t m, int64_t src_width, const void* src, const int32_t* idx,
+                    int64_t width, void* dst, void* stream);
+#define GLX_CERTIFIED_MAX_HIST 64
+typedef struct glx_certified_info {
+  int64_t iters;         /* FISTA iterations in total                                           */
+  int64_t checks;        /* certificates of the (reduced) problem taken inside the loop          */
+  int64_t compactions;   /* gathers of A into a narrower buffer                                  */
+  int64_t kept;          /* rows the last screening test did not prove zero (n with screen = 0)  */
+  int64_t listed;        /* entries written to kept_rows_dev (0: none)                           */
+  int64_t width;         /* columns of the last reduced problem (kept rounded up to 64; n without a
+                            compaction)                                                          */
+  int64_t rounds;        /* 1 + the times the loop resumed because the full problem's gap missed tol */
+  int32_t converged;     /* the full problem's rel_gap <= tol                                    */
+  int32_t fused;         /* the step ran in the epilogue of A^T r at the full width              */
+  double  passes;        /* passes over A, each weighted by its width / n (the iterations' two, the
+                            checks' two, a compaction's read, the column norms' one, the final
+                            certificates' two)                                                   */
+  double  tt;            /* seconds inside the call, stream-synchronised                         */
+  double  inner_rel_gap; /* rel_gap of the reduced problem at its last check                     */
+  double  cert[8];       /* glx_certificate's record of the returned x on the full problem       */
+  int64_t kept_hist[GLX_CERTIFIED_MAX_HIST];   /* kept rows after each of the first 64 compactions */
+} glx_certified_info;
+/* Device bytes glx_certified_solve needs (screen != 0 adds the two compaction buffers: at most
+ * 0.9 m n and 0.81 m n elements). */
+int glx_certified_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int screen, size_t* bytes);
+/* One line: the tiles of the two passes at the full width, where the step runs ("fused ..." or
+ * "row kernel ...") and whether screening is on. Resolved on the host; needs no device. */
+int glx_certified_describe(int dtype, int64_t m, int64_t n, int64_t l, int screen, char* out, size_t cap);
+/* The whole solve. prob->x holds x0 on entry and the result on return; prob->method is ignored;
+ * mu = prob->mu0. Checks run before the first iteration, every check_every iterations and at maxit
+ * (the bound on the total). At the stop x is scattered back to n x l and the certificate of the full
+ * problem on the caller's A is taken: info->cert. Where its rel_gap exceeds tol (a screened row may
+ * bind the rescaling s) the loop resumes on the reduced problem with its internal target halved, at
+ * most 5 times. col_norms_dev (n device doubles) with col_stats (host: [max, sum of squares]) as
+ * glx_col_norms gives them, or both NULL: computed here. kept_rows_dev (may be NULL; room for n
+ * rounded up to 64 device ints): its first info->listed entries receive the rows of the full problem
+ * that are not proven zero at the optimum (those the last test kept; right after a compaction, the
+ * columns of the reduced problem), ascending, with -1 entries for padding; info->listed = 0 (nothing
+ * written) where no test ran or every row is proven zero. GLX_E_INVALID for a communicator, l > 128,
+ * n >= 2^31 - 64, mu < 0 or NaN, t or tol not positive, maxit < 0, check_every < 1, a NULL or not
+ * 16-byte aligned A, b or x, and a workspace that is too small or not 256-byte aligned. */
+int glx_certified_solve(const glx_problem* prob, double t, double tol, int64_t maxit, int screen,
+                        int check_every, const double* col_norms_dev, const double* col_stats,
+                        int32_t* kept_rows_dev, void* workspace, size_t workspace_bytes,
+                        glx_certified_info* info, void* stream);
+
 /* ---- multi-GPU (row-sharded A; A^T r all-reduced, or reduce-scattered with the row-sharded step) ---- */
 #define GLX_COMM_ID_BYTES 128
 int  glx_comm_unique_id(uint8_t id[GLX_COMM_ID_BYTES]);
