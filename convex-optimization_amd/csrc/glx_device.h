@@ -42,7 +42,9 @@ __device__ inline bool red_skipped(const Red& red) {
 // nparts >= 0: only nparts workgroups of the launch take part, each with a distinct slot in
 // [0, nparts) (the K-split A^T R kernels: one per panel + the publisher, so the split count is
 // not bounded by the partials row); the arrival shards are then keyed by slot, not blockIdx.
-template <int NV, unsigned MAXMASK, int NW = 4>
+// WT (Red::parts_only): the block values go out as write-through (sc1) stores, for a reader in the
+// same launch (the residual finalize at the head of k_atr_prox, kernels_atr.hip fin_head_run).
+template <int NV, unsigned MAXMASK, int NW = 4, bool WT = false>
 __device__ bool grid_reduce(double (&v)[NV], const Red& red, int slot = -1, int nparts = -1) {
   static_assert(NW == 4 || NW == 8, "4- or 8-wave blocks");
   constexpr int NTHR = 64 * NW;
@@ -64,8 +66,12 @@ __device__ bool grid_reduce(double (&v)[NV], const Red& red, int slot = -1, int 
   if (red.parts_only) {   // uniform over the grid: the block values are the result
     if (threadIdx.x == 0) {
 #pragma unroll
-      for (int j = 0; j < NV; ++j)
-        red.part[(slot < 0 ? (int)blockIdx.x : slot) * NV + j] = waves_combine<NW>((MAXMASK >> j) & 1, sh[j]);
+      for (int j = 0; j < NV; ++j) {
+        double* dst = &red.part[(slot < 0 ? (int)blockIdx.x : slot) * NV + j];
+        const double bv = waves_combine<NW>((MAXMASK >> j) & 1, sh[j]);
+        if constexpr (WT) __hip_atomic_store(dst, bv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else *dst = bv;
+      }
     }
     return false;
   }
@@ -258,6 +264,163 @@ __device__ inline T slab_sum(const T* __restrict__ g, int S, int64_t stride, int
 
 
 template <typename T> __device__ inline T tabs(T v) { return v < T(0) ? -v : v; }
+
+// ------------------------------------------------------------------------------------------
+// The residual finalize's element work (k_finalize_residual, kernels_elem.hip), shared with the
+// head of k_atr_prox (kernels_atr.hip) so that both write the same bits.
+//
+// The S slabs of one residual element are split over G adjacent lanes (G = 1, 2, 4 or 8, so a
+// lane takes at most 8 slabs). A lane issues its loads back to back and adds them in slab
+// order; the G partial sums then combine by an xor butterfly, which gives every lane of the
+// group the same bits ((p0 + p1) + (p2 + p3) ...). The order is fixed, so the result is
+// deterministic, and G = 1 is the plain sequential sum. With few rows and a deep split (the
+// per-rank shards of a multi-GPU run: m = 1024, S = 32) this spreads the slab reads over the
+// whole grid instead of leaving them to m*l threads with S-long load chains (22 -> 11.6 us at
+// m = 1024). Splitting further than 8 slabs per lane measured slower (NS: 13.7 -> 17.9 us).
+// ------------------------------------------------------------------------------------------
+constexpr int kSlabLoads = 8;
+
+// group_slab_sum in two halves, so a caller can issue the loads of several sources before the
+// first add (round 5: the finalize's two sources, one round trip instead of two)
+template <typename T, int G>
+__device__ inline int group_slab_load(const T* __restrict__ P, int S, int64_t ml, int64_t idx, int sub,
+                                      T (&a)[kSlabLoads]) {
+  const int per = (S + G - 1) / G;
+  const int k0 = sub * per;
+  const int cnt = S - k0 < per ? S - k0 : per;   // <= 0 for an empty trailing lane
+#pragma unroll
+  for (int k = 0; k < kSlabLoads; ++k) a[k] = k < cnt ? P[(int64_t)(k0 + k) * ml + idx] : T(0);
+  return cnt;
+}
+template <typename T, int G>
+__device__ inline T group_slab_fold(const T (&a)[kSlabLoads], int cnt) {
+  T v = a[0];
+#pragma unroll
+  for (int k = 1; k < kSlabLoads; ++k)
+    if (k < cnt) v = v + a[k];
+#pragma unroll
+  for (int off = 1; off < G; off <<= 1) v = v + __shfl_xor(v, off);
+  return v;
+}
+template <typename T, int G>
+__device__ inline T group_slab_sum(const T* __restrict__ P, int S, int64_t ml, int64_t idx, int sub) {
+  T a[kSlabLoads];
+  const int cnt = group_slab_load<T, G>(P, S, ml, idx, sub, a);
+  return group_slab_fold<T, G>(a, cnt);
+}
+
+// *cmax, or (cmp != NULL: the trial's sums still pending as Red::parts_only partials, cmnv values
+// per slot) the max of their column 3 over cmnp slots, by every workgroup for itself (all 256
+// threads call this; the result is order-independent)
+__device__ inline double pending_max(const double* cmax, const double* __restrict__ cmp, int cmnp, int cmnv) {
+  if (cmp == nullptr) return *cmax;
+  __shared__ double wmax[4];
+  double mv = -__builtin_inf();
+  for (int i = threadIdx.x; i < cmnp; i += 256) mv = nan_max(mv, cmp[i * cmnv + 3]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mv = nan_max(mv, __shfl_xor(mv, off));
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mv;
+  __syncthreads();
+  return nan_max(nan_max(wmax[0], wmax[1]), nan_max(wmax[2], wmax[3]));
+}
+
+// count(|cx| > 1e-6 cm) over this thread's indices tid, tid + stride, ...: the first kCountAhead
+// values already in cxv (loaded ahead), the rest read here
+constexpr int kCountAhead = 2;
+template <typename T>
+__device__ inline double count_above(const T* __restrict__ cx, int64_t cn, const T (&cxv)[kCountAhead],
+                                     int64_t tid, int64_t stride, double cm) {
+  const T thr = (T)1e-6 * (T)cm;
+  double c = 0.0;
+#pragma unroll
+  for (int q = 0; q < kCountAhead; ++q)
+    if (tid + q * stride < cn) c += (tabs(cxv[q]) > thr) ? 1.0 : 0.0;
+  for (int64_t idx = tid + kCountAhead * stride; idx < cn; idx += stride) c += (tabs(cx[idx]) > thr) ? 1.0 : 0.0;
+  return c;
+}
+
+// What a residual finalize reads and writes (launch_finalize_residual's arguments): R[src] = the
+// sum of source src's slabs - B, the chain forms, and the count over cx.
+template <typename T>
+struct FinSrc {
+  const T* P;        // the slabs: source sr at P + sr * S * ml; chain: S0 slabs, then S at P + S0 * ml
+  const T* B;
+  T* R[3];
+  const T* cx;
+  int64_t ml, cn;
+  int S, S0, chain;
+};
+
+// The work of one 256-thread block vb of nvb of a residual finalize: the first kCountAhead values
+// of the count into cxv (their latencies overlap the slab loads), the block's residual elements
+// stored, their squares added to v[0, NSRC). k_finalize_residual calls it with (blockIdx.x,
+// gridDim.x); the head of k_atr_prox walks the same blocks, several per workgroup, and stores the
+// residuals write-through (WT) for the readers of the same launch. live / skipped: the gate and
+// the device-side cancellation of k_finalize_residual (true / false elsewhere). Returns false
+// where a cancelled launch returns.
+template <typename T, int NSRC, int G, bool WT>
+__device__ inline bool fin_block_elems(const FinSrc<T>& f, int64_t vb, int64_t nvb, bool live, bool skipped,
+                                       T (&cxv)[kCountAhead], double (&v)[4]) {
+  auto put = [](T* dst, T val) {
+    if constexpr (WT) __hip_atomic_store(dst, val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *dst = val;
+  };
+  const int sub = threadIdx.x % G;
+  const int64_t tid = vb * 256 + threadIdx.x;
+  const int64_t stride = nvb * 256;
+  const int64_t ml = f.ml;
+#pragma unroll
+  for (int q = 0; q < kCountAhead; ++q)
+    cxv[q] = (f.cx != nullptr && tid + q * stride < f.cn) ? f.cx[tid + q * stride] : T(0);
+  // residual elements: G lanes per element; the lanes of a group share idx, so they enter and
+  // leave the loop together and the butterfly only reads active partners
+  for (int64_t idx = tid / G; idx < ml; idx += stride / G) {
+    const T bv = f.B[idx];
+    if (NSRC == 2 && f.chain) {   // split-candidate: R0 = (A p_thr - b) + A e (always live)
+      // chain 2 (round 6, the fused A e pass): the slabs behind P0 are A p, so R0 = A p - b and
+      // R1 = A p_thr - b = R0 - A e
+      T a1[kSlabLoads], a0[kSlabLoads];
+      const int c1 = group_slab_load<T, G>(f.P + (int64_t)f.S0 * ml, f.S, ml, idx, sub, a1);
+      const int c0 = group_slab_load<T, G>(f.P, f.S0, ml, idx, sub, a0);
+      T r1, r0;
+      if (f.chain == 2) {
+        r0 = group_slab_fold<T, G>(a1, c1) - bv;
+        r1 = r0 - group_slab_fold<T, G>(a0, c0);
+      } else {
+        r1 = group_slab_fold<T, G>(a1, c1) - bv;
+        r0 = r1 + group_slab_fold<T, G>(a0, c0);
+      }
+      if (skipped) return false;
+      if (sub == 1 % G) put(f.R[1] + idx, r1);
+      if (f.R[0] != nullptr && sub == 0) put(f.R[0] + idx, r0);
+      if (sub == 0) {
+        v[0] += (double)(r0 * r0);
+        v[1] += (double)(r1 * r1);
+      }
+      continue;
+    }
+    T a[NSRC][kSlabLoads];   // every source's slab loads issued before the first add
+    int cs[NSRC];
+    if (live) {
+#pragma unroll
+      for (int sr = 0; sr < NSRC; ++sr)
+        cs[sr] = group_slab_load<T, G>(f.P + (int64_t)sr * f.S * ml, f.S, ml, idx, sub, a[sr]);
+    }
+#pragma unroll
+    for (int sr = 0; sr < NSRC; ++sr) {
+      T r;
+      if (live) {
+        r = group_slab_fold<T, G>(a[sr], cs[sr]) - bv;
+        if (skipped) return false;
+        if (sub == sr % G) put(f.R[sr] + idx, r);
+      } else {
+        r = f.R[sr][idx];
+      }
+      if (sub == 0) v[sr] += (double)(r * r);
+    }
+  }
+  return true;
+}
 
 // Device-side control of a ProxGD (mode 0) / FProxGD (mode 1) line-search iteration (struct Ctl,
 // solver.cpp dc_run / fista_dc_run): the Armijo test of gl_ProxGD_primal.py:89-92 (FProxGD's

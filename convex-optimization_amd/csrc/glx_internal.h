@@ -229,7 +229,7 @@ struct SessionKnobs {
       unfused_spec{"GLX_UNFUSED_SPEC"}, fused_trial{"GLX_FUSED_TRIAL"}, readback{"GLX_READBACK"},
       attach_pub{"GLX_ATTACH_PUB"}, spec_grad{"GLX_SPEC_GRAD"}, spec_ax_pub{"GLX_SPEC_AX_PUB"},
       shard_derive{"GLX_SHARD_DERIVE"}, defer_red{"GLX_DEFER_RED"}, ax_keep_mib{"GLX_AX_KEEP_MIB"},
-      atr_keep_mib{"GLX_ATR_KEEP_MIB"};
+      atr_keep_mib{"GLX_ATR_KEEP_MIB"}, fin_head{"GLX_FIN_HEAD"};
 };
 constexpr int kMaxShardRanks = 64;   // ranks (or modelled ranks) of the row-sharded schedules
 // The row-sharded schedule of ProxGD (solver.cpp iter_proxgd_shard) / FProxGD (iter_fista_shard):
@@ -272,9 +272,15 @@ struct SessionMode {
   int nsets = 2;                  // gradient sets
   bool defer = false;             // deferred reductions (single GPU)
   int gemv_blocks = 0;            // SGD / GD, l = 1: workgroups of the one-pass form (0: two passes)
+  // round 8: the speculative trial's finalize may run at the head of k_atr_prox (the path asks
+  // for it; the session still checks co-residency on its device, fin_head_fits)
+  bool fin_head = false;
   ShardMode sh;
 };
 SessionMode session_mode(const glx_problem& P, const glx_opts& O);
+// The co-residency guard of the finalize head: every workgroup of the launch (n / 64 panels + the
+// publisher) waits for all the others, so all of them must fit on the device at once.
+bool fin_head_fits(int64_t n, int cus, int per_cu);
 // the kernels the session launches (glx_session_describe, glx_mode_describe)
 std::string describe_mode(const SessionMode& md);
 
@@ -315,10 +321,38 @@ void launch_atr(const GemmPlan& p, const T* A, const T* R, T* Gp, hipStream_t st
 // With S = atr_S > 1 K splits the blocks write slabs Gp[S][n][l] and the last block of each
 // 64-row panel (counter pcnt[panel], zero before the first launch, reset by that block) sums
 // them in slab order and runs the trial.
+// head != NULL (round 8; f64, atr_prox_head_ok): the launch first runs the residual finalize that
+// produces R — launch_finalize_residual's two-source forms with Red::parts_only, the same
+// 256-thread blocks walked by the panel workgroups (block w, w + panels, ...), the same bits —
+// while its first rows of A are in flight, and every workgroup waits for all of them before it
+// reads R. Needs every workgroup of the launch resident at once (fin_head_fits).
+struct FinHead {
+  const double* P = nullptr;     // the slabs, as launch_finalize_residual's P with nsrc = 2
+  const double* B = nullptr;
+  double* R0 = nullptr;          // may be NULL with chain
+  double* R1 = nullptr;          // the launch's R
+  const double* cx = nullptr;    // the count's array (cn values), or NULL
+  const double* cmax = nullptr;  // *cmax, or cmax_parts / cmax_np / cmax_nv as launch_finalize_residual
+  const double* cmax_parts = nullptr;
+  double* part = nullptr;        // 4 sums per block, Red::parts_only layout
+  unsigned* ticket = nullptr;    // kTicketBytes, zero: the arrivals of this launch
+  unsigned* ticket_next = nullptr;   // may be NULL: zeroed for the next launch (never `ticket`)
+  int* abort = nullptr;          // set to 1 by a workgroup whose wait ran out (~1 s); it stores nothing
+  int64_t ml = 0, cn = 0;
+  int S = 1, S0 = 0, chain = 0, cmax_np = 0, cmax_nv = 6;
+  int nvb = 0;                   // the finalize's 256-thread blocks: finalize_blocks(ml, S, S0, cn)
+};
+// the plan's fused trial takes a head for this finalize (f64, WL 0, one K split, at most
+// kSlabLoads slabs per source)
+bool atr_prox_head_ok(const GemmPlan& p, int S, int S0);
+// workgroups of the head kernel one CU holds at once (hipOccupancyMaxActiveBlocksPerMultiprocessor)
+// and the device's CU count; the guard itself is session_mode.cpp's fin_head_fits
+void atr_prox_head_capacity(const GemmPlan& p, int* cus, int* per_cu);
 template <typename T>
 void launch_atr_prox(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, T* pp, T* pthr,
                      T* z, double t, double mu, double thres, Red red, hipStream_t st, Pub pub = Pub{},
-                     T* Gp = nullptr, unsigned* pcnt = nullptr, unsigned* zf = nullptr);
+                     T* Gp = nullptr, unsigned* pcnt = nullptr, unsigned* zf = nullptr,
+                     const FinHead* head = nullptr);
 // FISTA trial fused into A^T R (same plan condition): G = A^T R, then xc, v_next, y_next and the
 // four trial sums of k_fista_trial (PROX) into red (ec, zf: as launch_fista_trial).
 template <typename T>

@@ -41,10 +41,18 @@ template <int WL> constexpr int atr_pw() { return (WL == 3 || WL == 4) ? 32 : 64
 template <int WL> constexpr int atr_waves() { return (WL == 2 || WL == 4) ? 8 : 4; }
 template <int WL> constexpr int atr_ne() { return atr_pw<WL>() / 16; }
 
-template <typename T, int NT, int PF, int WL, bool NTL>
-__device__ inline int64_t atr_panel(const T* __restrict__ A, const T* __restrict__ R, int64_t m,
+// head (round 8, k_atr_prox's finalize head): a callable every thread of the workgroup runs once
+// the ring's first PF A loads are in flight and before any load of R (it produces R and holds
+// workgroup barriers); false from it: the panel is abandoned and -1 returned.
+// (R is written by the head, so only the plain form declares it __restrict__.)
+template <typename T, bool HEAD> struct AtrRPtr { typedef const T* __restrict__ type; };
+template <typename T> struct AtrRPtr<T, true> { typedef const T* type; };
+template <typename T, int NT, int PF, int WL, bool NTL, typename HeadFn = std::nullptr_t>
+__device__ inline int64_t atr_panel(const T* __restrict__ A,
+                                    typename AtrRPtr<T, !std::is_same<HeadFn, std::nullptr_t>::value>::type R, int64_t m,
                                     int64_t n, int S, typename MF<T>::acc_t (&acc)[4][NT],
-                                    int64_t pbx, int64_t pby, int keep_mib) {
+                                    int64_t pbx, int64_t pby, int keep_mib, HeadFn head = nullptr) {
+  constexpr bool HEAD = !std::is_same<HeadFn, std::nullptr_t>::value;
   typedef MF<T> M;
   typedef typename M::acc_t C;
   constexpr int L = 16 * NT;
@@ -113,9 +121,25 @@ __device__ inline int64_t atr_panel(const T* __restrict__ A, const T* __restrict
       for (int nt = 0; nt < NT; ++nt) acc[e][nt] = M::mma(a[p][e], rb[p][nt], acc[e][nt]);
   };
   GLX_CLK(1);
-  if (nst > 0) {
+  if constexpr (HEAD) {
+    if (nst > 0) {
 #pragma unroll
-    for (int p = 0; p < PF; ++p) ld(p, p);
+      for (int p = 0; p < PF; ++p)
+        lda(ap + (p < nst ? p : nst - 1) * 4 * n, a[p], std::integral_constant<bool, NTL>{});
+    }
+    if (!head()) return -1;
+    if (nst > 0) {
+#pragma unroll
+      for (int p = 0; p < PF; ++p)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) rb[p][nt] = rp[(p < nst ? p : nst - 1) * 4 * L + nt * 16];
+    }
+  }
+  if (nst > 0) {
+    if constexpr (!HEAD) {
+#pragma unroll
+      for (int p = 0; p < PF; ++p) ld(p, p);
+    }
     // Trip bounds as wave-uniform 32-bit scalars (readfirstlane): round 3's fused condition
     // `s0 + PF <= nst && (keep == 0 || s0 + 2 PF <= kt)` compiled into an exec-masked loop with
     // an s_nop per MFMA group, and k_atr_prox ran 180 us against round 2's 168 us on one box
@@ -290,20 +314,92 @@ __global__ __launch_bounds__(atr_waves<WL>() * 64) void k_atr_mfma(const T* __re
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Round 8: the residual finalize at the head of k_atr_prox (FinHead, glx_internal.h): the launch's
+// panel workgroups walk the finalize's 256-thread blocks (block w, w + nw, ...: fin_block_elems
+// and grid_reduce's parts_only form, so every residual and every partial is the separate kernel's
+// bit for bit) while their ring's first A loads are in flight. Opt-in (GLX_FIN_HEAD=1): at NS the
+// four blocks a workgroup walks in series, 19 loads per thread each, and the hand-off cost 20 us
+// where k_finalize_residual costs 13 ("Round 8").
+// Hand-off (MI355X_MICROARCH.md, visibility "Valid forms"): write-through (sc1) stores of R and
+// the partials, vmcnt(0), a workgroup barrier, one agent-scope add per workgroup on the sharded
+// ticket; then one lane polls the final counter with sc1 loads (s_sleep between polls, bounded by
+// s_memrealtime), runs ONE agent-scope acquire (it invalidates the CU's L1; the launch's
+// workgroups are not held to one per CU, so sc1 loads alone match no row of that table), waits
+// for it, and the workgroup passes a barrier before its first plain load of R. Called by every
+// thread of every workgroup of the launch, the publisher included (w < 0: no share, but it
+// arrives and waits, because it reduces the partials). False: the wait ran out (the launch's
+// workgroups were not all resident); *abort is set and the caller stores nothing.
+// The counters are not reset here: the next launch counts on the other ticket, which workgroup 0
+// of this one zeroes (every user of that one has retired: launches of a stream run in order).
+// ------------------------------------------------------------------------------------------
+constexpr uint64_t kHeadWaitTicks = 100000000ull;   // s_memrealtime runs at 100 MHz: one second
+__device__ inline bool fin_head_run(const FinHead& h, int64_t w, int64_t nw) {
+  __shared__ int head_ok;
+  if (blockIdx.x == 0 && threadIdx.x <= kTicketShards && h.ticket_next != nullptr)
+    __hip_atomic_store(h.ticket_next + threadIdx.x * kTicketStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int64_t nvb = h.nvb;   // launch_finalize_residual's grid (finalize_blocks)
+  if (w >= 0 && w < nvb) {
+    Red rd{h.part, nullptr, nullptr};
+    rd.parts_only = 1;
+    const FinSrc<double> f{h.P, h.B, {h.R0, h.R1, nullptr}, h.cx, h.ml, h.cn, h.S, h.S0, h.chain};
+    const double cm = h.cx != nullptr ? pending_max(h.cmax, h.cmax_parts, h.cmax_np, h.cmax_nv) : 0.0;
+    for (int64_t vb = w; vb < nvb; vb += nw) {
+      double v[4] = {0.0, 0.0, 0.0, 0.0};
+      double cxv[kCountAhead];
+      fin_block_elems<double, 2, 1, true>(f, vb, nvb, true, false, cxv, v);
+      if (h.cx != nullptr) v[3] = count_above(h.cx, h.cn, cxv, vb * 256 + threadIdx.x, nvb * 256, cm);
+      grid_reduce<4, 0u, 4, true>(v, rd, (int)vb);
+      __syncthreads();   // grid_reduce's LDS row is rewritten by the next block
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned ng = gridDim.x;
+    const unsigned sh = blockIdx.x & (kTicketShards - 1);
+    const unsigned nsh = ng < (unsigned)kTicketShards ? ng : (unsigned)kTicketShards;
+    const unsigned cnt = (ng - sh + kTicketShards - 1) / kTicketShards;
+    const unsigned prev = __hip_atomic_fetch_add(h.ticket + (1 + sh) * kTicketStride, 1u, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT);
+    if (prev == cnt - 1) __hip_atomic_fetch_add(h.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    int ok = 1;
+    while (__hip_atomic_load(h.ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != nsh) {
+      __builtin_amdgcn_s_sleep(2);
+      if (__builtin_amdgcn_s_memrealtime() - t0 > kHeadWaitTicks) {
+        ok = 0;
+        break;
+      }
+    }
+    if (ok) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
+      __hip_atomic_store(h.abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    head_ok = ok;
+  }
+  __syncthreads();
+  return head_ok != 0;
+}
+
 // ProxGD's line-search trial fused into A^T R (WL 0, one K split): once the block's LDS
 // reduction leaves each wave w the 16 gradient rows e == w of its panel — lane (i, q) holding
 // columns i and 16 + i of 4 rows, exactly the 16-lanes-per-row layout of k_prox_pgd — every
 // wave writes its rows of G and runs the trial on them (prox_pgd_row, the same arithmetic as
 // k_prox_pgd) with x = the thresholded iterate; the six trial sums are reduced over the grid.
-template <typename T, int NT, int PF, bool NTL, bool SPLIT, int WL>
-__global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && sizeof(T) == 8) ? 2 : 1) void k_atr_prox(const T* __restrict__ A, const T* __restrict__ R,
-                                                  T* __restrict__ G, int64_t m, int64_t n,
-                                                  const T* __restrict__ x, T* __restrict__ p,
-                                                  T* __restrict__ pthr, T* __restrict__ z,
-                                                  double t_, double tmu_, double thres_, Red red,
-                                                  Pub pub, int S, T* __restrict__ Gp,
-                                                  unsigned* __restrict__ pcnt,
-                                                  unsigned* __restrict__ zf, int keep_mib) {
+// HEAD (round 8; f64, WL 0, one K split): the launch first runs the residual finalize that produces
+// R (fin_head_run), between its ring's first A loads and its first load of R.
+template <typename T, int NT, int PF, bool NTL, bool SPLIT, int WL, bool HEAD>
+__device__ __forceinline__ void atr_prox_body(const T* __restrict__ A, typename AtrRPtr<T, HEAD>::type R,
+                                              T* __restrict__ G, int64_t m, int64_t n,
+                                              const T* __restrict__ x, T* __restrict__ p,
+                                              T* __restrict__ pthr, T* __restrict__ z,
+                                              double t_, double tmu_, double thres_, const Red& red,
+                                              const Pub& pub, int S, T* __restrict__ Gp,
+                                              unsigned* __restrict__ pcnt,
+                                              unsigned* __restrict__ zf, int keep_mib, const FinHead& fh) {
   // Cancelled by a device-side decision (solver.cpp dc_run): nothing is computed or stored, no
   // counter or ticket is touched. (Testing the flag after the main loop instead measured no
   // faster and would spend a whole pass per cancelled launch.) The decision record still goes
@@ -318,6 +414,10 @@ __global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && size
   // publisher reduce (nparts)
   const int nparts = SPLIT ? (int)(n / 64) + (pub.host ? 1 : 0) : -1;
   constexpr int NW = atr_waves<WL>();
+  if constexpr (HEAD) {   // the publisher reduces the head's partials: it waits for them too
+    static_assert(!SPLIT && WL == 0 && sizeof(T) == 8, "the finalize head: f64, WL 0, one K split");
+    if (pub.host != nullptr && blockIdx.x == 0 && !fin_head_run(fh, -1, 0)) return;
+  }
   if (publisher_first<6, 0x8u, NW>(pub, red, nparts)) return;
   typedef MF<T> M;
   constexpr int L = 16 * NT;
@@ -332,7 +432,14 @@ __global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && size
   // (the fused epilogue took 8-10 us of the kernel at NS and C2, profiles/r4_clk). Loading the
   // iterate rows before the main loop instead of after it measured 4-5 us slower at NS (+18
   // VGPRs live through the ring, profiles/r4_ab2).
-  const int64_t col0 = atr_panel<T, NT, PF, WL, NTL>(A, R, m, n, SPLIT ? S : 1, acc, panel, split, keep_mib);
+  int64_t col0;
+  if constexpr (HEAD) {
+    col0 = atr_panel<T, NT, PF, WL, NTL>(A, R, m, n, 1, acc, panel, split, keep_mib,
+                                         [&]() { return fin_head_run(fh, bid, n / 64); });
+    if (col0 < 0) return;   // the head's wait ran out (uniform over the workgroup)
+  } else {
+    col0 = atr_panel<T, NT, PF, WL, NTL>(A, R, m, n, SPLIT ? S : 1, acc, panel, split, keep_mib);
+  }
   GLX_CLK(4);
   T xa[4][NT];
 #pragma unroll
@@ -395,6 +502,32 @@ __global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && size
     zf_store_panel<atr_pw<WL>()>(msk, zf, n, L, col0);
   }
   GLX_CLK(3);
+}
+
+template <typename T, int NT, int PF, bool NTL, bool SPLIT, int WL>
+__global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && sizeof(T) == 8) ? 2 : 1) void k_atr_prox(const T* __restrict__ A, const T* __restrict__ R,
+                                                  T* __restrict__ G, int64_t m, int64_t n,
+                                                  const T* __restrict__ x, T* __restrict__ p,
+                                                  T* __restrict__ pthr, T* __restrict__ z,
+                                                  double t_, double tmu_, double thres_, Red red,
+                                                  Pub pub, int S, T* __restrict__ Gp,
+                                                  unsigned* __restrict__ pcnt,
+                                                  unsigned* __restrict__ zf, int keep_mib) {
+  atr_prox_body<T, NT, PF, NTL, SPLIT, WL, false>(A, R, G, m, n, x, p, pthr, z, t_, tmu_, thres_, red, pub, S, Gp,
+                                                  pcnt, zf, keep_mib, FinHead{});
+}
+// k_atr_prox with the finalize head (f64, WL 0, one K split). R is what the head writes: not
+// __restrict__, and no load of it is issued before the head's barrier.
+template <int NT, int PF, bool NTL>
+__global__ __launch_bounds__(256, 2) void k_atr_prox_head(const double* __restrict__ A, const double* R,
+                                                  double* __restrict__ G, int64_t m, int64_t n,
+                                                  const double* __restrict__ x, double* __restrict__ p,
+                                                  double* __restrict__ pthr, double* __restrict__ z,
+                                                  double t_, double tmu_, double thres_, Red red,
+                                                  Pub pub, unsigned* __restrict__ zf, int keep_mib,
+                                                  FinHead fh) {
+  atr_prox_body<double, NT, PF, NTL, false, 0, true>(A, R, G, m, n, x, p, pthr, z, t_, tmu_, thres_, red, pub, 1,
+                                                     nullptr, nullptr, zf, keep_mib, fh);
 }
 
 // FISTA's backtracking trial fused into A^T R the same way (WL 0, one K split): each wave runs
@@ -929,9 +1062,18 @@ void launch_atr(const GemmPlan& p, const T* A, const T* R, T* Gp, hipStream_t st
 template <typename T, int NT, int PF, bool NTL, int WL>
 static void atr_prox_go(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, T* pp,
                         T* pthr, T* z, double t, double mu, double thres, Red red, hipStream_t st,
-                        Pub pub, T* Gp, unsigned* pcnt, unsigned* zf) {
+                        Pub pub, T* Gp, unsigned* pcnt, unsigned* zf, const FinHead* head) {
   const dim3 grid((unsigned)(p.n / atr_pw<WL>() * p.atr_S + (pub.host ? 1 : 0)));
   const dim3 block(atr_waves<WL>() * 64);
+  if (head != nullptr) {
+    if constexpr (std::is_same<T, double>::value && WL == 0) {
+      static const size_t hpad = lds_pad(k_atr_prox_head<NT, PF, NTL>, "GLX_ATR_LDS_PAD");
+      glx_launch((k_atr_prox_head<NT, PF, NTL>), grid, block, hpad, st, A, R, G, p.m, p.n, x, pp, pthr, z, t,
+                 t * mu, thres, red, pub, zf, p.atr_keep_mib, *head);
+      return;
+    }
+    throw Error{GLX_E_INVALID, "fused A^T R + trial: the finalize head is built for the f64 four-wave panel"};
+  }
   if (WL != 3 && WL != 4 && p.atr_S > 1) {
     glx_launch((k_atr_prox<T, NT, PF, NTL, true, WL>), grid, block, 0, st, A, R, G, p.m,
                        p.n, x, pp, pthr, z, t, t * mu, thres, red, pub, p.atr_S, Gp, pcnt, zf, p.atr_keep_mib);
@@ -944,13 +1086,25 @@ static void atr_prox_go(const GemmPlan& p, const T* A, const T* R, T* G, const T
 template <typename T>
 void launch_atr_prox(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, T* pp, T* pthr,
                      T* z, double t, double mu, double thres, Red red, hipStream_t st, Pub pub,
-                     T* Gp, unsigned* pcnt, unsigned* zf) {
+                     T* Gp, unsigned* pcnt, unsigned* zf, const FinHead* head) {
   if (p.atr_S > 1 && (Gp == nullptr || pcnt == nullptr))
     throw Error{GLX_E_INVALID, "fused A^T R with K splits needs slab and counter buffers"};
+  FinHead hd;
+  if (head != nullptr) {
+    hd = *head;
+    if (hd.S0 <= 0) hd.S0 = hd.S;   // (as launch_finalize_residual)
+    if (!atr_prox_head_ok(p, hd.S, hd.S0) || red.skip != nullptr)
+      throw Error{GLX_E_INVALID, "fused A^T R + trial: this plan or finalize takes no head"};
+    if (!hd.P || !hd.B || !hd.R1 || (const void*)hd.R1 != (const void*)R || !hd.part || !hd.ticket || !hd.abort ||
+        hd.ticket_next == hd.ticket || (hd.chain == 0 && !hd.R0) || (hd.cx && !hd.cmax && !hd.cmax_parts))
+      throw Error{GLX_E_INVALID, "fused A^T R + trial: bad finalize head"};
+    hd.nvb = finalize_blocks(hd.ml, hd.S, hd.chain ? hd.S0 : 0, hd.cx ? hd.cn : 0);
+    head = &hd;
+  }
   atr_visit<T, true>(p, "fused A^T R + trial", [&](auto i, auto nt) {
     constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
     atr_prox_go<T, decltype(nt)::value, tile.pf, tile.ntl, tile.wl>(p, A, R, G, x, pp, pthr, z, t, mu, thres, red,
-                                                                  st, pub, Gp, pcnt, zf);
+                                                                  st, pub, Gp, pcnt, zf, head);
   });
 }
 
@@ -1145,10 +1299,31 @@ template void launch_atr_fista<float>(const GemmPlan&, const float*, const float
                                       float*, unsigned*, float*, unsigned*);
 template void launch_atr_prox<double>(const GemmPlan&, const double*, const double*, double*,
                                       const double*, double*, double*, double*, double, double,
-                                      double, Red, hipStream_t, Pub, double*, unsigned*, unsigned*);
+                                      double, Red, hipStream_t, Pub, double*, unsigned*, unsigned*,
+                                      const FinHead*);
 template void launch_atr_prox<float>(const GemmPlan&, const float*, const float*, float*,
                                      const float*, float*, float*, float*, double, double, double,
-                                     Red, hipStream_t, Pub, float*, unsigned*, unsigned*);
+                                     Red, hipStream_t, Pub, float*, unsigned*, unsigned*, const FinHead*);
+
+// the head kernel of the plan's tile: workgroups a CU holds at once, and the device's CUs
+void atr_prox_head_capacity(const GemmPlan& p, int* cus, int* per_cu) {
+  *cus = 0;
+  *per_cu = 0;
+  if (!atr_prox_head_ok(p, 1, 1)) return;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+    *cus = 0;
+    return;
+  }
+  atr_visit<double, true>(p, "fused A^T R + trial", [&](auto i, auto nt) {
+    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
+    if constexpr (tile.wl == 0)
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+              per_cu, k_atr_prox_head<decltype(nt)::value, tile.pf, tile.ntl>, 256, 0) != hipSuccess)
+        *per_cu = 0;
+  });
+}
 template void launch_atr<float>(const GemmPlan&, const float*, const float*, float*, hipStream_t);
 
 

@@ -39,50 +39,13 @@ static inline unsigned grid_for(int64_t work, int per_block) {
 // residual finalize: R = sum_s P[s] - B; out[0] = sum R^2, out[1] = count(|c| > 1e-6 *cmax)
 // over a second array c (the candidate iterate, fused here to save a launch); the last block
 // optionally records f = 0.5 out[0] + mu * (*rn) into fh (SGD/GD device-side history).
-//
-// The S slabs of one residual element are split over G adjacent lanes (G = 1, 2, 4 or 8, so a
-// lane takes at most 8 slabs). A lane issues its loads back to back and adds them in slab
-// order; the G partial sums then combine by an xor butterfly, which gives every lane of the
-// group the same bits ((p0 + p1) + (p2 + p3) ...). The order is fixed, so the result is
-// deterministic, and G = 1 is the plain sequential sum. With few rows and a deep split (the
-// per-rank shards of a multi-GPU run: m = 1024, S = 32) this spreads the slab reads over the
-// whole grid instead of leaving them to m*l threads with S-long load chains (22 -> 11.6 us at
-// m = 1024). Splitting further than 8 slabs per lane measured slower (NS: 13.7 -> 17.9 us).
+// The element work and the slab sums over G adjacent lanes are glx_device.h's (fin_block_elems,
+// group_slab_load / group_slab_fold), shared with the head of k_atr_prox.
 // ------------------------------------------------------------------------------------------
-constexpr int kSlabLoads = 8;
 static inline int finalize_groups(int S) {
   int g = 1;
   while (g * kSlabLoads < S) g *= 2;
   return g;
-}
-
-// group_slab_sum in two halves, so a caller can issue the loads of several sources before the
-// first add (round 5: the finalize's two sources, one round trip instead of two)
-template <typename T, int G>
-__device__ inline int group_slab_load(const T* __restrict__ P, int S, int64_t ml, int64_t idx, int sub,
-                                      T (&a)[kSlabLoads]) {
-  const int per = (S + G - 1) / G;
-  const int k0 = sub * per;
-  const int cnt = S - k0 < per ? S - k0 : per;   // <= 0 for an empty trailing lane
-#pragma unroll
-  for (int k = 0; k < kSlabLoads; ++k) a[k] = k < cnt ? P[(int64_t)(k0 + k) * ml + idx] : T(0);
-  return cnt;
-}
-template <typename T, int G>
-__device__ inline T group_slab_fold(const T (&a)[kSlabLoads], int cnt) {
-  T v = a[0];
-#pragma unroll
-  for (int k = 1; k < kSlabLoads; ++k)
-    if (k < cnt) v = v + a[k];
-#pragma unroll
-  for (int off = 1; off < G; off <<= 1) v = v + __shfl_xor(v, off);
-  return v;
-}
-template <typename T, int G>
-__device__ inline T group_slab_sum(const T* __restrict__ P, int S, int64_t ml, int64_t idx, int sub) {
-  T a[kSlabLoads];
-  const int cnt = group_slab_load<T, G>(P, S, ml, idx, sub, a);
-  return group_slab_fold<T, G>(a, cnt);
 }
 
 // Device-controlled ProxGD with a communicator (solver.cpp dc_queue): the trial's residual sums
@@ -112,36 +75,6 @@ __global__ void k_ctl_seed(double* state, int* abort, double s0, double s1, doub
   }
 }
 
-// *cmax, or (cmp != NULL: the trial's sums still pending as Red::parts_only partials, cmnv values
-// per slot) the max of their column 3 over cmnp slots, by every workgroup for itself (all 256
-// threads call this; the result is order-independent)
-__device__ inline double pending_max(const double* cmax, const double* __restrict__ cmp, int cmnp, int cmnv) {
-  if (cmp == nullptr) return *cmax;
-  __shared__ double wmax[4];
-  double mv = -__builtin_inf();
-  for (int i = threadIdx.x; i < cmnp; i += 256) mv = nan_max(mv, cmp[i * cmnv + 3]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mv = nan_max(mv, __shfl_xor(mv, off));
-  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mv;
-  __syncthreads();
-  return nan_max(nan_max(wmax[0], wmax[1]), nan_max(wmax[2], wmax[3]));
-}
-
-// count(|cx| > 1e-6 cm) over this thread's indices tid, tid + stride, ...: the first kCountAhead
-// values already in cxv (loaded ahead), the rest read here
-constexpr int kCountAhead = 2;
-template <typename T>
-__device__ inline double count_above(const T* __restrict__ cx, int64_t cn, const T (&cxv)[kCountAhead],
-                                     int64_t tid, int64_t stride, double cm) {
-  const T thr = (T)1e-6 * (T)cm;
-  double c = 0.0;
-#pragma unroll
-  for (int q = 0; q < kCountAhead; ++q)
-    if (tid + q * stride < cn) c += (tabs(cxv[q]) > thr) ? 1.0 : 0.0;
-  for (int64_t idx = tid + kCountAhead * stride; idx < cn; idx += stride) c += (tabs(cx[idx]) > thr) ? 1.0 : 0.0;
-  return c;
-}
-
 template <typename T, int NSRC, int G>
 __global__ __launch_bounds__(256) void k_finalize_residual(
     const T* __restrict__ P, int S, const T* __restrict__ B, T* __restrict__ R0, T* __restrict__ R1,
@@ -161,63 +94,11 @@ __global__ __launch_bounds__(256) void k_finalize_residual(
   const bool live = (gate == nullptr) || (*gate == epoch);
   if (!live && gate_mode == 0) return;  // uniform over the grid: nobody touches the ticket
   double v[4] = {0.0, 0.0, 0.0, 0.0};
-  T* rs[3] = {R0, R1, R2};
-  const int sub = threadIdx.x % G;
   const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * 256;
-  // the count's first kCountAhead values are loaded before the slab loads (their latencies
-  // overlap); the threshold (max |cx|) is known only later
+  const FinSrc<T> f{P, B, {R0, R1, R2}, cx, ml, cn, S, S0, chain};   // (the launcher's P0 is P)
   T cxv[kCountAhead];
-#pragma unroll
-  for (int q = 0; q < kCountAhead; ++q)
-    cxv[q] = (cx != nullptr && tid + q * stride < cn) ? cx[tid + q * stride] : T(0);
-  // residual elements: G lanes per element; the lanes of a group share idx, so they enter and
-  // leave the loop together and the butterfly only reads active partners
-  for (int64_t idx = tid / G; idx < ml; idx += stride / G) {
-    const T bv = B[idx];
-    if (NSRC == 2 && chain) {   // split-candidate: R0 = (A p_thr - b) + A e (always live)
-      // chain 2 (round 6, the fused A e pass): the slabs behind P0 are A p, so R0 = A p - b and
-      // R1 = A p_thr - b = R0 - A e
-      T a1[kSlabLoads], a0[kSlabLoads];
-      const int c1 = group_slab_load<T, G>(P + (int64_t)S0 * ml, S, ml, idx, sub, a1);
-      const int c0 = group_slab_load<T, G>(P0, S0, ml, idx, sub, a0);
-      T r1, r0;
-      if (chain == 2) {
-        r0 = group_slab_fold<T, G>(a1, c1) - bv;
-        r1 = r0 - group_slab_fold<T, G>(a0, c0);
-      } else {
-        r1 = group_slab_fold<T, G>(a1, c1) - bv;
-        r0 = r1 + group_slab_fold<T, G>(a0, c0);
-      }
-      if (skipped) return;
-      if (sub == 1 % G) rs[1][idx] = r1;
-      if (R0 != nullptr && sub == 0) rs[0][idx] = r0;
-      if (sub == 0) {
-        v[0] += (double)(r0 * r0);
-        v[1] += (double)(r1 * r1);
-      }
-      continue;
-    }
-    T a[NSRC][kSlabLoads];   // every source's slab loads issued before the first add
-    int cs[NSRC];
-    if (live) {
-#pragma unroll
-      for (int sr = 0; sr < NSRC; ++sr)
-        cs[sr] = group_slab_load<T, G>(P + (int64_t)sr * S * ml, S, ml, idx, sub, a[sr]);
-    }
-#pragma unroll
-    for (int sr = 0; sr < NSRC; ++sr) {
-      T r;
-      if (live) {
-        r = group_slab_fold<T, G>(a[sr], cs[sr]) - bv;
-        if (skipped) return;
-        if (sub == sr % G) rs[sr][idx] = r;
-      } else {
-        r = rs[sr][idx];
-      }
-      if (sub == 0) v[sr] += (double)(r * r);
-    }
-  }
+  if (!fin_block_elems<T, NSRC, G, false>(f, blockIdx.x, gridDim.x, live, skipped, cxv, v)) return;
   if (skipped) return;   // (threads without a residual element; uniform over the grid)
   if (cx != nullptr) v[3] = count_above(cx, cn, cxv, tid, stride, pending_max(cmax, cmp, cmnp, cmnv));
   const bool last = grid_reduce<4, 0u>(v, red);

@@ -303,6 +303,11 @@ bool ax_egat_ok(const GemmPlan& p, int esize) {
 }
 bool ax_derive_ok(const GemmPlan& p, int esize) { return esize == 8 && p.ax[1] == ax_tile(51328) && p.l == 32 && p.n % 16 == 0; }
 bool atr_prox_ok(const GemmPlan& p) { return fuses(EnvInt{"GLX_ATR_FUSE_SPLIT"}, p); }
+// the finalize head of the fused trial (kernels_atr.hip): built for the f64 four-wave 64-column
+// panel without K splits, one lane per residual element (at most kSlabLoads = 8 slabs a source)
+bool atr_prox_head_ok(const GemmPlan& p, int S, int S0) {
+  return atr_prox_ok(p) && p.esize == 8 && p.atr->wl == 0 && p.atr_S == 1 && S >= 1 && S <= 8 && S0 >= 0 && S0 <= 8;
+}
 int atr_prox_slots(const GemmPlan& p, bool pub) {
   return (int)(p.n / (p.atr->panel ? p.atr->panel : 64)) + (pub ? 1 : 0);
 }

@@ -331,11 +331,28 @@ SessionMode session_mode(const glx_problem& P, const glx_opts& O) {
   // (its publisher's reduction stretched the 33 us fused kernel by ~4 us); that opt-in form
   // (GLX_DEFER_RED=2) was removed in round 6.
   md.defer = !md.comm && md.dc_window == 0 && proxgd && md.spin_readback && md.attach_ok && !k.defer_red.is("0");
+  // Round 8: on that path the finalize of the speculative first trial runs at the head of the
+  // k_atr_prox queued behind it (launch_atr_prox's head) where the fused trial is the f64 four-wave
+  // panel without K splits; later trials, FProxGD, a communicator, device control and fh recording
+  // keep k_finalize_residual. The device's capacity is checked by the session (fin_head_fits).
+  // Opt-in (GLX_FIN_HEAD=1; unset or 0: the separate kernel everywhere): at NS the head measured
+  // level with the separate kernel, not faster — whole solves 2 495-2 557 it/s against the parent's
+  // 2 498-2 560, 200-step windows 2 537-2 548 against 2 544-2 555, three interleaved rounds on one
+  // box (profiles/r8_finhead/). A workgroup walks its four blocks of 19 loads per thread one after
+  // the other, then pays the write-through drain, the arrival, the poll and the L1 invalidate:
+  // about what the 12.9 us kernel and its boundary cost ("Round 8").
+  md.fin_head = md.defer && f64 && md.fused_ok && !md.unfused_spec && a.line_search() &&
+                atr_prox_head_ok(plan, 1, 1) && k.fin_head.is("1");
   // SGD / GD with l = 1: the descent pass reads A once (kernels_gemv.hip); GLX_GEMV_FUSED=0
   // selects the two-pass path (A @ [x | thr(x)], then A^T r)
   if ((P.method == GLX_SGD || P.method == GLX_GD) && !k.gemv_fused.is("0"))
     md.gemv_blocks = gemv_fused_blocks(md.esize, P.m, P.n, P.l);
   return md;
+}
+
+// n / 64 panel workgroups and the publisher against the workgroups the device holds at once
+bool fin_head_fits(int64_t n, int cus, int per_cu) {
+  return cus > 0 && per_cu > 0 && n / 64 + 1 <= (int64_t)cus * per_cu;
 }
 
 // the kernels this session actually launches (bench.py re-derived the plan)

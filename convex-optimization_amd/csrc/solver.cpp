@@ -130,6 +130,7 @@ class SessionBase {
   virtual void progress(int64_t out[4]) const = 0;
   virtual void trace(double* sp_after, int64_t cap, int64_t* n, int64_t phase_info[6]) const = 0;
   virtual std::string describe() const = 0;
+  virtual std::string fin_form() const = 0;
   virtual int64_t split_trace(double* out, int64_t cap) const = 0;
 };
 
@@ -240,6 +241,18 @@ class Session : public SessionBase {
       std::memset(dc_ring_, 0, sizeof(double) * kCtlRec * kCtlMaxBatch);   // tags start at 1
       GLX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&dc_ring_dev_), dc_ring_, 0));
     }
+    if (md_.fin_head) {   // decided once: every workgroup of the head launch must be resident
+      int cus = 0, per_cu = 0;
+      atr_prox_head_capacity(md_.plan, &cus, &per_cu);
+      fin_head_ = fin_head_fits(n_, cus, per_cu);
+    }
+    if (fin_head_) {
+      GLX_HIP(hipMalloc(reinterpret_cast<void**>(&htick_), 2 * kTicketBytes));
+      GLX_HIP(hipMemsetAsync(htick_, 0, 2 * kTicketBytes, st_));
+      GLX_HIP(hipHostMalloc(reinterpret_cast<void**>(&habort_), 64, hipHostMallocMapped | hipHostMallocCoherent));
+      *habort_ = 0;
+      GLX_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&habort_dev_), habort_, 0));
+    }
     GLX_HIP(hipMemsetAsync(ticket_, 0, kTicketBytes, st_));
     GLX_HIP(hipMemsetAsync(pcnt_, 0, sizeof(unsigned) * (P.n / 64 + 64), st_));
     GLX_HIP(hipMemsetAsync(flag_, 0, 256, st_));
@@ -264,6 +277,8 @@ class Session : public SessionBase {
   ~Session() override {
     if (hs_) (void)hipHostFree(hs_);
     if (dc_ring_) (void)hipHostFree(dc_ring_);
+    if (htick_) (void)hipFree(htick_);
+    if (habort_) (void)hipHostFree(habort_);
     if (rb_event_) (void)hipEventDestroy(rb_event_);
     for (auto& v : ev_)
       for (auto& p : v) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -377,6 +392,9 @@ class Session : public SessionBase {
   }
 
   std::string describe() const override { return describe_mode(md_); }
+  // where the speculative trial's residual finalize runs: at the head of k_atr_prox, or as
+  // k_finalize_residual (every other finalize of the session is that kernel either way)
+  std::string fin_form() const override { return fin_head_ ? "fin=head" : "fin=kernel"; }
 
   void progress(int64_t out[4]) const override {
     out[0] = prog_k_.load(std::memory_order_relaxed);
@@ -534,6 +552,29 @@ class Session : public SessionBase {
       flush_fin_pending();
       rd.part = fpart_;
       rd.parts_only = 1;
+    }
+    const int S0 = gat ? gs_of(qeg_) : 0;
+    if (head_next_ && dfin && fin_head_ && nsrc == 2 && atr_prox_head_ok(md_.plan, S, S0 > 0 ? S0 : S)) {
+      // round 8: the k_atr_prox queued right behind this call runs the finalize at its head
+      if constexpr (std::is_same<T, double>::value) {
+        FinHead h;
+        h.P = Pp_; h.B = B_; h.R0 = rsc[0]; h.R1 = rsc[1];
+        h.cx = cx; h.cn = cx ? nl_ : 0;
+        h.cmax = cmax;
+        h.cmax_parts = dmax ? ptr_.part : nullptr;
+        h.cmax_np = dmax ? ptr_.np : 0;
+        h.cmax_nv = dmax ? ptr_.nv : 6;
+        h.part = fpart_;
+        h.ticket = htick_ + hflip_ * (kTicketBytes / sizeof(unsigned));
+        h.ticket_next = htick_ + (hflip_ ^ 1) * (kTicketBytes / sizeof(unsigned));
+        h.abort = habort_dev_;
+        h.ml = ml_; h.S = S; h.S0 = S0; h.chain = chain ? (qeg_ ? 2 : 1) : 0;
+        hpend_ = h;
+        hpend_on_ = true;
+        hflip_ ^= 1;
+        pfin_ = Pend{fpart_, finalize_blocks(ml_, S, S0, cx ? nl_ : 0), 4, 0u, scal_ + slot};
+        return;
+      }
     }
     launch_finalize_residual<T>(Pp_, S, B_, nsrc, rsc,
                                 ml_, nullptr, 0, 1, cx,
@@ -780,6 +821,9 @@ class Session : public SessionBase {
     while (*hs != seq) {
       __builtin_ia32_pause();
       if ((++spins & 0xFFFFF) == 0) {
+        if (habort_ != nullptr && *static_cast<volatile int*>(habort_) != 0)
+          throw Error{GLX_E_HIP, "k_atr_prox: the finalize head's barrier timed out (the launch's workgroups "
+                                 "were not all resident); without GLX_FIN_HEAD=1 the separate finalize kernel runs"};
         if (spins == 0x100000) t0 = std::chrono::steady_clock::now();
         else stalled_wait(t0, [&] { return *hs == seq; }, "scalar readback");
       }
@@ -981,9 +1025,12 @@ class Session : public SessionBase {
         const bool axp = spec && md_.fused_ok && comm_ != nullptr && late_pub && md_.attach_ok &&
                          md_.spec_ax_pub && ax_pub_ok(md_.plan, md_.smode == 1 ? 1 : nsrc);
         carry_ = late_pub;
+        // (round 8) the speculative kernel below reads R_[rpt]: it can run this finalize at its head
+        head_next_ = spec && md_.fused_ok && late_pub && comm_ == nullptr && !md_.unfused_spec;
         residuals(nsrc, xs, rs, S_RT, X_[ip_], scal_ + S_TR + 3, nullptr, 0.0,
                   late_pub ? nullptr : &seq, merge ? tail(nset(gset_)) : nullptr, skip_ax, axp, md_.emode);
         carry_ = false;
+        head_next_ = false;
         std::pair<const T*, int> sg;
         if (spec && md_.fused_ok) {
           // the next iteration's A^T r and first trial at the candidate p_thr, into the other
@@ -1481,6 +1528,10 @@ class Session : public SessionBase {
   void atr_prox(const T* r, int set, const T* x, int op, int opt, int oz, double t, int tail_n = 0,
                 unsigned* pub_seq = nullptr, Pub* pub_out = nullptr) {
     const double* extra = tail_n ? tail(set) : nullptr;
+    const bool hd = hpend_on_;   // the finalize that produces r rides this launch (residuals())
+    hpend_on_ = false;
+    if (hd && (comm_ || md_.unfused_spec || (const void*)hpend_.R1 != (const void*)r))
+      throw Error{GLX_E_STATE, "finalize head: the pending finalize does not belong to this A^T r"};
     if (comm_ || md_.unfused_spec) {
       const std::pair<const T*, int> g = gradient(r, set, tail_n);
       Pub pb;
@@ -1511,7 +1562,7 @@ class Session : public SessionBase {
       rd.parts_only = 1;
     }
     launch_atr_prox<T>(md_.plan, A_, r, Gs_[set], x, X_[op], X_[opt], X_[oz], t, mu_, O_.thres,
-                       rd, st_, pb, Gps_[set], pcnt_, ezf());
+                       rd, st_, pb, Gps_[set], pcnt_, ezf(), hd ? &hpend_ : nullptr);
     check_launch();
     ptr_ = dtr ? Pend{tpart_[tb_], atr_prox_slots(md_.plan, pb.host != nullptr), 6, 0x8u, scal_ + S_TR} : Pend{};
     prof_end(1, e0);
@@ -2131,6 +2182,16 @@ class Session : public SessionBase {
   int tb_ = 0;
   Pend ptr_, pfin_;
   bool carry_ = false;         // while queuing: the next packet rides the speculative kernel
+  // Round 8, the finalize at the head of k_atr_prox (md_.fin_head and the device's capacity):
+  // residuals() hands its finalize to the speculative kernel queued right behind it
+  bool fin_head_ = false;
+  bool head_next_ = false;     // while queuing: that kernel follows this residuals() call
+  bool hpend_on_ = false;      // hpend_ waits for the next launch_atr_prox
+  FinHead hpend_;
+  unsigned* htick_ = nullptr;  // two arrival tickets (kTicketBytes each), used alternately
+  int hflip_ = 0;
+  int* habort_ = nullptr;      // host-mapped: set by a workgroup whose head wait ran out
+  int* habort_dev_ = nullptr;
   int tr_slot_ = S_TR;         // the packet slots of the current trial's sums
   T* At_ = nullptr;            // A^T (split-candidate gather form)
   void* glists_ = nullptr;     // the gather's per-column index lists of e
@@ -2461,6 +2522,15 @@ int glx_kernel_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_
   });
 }
 
+int glx_session_fin_form(glx_session* s, char* out, size_t cap) {
+  return guarded([&] {
+    if (!s || !out || cap == 0) throw Error{GLX_E_INVALID, "null argument"};
+    std::snprintf(out, cap, "%s", s->impl->fin_form().c_str());
+  });
+}
+
+int glx_fin_head_fits(int64_t n, int cus, int per_cu) { return fin_head_fits(n, cus, per_cu) ? 1 : 0; }
+
 int glx_plan_describe(int dtype, int64_t m, int64_t n, int64_t l, char* out, size_t cap) {
   return guarded([&] {
     if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "bad dtype"};
@@ -2684,6 +2754,69 @@ int glx_trial_proxgd(int dtype, int64_t m, int64_t n, int64_t l, const void* A, 
     if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
     else go(static_cast<float*>(nullptr));
     check_launch();
+  });
+}
+
+int glx_fin_atr_prox(int64_t m, int64_t n, int64_t l, const void* A, const void* P, int S, int S0,
+                     int chain, const void* B, void* R0, void* R1, const void* cx, const double* cmax,
+                     const double* cmax_parts, int cmax_np, double* fin_parts, int* fin_blocks,
+                     void* G, const void* x, double t, double mu, double thres, int emode, void* p,
+                     void* pthr, void* z, void* sums_dev, uint32_t* zf, int head, void* head_ws,
+                     void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GemmPlan plan;
+    KernelWs k = kernel_setup(GLX_F64, m, n, l, ws, wsb, 0, st, &plan, true);
+    plan.atr = atr_tile(8);   // the f64 four-wave panel, one K split
+    plan.atr_S = 1;
+    if (chain < 0 || chain > 2 || S < 1 || S > 8 || (chain != 0 && (S0 < 1 || S0 > 8)))
+      throw Error{GLX_E_INVALID, "chain must be 0..2, S (and with a chain S0) 1..8"};
+    if (!atr_prox_head_ok(plan, S, chain ? S0 : S))
+      throw Error{GLX_E_INVALID, "needs n % 64 == 0, m % 4 == 0 and l in {16, 32}"};
+    if (!A || !P || !B || !R1 || (chain == 0 && !R0) || !fin_parts || !G || !x || !p || !pthr || !z || !sums_dev ||
+        !head_ws || (cx && !cmax && !cmax_parts))
+      throw Error{GLX_E_INVALID, "null argument"};
+    if ((emode != 0) != (zf != nullptr)) throw Error{GLX_E_INVALID, "emode and zf go together"};
+    const int64_t ml = m * l, nl = n * l;
+    const int nvb = finalize_blocks(ml, S, chain ? S0 : 0, cx ? nl : 0);
+    if (fin_blocks) *fin_blocks = nvb;
+    Red red{k.part, k.ticket, static_cast<double*>(sums_dev)};
+    const double* Pd = static_cast<const double*>(P);
+    if (head == 0) {
+      Red rf{fin_parts, nullptr, nullptr};
+      rf.parts_only = 1;
+      double* rs[3] = {static_cast<double*>(R0), static_cast<double*>(R1), nullptr};
+      launch_finalize_residual<double>(Pd, S, (const double*)B, 2, rs, ml, nullptr, 0, 1, (const double*)cx,
+                                       cx ? nl : 0, cmax, nullptr, 0.0, nullptr, rf, st, nullptr, nullptr, 0,
+                                       chain, chain ? S0 : 0, Ctl{}, cmax_parts, cmax_np, 6);
+      check_launch();
+      launch_atr_prox<double>(plan, (const double*)A, (const double*)R1, (double*)G, (const double*)x,
+                              (double*)p, (double*)pthr, (double*)z, t, mu, thres, red, st, Pub{}, nullptr,
+                              k.pcnt, zf);
+      check_launch();
+      return;
+    }
+    int cus = 0, per_cu = 0;
+    atr_prox_head_capacity(plan, &cus, &per_cu);
+    if (!fin_head_fits(n, cus, per_cu))
+      throw Error{GLX_E_INVALID, "the finalize head: the device cannot hold the launch's workgroups at once"};
+    GLX_HIP(hipMemsetAsync(head_ws, 0, 8192, st));
+    FinHead h;
+    h.P = Pd; h.B = (const double*)B; h.R0 = (double*)R0; h.R1 = (double*)R1;
+    h.cx = (const double*)cx; h.cn = cx ? nl : 0;
+    h.cmax = cmax; h.cmax_parts = cmax_parts; h.cmax_np = cmax_np; h.cmax_nv = 6;
+    h.part = fin_parts;
+    h.ticket = static_cast<unsigned*>(head_ws);
+    h.ticket_next = h.ticket + kTicketBytes / sizeof(unsigned);
+    h.abort = reinterpret_cast<int*>(static_cast<char*>(head_ws) + 2 * kTicketBytes);
+    h.ml = ml; h.S = S; h.S0 = chain ? S0 : 0; h.chain = chain;
+    launch_atr_prox<double>(plan, (const double*)A, (const double*)R1, (double*)G, (const double*)x, (double*)p,
+                            (double*)pthr, (double*)z, t, mu, thres, red, st, Pub{}, nullptr, k.pcnt, zf, &h);
+    check_launch();
+    int aborted = 0;
+    GLX_HIP(hipMemcpyAsync(&aborted, h.abort, sizeof(int), hipMemcpyDeviceToHost, st));
+    GLX_HIP(hipStreamSynchronize(st));
+    if (aborted != 0) throw Error{GLX_E_HIP, "k_atr_prox: the finalize head's barrier timed out"};
   });
 }
 

@@ -133,6 +133,13 @@ _SIGS = {
                                  c_void_p, c_double, c_double, c_double, c_int, c_int, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),
+    "glx_fin_atr_prox": (c_int, [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                 POINTER(c_int), c_void_p, c_void_p, c_double, c_double, c_double, c_int,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]),
+    "glx_fin_head_fits": (c_int, [c_int64, c_int, c_int]),
+    "glx_session_fin_form": (c_int, [c_void_p, c_char_p, c_size_t]),
     "glx_trial_fista": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_double, c_double, c_double, c_double,
                                 c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p,

@@ -227,6 +227,42 @@ def trial_proxgd(x: torch.Tensor, G: Optional[torch.Tensor], t: float, mu: float
     return {"G": G, "p": p, "pthr": pthr, "z": z, "sums": sums, "zf": zf}
 
 
+def fin_atr_prox(A: torch.Tensor, P: torch.Tensor, B: torch.Tensor, x: torch.Tensor, t: float, mu: float,
+                 S: int, S0: int = 0, chain: int = 0, cx: Optional[torch.Tensor] = None,
+                 cmax: Optional[torch.Tensor] = None, cmax_parts: Optional[torch.Tensor] = None,
+                 thres: float = 1e-3, emode: bool = False, head: bool = True
+                 ) -> Dict[str, Optional[torch.Tensor]]:
+    """A residual finalize and the fused A^T R + ProxGD trial behind it (glx_fin_atr_prox; float64).
+    P: the slabs ((S0 + S, m, l) with a chain, else (2 S, m, l): source 0 then source 1). head=False:
+    k_finalize_residual then k_atr_prox; head=True: one launch with the finalize at the head of
+    k_atr_prox. cx: the count's array (n, l) with cmax (1 float64) or cmax_parts ((np, 6) float64
+    trial partials, the max of column 3). Returns a dict with R0, R1, fin_parts ((blocks, 4)), G, p,
+    pthr, z, sums (6) and zf."""
+    m, n = A.shape
+    l = x.shape[1]
+    if A.dtype != torch.float64:
+        raise ValueError("float64 required")
+    dev = A.device
+    nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)  # noqa: E731
+    R0, R1 = nan(m, l), nan(m, l)
+    G, p, pthr, z = nan(n, l), nan(n, l), nan(n, l), nan(n, l)
+    parts = nan(1024, 4)
+    sums = nan(6)
+    zf = _zf_arg(None, bool(emode), n, dev)
+    hws = torch.zeros(8192, dtype=torch.uint8, device=dev)
+    ws = _trial_ws(_lib.GLX_F64, m, n, l, dev)
+    nb = ctypes.c_int(0)
+    check(lib().glx_fin_atr_prox(m, n, l, A.data_ptr(), P.data_ptr(), int(S), int(S0), int(chain),
+                                 B.data_ptr(), R0.data_ptr(), R1.data_ptr(), _ptr(cx), _ptr(cmax),
+                                 _ptr(cmax_parts), 0 if cmax_parts is None else int(cmax_parts.shape[0]),
+                                 parts.data_ptr(), ctypes.byref(nb), G.data_ptr(), x.data_ptr(), float(t),
+                                 float(mu), float(thres), 1 if emode else 0, p.data_ptr(), pthr.data_ptr(),
+                                 z.data_ptr(), sums.data_ptr(), _ptr(zf), 1 if head else 0, hws.data_ptr(),
+                                 ws.data_ptr(), ws.numel(), _stream(dev)))
+    return {"R0": R0, "R1": R1, "fin_parts": parts[:nb.value], "G": G, "p": p, "pthr": pthr, "z": z,
+            "sums": sums, "zf": zf}
+
+
 def trial_fista(y: Optional[torch.Tensor], G: Optional[torch.Tensor], xk: torch.Tensor, t: float,
                 mu: float, theta: float, theta_next: float, thres: float = 1e-3,
                 delta: float = 0.0, form: int = 0, prox: bool = True, split: bool = False,

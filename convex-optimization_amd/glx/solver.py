@@ -252,6 +252,14 @@ class Session:
         check(lib().glx_session_describe(self.h, buf, len(buf)))
         return buf.value.decode()
 
+    def fin_form(self) -> str:
+        """"fin=head" where the speculative trial's residual finalize runs at the head of
+        k_atr_prox, "fin=kernel" where it is k_finalize_residual (glx_session_fin_form; describe()
+        itself is unchanged, its recorded strings are compared whole)."""
+        buf = ctypes.create_string_buffer(64)
+        check(lib().glx_session_fin_form(self.h, buf, len(buf)))
+        return buf.value.decode()
+
     def split_trace(self) -> np.ndarray:
         """Per trial batch: ProxGD's flagged rows of e, FProxGD's nnz(e_c) of a gathered batch
         (row form: flagged rows) or -1 for a dense batch (glx_session_split_trace)."""

@@ -311,6 +311,33 @@ int glx_trial_proxgd(int dtype, int64_t m, int64_t n, int64_t l, const void* A, 
                      void* G, const void* x, double t, double mu, double thres, int form, int emode,
                      void* p, void* pthr, void* z, void* sums_dev, uint32_t* zf, void* workspace,
                      size_t workspace_bytes, void* stream);
+/* A residual finalize and the fused A^T R + ProxGD trial behind it (fp64; n % 64 == 0, m % 4 == 0,
+ * l in {16, 32}; the four-wave 64-column panel without K splits whatever the shape's plan):
+ *   the finalize: R0 = sum of source 0's slabs - B, R1 = the same of source 1 (chain 0: S slabs a
+ *     source, source 1 behind source 0), or the chained forms of the split-candidate trial (S0
+ *     slabs of A e, then S slabs: chain 1 R1 = slabs - B, R0 = R1 + A e; chain 2 R0 = slabs - B,
+ *     R1 = R0 - A e; R0 may be NULL with a chain); fin_parts receives its four sums per
+ *     256-thread block (sum R0^2, sum R1^2, 0, count(|cx| > 1e-6 max) with cx of n * l values or
+ *     NULL; the max is *cmax or, cmax_parts != NULL, the max of column 3 of cmax_np partials of 6
+ *     values), *fin_blocks their number (at most 1024);
+ *   the trial: glx_trial_proxgd's form 1 with R = R1 (emode with zf).
+ * head = 0: k_finalize_residual, then k_atr_prox. head = 1: one launch, the finalize at the head of
+ * k_atr_prox; every bit equals head = 0. GLX_E_INVALID where the device cannot hold the launch's
+ * n / 64 workgroups at once, GLX_E_HIP if the head's barrier times out. head_ws: 8192 bytes of
+ * device memory (cleared here). workspace: glx_trial_workspace_bytes. Returns after the launch has
+ * finished (it reads the barrier's abort word back). */
+int glx_fin_atr_prox(int64_t m, int64_t n, int64_t l, const void* A, const void* P, int S, int S0,
+                     int chain, const void* B, void* R0, void* R1, const void* cx, const double* cmax,
+                     const double* cmax_parts, int cmax_np, double* fin_parts, int* fin_blocks,
+                     void* G, const void* x, double t, double mu, double thres, int emode, void* p,
+                     void* pthr, void* z, void* sums_dev, uint32_t* zf, int head, void* head_ws,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* The finalize head's co-residency guard: 1 where n / 64 + 1 workgroups fit cus * per_cu. */
+int glx_fin_head_fits(int64_t n, int cus, int per_cu);
+/* "fin=head" where this session runs the speculative trial's residual finalize at the head of
+ * k_atr_prox (single GPU, host control, deferred reductions, the f64 four-wave panel, and a device
+ * that holds all its workgroups at once) and GLX_FIN_HEAD=1 asks for it, else "fin=kernel". */
+int glx_session_fin_form(glx_session* s, char* out, size_t cap);
 /* FProxGD's / FGD's trial with the next combine (gl_FProxGD_primal.py:92-102, 136-145):
  * xc = prox_{t mu}(y - t G) (prox = 1) or y - t G (prox = 0, FGD),
  * vnext = thr(xk) + (xc - thr(xk)) / theta, ynext = (1 - theta_next) thr(xc) + theta_next vnext.
