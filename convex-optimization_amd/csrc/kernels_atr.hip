@@ -615,180 +615,31 @@ __global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && size
   }
 }
 
-// Dual ADMM's row step on the panel layout an A^T R epilogue holds (gl_ADMM_dual.py:64-67): wave
-// w < NE owns the 16 rows e == w of the panel at col0, lane (i, q) holding columns i (and 16 + i)
-// of 4 of them: xa = those values of the iterate, gs of g. Runs admm_dual_row (the arithmetic of
-// k_admm_dual, kernels_admm.hip), hands the two sums [sum_i ||x+_i||, max |x+|] to grid_reduce
-// and then stores G (when non-null), u+, x+ and r, as k_atr_prox orders them. Called by every
-// thread of the workgroup (waves past NE reduce identities). Shared by k_atr_admm and
-// k_admm_dual_panel, so the fused and the unfused form write the same bits, sums included.
-template <typename T, int NT, int WL>
-__device__ inline void admm_panel_rows(const T (&xa)[4][NT], const T (&gs)[4][NT], int64_t col0,
-                                       T* __restrict__ G, T* __restrict__ un, T* __restrict__ xn,
-                                       T* __restrict__ rn, T rho, T taurho, T mu, const Red& red,
-                                       int slot, int nparts) {
-  typedef MF<T> M;
-  constexpr int L = 16 * NT;
-  constexpr int NW = atr_waves<WL>();
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int i = lane & 15;
-  const bool mine = wave < atr_ne<WL>();
-  double accr[2] = {0.0, -__builtin_inf()};
-  T us[4][NT], xs[4][NT], rs[4][NT];
-  if (mine) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      bool ok[NT];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) ok[nt] = true;
-      admm_dual_row<T, 16, NT>(xa[r], gs[r], ok, true, i, rho, taurho, mu, us[r], xs[r], rs[r], accr);
-    }
-  }
-  grid_reduce<2, 0x2u, NW>(accr, red, slot, nparts);
-  if (!mine) return;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      if (G != nullptr) G[row * L + nt * 16 + i] = gs[r][nt];
-      un[row * L + nt * 16 + i] = us[r][nt];
-      xn[row * L + nt * 16 + i] = xs[r][nt];
-      rn[row * L + nt * 16 + i] = rs[r][nt];
-    }
-  }
-}
-
-// The row step fused into g = A^T z: once the block's reduction (and, with K splits, the last
-// arriver's slab combine) leaves each wave its 16 complete rows of g, admm_panel_rows runs on
-// them with x the current iterate. No packet, no masks.
-template <typename T, int NT, int PF, bool NTL, bool SPLIT, int WL>
-__global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && sizeof(T) == 8) ? 2 : 1) void k_atr_admm(const T* __restrict__ A, const T* __restrict__ Z,
-                                                  T* __restrict__ G, int64_t m, int64_t n,
-                                                  const T* __restrict__ x, T* __restrict__ un,
-                                                  T* __restrict__ xn, T* __restrict__ rn,
-                                                  double rho_, double taurho_, double mu_, Red red,
-                                                  int S, T* __restrict__ Gp,
-                                                  unsigned* __restrict__ pcnt, int keep_mib) {
-  const int nparts = SPLIT ? (int)(n / 64) : -1;   // with K splits only the panel owners reduce
-  typedef MF<T> M;
-  constexpr int L = 16 * NT;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int i = lane & 15;
-  typename M::acc_t acc[4][NT];
-  const int64_t bid = (int64_t)blockIdx.x;
-  const int64_t panel = SPLIT ? bid / S : bid, split = SPLIT ? bid % S : 0;
-  const int64_t col0 = atr_panel<T, NT, PF, WL, NTL>(A, Z, m, n, SPLIT ? S : 1, acc, panel, split, keep_mib);
-  T xa[4][NT], gs[4][NT];
-#pragma unroll
-  for (int e = 0; e < atr_ne<WL>(); ++e) {
-    if (e != wave) continue;   // wave w owns the rows e == w (4 per lane group)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t row = col0 + atr_col<T>(M::row(lane, r), e);
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) xa[r][nt] = x[row * L + nt * 16 + i];
-    }
-  }
-  int slot = (int)blockIdx.x;
-  if constexpr (SPLIT) {   // fixed reduction slots, see atr_split_combine
-    if (!atr_split_combine<T, NT>(acc, Gp, n, S, panel, split, pcnt, &slot)) return;
-  }
-#pragma unroll
-  for (int e = 0; e < atr_ne<WL>(); ++e) {
-    if (e != wave) continue;   // (static register index into acc)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) gs[r][nt] = acc[e][nt][r];
-  }
-  admm_panel_rows<T, NT, WL>(xa, gs, col0, G, un, xn, rn, (T)rho_, (T)taurho_, (T)mu_, red, slot, nparts);
-}
-
-// The unfused form on the same layout: g = the sum, in slab order (atr_split_combine's order), of
-// the S slabs launch_atr wrote under the same plan; one workgroup per panel, slot = panel. Every
-// bit it writes, the two sums included, equals k_atr_admm's.
-template <typename T, int NT, int WL>
-__global__ __launch_bounds__(atr_waves<WL>() * 64) void k_admm_dual_panel(const T* __restrict__ x, const T* __restrict__ g, int S,
-                                                  T* __restrict__ gout, T* __restrict__ un,
-                                                  T* __restrict__ xn, T* __restrict__ rn, int64_t n,
-                                                  double rho_, double taurho_, double mu_, Red red) {
-  typedef MF<T> M;
-  constexpr int L = 16 * NT;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int i = lane & 15;
-  const int64_t col0 = (int64_t)blockIdx.x * atr_pw<WL>();
-  const int64_t nl = n * L;
-  T xa[4][NT], gs[4][NT];
-  if (wave < atr_ne<WL>()) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        xa[r][nt] = x[row * L + nt * 16 + i];
-        gs[r][nt] = slab_sum(g, S, nl, row * L + nt * 16 + i);
-      }
-    }
-  }
-  admm_panel_rows<T, NT, WL>(xa, gs, col0, gout, un, xn, rn, (T)rho_, (T)taurho_, (T)mu_, red,
-                             (int)blockIdx.x, -1);
-}
-
-// The certificate's row terms on the panel layout an A^T R epilogue holds (as admm_panel_rows):
-// xa = the wave's values of the iterate, gs of g = A^T r. Runs cert_row, hands its five sums to
-// grid_reduce and then stores G (when non-null) and the rows' ||g_i|| as doubles (rn, when
-// non-null). Called by every thread of the workgroup (waves past NE reduce identities). Shared by
-// k_atr_cert and k_cert_panel, so the fused and the unfused form write the same bits, sums
-// included.
-template <typename T, int NT, int WL>
-__device__ inline void cert_panel_rows(const T (&xa)[4][NT], const T (&gs)[4][NT], int64_t col0,
-                                       T* __restrict__ G, double* __restrict__ rn, T mu,
-                                       const Red& red, int slot, int nparts) {
-  typedef MF<T> M;
-  constexpr int L = 16 * NT;
-  constexpr int NW = atr_waves<WL>();
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int i = lane & 15;
-  const bool mine = wave < atr_ne<WL>();
-  double accr[5] = {0.0, -__builtin_inf(), -__builtin_inf(), 0.0, 0.0};
-  T gn[4];
-  if (mine) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      bool ok[NT];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) ok[nt] = true;
-      gn[r] = cert_row<T, 16, NT>(xa[r], gs[r], ok, true, i, mu, accr);
-    }
-  }
-  grid_reduce<5, 0x6u, NW>(accr, red, slot, nparts);
-  if (!mine) return;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
-    if (G != nullptr) {
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) G[row * L + nt * 16 + i] = gs[r][nt];
-    }
-    if (rn != nullptr && i == 0) rn[row] = (double)gn[r];
-  }
-}
-
-// The certificate's row terms fused into g = A^T r, assembled as k_atr_admm is: once the block's
-// reduction (and, with K splits, the last arriver's slab combine) leaves each wave its 16
-// complete rows of g, cert_panel_rows runs on them with x the iterate. G is written only where
-// the caller asks for it.
-template <typename T, int NT, int PF, bool NTL, bool SPLIT, int WL>
-__global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && sizeof(T) == 8) ? 2 : 1) void k_atr_cert(const T* __restrict__ A, const T* __restrict__ R,
-                                                  T* __restrict__ G, int64_t m, int64_t n,
-                                                  const T* __restrict__ x, double* __restrict__ rn,
-                                                  double mu_, Red red, int S, T* __restrict__ Gp,
-                                                  unsigned* __restrict__ pcnt, int keep_mib) {
+// ------------------------------------------------------------------------------------------
+// The "rows after the product" epilogues (dual ADMM's row step, the certificate's row terms, dual
+// ALM's inner step). Each is a policy Epi, a struct of pointers and scalars with
+//   kIterate                                  the frame loads the wave's rows of Epi::x into xa
+//   rows<NT, WL>(xa, gs, col0, slot, nparts)  the row arithmetic on the panel layout an A^T R
+//                                             epilogue holds: wave w < NE owns the 16 rows e == w
+//                                             of the panel at col0, lane (i, q) holding columns i
+//                                             (and 16 + i) of 4 of them; gs = those values of the
+//                                             product. Called by every thread of the workgroup.
+// and runs under two frames: atr_rows_body at the end of the product (the k_atr_* kernels) and
+// panel_rows_body on the slabs launch_atr wrote under the same plan (the k_*_panel kernels). One
+// rows() serves both, so the fused and the unfused form write the same bits, sums included.
+// rows() hands the policy's pointers to a static run(): __restrict__ tells the compiler something
+// only on a function's parameters, and without it the row stores are scheduled as if they could
+// alias (k_admm_dual_panel's NT 2 form grew by 60 instructions).
+// The kernels hand their policy over by reference: how a packet reaches a body decides whether
+// the kernel gets a scratch frame (round 8, k_atr_prox).
+// ------------------------------------------------------------------------------------------
+// The frame fused into the product: once the block's reduction (and, with K splits, the last
+// arriver's slab combine) leaves each wave its 16 complete rows, Epi::rows runs on them. No
+// packet, no masks. The iterate's rows are loaded before the combine, not after it.
+template <typename T, int NT, int PF, bool NTL, bool SPLIT, int WL, typename Epi>
+__device__ __forceinline__ void atr_rows_body(const T* __restrict__ A, const T* __restrict__ R, int64_t m,
+                                              int64_t n, int S, T* __restrict__ Gp,
+                                              unsigned* __restrict__ pcnt, int keep_mib, const Epi& epi) {
   const int nparts = SPLIT ? (int)(n / 64) : -1;   // with K splits only the panel owners reduce
   typedef MF<T> M;
   constexpr int L = 16 * NT;
@@ -800,14 +651,16 @@ __global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && size
   const int64_t panel = SPLIT ? bid / S : bid, split = SPLIT ? bid % S : 0;
   const int64_t col0 = atr_panel<T, NT, PF, WL, NTL>(A, R, m, n, SPLIT ? S : 1, acc, panel, split, keep_mib);
   T xa[4][NT], gs[4][NT];
+  if constexpr (Epi::kIterate) {
 #pragma unroll
-  for (int e = 0; e < atr_ne<WL>(); ++e) {
-    if (e != wave) continue;   // wave w owns the rows e == w (4 per lane group)
+    for (int e = 0; e < atr_ne<WL>(); ++e) {
+      if (e != wave) continue;   // wave w owns the rows e == w (4 per lane group)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t row = col0 + atr_col<T>(M::row(lane, r), e);
+      for (int r = 0; r < 4; ++r) {
+        const int64_t row = col0 + atr_col<T>(M::row(lane, r), e);
 #pragma unroll
-      for (int nt = 0; nt < NT; ++nt) xa[r][nt] = x[row * L + nt * 16 + i];
+        for (int nt = 0; nt < NT; ++nt) xa[r][nt] = epi.x[row * L + nt * 16 + i];
+      }
     }
   }
   int slot = (int)blockIdx.x;
@@ -822,16 +675,13 @@ __global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && size
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) gs[r][nt] = acc[e][nt][r];
   }
-  cert_panel_rows<T, NT, WL>(xa, gs, col0, G, rn, (T)mu_, red, slot, nparts);
+  epi.template rows<NT, WL>(xa, gs, col0, slot, nparts);
 }
 
-// The unfused form on the same layout: g = the sum, in slab order (atr_split_combine's order), of
-// the S slabs launch_atr wrote under the same plan; one workgroup per panel, slot = panel. Every
-// bit it writes, the five sums included, equals k_atr_cert's.
-template <typename T, int NT, int WL>
-__global__ __launch_bounds__(atr_waves<WL>() * 64) void k_cert_panel(const T* __restrict__ x, const T* __restrict__ g, int S,
-                                                  T* __restrict__ gout, double* __restrict__ rn,
-                                                  int64_t n, double mu_, Red red) {
+// The unfused frame on the same layout: the product = the sum, in slab order (atr_split_combine's
+// order), of the S slabs of g; one workgroup per panel, slot = panel.
+template <typename T, int NT, int WL, typename Epi>
+__device__ __forceinline__ void panel_rows_body(const T* __restrict__ g, int S, int64_t n, const Epi& epi) {
   typedef MF<T> M;
   constexpr int L = 16 * NT;
   const int lane = threadIdx.x & 63;
@@ -846,109 +696,226 @@ __global__ __launch_bounds__(atr_waves<WL>() * 64) void k_cert_panel(const T* __
       const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
-        xa[r][nt] = x[row * L + nt * 16 + i];
+        if constexpr (Epi::kIterate) xa[r][nt] = epi.x[row * L + nt * 16 + i];
         gs[r][nt] = slab_sum(g, S, nl, row * L + nt * 16 + i);
       }
     }
   }
-  cert_panel_rows<T, NT, WL>(xa, gs, col0, gout, rn, (T)mu_, red, (int)blockIdx.x, -1);
+  epi.template rows<NT, WL>(xa, gs, col0, (int)blockIdx.x, -1);
 }
 
-// One step of dual ALM's inner loop (gl_ALM_dual.py:56-61) on the panel layout of an A^T R
-// epilogue, A = Qn (n x n, symmetric) and R = y: ps = the wave's 16 complete rows of P = Qn y.
-// Runs alm_inner_row and stores u+ (un; may be u itself: a row's lanes read their own elements
-// before they write them) and, where yn != NULL, y+. yn is never the y the product reads: other
-// workgroups may still be streaming it. No sums, so no grid reduction; waves past NE have no rows.
-// Shared by k_atr_alm and k_alm_inner_panel, so both write the same bits.
+// Dual ADMM's row step (gl_ADMM_dual.py:64-67): xa = the wave's values of the iterate, gs of
+// g = A^T z. Runs admm_dual_row (the arithmetic of k_admm_dual, kernels_admm.hip), hands the two
+// sums [sum_i ||x+_i||, max |x+|] to grid_reduce and then stores G (when non-null), u+, x+ and r,
+// as k_atr_prox orders them (waves past NE reduce identities).
+template <typename T>
+struct AdmmRows {
+  static constexpr bool kIterate = true;
+  const T* x;
+  T *G, *un, *xn, *rn;
+  T rho, taurho, mu;
+  const Red& red;
+  template <int NT, int WL>
+  __device__ __forceinline__ void rows(const T (&xa)[4][NT], const T (&gs)[4][NT], int64_t col0, int slot,
+                                       int nparts) const {
+    run<NT, WL>(xa, gs, col0, G, un, xn, rn, rho, taurho, mu, red, slot, nparts);
+  }
+  template <int NT, int WL>
+  static __device__ inline void run(const T (&xa)[4][NT], const T (&gs)[4][NT], int64_t col0,
+                                    T* __restrict__ G, T* __restrict__ un, T* __restrict__ xn,
+                                    T* __restrict__ rn, T rho, T taurho, T mu, const Red& red, int slot,
+                                    int nparts) {
+    typedef MF<T> M;
+    constexpr int L = 16 * NT;
+    constexpr int NW = atr_waves<WL>();
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int i = lane & 15;
+    const bool mine = wave < atr_ne<WL>();
+    double accr[2] = {0.0, -__builtin_inf()};
+    T us[4][NT], xs[4][NT], rs[4][NT];
+    if (mine) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        bool ok[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) ok[nt] = true;
+        admm_dual_row<T, 16, NT>(xa[r], gs[r], ok, true, i, rho, taurho, mu, us[r], xs[r], rs[r], accr);
+      }
+    }
+    grid_reduce<2, 0x2u, NW>(accr, red, slot, nparts);
+    if (!mine) return;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        if (G != nullptr) G[row * L + nt * 16 + i] = gs[r][nt];
+        un[row * L + nt * 16 + i] = us[r][nt];
+        xn[row * L + nt * 16 + i] = xs[r][nt];
+        rn[row * L + nt * 16 + i] = rs[r][nt];
+      }
+    }
+  }
+};
+
+template <typename T, int NT, int PF, bool NTL, bool SPLIT, int WL>
+__global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && sizeof(T) == 8) ? 2 : 1) void k_atr_admm(const T* __restrict__ A, const T* __restrict__ Z,
+                                                  T* __restrict__ G, int64_t m, int64_t n,
+                                                  const T* __restrict__ x, T* __restrict__ un,
+                                                  T* __restrict__ xn, T* __restrict__ rn,
+                                                  double rho_, double taurho_, double mu_, Red red,
+                                                  int S, T* __restrict__ Gp,
+                                                  unsigned* __restrict__ pcnt, int keep_mib) {
+  const AdmmRows<T> epi{x, G, un, xn, rn, (T)rho_, (T)taurho_, (T)mu_, red};
+  atr_rows_body<T, NT, PF, NTL, SPLIT, WL>(A, Z, m, n, S, Gp, pcnt, keep_mib, epi);
+}
+template <typename T, int NT, int WL>
+__global__ __launch_bounds__(atr_waves<WL>() * 64) void k_admm_dual_panel(const T* __restrict__ x, const T* __restrict__ g, int S,
+                                                  T* __restrict__ gout, T* __restrict__ un,
+                                                  T* __restrict__ xn, T* __restrict__ rn, int64_t n,
+                                                  double rho_, double taurho_, double mu_, Red red) {
+  const AdmmRows<T> epi{x, gout, un, xn, rn, (T)rho_, (T)taurho_, (T)mu_, red};
+  panel_rows_body<T, NT, WL>(g, S, n, epi);
+}
+
+// The certificate's row terms: xa = the wave's values of the iterate, gs of g = A^T r. Runs
+// cert_row, hands its five sums to grid_reduce and then stores G (only where the caller asks for
+// it) and the rows' ||g_i|| as doubles (rn, when non-null). Waves past NE reduce identities.
+template <typename T>
+struct CertRows {
+  static constexpr bool kIterate = true;
+  const T* x;
+  T* G;
+  double* rn;
+  T mu;
+  const Red& red;
+  template <int NT, int WL>
+  __device__ __forceinline__ void rows(const T (&xa)[4][NT], const T (&gs)[4][NT], int64_t col0, int slot,
+                                       int nparts) const {
+    run<NT, WL>(xa, gs, col0, G, rn, mu, red, slot, nparts);
+  }
+  template <int NT, int WL>
+  static __device__ inline void run(const T (&xa)[4][NT], const T (&gs)[4][NT], int64_t col0,
+                                    T* __restrict__ G, double* __restrict__ rn, T mu, const Red& red,
+                                    int slot, int nparts) {
+    typedef MF<T> M;
+    constexpr int L = 16 * NT;
+    constexpr int NW = atr_waves<WL>();
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int i = lane & 15;
+    const bool mine = wave < atr_ne<WL>();
+    double accr[5] = {0.0, -__builtin_inf(), -__builtin_inf(), 0.0, 0.0};
+    T gn[4];
+    if (mine) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        bool ok[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) ok[nt] = true;
+        gn[r] = cert_row<T, 16, NT>(xa[r], gs[r], ok, true, i, mu, accr);
+      }
+    }
+    grid_reduce<5, 0x6u, NW>(accr, red, slot, nparts);
+    if (!mine) return;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
+      if (G != nullptr) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) G[row * L + nt * 16 + i] = gs[r][nt];
+      }
+      if (rn != nullptr && i == 0) rn[row] = (double)gn[r];
+    }
+  }
+};
+
+template <typename T, int NT, int PF, bool NTL, bool SPLIT, int WL>
+__global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && sizeof(T) == 8) ? 2 : 1) void k_atr_cert(const T* __restrict__ A, const T* __restrict__ R,
+                                                  T* __restrict__ G, int64_t m, int64_t n,
+                                                  const T* __restrict__ x, double* __restrict__ rn,
+                                                  double mu_, Red red, int S, T* __restrict__ Gp,
+                                                  unsigned* __restrict__ pcnt, int keep_mib) {
+  const CertRows<T> epi{x, G, rn, (T)mu_, red};
+  atr_rows_body<T, NT, PF, NTL, SPLIT, WL>(A, R, m, n, S, Gp, pcnt, keep_mib, epi);
+}
+template <typename T, int NT, int WL>
+__global__ __launch_bounds__(atr_waves<WL>() * 64) void k_cert_panel(const T* __restrict__ x, const T* __restrict__ g, int S,
+                                                  T* __restrict__ gout, double* __restrict__ rn,
+                                                  int64_t n, double mu_, Red red) {
+  const CertRows<T> epi{x, gout, rn, (T)mu_, red};
+  panel_rows_body<T, NT, WL>(g, S, n, epi);
+}
+
+// One step of dual ALM's inner loop (gl_ALM_dual.py:56-61), A = Qn (n x n, symmetric) and R = y:
+// ps = the wave's 16 complete rows of P = Qn y. Reads y, J and u itself, runs alm_inner_row and
+// stores u+ (un; may be u itself: a row's lanes read their own elements before they write them)
+// and, where yn != NULL, y+. yn is never the y the product reads: other workgroups may still be
+// streaming it. No iterate, no sums, so no grid reduction and no slot; waves past NE have no rows.
 template <typename T>
 struct AlmScalars {
   T t, mu, gamma, a1, gn;
 };
-template <typename T, int NT, int WL>
-__device__ inline void alm_panel_rows(const T (&ps)[4][NT], int64_t col0, const T* __restrict__ y,
-                                      const T* __restrict__ J, const T* u, T* un, T* __restrict__ yn,
-                                      const AlmScalars<T>& sc) {
-  typedef MF<T> M;
-  constexpr int L = 16 * NT;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int i = lane & 15;
-  if (wave >= atr_ne<WL>()) return;
+template <typename T>
+struct AlmRows {
+  static constexpr bool kIterate = false;
+  const T *y, *J, *u;
+  T *un, *yn;
+  const AlmScalars<T>& sc;
+  template <int NT, int WL>
+  __device__ __forceinline__ void rows(const T (&)[4][NT], const T (&ps)[4][NT], int64_t col0, int, int) const {
+    run<NT, WL>(ps, col0, y, J, u, un, yn, sc);
+  }
+  template <int NT, int WL>
+  static __device__ inline void run(const T (&ps)[4][NT], int64_t col0, const T* __restrict__ y,
+                                    const T* __restrict__ J, const T* u, T* un, T* __restrict__ yn,
+                                    const AlmScalars<T>& sc) {
+    typedef MF<T> M;
+    constexpr int L = 16 * NT;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int i = lane & 15;
+    if (wave >= atr_ne<WL>()) return;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
-    T yv[NT], jv[NT], uv[NT], uo[NT], yo[NT];
+    for (int r = 0; r < 4; ++r) {
+      const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
+      T yv[NT], jv[NT], uv[NT], uo[NT], yo[NT];
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      yv[nt] = y[row * L + nt * 16 + i];
-      jv[nt] = J[row * L + nt * 16 + i];
-      uv[nt] = u[row * L + nt * 16 + i];
-    }
-    alm_inner_row<T, 16, NT>(ps[r], yv, jv, uv, sc.t, sc.mu, sc.gamma, sc.a1, sc.gn, uo, yo);
+      for (int nt = 0; nt < NT; ++nt) {
+        yv[nt] = y[row * L + nt * 16 + i];
+        jv[nt] = J[row * L + nt * 16 + i];
+        uv[nt] = u[row * L + nt * 16 + i];
+      }
+      alm_inner_row<T, 16, NT>(ps[r], yv, jv, uv, sc.t, sc.mu, sc.gamma, sc.a1, sc.gn, uo, yo);
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-      un[row * L + nt * 16 + i] = uo[nt];
-      if (yn != nullptr) yn[row * L + nt * 16 + i] = yo[nt];
+      for (int nt = 0; nt < NT; ++nt) {
+        un[row * L + nt * 16 + i] = uo[nt];
+        if (yn != nullptr) yn[row * L + nt * 16 + i] = yo[nt];
+      }
     }
   }
-}
+};
 
-// The inner step fused into P = Qn^T y (= Qn y): once the block's reduction (and, with K splits,
-// the last arriver's slab combine) leaves each wave its 16 complete rows of P, alm_panel_rows runs
-// on them. One launch per inner step.
+// The inner step fused into P = Qn^T y (= Qn y): one launch per inner step.
 template <typename T, int NT, int PF, bool NTL, bool SPLIT, int WL>
 __global__ __launch_bounds__(atr_waves<WL>() * 64, ((WL == 0 || WL == 3) && sizeof(T) == 8) ? 2 : 1) void k_atr_alm(const T* __restrict__ Qn, const T* __restrict__ y,
                                                   int64_t n, const T* __restrict__ J, const T* u, T* un,
                                                   T* __restrict__ yn, AlmScalars<T> sc, int S,
                                                   T* __restrict__ Gp, unsigned* __restrict__ pcnt,
                                                   int keep_mib) {
-  typedef MF<T> M;
-  const int wave = threadIdx.x >> 6;
-  typename M::acc_t acc[4][NT];
-  const int64_t bid = (int64_t)blockIdx.x;
-  const int64_t panel = SPLIT ? bid / S : bid, split = SPLIT ? bid % S : 0;
-  const int64_t col0 = atr_panel<T, NT, PF, WL, NTL>(Qn, y, n, n, SPLIT ? S : 1, acc, panel, split, keep_mib);
-  if constexpr (SPLIT) {
-    int slot;
-    if (!atr_split_combine<T, NT>(acc, Gp, n, S, panel, split, pcnt, &slot)) return;
-  }
-  T ps[4][NT];
-#pragma unroll
-  for (int e = 0; e < atr_ne<WL>(); ++e) {
-    if (e != wave) continue;   // (static register index into acc)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) ps[r][nt] = acc[e][nt][r];
-  }
-  alm_panel_rows<T, NT, WL>(ps, col0, y, J, u, un, yn, sc);
+  const AlmRows<T> epi{y, J, u, un, yn, sc};
+  atr_rows_body<T, NT, PF, NTL, SPLIT, WL>(Qn, y, n, n, S, Gp, pcnt, keep_mib, epi);
 }
-
-// The unfused form on the same layout: P = the sum, in slab order (atr_split_combine's order), of
-// the S slabs launch_atr wrote; one workgroup per panel. Every bit equals k_atr_alm's.
 template <typename T, int NT, int WL>
 __global__ __launch_bounds__(atr_waves<WL>() * 64) void k_alm_inner_panel(const T* __restrict__ P, int S, int64_t n,
                                                   const T* __restrict__ y, const T* __restrict__ J,
                                                   const T* u, T* un, T* __restrict__ yn,
                                                   AlmScalars<T> sc) {
-  typedef MF<T> M;
-  constexpr int L = 16 * NT;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int i = lane & 15;
-  const int64_t col0 = (int64_t)blockIdx.x * atr_pw<WL>();
-  const int64_t nl = n * L;
-  T ps[4][NT];
-  if (wave < atr_ne<WL>()) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t row = col0 + atr_col<T>(M::row(lane, r), wave);
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) ps[r][nt] = slab_sum(P, S, nl, row * L + nt * 16 + i);
-    }
-  }
-  alm_panel_rows<T, NT, WL>(ps, col0, y, J, u, un, yn, sc);
+  const AlmRows<T> epi{y, J, u, un, yn, sc};
+  panel_rows_body<T, NT, WL>(P, S, n, epi);
 }
+
 
 // A^T R on VALU: a thread owns E consecutive columns of A over a row range; R[row][c0..c0+LB)
 // is wave-uniform (scalar loads). Gp[blockIdx.y][n][l].
@@ -1059,36 +1026,55 @@ void launch_atr(const GemmPlan& p, const T* A, const T* R, T* Gp, hipStream_t st
   });
 }
 
-template <typename T, int NT, int PF, bool NTL, int WL>
-static void atr_prox_go(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, T* pp,
-                        T* pthr, T* z, double t, double mu, double thres, Red red, hipStream_t st,
-                        Pub pub, T* Gp, unsigned* pcnt, unsigned* zf, const FinHead* head) {
-  const dim3 grid((unsigned)(p.n / atr_pw<WL>() * p.atr_S + (pub.host ? 1 : 0)));
-  const dim3 block(atr_waves<WL>() * 64);
-  if (head != nullptr) {
-    if constexpr (std::is_same<T, double>::value && WL == 0) {
-      static const size_t hpad = lds_pad(k_atr_prox_head<NT, PF, NTL>, "GLX_ATR_LDS_PAD");
-      glx_launch((k_atr_prox_head<NT, PF, NTL>), grid, block, hpad, st, A, R, G, p.m, p.n, x, pp, pthr, z, t,
-                 t * mu, thres, red, pub, zf, p.atr_keep_mib, *head);
-      return;
+// The template arguments of a fused A^T R kernel after T, as one type a generic lambda reads.
+template <int NT_, int PF_, bool NTL_, bool SPLIT_, int WL_>
+struct AtrArgs {
+  static constexpr int NT = NT_, PF = PF_, WL = WL_;
+  static constexpr bool NTL = NTL_, SPLIT = SPLIT_;
+};
+
+// The one launcher of the fused A^T R families. kernel_of(AtrArgs) names the family's kernel at
+// those arguments; go(AtrArgs, kernel, grid, block, pad, S) makes the launch with its own argument
+// list. The grid is a 1-D n / panel * S workgroups (+ `extra`: the publisher's). With K splits on a
+// 64-column panel the SPLIT kernel runs without an occupancy pad; otherwise the plain one (the S = 1
+// kernel keeps 2 blocks per CU) with S = 1. The planner never splits K on the 32-column panel
+// (fuses(), planner.cpp), so no SPLIT kernel is built for it.
+template <typename T, typename KernelOf, typename Go>
+static void atr_fused_launch(const GemmPlan& p, const char* what, int extra, const T* Gp, const unsigned* pcnt,
+                             KernelOf kernel_of, Go&& go) {
+  if (p.atr_S > 1 && (Gp == nullptr || pcnt == nullptr))
+    throw Error{GLX_E_INVALID, "fused A^T R with K splits needs slab and counter buffers"};
+  atr_visit<T, true>(p, what, [&](auto i, auto nt) {
+    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
+    constexpr int NT = decltype(nt)::value, WL = tile.wl;
+    const dim3 grid((unsigned)(p.n / atr_pw<WL>() * p.atr_S + extra));
+    const dim3 block(atr_waves<WL>() * 64);
+    if constexpr (WL != 3 && WL != 4) {
+      if (p.atr_S > 1) {
+        const AtrArgs<NT, tile.pf, tile.ntl, true, WL> a;
+        go(a, kernel_of(a), grid, block, (size_t)0, p.atr_S);
+        return;
+      }
     }
-    throw Error{GLX_E_INVALID, "fused A^T R + trial: the finalize head is built for the f64 four-wave panel"};
-  }
-  if (WL != 3 && WL != 4 && p.atr_S > 1) {
-    glx_launch((k_atr_prox<T, NT, PF, NTL, true, WL>), grid, block, 0, st, A, R, G, p.m,
-                       p.n, x, pp, pthr, z, t, t * mu, thres, red, pub, p.atr_S, Gp, pcnt, zf, p.atr_keep_mib);
-    return;
-  }
-  static const size_t pad = lds_pad(k_atr_prox<T, NT, PF, NTL, false, WL>, "GLX_ATR_LDS_PAD");
-  glx_launch((k_atr_prox<T, NT, PF, NTL, false, WL>), grid, block, pad, st, A, R, G, p.m,
-                     p.n, x, pp, pthr, z, t, t * mu, thres, red, pub, 1, Gp, pcnt, zf, p.atr_keep_mib);
+    const AtrArgs<NT, tile.pf, tile.ntl, false, WL> a;
+    static const size_t pad = lds_pad(kernel_of(a), "GLX_ATR_LDS_PAD");
+    go(a, kernel_of(a), grid, block, pad, 1);
+  });
 }
+
+// The launcher of the unfused twins: go(NT, WL, grid, block), one workgroup per panel.
+template <typename T, typename Go>
+static void panel_rows_launch(const GemmPlan& p, const char* what, Go&& go) {
+  atr_visit<T, true>(p, what, [&](auto i, auto nt) {
+    constexpr int WL = kAtrTiles[decltype(i)::value].wl;
+    go(nt, std::integral_constant<int, WL>{}, dim3((unsigned)(p.n / atr_pw<WL>())), dim3(atr_waves<WL>() * 64));
+  });
+}
+
 template <typename T>
 void launch_atr_prox(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, T* pp, T* pthr,
                      T* z, double t, double mu, double thres, Red red, hipStream_t st, Pub pub,
                      T* Gp, unsigned* pcnt, unsigned* zf, const FinHead* head) {
-  if (p.atr_S > 1 && (Gp == nullptr || pcnt == nullptr))
-    throw Error{GLX_E_INVALID, "fused A^T R with K splits needs slab and counter buffers"};
   FinHead hd;
   if (head != nullptr) {
     hd = *head;
@@ -1101,117 +1087,74 @@ void launch_atr_prox(const GemmPlan& p, const T* A, const T* R, T* G, const T* x
     hd.nvb = finalize_blocks(hd.ml, hd.S, hd.chain ? hd.S0 : 0, hd.cx ? hd.cn : 0);
     head = &hd;
   }
-  atr_visit<T, true>(p, "fused A^T R + trial", [&](auto i, auto nt) {
-    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
-    atr_prox_go<T, decltype(nt)::value, tile.pf, tile.ntl, tile.wl>(p, A, R, G, x, pp, pthr, z, t, mu, thres, red,
-                                                                  st, pub, Gp, pcnt, zf, head);
-  });
+  atr_fused_launch<T>(
+      p, "fused A^T R + trial", pub.host ? 1 : 0, Gp, pcnt,
+      [](auto a) { return &k_atr_prox<T, a.NT, a.PF, a.NTL, a.SPLIT, a.WL>; },
+      [&](auto a, auto kernel, dim3 grid, dim3 block, size_t pad, int S) {
+        if (head != nullptr) {
+          if constexpr (std::is_same<T, double>::value && a.WL == 0) {
+            static const size_t hpad = lds_pad(k_atr_prox_head<a.NT, a.PF, a.NTL>, "GLX_ATR_LDS_PAD");
+            glx_launch((k_atr_prox_head<a.NT, a.PF, a.NTL>), grid, block, hpad, st, A, R, G, p.m, p.n, x, pp, pthr, z, t,
+                       t * mu, thres, red, pub, zf, p.atr_keep_mib, *head);
+            return;
+          }
+          throw Error{GLX_E_INVALID, "fused A^T R + trial: the finalize head is built for the f64 four-wave panel"};
+        }
+        glx_launch(kernel, grid, block, pad, st, A, R, G, p.m, p.n, x, pp, pthr, z, t, t * mu, thres, red, pub, S, Gp,
+                   pcnt, zf, p.atr_keep_mib);
+      });
 }
 
-template <typename T, int NT, int PF, bool NTL, int WL>
-static void atr_fista_go(const GemmPlan& p, const T* A, const T* R, T* G, const T* y, const T* xk,
-                         T* xc, T* vn, T* yn, double t, double mu, double thres, double theta,
-                         double theta_next, Red red, hipStream_t st, Pub pub, T* Gp, unsigned* pcnt,
-                         T* ec, unsigned* zf) {
-  const dim3 grid((unsigned)(p.n / atr_pw<WL>() * p.atr_S + (pub.host ? 1 : 0)));
-  const dim3 block(atr_waves<WL>() * 64);
-  if (WL != 3 && WL != 4 && p.atr_S > 1) {
-    glx_launch((k_atr_fista<T, NT, PF, NTL, true, WL>), grid, block, 0, st, A, R, G, p.m,
-                       p.n, y, xk, xc, vn, yn, t, t * mu, thres, theta, 1.0 - theta_next,
-                       theta_next, red, pub, p.atr_S, Gp, pcnt, ec, zf, p.atr_keep_mib);
-    return;
-  }
-  static const size_t pad = lds_pad(k_atr_fista<T, NT, PF, NTL, false, WL>, "GLX_ATR_LDS_PAD");
-  glx_launch((k_atr_fista<T, NT, PF, NTL, false, WL>), grid, block, pad, st, A, R, G, p.m,
-                     p.n, y, xk, xc, vn, yn, t, t * mu, thres, theta, 1.0 - theta_next, theta_next,
-                     red, pub, 1, Gp, pcnt, ec, zf, p.atr_keep_mib);
-}
 template <typename T>
 void launch_atr_fista(const GemmPlan& p, const T* A, const T* R, T* G, const T* y, const T* xk,
                       T* xc, T* vn, T* yn, double t, double mu, double thres, double theta,
                       double theta_next, Red red, hipStream_t st, Pub pub, T* Gp, unsigned* pcnt,
                       T* ec, unsigned* zf) {
-  if (p.atr_S > 1 && (Gp == nullptr || pcnt == nullptr))
-    throw Error{GLX_E_INVALID, "fused A^T R with K splits needs slab and counter buffers"};
-  atr_visit<T, true>(p, "fused A^T R + FISTA trial", [&](auto i, auto nt) {
-    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
-    atr_fista_go<T, decltype(nt)::value, tile.pf, tile.ntl, tile.wl>(p, A, R, G, y, xk, xc, vn, yn, t, mu, thres,
-                                                                   theta, theta_next, red, st, pub, Gp, pcnt, ec, zf);
-  });
+  atr_fused_launch<T>(
+      p, "fused A^T R + FISTA trial", pub.host ? 1 : 0, Gp, pcnt,
+      [](auto a) { return &k_atr_fista<T, a.NT, a.PF, a.NTL, a.SPLIT, a.WL>; },
+      [&](auto, auto kernel, dim3 grid, dim3 block, size_t pad, int S) {
+        glx_launch(kernel, grid, block, pad, st, A, R, G, p.m, p.n, y, xk, xc, vn, yn, t, t * mu, thres, theta,
+                   1.0 - theta_next, theta_next, red, pub, S, Gp, pcnt, ec, zf, p.atr_keep_mib);
+      });
 }
 
-template <typename T, int NT, int PF, bool NTL, int WL>
-static void atr_admm_go(const GemmPlan& p, const T* A, const T* Z, T* G, const T* x, T* un, T* xn,
-                        T* rn, double rho, double taurho, double mu, Red red, hipStream_t st, T* Gp,
-                        unsigned* pcnt) {
-  const dim3 grid((unsigned)(p.n / atr_pw<WL>() * p.atr_S));
-  const dim3 block(atr_waves<WL>() * 64);
-  if (WL != 3 && WL != 4 && p.atr_S > 1) {
-    glx_launch((k_atr_admm<T, NT, PF, NTL, true, WL>), grid, block, 0, st, A, Z, G, p.m, p.n, x, un, xn,
-               rn, rho, taurho, mu, red, p.atr_S, Gp, pcnt, p.atr_keep_mib);
-    return;
-  }
-  static const size_t pad = lds_pad(k_atr_admm<T, NT, PF, NTL, false, WL>, "GLX_ATR_LDS_PAD");
-  glx_launch((k_atr_admm<T, NT, PF, NTL, false, WL>), grid, block, pad, st, A, Z, G, p.m, p.n, x, un, xn,
-             rn, rho, taurho, mu, red, 1, Gp, pcnt, p.atr_keep_mib);
-}
 template <typename T>
 void launch_atr_admm(const GemmPlan& p, const T* A, const T* Z, T* G, const T* x, T* un, T* xn, T* rn,
                      double rho, double taurho, double mu, Red red, hipStream_t st, T* Gp,
                      unsigned* pcnt) {
-  if (p.atr_S > 1 && (Gp == nullptr || pcnt == nullptr))
-    throw Error{GLX_E_INVALID, "fused A^T R with K splits needs slab and counter buffers"};
-  atr_visit<T, true>(p, "fused A^T z + ADMM row step", [&](auto i, auto nt) {
-    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
-    atr_admm_go<T, decltype(nt)::value, tile.pf, tile.ntl, tile.wl>(p, A, Z, G, x, un, xn, rn, rho, taurho, mu,
-                                                                  red, st, Gp, pcnt);
-  });
+  atr_fused_launch<T>(
+      p, "fused A^T z + ADMM row step", 0, Gp, pcnt,
+      [](auto a) { return &k_atr_admm<T, a.NT, a.PF, a.NTL, a.SPLIT, a.WL>; },
+      [&](auto, auto kernel, dim3 grid, dim3 block, size_t pad, int S) {
+        glx_launch(kernel, grid, block, pad, st, A, Z, G, p.m, p.n, x, un, xn, rn, rho, taurho, mu, red, S, Gp, pcnt,
+                   p.atr_keep_mib);
+      });
 }
-
 template <typename T>
 void launch_admm_dual_panel(const GemmPlan& p, const T* x, const T* g, int S, T* gout, T* un, T* xn,
                             T* rn, double rho, double taurho, double mu, Red red, hipStream_t st) {
-  atr_visit<T, true>(p, "ADMM row step on the panel layout", [&](auto i, auto nt) {
-    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
-    constexpr int WL = tile.wl, NT = decltype(nt)::value;
-    glx_launch((k_admm_dual_panel<T, NT, WL>), dim3((unsigned)(p.n / atr_pw<WL>())), dim3(atr_waves<WL>() * 64),
-               0, st, x, g, S, gout, un, xn, rn, p.n, rho, taurho, mu, red);
+  panel_rows_launch<T>(p, "ADMM row step on the panel layout", [&](auto nt, auto wl, dim3 grid, dim3 block) {
+    glx_launch((k_admm_dual_panel<T, nt.value, wl.value>), grid, block, 0, st, x, g, S, gout, un, xn, rn, p.n, rho,
+               taurho, mu, red);
   });
 }
 
-template <typename T, int NT, int PF, bool NTL, int WL>
-static void atr_cert_go(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, double* rn, double mu,
-                        Red red, hipStream_t st, T* Gp, unsigned* pcnt) {
-  const dim3 grid((unsigned)(p.n / atr_pw<WL>() * p.atr_S));
-  const dim3 block(atr_waves<WL>() * 64);
-  if (WL != 3 && WL != 4 && p.atr_S > 1) {
-    glx_launch((k_atr_cert<T, NT, PF, NTL, true, WL>), grid, block, 0, st, A, R, G, p.m, p.n, x, rn, mu, red,
-               p.atr_S, Gp, pcnt, p.atr_keep_mib);
-    return;
-  }
-  static const size_t pad = lds_pad(k_atr_cert<T, NT, PF, NTL, false, WL>, "GLX_ATR_LDS_PAD");
-  glx_launch((k_atr_cert<T, NT, PF, NTL, false, WL>), grid, block, pad, st, A, R, G, p.m, p.n, x, rn, mu, red,
-             1, Gp, pcnt, p.atr_keep_mib);
-}
 template <typename T>
 void launch_atr_cert(const GemmPlan& p, const T* A, const T* R, T* G, const T* x, double* rn, double mu,
                      Red red, hipStream_t st, T* Gp, unsigned* pcnt) {
-  if (p.atr_S > 1 && (Gp == nullptr || pcnt == nullptr))
-    throw Error{GLX_E_INVALID, "fused A^T R with K splits needs slab and counter buffers"};
-  atr_visit<T, true>(p, "fused A^T r + certificate rows", [&](auto i, auto nt) {
-    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
-    atr_cert_go<T, decltype(nt)::value, tile.pf, tile.ntl, tile.wl>(p, A, R, G, x, rn, mu, red, st, Gp, pcnt);
-  });
+  atr_fused_launch<T>(
+      p, "fused A^T r + certificate rows", 0, Gp, pcnt,
+      [](auto a) { return &k_atr_cert<T, a.NT, a.PF, a.NTL, a.SPLIT, a.WL>; },
+      [&](auto, auto kernel, dim3 grid, dim3 block, size_t pad, int S) {
+        glx_launch(kernel, grid, block, pad, st, A, R, G, p.m, p.n, x, rn, mu, red, S, Gp, pcnt, p.atr_keep_mib);
+      });
 }
-
 template <typename T>
 void launch_cert_panel(const GemmPlan& p, const T* x, const T* g, int S, T* gout, double* rn, double mu,
                        Red red, hipStream_t st) {
-  atr_visit<T, true>(p, "certificate rows on the panel layout", [&](auto i, auto nt) {
-    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
-    constexpr int WL = tile.wl, NT = decltype(nt)::value;
-    glx_launch((k_cert_panel<T, NT, WL>), dim3((unsigned)(p.n / atr_pw<WL>())), dim3(atr_waves<WL>() * 64),
-               0, st, x, g, S, gout, rn, p.n, mu, red);
+  panel_rows_launch<T>(p, "certificate rows on the panel layout", [&](auto nt, auto wl, dim3 grid, dim3 block) {
+    glx_launch((k_cert_panel<T, nt.value, wl.value>), grid, block, 0, st, x, g, S, gout, rn, p.n, mu, red);
   });
 }
 
@@ -1219,44 +1162,26 @@ template <typename T>
 static AlmScalars<T> alm_scalars(double t, double mu, double gamma, double gamma_next) {
   return AlmScalars<T>{(T)t, (T)mu, (T)gamma, (T)(1.0 - gamma_next), (T)gamma_next};
 }
-template <typename T, int NT, int PF, bool NTL, int WL>
-static void atr_alm_go(const GemmPlan& p, const T* Qn, const T* y, const T* J, const T* u, T* un, T* yn,
-                       const AlmScalars<T>& sc, hipStream_t st, T* Gp, unsigned* pcnt) {
-  const dim3 grid((unsigned)(p.n / atr_pw<WL>() * p.atr_S));
-  const dim3 block(atr_waves<WL>() * 64);
-  if (WL != 3 && WL != 4 && p.atr_S > 1) {
-    glx_launch((k_atr_alm<T, NT, PF, NTL, true, WL>), grid, block, 0, st, Qn, y, p.n, J, u, un, yn, sc,
-               p.atr_S, Gp, pcnt, p.atr_keep_mib);
-    return;
-  }
-  static const size_t pad = lds_pad(k_atr_alm<T, NT, PF, NTL, false, WL>, "GLX_ATR_LDS_PAD");
-  glx_launch((k_atr_alm<T, NT, PF, NTL, false, WL>), grid, block, pad, st, Qn, y, p.n, J, u, un, yn, sc, 1,
-             Gp, pcnt, p.atr_keep_mib);
-}
 template <typename T>
 void launch_atr_alm(const GemmPlan& p, const T* Qn, const T* y, const T* J, const T* u, T* un, T* yn,
                     double t, double mu, double gamma, double gamma_next, hipStream_t st, T* Gp,
                     unsigned* pcnt) {
   if (p.m != p.n) throw Error{GLX_E_INVALID, "fused Qn y: the plan must be of the square (n, n, l)"};
   if (yn == y) throw Error{GLX_E_INVALID, "fused Qn y: y+ must not be written over the product's operand"};
-  if (p.atr_S > 1 && (Gp == nullptr || pcnt == nullptr))
-    throw Error{GLX_E_INVALID, "fused A^T R with K splits needs slab and counter buffers"};
   const AlmScalars<T> sc = alm_scalars<T>(t, mu, gamma, gamma_next);
-  atr_visit<T, true>(p, "fused Qn y + ALM inner step", [&](auto i, auto nt) {
-    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
-    atr_alm_go<T, decltype(nt)::value, tile.pf, tile.ntl, tile.wl>(p, Qn, y, J, u, un, yn, sc, st, Gp, pcnt);
-  });
+  atr_fused_launch<T>(
+      p, "fused Qn y + ALM inner step", 0, Gp, pcnt,
+      [](auto a) { return &k_atr_alm<T, a.NT, a.PF, a.NTL, a.SPLIT, a.WL>; },
+      [&](auto, auto kernel, dim3 grid, dim3 block, size_t pad, int S) {
+        glx_launch(kernel, grid, block, pad, st, Qn, y, p.n, J, u, un, yn, sc, S, Gp, pcnt, p.atr_keep_mib);
+      });
 }
-
 template <typename T>
 void launch_alm_inner_panel(const GemmPlan& p, const T* P, int S, const T* y, const T* J, const T* u, T* un,
                             T* yn, double t, double mu, double gamma, double gamma_next, hipStream_t st) {
   const AlmScalars<T> sc = alm_scalars<T>(t, mu, gamma, gamma_next);
-  atr_visit<T, true>(p, "ALM inner step on the panel layout", [&](auto i, auto nt) {
-    constexpr const AtrTile& tile = kAtrTiles[decltype(i)::value];
-    constexpr int WL = tile.wl, NT = decltype(nt)::value;
-    glx_launch((k_alm_inner_panel<T, NT, WL>), dim3((unsigned)(p.n / atr_pw<WL>())), dim3(atr_waves<WL>() * 64),
-               0, st, P, S, p.n, y, J, u, un, yn, sc);
+  panel_rows_launch<T>(p, "ALM inner step on the panel layout", [&](auto nt, auto wl, dim3 grid, dim3 block) {
+    glx_launch((k_alm_inner_panel<T, nt.value, wl.value>), grid, block, 0, st, P, S, p.n, y, J, u, un, yn, sc);
   });
 }
 

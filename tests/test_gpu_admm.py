@@ -37,7 +37,10 @@ and of both sums, at the shapes whose plan fuses (asserted from glx_admm_describ
 given m there, so it runs on the panel layout a solve's unfused arm takes (k_admm_dual_panel: the
 lanes hold the rows the epilogue's lanes hold, which is what makes the fp64 sums' order, and so
 their last bit, the same); the generic row layout of test 1 orders that sum differently. The
-panel layout's values are also held to test 1's bars.
+panel layout's values are also held to test 1's bars. Beside the planner's own choice, every tile
+built for a fused epilogue runs by name (GLX_ATR_VARIANT, with one and two K splits where the tile
+takes splits; the tile and S are asserted from the describe string) at (64, 64, 16) and
+(192, 256, 32).
 
 3. k_gram against float64 NumPy: the inputs are rounded to T first, the products of doubles are
 rounded once each and every entry is a sum of `rows` terms, so
@@ -63,6 +66,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from tile_cases import ROWS as TILE_ROWS
 
 pytestmark = pytest.mark.gpu
 
@@ -183,23 +187,39 @@ def test_row_kernel_against_wider_type(n, l, dt):
     assert np.isnan(out2["sums"].cpu().numpy()).all()
 
 
-FUSED_CASES = [(64, 64, 16, np.float64, None), (128, 128, 32, np.float64, None),
-               (192, 256, 32, np.float64, None), (128, 256, 32, np.float32, None),
-               (64, 64, 16, np.float64, "2")]
+FUSED_CASES = [(64, 64, 16, np.float64, None, None), (128, 128, 32, np.float64, None, None),
+               (192, 256, 32, np.float64, None, None), (128, 256, 32, np.float32, None, None),
+               (64, 64, 16, np.float64, "2", None)]
+FUSED_IDS = ["64x64x16", "128x128x32", "192x256x32", "f32_128x256x32", "64x64x16_S2"]
+# every fused tile by name (GLX_ATR_VARIANT) with the K splits it takes under an epilogue, at one
+# panel with NT = 1 and at several panels with NT = 2 and m not a power of two: four-wave,
+# eight-wave (1028) and 32-column (38, 1038) row ownership, split and not
+FUSED_TILES = [(8, (np.float64,), (1, 2)), (1008, (np.float64, np.float32), (1, 2)),
+               (1028, (np.float64, np.float32), (1, 2)), (38, (np.float64,), (1,)), (1038, (np.float64,), (1,))]
+for _shape in ((64, 64, 16), (192, 256, 32)):
+    for _tile, _dts, _Ss in FUSED_TILES:
+        for _dt in _dts:
+            for _S in _Ss:
+                FUSED_CASES.append(_shape + (_dt, str(_S), _tile))
+                FUSED_IDS.append("%s%dx%dx%d_t%d_S%d" % (("f32_" if _dt == np.float32 else "",) + _shape + (_tile, _S)))
+ATR_NAMES = {row[1]: row[4] for row in TILE_ROWS if row[0] == "atr"}   # tile -> its name in a describe string
 
 
-@pytest.mark.parametrize("m,n,l,dt,splits", FUSED_CASES,
-                         ids=["64x64x16", "128x128x32", "192x256x32", "f32_128x256x32", "64x64x16_S2"])
-def test_fused_form_is_bit_identical(m, n, l, dt, splits, monkeypatch):
+@pytest.mark.parametrize("m,n,l,dt,splits,tile", FUSED_CASES, ids=FUSED_IDS)
+def test_fused_form_is_bit_identical(m, n, l, dt, splits, tile, monkeypatch):
     torch = _torch()
     from glx import _lib, kernels
     if splits is not None:
         monkeypatch.setenv("GLX_ATR_S", splits)
+    if tile is not None:
+        monkeypatch.setenv("GLX_ATR_VARIANT", str(tile))
     gdt = _lib.GLX_F64 if dt == np.float64 else _lib.GLX_F32
     d = _lib.admm_describe(gdt, m, n, l)
     assert "projection=fused" in d, d
     if splits is not None:
         assert "S=%s" % splits in d.split("A^T z=")[1], d
+    if tile is not None:   # the named tile and S were planned
+        assert d.split("A^T z=")[1].split(";")[0] == ATR_NAMES[tile].format(S=splits), d
     rng = np.random.default_rng(m + n + l)
     A = torch.from_numpy(rng.standard_normal((m, n)).astype(dt)).cuda()
     Z = torch.from_numpy((rng.standard_normal((m, l)) * 0.01).astype(dt)).cuda()

@@ -30,7 +30,10 @@ hold rows outside the ball, rows strictly inside it, an all-zero row (which stay
 other row is bit-identical to the first run. gamma_next = 0 leaves a NaN-filled y_out untouched.
 
 2. The fused form (form 1, k_atr_alm) against form 0 (k_alm_inner_panel) on the product that
-kernels.gradient(Qn, y) wrote: every bit of u+ and y+, at the shapes whose plan fuses.
+kernels.gradient(Qn, y) wrote: every bit of u+ and y+, at the shapes whose plan fuses, and on every
+tile built for a fused epilogue by name (GLX_ATR_VARIANT, with one and two K splits where the tile
+takes splits; the tile and S are asserted from the describe string) at n = 128, l = 16 and n = 192,
+l = 32. Both forms are also held to test 1's bars there (P's bar is form 1's).
 
 3. The inner loop (glx_alm_inner_run) against the NumPy loop: within 1e-10 of max |u|. The step
 y -> u+ is non-expansive for t rho <= 1 (a projection after a gradient step of step t <= 1 / ||Qn||),
@@ -59,6 +62,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from tile_cases import ROWS as TILE_ROWS
 
 import alm_dual_ref
 
@@ -221,22 +225,46 @@ def test_inner_step_against_longdouble(n, l, arm, gamma, gnext):
         assert np.array_equal(v[:n - 1], first[:n - 1]), key
 
 
-@pytest.mark.parametrize("n,l", FUSED_SHAPES)
-def test_fused_step_is_bit_identical_to_unfused(n, l):
+# the planner's own tile and splits at FUSED_SHAPES, then every fused tile by name (GLX_ATR_VARIANT)
+# with the K splits it takes under an epilogue, at NT = 1 and at NT = 2 with n not a power of two:
+# four-wave, eight-wave (1028) and 32-column (38, 1038) row ownership, split and not
+FUSED_TILES = [(8, (1, 2)), (1008, (1, 2)), (1028, (1, 2)), (38, (1,)), (1038, (1,))]
+FUSED_ARMS = [(n, l, None, None) for n, l in FUSED_SHAPES] + \
+    [(n, l, tile, S) for n, l in ((128, 16), (192, 32)) for tile, Ss in FUSED_TILES for S in Ss]
+ATR_NAMES = {row[1]: row[4] for row in TILE_ROWS if row[0] == "atr"}   # tile -> its name in a describe string
+
+
+@pytest.mark.parametrize("n,l,tile,S", FUSED_ARMS,
+                         ids=["%d-%d" % a[:2] + ("" if a[2] is None else "-t%d-S%d" % a[2:]) for a in FUSED_ARMS])
+def test_fused_step_is_bit_identical_to_unfused(n, l, tile, S, monkeypatch):
     torch = _torch()
     from glx import _lib, kernels
-    assert "inner step=fused" in _lib.alm_describe(_lib.GLX_F64, n, n, l)
+    if tile is not None:
+        monkeypatch.setenv("GLX_ATR_VARIANT", str(tile))
+        monkeypatch.setenv("GLX_ATR_S", str(S))
+    d = _lib.alm_describe(_lib.GLX_F64, n, n, l)
+    assert "inner step=fused" in d, d
+    if tile is not None:   # the named tile and S were planned
+        assert d.split("Qn y=")[1].split(";")[0] == ATR_NAMES[tile].format(S=S), d
     rng = np.random.default_rng(7 * n + l)
     A = rng.standard_normal((n // 2, n))
     Qn = alm_dual_ref.inner_matrix(A, alm_dual_ref.inverse_factor(A, 100.0), 100.0)
     _, y, J, u = _step_inputs(n, l, 1, seed=n + l)
     Qnd, yd, Jd, ud = _dev(Qn), _dev(y), _dev(J), _dev(u)
     Pd = kernels.gradient(Qnd, yd)
+    Pw = Qn.astype(W).T @ y.astype(W)
+    dP = (n + 2) * EPS * (np.abs(Qn).astype(W).T @ np.abs(y).astype(W))
     for gamma, gnext in ((1.0, 2 / 3), (2 / 8, 2 / 9), (2 / 501, 0.0)):
         f1 = _run_step(1, None, yd, Jd, ud, gamma, gnext, Qnd)
         f0 = _run_step(0, Pd, yd, Jd, ud, gamma, gnext)
         assert torch.equal(f1["u"].view(torch.int64), f0["u"].view(torch.int64))
         assert torch.equal(f1["y"].view(torch.int64), f0["y"].view(torch.int64))   # (NaN bits where unwritten)
+        # and the step itself under test 1's bars (both forms: they are the same bits)
+        ref = _step_reference(Pw, dP, y, J, u, gamma, gnext)
+        for key, bar in (("u", "bu"), ("y", "by")) if gnext != 0.0 else (("u", "bu"),):
+            err = np.abs(f1[key].cpu().numpy().astype(W) - ref[key])
+            _note(key + "+ tiles", float(np.max(err / np.maximum(ref[bar], np.finfo(np.float64).tiny))))
+            assert np.all(err <= ref[bar]), key
 
 
 # ---------------------------------------------------------------------------------------------

@@ -44,6 +44,9 @@ max that the NaN row feeds (sum ||x_i||, max kkt, sum kkt^2, and the row count) 
 the five sums and the row norms of form 1 (k_atr_cert) and of form 0 on the G it wrote, given m
 (k_cert_panel), bit for bit; the whole record and row norms of glx.certificate with fused = 1 and
 fused = 2, bit for bit; G within (m + 2) eps |A|^T |r| of float64 NumPy (the bar the issue sets).
+Beside the planner's own choice, every tile built for a fused epilogue runs by name
+(GLX_ATR_VARIANT, with one and two K splits where the tile takes splits; the tile and S are asserted
+from the describe string) at (64, 64, 16) and (192, 256, 32).
 
 3. Whole certificates. The products' bars, elementwise: dr = (n + 2) eps (|A| |x| + |b|) for
 r = A x - b (the issue's), dg = (m + 2) eps |A|^T |r| + |A|^T dr for g = A^T r. Then
@@ -80,6 +83,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from tile_cases import ROWS as TILE_ROWS
 
 import certificate_ref as cref
 
@@ -234,25 +238,41 @@ def test_row_kernel_against_wider_type(n, l, dt):
     assert np.array_equal(out2["row_norms"].cpu().numpy(), rn)
 
 
-FUSED_CASES = [(64, 64, 16, np.float64, None), (128, 128, 32, np.float64, None),
-               (192, 256, 32, np.float64, None), (128, 256, 32, np.float32, None),
-               (64, 64, 16, np.float64, "2")]
+FUSED_CASES = [(64, 64, 16, np.float64, None, None), (128, 128, 32, np.float64, None, None),
+               (192, 256, 32, np.float64, None, None), (128, 256, 32, np.float32, None, None),
+               (64, 64, 16, np.float64, "2", None)]
+FUSED_IDS = ["64x64x16", "128x128x32", "192x256x32", "f32_128x256x32", "64x64x16_S2"]
+# every fused tile by name (GLX_ATR_VARIANT) with the K splits it takes under an epilogue, at one
+# panel with NT = 1 and at several panels with NT = 2 and m not a power of two: four-wave,
+# eight-wave (1028) and 32-column (38, 1038) row ownership, split and not
+FUSED_TILES = [(8, (np.float64,), (1, 2)), (1008, (np.float64, np.float32), (1, 2)),
+               (1028, (np.float64, np.float32), (1, 2)), (38, (np.float64,), (1,)), (1038, (np.float64,), (1,))]
+for _shape in ((64, 64, 16), (192, 256, 32)):
+    for _tile, _dts, _Ss in FUSED_TILES:
+        for _dt in _dts:
+            for _S in _Ss:
+                FUSED_CASES.append(_shape + (_dt, str(_S), _tile))
+                FUSED_IDS.append("%s%dx%dx%d_t%d_S%d" % (("f32_" if _dt == np.float32 else "",) + _shape + (_tile, _S)))
+ATR_NAMES = {row[1]: row[4] for row in TILE_ROWS if row[0] == "atr"}   # tile -> its name in a describe string
 
 
-@pytest.mark.parametrize("m,n,l,dt,splits", FUSED_CASES,
-                         ids=["64x64x16", "128x128x32", "192x256x32", "f32_128x256x32", "64x64x16_S2"])
-def test_fused_form_is_bit_identical(m, n, l, dt, splits, monkeypatch):
+@pytest.mark.parametrize("m,n,l,dt,splits,tile", FUSED_CASES, ids=FUSED_IDS)
+def test_fused_form_is_bit_identical(m, n, l, dt, splits, tile, monkeypatch):
     torch = _torch()
     import glx
     from glx import _lib, kernels
     from glx.certificate import record
     if splits is not None:
         monkeypatch.setenv("GLX_ATR_S", splits)
+    if tile is not None:
+        monkeypatch.setenv("GLX_ATR_VARIANT", str(tile))
     gdt = _lib.GLX_F64 if dt == np.float64 else _lib.GLX_F32
     d = _lib.certificate_describe(gdt, m, n, l)
     assert "rows=fused" in d, d
     if splits is not None:
         assert "S=%s" % splits in d.split("A^T r=")[1], d
+    if tile is not None:   # the named tile and S were planned
+        assert d.split("A^T r=")[1].split(";")[0] == ATR_NAMES[tile].format(S=splits), d
     rng = np.random.default_rng(m + n + l)
     A = rng.standard_normal((m, n)).astype(dt)
     r = rng.standard_normal((m, l)).astype(dt)
