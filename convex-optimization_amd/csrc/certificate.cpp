@@ -127,10 +127,11 @@ void cert_rows(const CertPlan& pl, bool fused, const T* A, const T* R, const T* 
 
 template <typename T>
 void certificate(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const T* A, const T* X, const T* b,
-                 double mu, int fused_opt, T* G, double* rn, double* out, void* ws, hipStream_t st) {
+                 double mu, int fused_opt, T* G, double* rn, double* out, void* ws, hipStream_t st,
+                 const GroupView* grp) {
   CertWs w;
   cert_carve(pl, m, n, l, ws, &w);
-  const bool fused = use_fused(pl, fused_opt);
+  const bool fused = grp == nullptr && use_fused(pl, fused_opt);
   const int64_t ml = m * l;
   T *r = static_cast<T*>(w.r), *pa = static_cast<T*>(w.pa);
   GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
@@ -139,7 +140,13 @@ void certificate(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const T* A
   const T* xs[3] = {X, nullptr, nullptr};
   launch_ax<T>(pl.a, 1, A, xs, pa, nullptr, 0, st);
   launch_cert_fin<T>(pa, ax_split(pl.a, 1), b, r, ml, Red{w.part, w.ticket, w.rec}, st);
-  cert_rows<T>(pl, fused, A, r, X, mu, G, rn, w, Red{w.part, w.ticket, w.rec + 2}, st);
+  if (grp != nullptr) {   // the group terms on the slabs of the plain product
+    launch_atr<T>(pl.a, A, r, static_cast<T*>(w.gp), st);
+    launch_group_cert<T>(X, static_cast<const T*>(w.gp), pl.a.atr_S, G, rn, grp->ptr, grp->wts, grp->G, n, l,
+                         grp->max_run, mu, Red{w.part, w.ticket, w.rec + 2}, st);
+  } else {
+    cert_rows<T>(pl, fused, A, r, X, mu, G, rn, w, Red{w.part, w.ticket, w.rec + 2}, st);
+  }
   check_launch();
   GLX_HIP(hipMemcpyAsync(out, w.rec, sizeof(double) * kCertRec, hipMemcpyDeviceToHost, st));
   GLX_HIP(hipStreamSynchronize(st));
@@ -147,6 +154,28 @@ void certificate(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const T* A
 }
 
 }  // namespace
+
+void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                     double mu, int fused, void* G_out, double* rownorm_out, double* out, void* ws, size_t wsb,
+                     void* stream, const GroupView* grp) {
+  const CertPlan pl = cert_plan(dtype, m, n, l);
+  check_fused(fused);
+  if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+  if (!A || !X || !b) throw Error{GLX_E_INVALID, "A, X and b must be device pointers"};
+  if (!out) throw Error{GLX_E_INVALID, "null out"};
+  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(b) |
+       reinterpret_cast<uintptr_t>(G_out)) & 15)
+    throw Error{GLX_E_INVALID, "A, X, b, G_out must be 16-byte aligned"};
+  check_ws(pl, m, n, l, ws, wsb);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == GLX_F64)
+    certificate<double>(pl, m, n, l, (const double*)A, (const double*)X, (const double*)b, mu, fused,
+                        (double*)G_out, rownorm_out, out, ws, st, grp);
+  else
+    certificate<float>(pl, m, n, l, (const float*)A, (const float*)X, (const float*)b, mu, fused,
+                       (float*)G_out, rownorm_out, out, ws, st, grp);
+}
+
 }  // namespace glx
 
 using namespace glx;
@@ -172,22 +201,7 @@ int glx_certificate(int dtype, int64_t m, int64_t n, int64_t l, const void* A, c
                     double mu, int fused, void* G_out, double* rownorm_out, double* out, void* ws, size_t wsb,
                     void* stream) {
   return guarded([&] {
-    const CertPlan pl = cert_plan(dtype, m, n, l);
-    check_fused(fused);
-    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
-    if (!A || !X || !b) throw Error{GLX_E_INVALID, "A, X and b must be device pointers"};
-    if (!out) throw Error{GLX_E_INVALID, "null out"};
-    if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(b) |
-         reinterpret_cast<uintptr_t>(G_out)) & 15)
-      throw Error{GLX_E_INVALID, "A, X, b, G_out must be 16-byte aligned"};
-    check_ws(pl, m, n, l, ws, wsb);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == GLX_F64)
-      certificate<double>(pl, m, n, l, (const double*)A, (const double*)X, (const double*)b, mu, fused,
-                          (double*)G_out, rownorm_out, out, ws, st);
-    else
-      certificate<float>(pl, m, n, l, (const float*)A, (const float*)X, (const float*)b, mu, fused,
-                         (float*)G_out, rownorm_out, out, ws, st);
+    certificate_run(dtype, m, n, l, A, X, b, mu, fused, G_out, rownorm_out, out, ws, wsb, stream, nullptr);
   });
 }
 

@@ -753,6 +753,70 @@ __device__ inline unsigned fista_row(const T (&yv)[EPL], const T (&gv)[EPL], con
 }
 
 // ------------------------------------------------------------------------------------------
+// Feature groups (kernels_group.hip; DESIGN.md "Feature groups and weights"). A group is the
+// contiguous run of (ptr[g + 1] - ptr[g]) l elements of the row-major n x l iterate that starts at
+// ptr[g] l; a team of LPG adjacent lanes owns it, lane `sub` taking the elements sub, sub + LPG, ...
+// of the run (adjacent lanes adjacent addresses). GroupRun is what a lane knows of its team's run.
+// ------------------------------------------------------------------------------------------
+template <typename T>
+struct GroupRun {
+  int64_t base, len;   // first element, element count (0 where the team has no group this trip)
+  T w;                 // the group's weight, rounded to T
+  bool ok;
+};
+template <typename T>
+__device__ inline GroupRun<T> group_run(const int* __restrict__ ptr, const double* __restrict__ wts, int64_t grp,
+                                        int64_t G, int64_t l) {
+  GroupRun<T> r;
+  r.ok = grp < G;
+  const int64_t r0 = r.ok ? ptr[grp] : 0, r1 = r.ok ? ptr[grp + 1] : 0;
+  r.base = r0 * l;
+  r.len = (r1 - r0) * l;
+  r.w = r.ok ? (T)wts[grp] : T(1);
+  return r;
+}
+
+// fista_row's arithmetic for one element behind the prox value pv (the same expressions in the
+// same order, so a single-row group of weight 1 differs from the row kernel only in the order of
+// its norm's sum): writes v_next and y_next, adds to acc[0], acc[1], acc[3] and to psq where ok.
+template <typename T>
+__device__ inline void fista_elem(T pv, T yv, T gv, T xk, bool ok, T thres, T theta, T a1, T b1, T& vn, T& yn,
+                                  double (&acc)[4], T& psq) {
+  const T dl = pv - yv;
+  T xo = xk;
+  if (tabs(xo) < thres) xo = T(0);
+  vn = xo + (pv - xo) / theta;
+  const T pt = (tabs(pv) < thres) ? T(0) : pv;
+  yn = a1 * pt + b1 * vn;
+  if (ok) {
+    acc[0] += (double)(gv * dl);
+    acc[1] += (double)(dl * dl);
+    acc[3] = nan_max(acc[3], (double)tabs(pv));
+    psq = psq + pv * pv;
+  }
+}
+
+// The certificate's terms of one group from its three norms (cert_row's selection and NaN rules,
+// with mu w_g in place of mu): gn = ||g_[g]||, xn = ||x_[g]||, kn = ||g_[g] + muw x_[g] / xn||.
+// acc: [sum w_g ||x_[g]||, max ||g_[g]|| / w_g, max kkt, sum kkt^2, nonzero groups]. Returns
+// ||g_[g]|| / w_g (one division in T).
+template <typename T>
+__device__ inline T group_cert_terms(T gn, T xn, T kn, T muw, T w, bool lead, double (&acc)[5]) {
+  T d = gn - muw;
+  d = (d < T(0)) ? T(0) : d;   // NaN compares false and stays
+  const T kkt = (xn == T(0)) ? d : kn;
+  const T gq = gn / w;
+  if (lead) {
+    acc[0] += (double)(w * xn);
+    acc[1] = nan_max(acc[1], (double)gq);
+    acc[2] = nan_max(acc[2], (double)kkt);
+    acc[3] += (double)kkt * (double)kkt;
+    acc[4] += (xn != xn) ? (double)xn : (xn != T(0) ? 1.0 : 0.0);
+  }
+  return gq;
+}
+
+// ------------------------------------------------------------------------------------------
 // Dual ADMM's row step (gl_ADMM_dual.py:44-46, 64-67) for a lane that holds EPL elements of the
 // row (as prox_pgd_row), with g = A^T z, in the reference's evaluation order:
 //   w = x / rho - g,  u+ = (mu w) / max(||w||, mu)  (np.clip(., a_min=mu): NaN stays NaN),

@@ -506,6 +506,67 @@ void launch_scatter_rows(const T* src, const int* idx, int64_t wp, int64_t l, T*
 // out[j] = map[idx[j]] (idx[j] itself where map == NULL), -1 where idx[j] < 0
 void launch_compose_list(const int* map, const int* idx, int64_t wp, int* out, hipStream_t st);
 
+// ---- feature groups and weights (kernels_group.hip, group.cpp; DESIGN.md "Feature groups and weights") ----
+// Groups are the contiguous row ranges [ptr[g], ptr[g + 1]) of the n x l iterate, g < G; wts holds
+// G doubles (rounded to T in the kernels); max_run = the largest range, which picks the lane layout
+// (group_layout names it). nrows = the rows of the arrays (the slab stride is nrows * l): rows from
+// ptr[G] on belong to no group.
+//   launch_group_fista: the FISTA step on S slabs of launch_atr: w = y - t g, per group
+//       xc = w max(||w|| - t mu w_g, 0) / ((||w|| < thres) + ||w||), then fista_row's momentum per
+//       element; red.out = [sum g (xc - y), sum (xc - y)^2, sum_g w_g ||xc_[g]||, max |xc|]; rows past
+//       ptr[G] of xc, vnext, ynext are written 0
+//   launch_group_cert: red.out = [sum_g w_g ||x_[g]||, max_g ||g_[g]|| / w_g, max kkt, sum kkt^2,
+//       nonzero groups]; gout (may be NULL) receives g, rn (may be NULL) ||g_[g]|| / w_g as G doubles
+//   launch_group_cnorm: gcn[g] = sqrt(sum_{i in [g]} cn[i]^2) / w_g; red.out = [max_g gcn[g]]
+//   launch_group_expand: klist = kcnt[0] kept groups, ascending (launch_screen's list and count) ->
+//       rows_out (their rows, ascending, -1 up to ecnt[1]), the reduced ptr_out (kept + 1), w_out,
+//       gcn_out, map_out (map composed: ids of the full problem; map NULL = identity),
+//       ecnt = [rows, rows rounded up to 64]
+std::string group_layout(int64_t max_len);
+template <typename T>
+void launch_group_fista(const T* y, const T* g, int S, const T* xk, T* xc, T* vnext, T* ynext, const int* ptr,
+                        const double* wts, int64_t G, int64_t nrows, int64_t l, int64_t max_run, double t, double mu,
+                        double thres, double theta, double theta_next, Red red, hipStream_t st);
+template <typename T>
+void launch_group_cert(const T* x, const T* g, int S, T* gout, double* rn, const int* ptr, const double* wts,
+                       int64_t G, int64_t nrows, int64_t l, int64_t max_run, double mu, Red red, hipStream_t st);
+void launch_group_cnorm(const double* cn, const int* ptr, const double* wts, int64_t G, int64_t max_run, double* gcn,
+                        Red red, hipStream_t st);
+void launch_group_expand(const int* klist, const int* kcnt, const int* ptr, const double* wts, const double* gcn,
+                         const int* map, int* rows_out, int* ptr_out, double* w_out, double* gcn_out, int* map_out,
+                         int* ecnt, hipStream_t st);
+
+// The groups of a problem as the drivers pass them on: device ptr / wts as above, and the host's
+// figures of the FULL problem (a reduced problem keeps them: they only have to bound its own).
+struct GroupView {
+  const int* ptr = nullptr;
+  const double* wts = nullptr;
+  int64_t G = 0;
+  int64_t max_run = 1;
+  double w_min = 1.0;
+};
+// glx_certificate's body (certificate.cpp): grp == NULL is the row certificate; with groups the
+// A^T pass is launch_atr and the group terms follow (launch_group_cert), rownorm_out then takes G
+// doubles ||g_[g]|| / w_g and fused is ignored. Throws Error.
+void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                     double mu, int fused, void* G_out, double* rownorm_out, double* out, void* ws, size_t wsb,
+                     void* stream, const GroupView* grp);
+// The certified solve (screen.cpp), rows (grp == NULL) or groups: one loop, glx_certified_solve's
+// arguments and checks. With groups the step is launch_atr + launch_group_fista, the screen runs on
+// the G "rows" ||g_[g]|| / w_g against gcn (launch_group_cnorm, computed here) and
+// launch_group_expand turns its list into rows; info->kept and kept_hist then count groups.
+// kept_groups_dev (may be NULL): as kept_rows_dev, for groups; *listed_groups = the entries written.
+size_t certified_bytes(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t G);
+std::string certified_describe(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run);
+void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit, int screen, int check_every,
+                   const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev, void* ws,
+                   size_t wsb, glx_certified_info* info, void* stream, const GroupView* grp,
+                   int32_t* kept_groups_dev, int64_t* listed_groups);
+// The rounding guards, host only (screen.cpp / group.cpp); out = [s_safe, gap+, rho+]
+double gamma_k(double k, double u);
+void group_screen_guard(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run,
+                        double w_min, double gcol_max, double csq, double bn, double* out);
+
 // ---- shared by the two ADMM drivers (defined in admm.cpp) ----
 namespace admm {
 constexpr int kMaxL = 32;    // the Gram kernel and the host Jacobi sweep

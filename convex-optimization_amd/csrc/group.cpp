@@ -1,0 +1,396 @@
+// group.cpp — feature groups and weights (DESIGN.md "Feature groups and weights"): the C entries of
+//   P(x) = 1/2 ||A x - b||_F^2 + mu sum_g w_g ||x_[g]||_F,   [g] = rows ptr[g] .. ptr[g + 1] - 1 of x.
+// The certificate and the certified solve are the row ones' (certificate.cpp certificate_run,
+// screen.cpp certified_run) with a GroupView: this unit validates the caller's host description of
+// the groups before any launch, uploads it behind the callee's workspace, composes the grouped
+// rounding guard and exposes the four kernels of kernels_group.hip one launch at a time.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "glx.h"
+#include "glx_internal.h"
+
+namespace glx {
+namespace {
+
+#define GLX_HIP(expr)                                                                          \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess) throw Error{GLX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)}; \
+  } while (0)
+
+inline void check_launch() {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) throw Error{GLX_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)};
+}
+
+template <typename F>
+int guarded(F&& f) {
+  try {
+    f();
+    return GLX_OK;
+  } catch (const Error& e) {
+    g_last_error = e.msg;
+    return e.code;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return GLX_E_STATE;
+  } catch (...) {
+    g_last_error = "unknown error";
+    return GLX_E_STATE;
+  }
+}
+
+using admm::Carver;
+
+// What the host knows of a valid description: the figures the layout and the guard need.
+struct GroupFacts {
+  int64_t max_run = 1;
+  double w_min = 1.0;
+};
+// GLX_E_INVALID for a description that is not G >= 1 strictly increasing offsets from 0 to n with
+// positive finite weights (host arrays: nothing is launched before this passes).
+GroupFacts check_groups(int64_t n, int64_t G, const int32_t* ptr, const double* wts) {
+  if (G < 1) throw Error{GLX_E_INVALID, "groups: G must be >= 1"};
+  if (!ptr || !wts) throw Error{GLX_E_INVALID, "groups: group_ptr and weights must be host arrays"};
+  if (G > n) throw Error{GLX_E_INVALID, "groups: more groups than rows"};
+  if (ptr[0] != 0) throw Error{GLX_E_INVALID, "groups: group_ptr[0] must be 0"};
+  if ((int64_t)ptr[G] != n) throw Error{GLX_E_INVALID, "groups: group_ptr[G] must be n"};
+  GroupFacts f;
+  f.w_min = std::numeric_limits<double>::infinity();
+  for (int64_t g = 0; g < G; ++g) {
+    const int64_t run = (int64_t)ptr[g + 1] - (int64_t)ptr[g];
+    if (run < 1) throw Error{GLX_E_INVALID, "groups: group_ptr must be strictly increasing"};
+    if (!(wts[g] > 0.0) || !std::isfinite(wts[g]))
+      throw Error{GLX_E_INVALID, "groups: every weight must be positive and finite"};
+    f.max_run = std::max(f.max_run, run);
+    f.w_min = std::min(f.w_min, wts[g]);
+  }
+  return f;
+}
+void check_dims(int dtype, int64_t n, int64_t l) {
+  if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+  if (n <= 0 || l <= 0) throw Error{GLX_E_INVALID, "n, l must be positive"};
+  if (l > kMaxL) throw Error{GLX_E_INVALID, "the group entries take l <= 128"};
+  if (n > (int64_t)0x7fffffc0) throw Error{GLX_E_INVALID, "the group entries take n < 2^31 - 64"};
+}
+void check_ws(size_t need, const void* ws, size_t wsb, const char* who) {
+  if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
+  if (wsb < need) throw Error{GLX_E_INVALID, std::string("workspace too small (") + who + ")"};
+  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
+}
+
+// the description's device copy, behind `head` bytes of the callee's workspace
+struct GroupDev {
+  void* head;
+  int* ptr;
+  double* wts;
+};
+size_t group_carve(size_t head, int64_t G, void* base, GroupDev* out) {
+  Carver c(base);
+  GroupDev d;
+  d.head = c.take(head);
+  d.ptr = static_cast<int*>(c.take(sizeof(int) * (size_t)(G + 1)));
+  d.wts = static_cast<double*>(c.take(sizeof(double) * (size_t)G));
+  if (out) *out = d;
+  return c.off + 256;
+}
+// (the host arrays are the caller's and may go away after the call: the copies are complete on return).
+// A float32 problem takes its weights rounded to float32 here, once, so that the step, the
+// certificate and gcn all speak of the same problem.
+GroupView upload(int dtype, const GroupDev& d, int64_t G, const int32_t* ptr, const double* wts,
+                 const GroupFacts& f, hipStream_t st) {
+  std::vector<double> wr;
+  if (dtype == GLX_F32) {
+    wr.resize((size_t)G);
+    for (int64_t g = 0; g < G; ++g) {
+      wr[(size_t)g] = (double)(float)wts[g];
+      if (!(wr[(size_t)g] > 0.0) || !std::isfinite(wr[(size_t)g]))
+        throw Error{GLX_E_INVALID, "groups: every weight must be positive and finite in float32"};
+    }
+    wts = wr.data();
+  }
+  GLX_HIP(hipMemcpyAsync(d.ptr, ptr, sizeof(int) * (size_t)(G + 1), hipMemcpyHostToDevice, st));
+  GLX_HIP(hipMemcpyAsync(d.wts, wts, sizeof(double) * (size_t)G, hipMemcpyHostToDevice, st));
+  GLX_HIP(hipStreamSynchronize(st));
+  GroupView v;
+  v.ptr = d.ptr;
+  v.wts = d.wts;
+  v.G = G;
+  v.max_run = f.max_run;
+  v.w_min = dtype == GLX_F32 ? (double)(float)f.w_min : f.w_min;
+  return v;
+}
+
+size_t cert_bytes(int dtype, int64_t m, int64_t n, int64_t l) {
+  size_t b = 0;
+  if (glx_certificate_workspace_bytes(dtype, m, n, l, &b) != GLX_OK) throw Error{GLX_E_INVALID, g_last_error};
+  return b;
+}
+
+// the one-launch entries' head: [partials | ticket]
+constexpr size_t kStepHead = sizeof(double) * kMaxRedVals * kMaxBlocks + 256 + kTicketBytes;
+struct StepWs {
+  double* part;
+  unsigned* ticket;
+};
+StepWs step_head(void* head) {
+  Carver c(head);
+  StepWs w;
+  w.part = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals * kMaxBlocks));
+  w.ticket = static_cast<unsigned*>(c.take(kTicketBytes));
+  return w;
+}
+
+}  // namespace
+
+// The grouped rounding guard (DESIGN.md "Feature groups and weights", "The guard"). rec: the group
+// certificate's record of the stored r^ and g^ = A^T r^ in dtype arithmetic. Every quantity is an
+// upper bound; NaN propagates (and then keeps every group in k_screen).
+void group_screen_guard(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run,
+                        double w_min, double gcol_max, double csq, double bn, double* out) {
+  const double u = dtype == GLX_F64 ? DBL_EPSILON : (double)FLT_EPSILON;   // eps of A's dtype
+  const double u64 = DBL_EPSILON;
+  const double rr = rec[0], rb = rec[1], sxw = rec[2], gmax = rec[3];
+  const double rn = std::sqrt(rr);
+  const double K = (double)max_run * (double)l;   // terms of a group's norm
+  const double gm = gamma_k((double)m + 2.0, u), gn = gamma_k((double)n + 2.0, u);
+  const double gK = gamma_k(K + 3.0, u);          // the norm in A's dtype, then the weight's rounding
+  // the stored gcn are low by the column norms' gamma64_{m+2} and their own root and division
+  const double up = (1.0 + gamma_k((double)m + 2.0, u64)) * (1.0 + gamma_k((double)max_run + 3.0, u64));
+  // 1. dual feasibility: ||A_[g]^T r^|| / w_g <= ||g^_[g]|| / w_g + gm (||A_[g]||_F / w_g) ||r^||, the
+  //    per-column bounds summed in squares; the stored maximum may be low by its own gK
+  const double den = gmax * (1.0 + gK) + gm * gcol_max * up * rn;
+  const double s = den > mu ? mu / den : (den <= mu ? 1.0 : den);   // (NaN den: NaN)
+  // 2. the primal value: ||x||_F <= sum_g ||x_[g]|| <= rec[2] / w_min
+  const double dr = gn * std::sqrt(csq) * (sxw / w_min) + u * (rn + 2.0 * bn);
+  const double ml = (double)m * (double)l;
+  const double g_ml = gamma_k(ml + 2.0, u64);
+  const double bar_rr = g_ml * rr;
+  const double bar_rb = g_ml * rn * bn;
+  const double bar_sx = (gK + gamma_k((double)n + 2.0, u64)) * sxw;   // at most n groups in the fp64 sum
+  const double gap = 0.5 * (1.0 + s * s) * rr + s * rb + mu * sxw;
+  const double bars = rn * dr + 0.5 * dr * dr + 0.5 * (1.0 + s * s) * bar_rr + s * bar_rb + mu * bar_sx;
+  const double gap_p = (gap > 0.0 ? gap : (gap <= 0.0 ? 0.0 : gap)) + bars;
+  // 3. the group's own value: s ||A_[g]^T r^|| / w_g <= s rn[g] (1 + gK) + s gm (||A_[g]||_F / w_g) ||r^||
+  //    and rn[g] <= (1 + gm) (||A_[g]||_F / w_g) ||r^||, so both are gcn[g] times a radius
+  double rho = std::sqrt(2.0 * gap_p) + s * gm * rn + s * gK * (1.0 + gm) * rn;
+  rho *= up;
+  out[0] = s;
+  out[1] = gap_p;
+  out[2] = rho;
+}
+
+}  // namespace glx
+
+using namespace glx;
+
+extern "C" {
+
+int glx_group_screen_guard(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l,
+                           int64_t max_run, double w_min, double gcol_max, double col_sumsq, double b_norm,
+                           double* out) {
+  return guarded([&] {
+    if (!rec || !out) throw Error{GLX_E_INVALID, "null argument"};
+    check_dims(dtype, n, l);
+    if (m <= 0) throw Error{GLX_E_INVALID, "m must be positive"};
+    if (max_run < 1 || max_run > n) throw Error{GLX_E_INVALID, "max_run must be in 1 .. n"};
+    if (!(w_min > 0.0) || !std::isfinite(w_min)) throw Error{GLX_E_INVALID, "w_min must be positive and finite"};
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    group_screen_guard(rec, mu, dtype, m, n, l, max_run, w_min, gcol_max, col_sumsq, b_norm, out);
+  });
+}
+
+int glx_group_certificate_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    if (G < 1 || G > n) throw Error{GLX_E_INVALID, "groups: G must be in 1 .. n"};
+    *bytes = group_carve(cert_bytes(dtype, m, n, l), G, nullptr, nullptr);
+  });
+}
+
+int glx_group_certificate_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, char* out,
+                                   size_t cap) {
+  return guarded([&] {
+    if (!out || cap == 0) throw Error{GLX_E_INVALID, "null out"};
+    check_dims(dtype, n, l);
+    if (max_run < 1 || max_run > n) throw Error{GLX_E_INVALID, "max_run must be in 1 .. n"};
+    const GemmPlan p = admm::a_plan(dtype, m, n, l);
+    std::snprintf(out, cap, "A x=%s; A^T r=%s; groups=group kernel (k_group_cert, %s)", admm::plan_field(p, 0).c_str(),
+                  admm::plan_field(p, 3).c_str(), group_layout(max_run * l).c_str());
+  });
+}
+
+int glx_group_certificate(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                          double mu, int64_t G, const int32_t* group_ptr, const double* weights, void* G_out,
+                          double* groupnorm_out, double* out, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_dims(dtype, n, l);
+    const GroupFacts f = check_groups(n, G, group_ptr, weights);
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    if (!A || !X || !b) throw Error{GLX_E_INVALID, "A, X and b must be device pointers"};
+    if (!out) throw Error{GLX_E_INVALID, "null out"};
+    const size_t head = cert_bytes(dtype, m, n, l);
+    check_ws(group_carve(head, G, nullptr, nullptr), ws, wsb, "glx_group_certificate_workspace_bytes");
+    GroupDev d;
+    group_carve(head, G, ws, &d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const GroupView v = upload(dtype, d, G, group_ptr, weights, f, st);
+    certificate_run(dtype, m, n, l, A, X, b, mu, 0, G_out, groupnorm_out, out, d.head, head, stream, &v);
+  });
+}
+
+int glx_group_certified_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, int screen,
+                                        size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    if (G < 1 || G > n) throw Error{GLX_E_INVALID, "groups: G must be in 1 .. n"};
+    *bytes = group_carve(certified_bytes(dtype, m, n, l, screen != 0, G), G, nullptr, nullptr);
+  });
+}
+
+int glx_group_certified_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, int screen, char* out,
+                                 size_t cap) {
+  return guarded([&] {
+    if (!out || cap == 0) throw Error{GLX_E_INVALID, "null out"};
+    if (max_run < 1 || max_run > n) throw Error{GLX_E_INVALID, "max_run must be in 1 .. n"};
+    std::snprintf(out, cap, "%s", certified_describe(dtype, m, n, l, screen != 0, max_run).c_str());
+  });
+}
+
+int glx_group_certified_solve(const glx_problem* prob, int64_t G, const int32_t* group_ptr, const double* weights,
+                              double t, double tol, int64_t maxit, int screen, int check_every,
+                              const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev,
+                              int32_t* kept_groups_dev, void* ws, size_t wsb, glx_group_certified_info* info,
+                              void* stream) {
+  return guarded([&] {
+    if (!prob || !info) throw Error{GLX_E_INVALID, "null problem/info"};
+    if (prob->comm != nullptr) throw Error{GLX_E_INVALID, "the certified solve is single-GPU: comm must be NULL"};
+    check_dims(prob->dtype, prob->n, prob->l);
+    const GroupFacts f = check_groups(prob->n, G, group_ptr, weights);
+    const size_t head = certified_bytes(prob->dtype, prob->m, prob->n, prob->l, screen != 0, G);
+    check_ws(group_carve(head, G, nullptr, nullptr), ws, wsb, "glx_group_certified_workspace_bytes");
+    if (!prob->A || !prob->b || !prob->x) throw Error{GLX_E_INVALID, "A, b and x must be device pointers"};
+    GroupDev d;
+    group_carve(head, G, ws, &d);
+    const GroupView v = upload(prob->dtype, d, G, group_ptr, weights, f, static_cast<hipStream_t>(stream));
+    std::memset(info, 0, sizeof *info);
+    int64_t listed_groups = 0;
+    certified_run(prob, t, tol, maxit, screen, check_every, col_norms_dev, col_stats, kept_rows_dev, d.head, head,
+                  &info->base, stream, &v, kept_groups_dev, &listed_groups);
+    info->kept_groups = screen != 0 ? info->base.kept : G;
+    info->listed_groups = listed_groups;
+    info->max_run = f.max_run;
+  });
+}
+
+/* ---- one launch at a time ---- */
+
+int glx_group_workspace_bytes(int64_t G, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    if (G < 1) throw Error{GLX_E_INVALID, "groups: G must be >= 1"};
+    *bytes = group_carve(kStepHead, G, nullptr, nullptr);
+  });
+}
+
+int glx_group_step(int dtype, int64_t n, int64_t rows, int64_t l, int64_t G, const int32_t* group_ptr,
+                   const double* weights, const void* y, const void* g, int S, const void* xk, double t, double mu,
+                   double thres, double theta, double theta_next, void* xc, void* vnext, void* ynext,
+                   void* sums_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_dims(dtype, n, l);
+    const GroupFacts f = check_groups(n, G, group_ptr, weights);
+    if (rows < n || rows > n + 63) throw Error{GLX_E_INVALID, "rows must be in n .. n + 63 (the padded width)"};
+    if (S < 1 || S > kMaxSplit) throw Error{GLX_E_INVALID, "S must be in 1 .. 64"};
+    if (!y || !g || !xk || !xc || !vnext || !ynext || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
+    check_ws(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, "glx_group_workspace_bytes");
+    GroupDev d;
+    group_carve(kStepHead, G, ws, &d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const GroupView v = upload(dtype, d, G, group_ptr, weights, f, st);
+    const StepWs w = step_head(d.head);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    const Red red{w.part, w.ticket, static_cast<double*>(sums_dev)};
+    if (dtype == GLX_F64)
+      launch_group_fista<double>((const double*)y, (const double*)g, S, (const double*)xk, (double*)xc,
+                                 (double*)vnext, (double*)ynext, v.ptr, v.wts, G, rows, l, v.max_run, t, mu, thres,
+                                 theta, theta_next, red, st);
+    else
+      launch_group_fista<float>((const float*)y, (const float*)g, S, (const float*)xk, (float*)xc, (float*)vnext,
+                                (float*)ynext, v.ptr, v.wts, G, rows, l, v.max_run, t, mu, thres, theta, theta_next,
+                                red, st);
+    check_launch();
+  });
+}
+
+int glx_group_certificate_step(int dtype, int64_t n, int64_t l, int64_t G, const int32_t* group_ptr,
+                               const double* weights, const void* x, const void* g, int S, double mu, void* gout,
+                               double* groupnorm_out, void* sums_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_dims(dtype, n, l);
+    const GroupFacts f = check_groups(n, G, group_ptr, weights);
+    if (S < 1 || S > kMaxSplit) throw Error{GLX_E_INVALID, "S must be in 1 .. 64"};
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    if (!x || !g || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
+    check_ws(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, "glx_group_workspace_bytes");
+    GroupDev d;
+    group_carve(kStepHead, G, ws, &d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const GroupView v = upload(dtype, d, G, group_ptr, weights, f, st);
+    const StepWs w = step_head(d.head);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    const Red red{w.part, w.ticket, static_cast<double*>(sums_dev)};
+    if (dtype == GLX_F64)
+      launch_group_cert<double>((const double*)x, (const double*)g, S, (double*)gout, groupnorm_out, v.ptr, v.wts, G,
+                                n, l, v.max_run, mu, red, st);
+    else
+      launch_group_cert<float>((const float*)x, (const float*)g, S, (float*)gout, groupnorm_out, v.ptr, v.wts, G, n,
+                               l, v.max_run, mu, red, st);
+    check_launch();
+  });
+}
+
+int glx_group_cnorm(int64_t n, int64_t G, const int32_t* group_ptr, const double* weights,
+                    const double* col_norms_dev, double* gcn_dev, double* max_dev, void* ws, size_t wsb,
+                    void* stream) {
+  return guarded([&] {
+    check_dims(GLX_F64, n, 1);
+    const GroupFacts f = check_groups(n, G, group_ptr, weights);
+    if (!col_norms_dev || !gcn_dev || !max_dev) throw Error{GLX_E_INVALID, "null argument"};
+    check_ws(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, "glx_group_workspace_bytes");
+    GroupDev d;
+    group_carve(kStepHead, G, ws, &d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const GroupView v = upload(GLX_F64, d, G, group_ptr, weights, f, st);
+    const StepWs w = step_head(d.head);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    launch_group_cnorm(col_norms_dev, v.ptr, v.wts, G, v.max_run, gcn_dev, Red{w.part, w.ticket, max_dev}, st);
+    check_launch();
+  });
+}
+
+int glx_group_expand(const int32_t* kept_dev, const int32_t* kept_count_dev, const int32_t* group_ptr_dev,
+                     const double* weights_dev, const double* gcn_dev, const int32_t* map_dev, int32_t* rows_out,
+                     int32_t* group_ptr_out, double* weights_out, double* gcn_out, int32_t* map_out,
+                     int32_t* count_out, void* stream) {
+  return guarded([&] {
+    if (!kept_dev || !kept_count_dev || !group_ptr_dev || !weights_dev || !gcn_dev || !rows_out || !group_ptr_out ||
+        !weights_out || !gcn_out || !map_out || !count_out)
+      throw Error{GLX_E_INVALID, "null argument"};
+    launch_group_expand(kept_dev, kept_count_dev, group_ptr_dev, weights_dev, gcn_dev, map_dev, rows_out,
+                        group_ptr_out, weights_out, gcn_out, map_out, count_out, static_cast<hipStream_t>(stream));
+    check_launch();
+  });
+}
+
+}  // extern "C"

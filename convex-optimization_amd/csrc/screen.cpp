@@ -11,6 +11,11 @@
 // the FISTA epilogue of A^T r (launch_atr_fista) or, where the plan does not fuse, launch_atr and the
 // row kernel (launch_fista_trial); thres is the dtype's smallest normal number, with which
 // fista_row's denominator switch and hard threshold are no-ops. Single GPU; beside certificate.cpp.
+// The same loop solves the grouped problem mu sum_g w_g ||x_[g]||_F (DESIGN.md "Feature groups and
+// weights"; entries in group.cpp): with a GroupView the step is launch_atr + launch_group_fista, the
+// certificate takes the view, the screen runs on the G "rows" ||g_[g]|| / w_g against
+// ||A_[g]||_F / w_g under group_screen_guard, and launch_group_expand turns the kept groups into the
+// row list a compaction gathers with. Without a view every call and every byte is the row solve's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +32,14 @@
 #include "glx_internal.h"
 
 namespace glx {
+
+// gamma_k = k u / (1 - k u): the bar of a k-term dot product in unit roundoff u (infinite once
+// k u >= 1, which switches screening off)
+double gamma_k(double k, double u) {
+  const double ku = k * u;
+  return ku < 1.0 ? ku / (1.0 - ku) : std::numeric_limits<double>::infinity();
+}
+
 namespace {
 
 #define GLX_HIP(expr)                                                                          \
@@ -61,13 +74,6 @@ using admm::Carver;
 using admm::plan_field;
 
 inline int64_t pad64(int64_t v) { return (v + 63) / 64 * 64; }
-
-// gamma_k = k u / (1 - k u): the bar of a k-term dot product in unit roundoff u (infinite once
-// k u >= 1, which switches screening off)
-double gamma_k(double k, double u) {
-  const double ku = k * u;
-  return ku < 1.0 ? ku / (1.0 - ku) : std::numeric_limits<double>::infinity();
-}
 
 // The rounding guard (DESIGN.md "Certified solve and screening", "The guard, term by term").
 // rec: the certificate's record of the stored residual r^ and g^ = A^T r^ in dtype arithmetic.
@@ -163,8 +169,13 @@ struct Ws {
   void* abuf[2];
   size_t cert_bytes;
   int64_t cap[2];
+  // groups (G > 0): the two reduced descriptions a compaction alternates between, the full
+  // problem's gcn, and the screen's list of kept groups
+  int *gptr[2], *gmap[2], *glist;
+  double *gw[2], *ggcn[2], *gcn_full;
 };
-size_t carve(int dtype, int64_t m, int64_t n, int64_t l, bool screen, bool own_norms, void* base, Ws* out) {
+size_t carve(int dtype, int64_t m, int64_t n, int64_t l, bool screen, bool own_norms, void* base, Ws* out,
+             int64_t G = 0) {
   const size_t es = dtype == GLX_F64 ? 8 : 4;
   const Extent e = extent(dtype, m, n, l, screen);
   const int64_t np = pad64(n);
@@ -193,15 +204,24 @@ size_t carve(int dtype, int64_t m, int64_t n, int64_t l, bool screen, bool own_n
   w.cap[0] = screen ? buf_width(n) : 0;
   w.cap[1] = screen ? buf_width(w.cap[0]) : 0;
   for (int i = 0; i < 2; ++i) w.abuf[i] = c.take(es * (size_t)m * (size_t)w.cap[i]);
+  for (int i = 0; i < 2; ++i) {   // (behind everything the row solve uses: its layout is unchanged)
+    w.gptr[i] = static_cast<int*>(c.take(G > 0 ? sizeof(int) * (size_t)(G + 1) : 0));
+    w.gmap[i] = static_cast<int*>(c.take(sizeof(int) * (size_t)G));
+    w.gw[i] = static_cast<double*>(c.take(sizeof(double) * (size_t)G));
+    w.ggcn[i] = static_cast<double*>(c.take(sizeof(double) * (size_t)G));
+  }
+  w.gcn_full = static_cast<double*>(c.take(sizeof(double) * (size_t)G));
+  w.glist = static_cast<int*>(c.take(G > 0 ? sizeof(int) * (size_t)pad64(G) : 0));
   if (out) *out = w;
   return c.off + 256;
 }
 
-std::string describe_certified(int dtype, int64_t m, int64_t n, int64_t l, bool screen) {
+std::string describe_certified(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run = 0) {
   const CPlan p = cplan(dtype, m, n, l);
   std::string s = "FISTA, fixed step, exact prox; A y=" + plan_field(p.a, 0) + "; A^T r=" + plan_field(p.a, 3) +
                   "; step=";
-  s += p.fuse ? "fused (k_atr_fista, the A^T r epilogue)" : "row kernel (k_fista_trial)";
+  if (max_run > 0) s += "group kernel (k_group_fista, " + group_layout(max_run * l) + ")";
+  else s += p.fuse ? "fused (k_atr_fista, the A^T r epilogue)" : "row kernel (k_fista_trial)";
   s += screen ? "; screening=gap-safe, compaction to multiples of 64 at <= 0.9 of the width" : "; screening=off";
   return s;
 }
@@ -222,7 +242,11 @@ Composed compose(const double* rec, double mu) {
 }
 
 void cert_call(int dtype, int64_t m, int64_t w, int64_t l, const void* A, const void* x, const void* b, double mu,
-               double* rn, double* rec, const Ws& ws, hipStream_t st) {
+               double* rn, double* rec, const Ws& ws, hipStream_t st, const GroupView* grp = nullptr) {
+  if (grp != nullptr) {   // (rn: ||g_[g]|| / w_g of the grp->G groups)
+    certificate_run(dtype, m, w, l, A, x, b, mu, 0, nullptr, rn, rec, ws.cert, ws.cert_bytes, st, grp);
+    return;
+  }
   const int rc = glx_certificate(dtype, m, w, l, A, x, b, mu, 0, nullptr, rn, rec, ws.cert, ws.cert_bytes, st);
   if (rc != GLX_OK) throw Error{rc, "certified solve: " + g_last_error};
 }
@@ -230,9 +254,10 @@ void cert_call(int dtype, int64_t m, int64_t w, int64_t l, const void* A, const 
 template <typename T>
 void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T* X, double mu, double t,
            double tol, int64_t maxit, bool screen, int check_every, const double* cn_in, const double* cstats_in,
-           int32_t* kept_rows, void* wsp, glx_certified_info* info, hipStream_t st) {
+           int32_t* kept_rows, void* wsp, glx_certified_info* info, hipStream_t st, const GroupView* grp,
+           int32_t* kept_groups, int64_t* listed_groups) {
   Ws w;
-  carve(dtype, m, n, l, screen, cn_in == nullptr, wsp, &w);
+  carve(dtype, m, n, l, screen, cn_in == nullptr, wsp, &w, grp != nullptr ? grp->G : 0);
   const size_t es = sizeof(T);
   const double thres = std::is_same<T, double>::value ? DBL_MIN : (double)FLT_MIN;
   const int64_t ml = m * l;
@@ -247,7 +272,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
   const Red red0{w.part, w.ticket, w.red}, red1{w.part, w.ticket, w.red + 4}, red2{w.part, w.ticket, w.red + 10};
 
   // the column figures and ||b||_F (screening only)
-  double cmax = 0.0, csq = 0.0, bn = 0.0;
+  double cmax = 0.0, csq = 0.0, bn = 0.0, gcol_max = 0.0;
   const double* cn = nullptr;
   if (screen) {
     if (cn_in != nullptr) {
@@ -271,7 +296,20 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
       cmax = h[1];
       csq = h[2];
     }
+    if (grp != nullptr) {   // gcn[g] = ||A_[g]||_F / w_g and its maximum, which stands in for cmax
+      launch_group_cnorm(cn, grp->ptr, grp->wts, grp->G, grp->max_run, w.gcn_full,
+                         Red{w.part, w.ticket, w.red + 12}, st);
+      check_launch();
+      GLX_HIP(hipMemcpyAsync(&gcol_max, w.red + 12, sizeof(double), hipMemcpyDeviceToHost, st));
+      GLX_HIP(hipStreamSynchronize(st));
+    }
   }
+  // the groups of the current (reduced) problem; gmap: its groups -> the full problem's (NULL: identity)
+  GroupView gcur = grp != nullptr ? *grp : GroupView{};
+  const double* gcn = w.gcn_full;
+  const int* gmap = nullptr;
+  int gside = 0;             // the description the next k_group_expand writes
+  int64_t listed_g = 0;      // groups the last screen kept (valid with `listed`)
 
   // the current (reduced) problem
   const T* Ac = A;
@@ -284,7 +322,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     *yn = static_cast<T*>(w.x[3]), *vn = static_cast<T*>(w.x[4]);
   GLX_HIP(hipMemcpyAsync(x, X, es * n * l, hipMemcpyDeviceToDevice, st));
   GLX_HIP(hipMemcpyAsync(y, X, es * n * l, hipMemcpyDeviceToDevice, st));
-  info->fused = pl.fuse ? 1 : 0;
+  info->fused = pl.fuse && grp == nullptr ? 1 : 0;
 
   double target = tol;
   int64_t k = 1;       // momentum index: theta = 2 / (k + 1)
@@ -304,7 +342,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
       launch_scatter_rows<T>(x, map, wc, l, X, st);
       check_launch();
     }
-    cert_call(dtype, m, n, l, A, X, b, mu, nullptr, info->cert, w, st);
+    cert_call(dtype, m, n, l, A, X, b, mu, nullptr, info->cert, w, st, grp);
     info->passes += 2.0;
     return compose(info->cert, mu);
   };
@@ -313,23 +351,33 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
   // where it pays, a compaction. Returns true when the reduced problem meets `target`.
   auto check = [&]() -> bool {
     ++info->checks;
-    cert_call(dtype, m, wc, l, Ac, x, b, mu, w.rn, rec, w, st);
+    cert_call(dtype, m, wc, l, Ac, x, b, mu, w.rn, rec, w, st, grp != nullptr ? &gcur : nullptr);
     info->passes += 2.0 * (double)wc / (double)n;
     const Composed c = compose(rec, mu);
     info->inner_rel_gap = c.rel;
     const bool met = c.rel <= target;
     if (!screen) return met;
     double gd[3];
-    screen_guard(rec, mu, dtype, m, wc, l, cmax, csq, bn, gd);
     const double mu_lo = mu * (1.0 - 4.0 * DBL_EPSILON);   // the test's own three roundings in fp64
-    launch_screen(w.rn, cn, wc, gd[0], gd[2], mu_lo, nullptr, w.list, w.cnt, w.bal, w.sticket, st);
-    check_launch();
-    int hc[2];
-    GLX_HIP(hipMemcpyAsync(hc, w.cnt, sizeof hc, hipMemcpyDeviceToHost, st));
+    int hc[4] = {0, 0, 0, 0};
+    if (grp != nullptr) {   // the same test on the G "rows" of groups, then their rows
+      group_screen_guard(rec, mu, dtype, m, wc, l, grp->max_run, grp->w_min, gcol_max, csq, bn, gd);
+      launch_screen(w.rn, gcn, gcur.G, gd[0], gd[2], mu_lo, nullptr, w.glist, w.cnt, w.bal, w.sticket, st);
+      launch_group_expand(w.glist, w.cnt, gcur.ptr, gcur.wts, gcn, gmap, w.list, w.gptr[gside], w.gw[gside],
+                          w.ggcn[gside], w.gmap[gside], w.cnt + 2, st);
+      check_launch();
+      GLX_HIP(hipMemcpyAsync(hc, w.cnt, sizeof hc, hipMemcpyDeviceToHost, st));
+    } else {
+      screen_guard(rec, mu, dtype, m, wc, l, cmax, csq, bn, gd);
+      launch_screen(w.rn, cn, wc, gd[0], gd[2], mu_lo, nullptr, w.list, w.cnt, w.bal, w.sticket, st);
+      check_launch();
+      GLX_HIP(hipMemcpyAsync(hc, w.cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
     GLX_HIP(hipStreamSynchronize(st));
-    const int64_t kept = hc[0], wp = hc[1];
+    const int64_t kept = hc[0], wp = grp != nullptr ? hc[3] : hc[1];   // (kept counts groups there)
     info->kept = kept;
     listed = wp;   // w.list names the rows of the current problem that are not proven zero
+    listed_g = kept;
     if (met || wp * 10 > wc * 9) return met;
     if (kept == 0) {   // every row is zero at the optimum
       all_zero = true;
@@ -344,7 +392,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     launch_gather_cols<T>(Ac, m, wc, w.list, wp, An, st);
     launch_gather_rows<T>(x, w.list, wp, l, xc, st);
     double* cnn = w.cn[cn == w.cn[0] ? 1 : 0];
-    launch_gather_rows<double>(cn, w.list, wp, 1, cnn, st);
+    if (grp == nullptr) launch_gather_rows<double>(cn, w.list, wp, 1, cnn, st);
     int* mapn = w.map[mapi ^ 1];
     launch_compose_list(map, w.list, wp, mapn, st);
     check_launch();
@@ -353,7 +401,15 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     GLX_HIP(hipMemcpyAsync(y, x, es * wp * l, hipMemcpyDeviceToDevice, st));   // the momentum restarts
     k = 1;
     Ac = An;
-    cn = cnn;
+    if (grp == nullptr) cn = cnn;
+    if (grp != nullptr) {   // k_group_expand wrote the reduced description beside the row list
+      gcur.ptr = w.gptr[gside];
+      gcur.wts = w.gw[gside];
+      gcur.G = kept;
+      gcn = w.ggcn[gside];
+      gmap = w.gmap[gside];
+      gside ^= 1;
+    }
     map = mapn;
     mapi ^= 1;
     side ^= 1;
@@ -372,7 +428,11 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     launch_ax<T>(pl.a, 1, Ac, xs, static_cast<T*>(w.pa), nullptr, 0, st);
     launch_cert_fin<T>(static_cast<T*>(w.pa), ax_split(pl.a, 1), b, r, ml, red0, st);
     T* gp = static_cast<T*>(w.gp);
-    if (pl.fuse) {
+    if (grp != nullptr) {   // the grouped step is never fused: A^T r, then the group kernel on its slabs
+      launch_atr<T>(pl.a, Ac, r, gp, st);
+      launch_group_fista<T>(y, gp, pl.a.atr_S, x, xc, vn, yn, gcur.ptr, gcur.wts, gcur.G, wc, l, grp->max_run, t, mu,
+                            thres, theta, theta_next, red1, st);
+    } else if (pl.fuse) {
       launch_atr_fista<T>(pl.a, Ac, r, static_cast<T*>(w.g), y, x, xc, vn, yn, t, mu, thres, theta, theta_next, red1,
                           st, Pub{}, pl.a.atr_S > 1 ? gp : nullptr, w.pcnt);
     } else {
@@ -388,7 +448,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     info->passes += 2.0 * (double)wc / (double)n;
   };
 
-  info->kept = n;
+  info->kept = grp != nullptr ? grp->G : n;
   Composed full{};
   for (int round = 0;; ++round) {
     info->rounds = round + 1;
@@ -413,6 +473,13 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
   } else if (kept_rows != nullptr && wc > 0 && listed < 0 && map != nullptr) {
     GLX_HIP(hipMemcpyAsync(kept_rows, map, sizeof(int) * wc, hipMemcpyDeviceToDevice, st));
     info->listed = wc;
+  }
+  if (listed_groups != nullptr) *listed_groups = 0;
+  if (grp != nullptr && kept_groups != nullptr && wc > 0 && (listed > 0 || gmap != nullptr)) {
+    const int* src = listed > 0 ? w.gmap[gside] : gmap;   // the last expand's map, or the current problem's
+    const int64_t cnt = listed > 0 ? listed_g : gcur.G;
+    GLX_HIP(hipMemcpyAsync(kept_groups, src, sizeof(int) * cnt, hipMemcpyDeviceToDevice, st));
+    if (listed_groups != nullptr) *listed_groups = cnt;
   }
   GLX_HIP(hipStreamSynchronize(st));
   info->iters = it;
@@ -447,6 +514,49 @@ size_t step_carve(int64_t m, int64_t n, void* base, StepWs* out) {
 }
 
 }  // namespace
+
+size_t certified_bytes(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t G) {
+  check_shape(dtype, m, n, l);
+  return carve(dtype, m, n, l, screen, true, nullptr, nullptr, G);
+}
+
+std::string certified_describe(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run) {
+  check_shape(dtype, m, n, l);
+  return describe_certified(dtype, m, n, l, screen, max_run);
+}
+
+void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit, int screen, int check_every,
+                   const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev, void* ws,
+                   size_t wsb, glx_certified_info* info, void* stream, const GroupView* grp,
+                   int32_t* kept_groups_dev, int64_t* listed_groups) {
+  if (!prob || !info) throw Error{GLX_E_INVALID, "null problem/info"};
+  if (prob->comm != nullptr) throw Error{GLX_E_INVALID, "the certified solve is single-GPU: comm must be NULL"};
+  check_shape(prob->dtype, prob->m, prob->n, prob->l);
+  if (!(prob->mu0 >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+  if (!(t > 0.0) || !std::isfinite(t)) throw Error{GLX_E_INVALID, "the step t must be positive and finite"};
+  if (!(tol > 0.0)) throw Error{GLX_E_INVALID, "tol must be positive"};
+  if (maxit < 0) throw Error{GLX_E_INVALID, "negative iteration limit"};
+  if (check_every < 1) throw Error{GLX_E_INVALID, "check_every must be >= 1"};
+  if (!prob->A || !prob->b || !prob->x) throw Error{GLX_E_INVALID, "A, b and x must be device pointers"};
+  if ((reinterpret_cast<uintptr_t>(prob->A) | reinterpret_cast<uintptr_t>(prob->b) |
+       reinterpret_cast<uintptr_t>(prob->x)) & 15)
+    throw Error{GLX_E_INVALID, "A, b, x must be 16-byte aligned"};
+  if ((col_norms_dev != nullptr) != (col_stats != nullptr))
+    throw Error{GLX_E_INVALID, "col_norms_dev and col_stats go together"};
+  check_ws(carve(prob->dtype, prob->m, prob->n, prob->l, screen != 0, true, nullptr, nullptr,
+                 grp != nullptr ? grp->G : 0),
+           ws, wsb, grp != nullptr ? "glx_group_certified_workspace_bytes" : "glx_certified_workspace_bytes");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (prob->dtype == GLX_F64)
+    solve<double>(prob->dtype, prob->m, prob->n, prob->l, (const double*)prob->A, (const double*)prob->b,
+                  (double*)prob->x, prob->mu0, t, tol, maxit, screen != 0, check_every, col_norms_dev, col_stats,
+                  kept_rows_dev, ws, info, st, grp, kept_groups_dev, listed_groups);
+  else
+    solve<float>(prob->dtype, prob->m, prob->n, prob->l, (const float*)prob->A, (const float*)prob->b,
+                 (float*)prob->x, prob->mu0, t, tol, maxit, screen != 0, check_every, col_norms_dev, col_stats,
+                 kept_rows_dev, ws, info, st, grp, kept_groups_dev, listed_groups);
+}
+
 }  // namespace glx
 
 using namespace glx;
@@ -539,31 +649,8 @@ int glx_certified_solve(const glx_problem* prob, double t, double tol, int64_t m
                         const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev,
                         void* ws, size_t wsb, glx_certified_info* info, void* stream) {
   return guarded([&] {
-    if (!prob || !info) throw Error{GLX_E_INVALID, "null problem/info"};
-    if (prob->comm != nullptr) throw Error{GLX_E_INVALID, "the certified solve is single-GPU: comm must be NULL"};
-    check_shape(prob->dtype, prob->m, prob->n, prob->l);
-    if (!(prob->mu0 >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
-    if (!(t > 0.0) || !std::isfinite(t)) throw Error{GLX_E_INVALID, "the step t must be positive and finite"};
-    if (!(tol > 0.0)) throw Error{GLX_E_INVALID, "tol must be positive"};
-    if (maxit < 0) throw Error{GLX_E_INVALID, "negative iteration limit"};
-    if (check_every < 1) throw Error{GLX_E_INVALID, "check_every must be >= 1"};
-    if (!prob->A || !prob->b || !prob->x) throw Error{GLX_E_INVALID, "A, b and x must be device pointers"};
-    if ((reinterpret_cast<uintptr_t>(prob->A) | reinterpret_cast<uintptr_t>(prob->b) |
-         reinterpret_cast<uintptr_t>(prob->x)) & 15)
-      throw Error{GLX_E_INVALID, "A, b, x must be 16-byte aligned"};
-    if ((col_norms_dev != nullptr) != (col_stats != nullptr))
-      throw Error{GLX_E_INVALID, "col_norms_dev and col_stats go together"};
-    check_ws(carve(prob->dtype, prob->m, prob->n, prob->l, screen != 0, true, nullptr, nullptr), ws, wsb,
-             "glx_certified_workspace_bytes");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (prob->dtype == GLX_F64)
-      solve<double>(prob->dtype, prob->m, prob->n, prob->l, (const double*)prob->A, (const double*)prob->b,
-                    (double*)prob->x, prob->mu0, t, tol, maxit, screen != 0, check_every, col_norms_dev, col_stats,
-                    kept_rows_dev, ws, info, st);
-    else
-      solve<float>(prob->dtype, prob->m, prob->n, prob->l, (const float*)prob->A, (const float*)prob->b,
-                   (float*)prob->x, prob->mu0, t, tol, maxit, screen != 0, check_every, col_norms_dev, col_stats,
-                   kept_rows_dev, ws, info, st);
+    certified_run(prob, t, tol, maxit, screen, check_every, col_norms_dev, col_stats, kept_rows_dev, ws, wsb, info,
+                  stream, nullptr, nullptr, nullptr);
   });
 }
 

@@ -15,12 +15,15 @@ Public surface:
     ``from glx.certificate import compose, record``);
   * ``solve_certified(A, b, mu)`` — a solve to a stated relative duality gap with gap-safe screening,
     and ``path(A, b)`` — the same over a decreasing sequence of mu, warm-started (``glx/screen.py``);
+  * ``groups=`` / ``weights=`` on ``certificate``, ``mu_max``, ``solve_certified`` and ``path`` — the
+    classical group lasso over contiguous feature groups with weights, and ``group_order(labels)``,
+    the host-only helper that sorts arbitrary labels into such groups;
   * ``dist`` — row sharding + RCCL communicator.
 """
 from ._lib import LIB_PATH, GlxError, lib  # noqa: F401
 from .solver import Session, solve  # noqa: F401
-from .certificate import certificate, mu_max  # noqa: F401
+from .certificate import certificate, group_order, mu_max  # noqa: F401
 from .screen import path, solve_certified  # noqa: F401
 
 __all__ = ["solve", "Session", "lib", "LIB_PATH", "GlxError", "certificate", "mu_max",
-           "solve_certified", "path"]
+           "solve_certified", "path", "group_order"]

@@ -77,6 +77,12 @@ class GlxCertifiedInfo(ctypes.Structure):
                 ("cert", c_double * 8), ("kept_hist", c_int64 * 64)]
 
 
+class GlxGroupCertifiedInfo(ctypes.Structure):
+    """glx_group_certified_info (include/glx.h): what glx_group_certified_solve reports."""
+    _fields_ = [("base", GlxCertifiedInfo), ("kept_groups", c_int64), ("listed_groups", c_int64),
+                ("max_run", c_int64), ("reserved", c_int64)]
+
+
 class GlxError(RuntimeError):
     """Error returned by libglx (message from glx_last_error())."""
 
@@ -219,6 +225,33 @@ _SIGS = {
     "glx_certified_solve": (c_int, [POINTER(GlxProblem), c_double, c_double, c_int64, c_int, c_int,
                                     c_void_p, POINTER(c_double), c_void_p, c_void_p, c_size_t,
                                     POINTER(GlxCertifiedInfo), c_void_p]),
+    "glx_group_certificate_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64,
+                                                      POINTER(c_size_t)]),
+    "glx_group_certificate_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_char_p, c_size_t]),
+    "glx_group_certificate": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double,
+                                      c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_double),
+                                      c_void_p, c_size_t, c_void_p]),
+    "glx_group_certified_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int,
+                                                    POINTER(c_size_t)]),
+    "glx_group_certified_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_char_p,
+                                             c_size_t]),
+    "glx_group_certified_solve": (c_int, [POINTER(GlxProblem), c_int64, c_void_p, c_void_p, c_double, c_double,
+                                          c_int64, c_int, c_int, c_void_p, POINTER(c_double), c_void_p,
+                                          c_void_p, c_void_p, c_size_t, POINTER(GlxGroupCertifiedInfo),
+                                          c_void_p]),
+    "glx_group_screen_guard": (c_int, [POINTER(c_double), c_double, c_int, c_int64, c_int64, c_int64, c_int64,
+                                       c_double, c_double, c_double, c_double, POINTER(c_double)]),
+    "glx_group_workspace_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
+    "glx_group_step": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_int, c_void_p, c_double, c_double, c_double, c_double, c_double,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_group_certificate_step": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_size_t, c_void_p]),
+    "glx_group_cnorm": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_size_t, c_void_p]),
+    "glx_group_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "glx_comm_unique_id": (c_int, [POINTER(c_uint8)]),
     "glx_comm_create": (c_int, [POINTER(c_void_p), POINTER(c_uint8), c_int, c_int]),
     "glx_comm_create_host": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),
@@ -326,6 +359,21 @@ def certified_describe(dtype: int, m: int, n: int, l: int, screen: bool = True) 
     whether screening is on (glx_certified_describe: resolved on the host, no device)."""
     buf = ctypes.create_string_buffer(2048)
     check(lib().glx_certified_describe(dtype, m, n, l, int(bool(screen)), buf, len(buf)))
+    return buf.value.decode()
+
+
+def group_certificate_describe(dtype: int, m: int, n: int, l: int, max_run: int) -> str:
+    """The tiles of the group certificate's two passes and the lane layout of its group kernel for
+    runs of up to ``max_run`` rows (glx_group_certificate_describe: host only)."""
+    buf = ctypes.create_string_buffer(2048)
+    check(lib().glx_group_certificate_describe(dtype, m, n, l, int(max_run), buf, len(buf)))
+    return buf.value.decode()
+
+
+def group_certified_describe(dtype: int, m: int, n: int, l: int, max_run: int, screen: bool = True) -> str:
+    """:func:`certified_describe` for the grouped solve (glx_group_certified_describe: host only)."""
+    buf = ctypes.create_string_buffer(2048)
+    check(lib().glx_group_certified_describe(dtype, m, n, l, int(max_run), int(bool(screen)), buf, len(buf)))
     return buf.value.decode()
 
 

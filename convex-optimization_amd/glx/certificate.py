@@ -16,6 +16,16 @@ rescaling ``s`` throws most of ``r`` away (0.2 to 0.96 of P at the ADMM solvers'
 against 2e-4 to 1e-3 of P for ALM's). That is why the KKT violation is reported beside it: for row i,
 ``||g_i + mu x_i / ||x_i|| ||`` where ``x_i != 0`` and ``max(||g_i|| - mu, 0)`` where ``x_i = 0``;
 ``kkt_max`` is the largest and ``kkt_fro`` the root of the sum of squares.
+
+Feature groups and weights (``groups=``, ``weights=``): the classical group lasso
+``P(x) = 1/2 ||A x - b||_F^2 + mu sum_g w_g ||x_[g]||_F`` over contiguous row ranges of x, given as
+a ``group_ptr`` array of G + 1 offsets (``group_ptr[0] = 0``, ``group_ptr[G] = n``, strictly
+increasing) and G weights ``w_g > 0`` (default 1). ``weights`` alone makes every row its own group:
+a weighted row lasso. Everything above carries over with "row" read as "group" and mu as mu w_g:
+the constraint is ``||(A^T theta)_[g]|| <= mu w_g``, ``gmax = max_g ||g_[g]|| / w_g``, and
+``nonzero_groups`` replaces ``nonzero_rows``. Labels that are not contiguous are the caller's to
+sort: :func:`group_order` gives the permutation and the offsets, the caller passes ``A[:, perm]``
+and un-permutes x; the library never gathers A for this.
 """
 from __future__ import annotations
 
@@ -38,6 +48,63 @@ def workspace(dtype: int, m: int, n: int, l: int, device) -> torch.Tensor:
     nbytes = ctypes.c_size_t(0)
     check(lib().glx_certificate_workspace_bytes(dtype, m, n, l, ctypes.byref(nbytes)))
     return torch.empty(int(nbytes.value), dtype=torch.uint8, device=device)
+
+
+def group_order(labels):
+    """Contiguous groups from arbitrary labels, on the host: ``(perm, group_ptr)`` with ``perm`` the
+    stable argsort of ``labels`` (rows of one label keep their order, labels ascend) and
+    ``group_ptr`` (int32, G + 1) the offsets of the sorted labels' runs. Solve with ``A[:, perm]`` and
+    ``groups=group_ptr``; then ``x[perm] = x_sorted`` puts the rows back."""
+    lab = np.asarray(labels)
+    if lab.ndim != 1 or lab.size == 0:
+        raise ValueError("labels must be a non-empty 1-D array")
+    perm = np.argsort(lab, kind="stable")
+    srt = lab[perm]
+    starts = np.flatnonzero(np.concatenate(([True], srt[1:] != srt[:-1])))
+    return perm.astype(np.int64), np.concatenate((starts, [lab.size])).astype(np.int32)
+
+
+def check_groups(groups, weights, n: int, l: int = 1):
+    """The host-side checks of ``groups`` / ``weights`` for an n-row iterate, before any device work.
+    Returns None where both are None (the row problem), else ``(group_ptr int32 (G + 1), weights
+    float64 (G))`` with the defaults filled in: single rows for ``groups=None``, 1 for
+    ``weights=None``. ValueError for offsets that do not start at 0, do not end at n or are not
+    strictly increasing, for a weight that is <= 0, NaN or infinite, for a length mismatch and for
+    l > 128."""
+    if groups is None and weights is None:
+        return None
+    n = int(n)
+    if int(l) > 128:
+        raise ValueError("groups: l <= 128")
+    if groups is None:
+        ptr = np.arange(n + 1, dtype=np.int64)
+    else:
+        if isinstance(groups, torch.Tensor):
+            groups = groups.cpu().numpy()
+        ptr = np.asarray(groups)
+        if ptr.ndim != 1 or ptr.size < 2:
+            raise ValueError("groups must be a 1-D group_ptr array of G + 1 >= 2 offsets")
+        if not np.issubdtype(ptr.dtype, np.integer):
+            raise ValueError("groups must hold integers")
+        ptr = ptr.astype(np.int64)
+        if ptr[0] != 0:
+            raise ValueError("groups: group_ptr[0] must be 0")
+        if ptr[-1] != n:
+            raise ValueError("groups: group_ptr[G] must be n = %d (is %d)" % (n, int(ptr[-1])))
+        if np.any(np.diff(ptr) < 1):
+            raise ValueError("groups: group_ptr must be strictly increasing")
+    G = ptr.size - 1
+    if weights is None:
+        w = np.ones(G, dtype=np.float64)
+    else:
+        if isinstance(weights, torch.Tensor):
+            weights = weights.cpu().numpy()
+        w = np.asarray(weights, dtype=np.float64)
+        if w.ndim != 1 or w.size != G:
+            raise ValueError("weights must have one entry per group (%d), got shape %s" % (G, tuple(w.shape)))
+        if not np.all(np.isfinite(w)) or np.any(w <= 0.0):
+            raise ValueError("every weight must be positive and finite")
+    return np.ascontiguousarray(ptr, dtype=np.int32), np.ascontiguousarray(w)
 
 
 def compose(rec, mu: float) -> Dict[str, Any]:
@@ -70,6 +137,35 @@ def _record(xd: torch.Tensor, Ad: torch.Tensor, bd: torch.Tensor, mu: float, fus
     return list(rec), rn, _lib.certificate_describe(gdt, m, n, l, fused)
 
 
+def compose_groups(rec, mu: float) -> Dict[str, Any]:
+    """:func:`compose` for the group certificate's record [||r||^2, <r, b>, sum_g w_g ||x_[g]||,
+    max_g ||g_[g]|| / w_g, kkt_max, sum_g kkt_g^2, nonzero groups, 0]: the same arithmetic,
+    ``nonzero_groups`` in place of ``nonzero_rows``."""
+    out = compose(rec, mu)
+    out["nonzero_groups"] = out.pop("nonzero_rows")
+    return out
+
+
+def _group_record(xd: torch.Tensor, Ad: torch.Tensor, bd: torch.Tensor, mu: float, gw, norms: bool):
+    ptr, w = gw
+    m, n = Ad.shape
+    l = xd.shape[1]
+    G = int(w.size)
+    device = Ad.device
+    gdt = _lib.GLX_F64 if Ad.dtype == torch.float64 else _lib.GLX_F32
+    rec = (ctypes.c_double * 8)()
+    with torch.cuda.device(device):
+        nb = ctypes.c_size_t(0)
+        check(lib().glx_group_certificate_workspace_bytes(gdt, m, n, l, G, ctypes.byref(nb)))
+        ws = torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+        gn = torch.empty(G, dtype=torch.float64, device=device) if norms else None
+        check(lib().glx_group_certificate(gdt, m, n, l, Ad.data_ptr(), xd.data_ptr(), bd.data_ptr(), float(mu), G,
+                                          ptr.ctypes.data, w.ctypes.data, None,
+                                          None if gn is None else gn.data_ptr(), rec, ws.data_ptr(), ws.numel(),
+                                          ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    return list(rec), gn, _lib.group_certificate_describe(gdt, m, n, l, int(np.diff(ptr).max()))
+
+
 def _inputs(x, A, b):
     lib()  # fail loudly before touching data if the library is missing
     device = A.device if isinstance(A, torch.Tensor) and A.is_cuda else _device({})
@@ -99,7 +195,7 @@ def record(x, A, b, mu, *, fused: int = 0) -> np.ndarray:
     return np.asarray(_record(xd, Ad, bd, float(mu), fused, False)[0], dtype=np.float64)
 
 
-def certificate(x, A, b, mu, *, fused: int = 0, row_norms: bool = False) -> Dict[str, Any]:
+def certificate(x, A, b, mu, groups=None, weights=None, *, fused: int = 0, row_norms: bool = False) -> Dict[str, Any]:
     """The duality gap and KKT violation of the iterate ``x`` at ``mu`` (module docstring).
 
     ``x`` (n x l), ``A`` (m x n) and ``b`` (m x l) are NumPy arrays or torch tensors and are not
@@ -109,11 +205,25 @@ def certificate(x, A, b, mu, *, fused: int = 0, row_norms: bool = False) -> Dict
     max(|primal|, tiny), ``scale`` (s), ``gmax``, ``kkt_max``, ``kkt_fro``, ``nonzero_rows``,
     ``fused`` (whether the fused form ran), ``plan`` (glx_certificate_describe's line) and, with
     ``row_norms=True``, ``row_norms``: ||g_i||_2 for every row, a float64 array of length n (NumPy
-    for NumPy inputs, a device tensor otherwise)."""
+    for NumPy inputs, a device tensor otherwise).
+
+    ``groups`` / ``weights`` (module docstring; both None: the row problem, today's path and bits):
+    the certificate of ``mu sum_g w_g ||x_[g]||_F``. ``nonzero_groups`` replaces ``nonzero_rows``,
+    ``gmax`` is ``max_g ||g_[g]|| / w_g``, ``fused`` is False (the group terms run behind the plain
+    product) and ``row_norms=True`` returns ``group_norms``: ``||g_[g]|| / w_g``, length G."""
     mu = float(mu)
     if not mu >= 0.0:
         raise ValueError("mu must be >= 0")
+    gw = check_groups(groups, weights, np.shape(A)[1] if len(np.shape(A)) == 2 else -1,
+                      np.shape(b)[1] if len(np.shape(b)) == 2 else 1)
     xd, Ad, bd = _inputs(x, A, b)
+    if gw is not None:
+        rec, gn, plan = _group_record(xd, Ad, bd, mu, gw, row_norms)
+        out = compose_groups(rec, mu)
+        out["plan"] = plan
+        if row_norms:
+            out["group_norms"] = gn if isinstance(A, torch.Tensor) else gn.cpu().numpy()
+        return out
     rec, rn, plan = _record(xd, Ad, bd, mu, fused, row_norms)
     out = compose(rec, mu)
     out["plan"] = plan
@@ -122,9 +232,13 @@ def certificate(x, A, b, mu, *, fused: int = 0, row_norms: bool = False) -> Dict
     return out
 
 
-def mu_max(A, b) -> float:
+def mu_max(A, b, groups=None, weights=None) -> float:
     """The smallest mu for which x = 0 is optimal, max_i ||(A^T b)_i||_2: the certificate's gmax at
-    x = 0, where r = -b."""
+    x = 0, where r = -b. With ``groups`` / ``weights``: max_g ||(A^T b)_[g]||_F / w_g."""
+    gw = check_groups(groups, weights, np.shape(A)[1] if len(np.shape(A)) == 2 else -1,
+                      np.shape(b)[1] if len(np.shape(b)) == 2 else 1)
     xd, Ad, bd = _inputs(None, A, b)
+    if gw is not None:
+        return float(_group_record(xd, Ad, bd, 0.0, gw, False)[0][3])
     rec, _, _ = _record(xd, Ad, bd, 0.0, 0, False)
     return float(rec[3])

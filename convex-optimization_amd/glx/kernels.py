@@ -668,3 +668,125 @@ def screen_guard(rec, mu: float, dtype: int, m: int, n: int, l: int, col_max: fl
     check(lib().glx_screen_guard(r, float(mu), int(dtype), int(m), int(n), int(l), float(col_max),
                                  float(col_sumsq), float(b_norm), out))
     return float(out[0]), float(out[1]), float(out[2])
+
+
+# ---- feature groups and weights (glx.h "feature groups and weights"; csrc/kernels_group.hip) ----
+def _group_args(groups, weights, n: int, l: int = 1):
+    """check_groups' host pair (ValueError before any device work), G and the workspace size's G."""
+    from .certificate import check_groups
+    gw = check_groups(groups if groups is not None else None, weights, n, l)
+    if gw is None:
+        gw = check_groups(None, [1.0] * int(n), n, l)
+    return gw[0], gw[1], int(gw[1].size)
+
+
+def _group_ws(G: int, device) -> torch.Tensor:
+    nb = ctypes.c_size_t(0)
+    check(lib().glx_group_workspace_bytes(int(G), ctypes.byref(nb)))
+    return torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+
+
+def group_step(y: torch.Tensor, G: torch.Tensor, xk: torch.Tensor, groups, weights, t: float, mu: float,
+               thres: float, theta: float, theta_next: float, out: Optional[Dict[str, torch.Tensor]] = None
+               ) -> Dict[str, torch.Tensor]:
+    """The grouped FISTA step in one launch (glx_group_step, k_group_fista) on the gradient ``G``:
+    (rows, l), or (S, rows, l) slabs summed in slab order. ``groups`` (group_ptr, G + 1 offsets ending
+    at n <= rows <= n + 63) and ``weights`` are host arrays; rows from n on belong to no group and come
+    back 0. Returns {"xc", "v_next", "y_next", "sums": [sum g (xc - y), sum (xc - y)^2,
+    sum_g w_g ||xc_[g]||, max |xc|]}. ``out``: tensors to write instead of fresh ones (tests put
+    canaries around them)."""
+    rows, l = y.shape
+    ptr, w, ng = _group_args(groups, weights, int(groups[-1]) if groups is not None else rows, l)
+    n = int(ptr[-1])
+    dev = y.device
+    S = _slabs(G, rows, l)
+    o = out if out is not None else {k: torch.full_like(y, float("nan")) for k in ("xc", "v_next", "y_next")}
+    sums = o.get("sums") if out is not None and "sums" in o else _nan_sums(4, dev)
+    ws = _group_ws(ng, dev)
+    check(lib().glx_group_step(_dt(y), n, rows, l, ng, ptr.ctypes.data, w.ctypes.data, y.data_ptr(), G.data_ptr(),
+                               S, xk.data_ptr(), float(t), float(mu), float(thres), float(theta), float(theta_next),
+                               o["xc"].data_ptr(), o["v_next"].data_ptr(), o["y_next"].data_ptr(), sums.data_ptr(),
+                               ws.data_ptr(), ws.numel(), _stream(dev)))
+    return {"xc": o["xc"], "v_next": o["v_next"], "y_next": o["y_next"], "sums": sums}
+
+
+def group_certificate_step(x: torch.Tensor, G: torch.Tensor, groups, weights, mu: float,
+                           want_g: bool = False) -> Dict[str, torch.Tensor]:
+    """The certificate's group terms in one launch (glx_group_certificate_step, k_group_cert) on the
+    gradient ``G`` ((n, l) or (S, n, l) slabs). Returns {"sums": [sum_g w_g ||x_[g]||,
+    max_g ||g_[g]|| / w_g, kkt_max, sum kkt^2, nonzero groups], "group_norms": ||g_[g]|| / w_g
+    (G float64)} and, with ``want_g``, "g": the summed gradient."""
+    n, l = x.shape
+    ptr, w, ng = _group_args(groups, weights, n, l)
+    dev = x.device
+    S = _slabs(G, n, l)
+    sums = _nan_sums(5, dev)
+    gn = torch.full((ng,), float("nan"), dtype=torch.float64, device=dev)
+    gout = torch.full_like(x, float("nan")) if want_g else None
+    ws = _group_ws(ng, dev)
+    check(lib().glx_group_certificate_step(_dt(x), n, l, ng, ptr.ctypes.data, w.ctypes.data, x.data_ptr(),
+                                           G.data_ptr(), S, float(mu), _ptr(gout), gn.data_ptr(), sums.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), _stream(dev)))
+    out = {"sums": sums, "group_norms": gn}
+    if want_g:
+        out["g"] = gout
+    return out
+
+
+def group_cnorm(col_norms: torch.Tensor, groups, weights) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gcn[g] = sqrt(sum_{i in [g]} col_norms[i]^2) / w_g in float64 and its maximum (glx_group_cnorm):
+    ||A_[g]||_F / w_g from :func:`col_norms`' output. Returns (gcn (G,), max (1,)), device tensors."""
+    n = int(col_norms.shape[0])
+    assert col_norms.dtype == torch.float64
+    ptr, w, ng = _group_args(groups, weights, n)
+    dev = col_norms.device
+    gcn = torch.full((ng,), float("nan"), dtype=torch.float64, device=dev)
+    mx = torch.full((1,), float("nan"), dtype=torch.float64, device=dev)
+    ws = _group_ws(ng, dev)
+    check(lib().glx_group_cnorm(n, ng, ptr.ctypes.data, w.ctypes.data, col_norms.data_ptr(), gcn.data_ptr(),
+                                mx.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return gcn, mx
+
+
+def group_expand(kept: torch.Tensor, count: torch.Tensor, group_ptr: torch.Tensor, weights: torch.Tensor,
+                 gcn: torch.Tensor, gmap: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """Kept groups to kept rows (glx_group_expand, k_group_expand). Device tensors: ``kept`` int32 (the
+    list of :func:`screen_step` run on groups), ``count`` int32 (count[0] = K entries of it),
+    ``group_ptr`` int32 (G + 1), ``weights`` / ``gcn`` float64 (G), ``gmap`` int32 (G) or None. Returns
+    {"rows": int32, n rounded up to 64 entries (the kept rows ascending, -1 up to count[1], -2
+    behind), "group_ptr" (G + 1, the first K + 1 written), "weights", "gcn", "map" (G, the first K
+    written), "count": int32 [rows, rows rounded up to 64]}; unwritten entries keep -2 / NaN."""
+    dev = kept.device
+    G = int(weights.shape[0])
+    for t in (kept, count, group_ptr) + ((gmap,) if gmap is not None else ()):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert weights.dtype == torch.float64 and gcn.dtype == torch.float64
+    assert int(group_ptr.shape[0]) == G + 1 and int(gcn.shape[0]) == G and int(kept.shape[0]) >= 1
+    n = int(group_ptr[-1])
+    K = int(count[0])
+    hk = kept[:K].cpu()
+    if not (0 <= K <= G and int(kept.shape[0]) >= K):
+        raise ValueError("group_expand: count[0] must be in 0 .. G and within the list")
+    if K and not (bool((hk[1:] > hk[:-1]).all()) and int(hk[0]) >= 0 and int(hk[-1]) < G):
+        raise ValueError("group_expand: the kept list must be ascending group indices below G")
+    rows = torch.full(((n + 63) // 64 * 64,), -2, dtype=torch.int32, device=dev)
+    ptr_o = torch.full((G + 1,), -2, dtype=torch.int32, device=dev)
+    map_o = torch.full((G,), -2, dtype=torch.int32, device=dev)
+    w_o = torch.full((G,), float("nan"), dtype=torch.float64, device=dev)
+    gcn_o = torch.full((G,), float("nan"), dtype=torch.float64, device=dev)
+    cnt = torch.full((2,), -2, dtype=torch.int32, device=dev)
+    check(lib().glx_group_expand(kept.data_ptr(), count.data_ptr(), group_ptr.data_ptr(), weights.data_ptr(),
+                                 gcn.data_ptr(), _ptr(gmap), rows.data_ptr(), ptr_o.data_ptr(), w_o.data_ptr(),
+                                 gcn_o.data_ptr(), map_o.data_ptr(), cnt.data_ptr(), _stream(dev)))
+    return {"rows": rows, "group_ptr": ptr_o, "weights": w_o, "gcn": gcn_o, "map": map_o, "count": cnt}
+
+
+def group_screen_guard(rec, mu: float, dtype: int, m: int, n: int, l: int, max_run: int, w_min: float,
+                       gcol_max: float, col_sumsq: float, b_norm: float) -> Tuple[float, float, float]:
+    """The grouped rounding guard (glx_group_screen_guard, host only, needs no device): from the group
+    certificate's record to (s_safe, gap+, rho+)."""
+    r = (ctypes.c_double * 8)(*[float(v) for v in rec])
+    out = (ctypes.c_double * 3)()
+    check(lib().glx_group_screen_guard(r, float(mu), int(dtype), int(m), int(n), int(l), int(max_run), float(w_min),
+                                       float(gcol_max), float(col_sumsq), float(b_norm), out))
+    return float(out[0]), float(out[1]), float(out[2])

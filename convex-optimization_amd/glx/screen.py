@@ -11,6 +11,15 @@ under a rounding guard (``glx_screen_guard``); the columns of the rows it proves
 two passes over A of every later iteration stream a narrower matrix (DESIGN.md "Certified solve and
 screening"). ``path`` solves a decreasing sequence of mu, each warm-started from the one before,
 with the column norms and lambda_max computed once. Everything runs on the GPU; there is no CPU path.
+
+With ``groups`` / ``weights`` (:mod:`glx.certificate`: contiguous row ranges as a ``group_ptr`` array,
+weights w_g > 0) the penalty is ``mu sum_g w_g ||x_[g]||_F``, the step is the plain A^T r followed by
+the group kernel, and the test runs on groups,
+
+    s ||g_[g]||_F / w_g + (||A_[g]||_F / w_g) sqrt(2 gap) < mu   =>   x*_[g] = 0,
+
+so that proving a group zero removes all its columns from A at once (``glx_group_certified_solve``;
+DESIGN.md "Feature groups and weights").
 """
 from __future__ import annotations
 
@@ -22,8 +31,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GlxCertifiedInfo, GlxProblem, check, lib
-from .certificate import _inputs, compose, mu_max
+from ._lib import GlxCertifiedInfo, GlxGroupCertifiedInfo, GlxProblem, check, lib
+from .certificate import _inputs, check_groups, compose, compose_groups, mu_max
 
 DEFAULT_MAXIT = 100000
 
@@ -56,8 +65,9 @@ def _check_mus(mus: Sequence[float]) -> List[float]:
     return out
 
 
-def _check_args(A, b, x0, tol, maxit, check_every):
-    """The argument checks that need no device (shapes from the arrays as they are)."""
+def _check_args(A, b, x0, tol, maxit, check_every, groups=None, weights=None):
+    """The argument checks that need no device (shapes from the arrays as they are). Returns
+    :func:`glx.certificate.check_groups`' pair, None for the row problem."""
     sa, sb = tuple(np.shape(A)), tuple(np.shape(b))
     if len(sa) != 2 or len(sb) != 2:
         raise ValueError("A and b must be 2-D (group lasso with l columns)")
@@ -71,13 +81,14 @@ def _check_args(A, b, x0, tol, maxit, check_every):
         raise ValueError("maxit must be >= 0")
     if int(check_every) < 1:
         raise ValueError("check_every must be >= 1")
+    return check_groups(groups, weights, sa[1], sb[1])
 
 
 class _Prepared:
     """What a sequence of solves on one (A, b) shares: the device copies, the step, the column norms
     and the workspace."""
 
-    def __init__(self, A, b, screen: bool, comm=None):
+    def __init__(self, A, b, screen: bool, comm=None, gw=None):
         from . import kernels
         from .solver import _lambda_max
         if comm is not None:
@@ -89,10 +100,17 @@ class _Prepared:
         self.device = self.Ad.device
         self.gdt = _lib.GLX_F64 if self.Ad.dtype == torch.float64 else _lib.GLX_F32
         self.screen = bool(screen)
+        self.gw = gw   # (group_ptr, weights) on the host, or None: rows
+        self.G = 0 if gw is None else int(gw[1].size)
+        self.max_run = 0 if gw is None else int(np.diff(gw[0]).max())
         with torch.cuda.device(self.device):
             nb = ctypes.c_size_t(0)   # (first: it refuses what the solve would, before any launch)
-            check(lib().glx_certified_workspace_bytes(self.gdt, self.m, self.n, self.l, int(self.screen),
-                                                      ctypes.byref(nb)))
+            if gw is None:
+                check(lib().glx_certified_workspace_bytes(self.gdt, self.m, self.n, self.l, int(self.screen),
+                                                          ctypes.byref(nb)))
+            else:
+                check(lib().glx_group_certified_workspace_bytes(self.gdt, self.m, self.n, self.l, self.G,
+                                                                int(self.screen), ctypes.byref(nb)))
             self.lam = float(_lambda_max(self.Ad))
             self.t = 1.0 / self.lam
             self.cn = self.cstats = None
@@ -110,8 +128,10 @@ class _Prepared:
             xd = xd.clone()   # the solve works in place
         p = GlxProblem(dtype=self.gdt, method=0, m=self.m, n=self.n, l=self.l, A=self.Ad.data_ptr(),
                        b=self.bd.data_ptr(), x=xd.data_ptr(), mu0=mu, comm=None)
-        info = GlxCertifiedInfo()
         rows = torch.full(((self.n + 63) // 64 * 64,), -1, dtype=torch.int32, device=self.device)
+        if self.gw is not None:
+            return self._solve_groups(mu, xd, p, rows, tol, maxit, check_every)
+        info = GlxCertifiedInfo()
         with torch.cuda.device(self.device):
             check(lib().glx_certified_solve(ctypes.byref(p), self.t, float(tol), int(maxit), int(self.screen),
                                             int(check_every), None if self.cn is None else self.cn.data_ptr(),
@@ -135,12 +155,44 @@ class _Prepared:
                    step_fused=bool(info.fused), screen=self.screen, tol=float(tol), step=self.t, mu=mu)
         return xd, out
 
+    def _solve_groups(self, mu, xd, p, rows, tol, maxit, check_every):
+        ptr, w = self.gw
+        ginfo = GlxGroupCertifiedInfo()
+        grps = torch.full((self.G,), -1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().glx_group_certified_solve(
+                ctypes.byref(p), self.G, ptr.ctypes.data, w.ctypes.data, self.t, float(tol), int(maxit),
+                int(self.screen), int(check_every), None if self.cn is None else self.cn.data_ptr(), self.cstats,
+                rows.data_ptr(), grps.data_ptr(), self.ws.data_ptr(), self.ws.numel(), ctypes.byref(ginfo),
+                ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        info = ginfo.base
+        out: Dict[str, Any] = compose_groups(list(info.cert), mu)
+        out["plan"] = _lib.group_certified_describe(self.gdt, self.m, self.n, self.l, self.max_run, self.screen)
+        nc = int(info.compactions)
+        if int(ginfo.listed_groups) > 0:
+            kept_groups = grps[:int(ginfo.listed_groups)].cpu().numpy().astype(np.int64)
+            kept_rows = rows[:int(info.listed)].cpu().numpy().astype(np.int64)
+            kept_rows = kept_rows[kept_rows >= 0]
+        elif self.screen and int(info.kept) == 0 and int(info.checks) > 0:
+            kept_groups = np.zeros(0, dtype=np.int64)
+            kept_rows = np.zeros(0, dtype=np.int64)
+        else:
+            kept_groups = np.arange(self.G, dtype=np.int64)
+            kept_rows = np.arange(self.n, dtype=np.int64)
+        out.update(converged=bool(info.converged), iterations=int(info.iters), checks=int(info.checks),
+                   compactions=nc, kept_history=[int(info.kept_hist[i]) for i in range(min(nc, 64))],
+                   kept=int(info.kept), kept_groups=kept_groups, kept_rows=kept_rows, width=int(info.width),
+                   rounds=int(info.rounds), passes=float(info.passes), tt=float(info.tt),
+                   inner_rel_gap=float(info.inner_rel_gap), step_fused=False, screen=self.screen, tol=float(tol),
+                   step=self.t, mu=mu)
+        return xd, out
+
     def result(self, xd: torch.Tensor):
         return xd.cpu().numpy() if self.numpy else xd
 
 
 def solve_certified(A, b, mu, x0=None, tol: float = 1e-6, maxit: int = DEFAULT_MAXIT, screen: bool = True,
-                    check_every: int = 10, comm=None) -> Tuple[Any, Dict[str, Any]]:
+                    check_every: int = 10, comm=None, groups=None, weights=None) -> Tuple[Any, Dict[str, Any]]:
     """Solve min_x 1/2 ||A x - b||_F^2 + mu sum_i ||x_i||_2 until the duality gap is at most ``tol``
     of the primal objective (or ``maxit`` iterations in total).
 
@@ -153,11 +205,17 @@ def solve_certified(A, b, mu, x0=None, tol: float = 1e-6, maxit: int = DEFAULT_M
     prove zero), ``kept_rows`` (their indices, ascending: every other row is zero at the optimum),
     ``width`` (columns of the last reduced problem), ``rounds``, ``passes`` (passes over A, each
     weighted by its width / n), ``tt`` (seconds inside the native call) and ``step``. Single GPU: a
-    communicator is refused."""
-    _check_args(A, b, x0, tol, maxit, check_every)
+    communicator is refused.
+
+    ``groups`` / ``weights`` (both None: the row problem, today's path and bits): solve
+    ``mu sum_g w_g ||x_[g]||_F`` over contiguous row ranges (``group_ptr`` array; ``weights`` alone:
+    single rows). ``info`` then carries ``nonzero_groups`` in place of ``nonzero_rows``, ``kept`` and
+    ``kept_history`` count groups, and ``kept_groups`` (ascending) stands next to ``kept_rows`` (the
+    rows of those groups)."""
+    gw = _check_args(A, b, x0, tol, maxit, check_every, groups, weights)
     if not float(mu) >= 0.0:
         raise ValueError("mu must be >= 0")
-    prep = _Prepared(A, b, screen, comm)
+    prep = _Prepared(A, b, screen, comm, gw)
     xd, info = prep.solve(mu, x0, tol, maxit, check_every)
     return prep.result(xd), info
 
@@ -167,21 +225,23 @@ def path(A, b, mus: Optional[Sequence[float]] = None, n_mus: int = 10, mu_min_ra
     """Certified solves over a decreasing sequence of mu: ``mus``, or the geometric grid of ``n_mus``
     values from ``glx.mu_max(A, b)`` down to ``mu_min_ratio`` of it (:func:`mu_grid`). Each solve is
     warm-started from the one before; the column norms and lambda_max are computed once. ``kw``:
-    ``tol``, ``maxit``, ``screen``, ``check_every`` of :func:`solve_certified`. Returns the list of
+    ``tol``, ``maxit``, ``screen``, ``check_every``, ``groups``, ``weights`` of :func:`solve_certified`
+    (with groups the grid starts at the grouped ``mu_max``). Returns the list of
     ``(mu, x, info)``; at mu = mu_max the entry is x = 0 with gap 0 and no iterations."""
-    unknown = set(kw) - {"tol", "maxit", "screen", "check_every", "comm"}
+    unknown = set(kw) - {"tol", "maxit", "screen", "check_every", "comm", "groups", "weights"}
     if unknown:
         raise TypeError("path() got unexpected keyword arguments %s" % sorted(unknown))
     tol, maxit = kw.get("tol", 1e-6), kw.get("maxit", DEFAULT_MAXIT)
     check_every = kw.get("check_every", 10)
-    _check_args(A, b, None, tol, maxit, check_every)
+    gw = _check_args(A, b, None, tol, maxit, check_every, kw.get("groups"), kw.get("weights"))
     if mus is not None:
         mus = _check_mus(mus)
     else:
         mu_grid(1.0, n_mus, mu_min_ratio)   # the grid's own checks, before any device work
-    prep = _Prepared(A, b, kw.get("screen", True), kw.get("comm"))
+    prep = _Prepared(A, b, kw.get("screen", True), kw.get("comm"), gw)
     if mus is None:
-        mus = mu_grid(mu_max(prep.Ad, prep.bd), n_mus, mu_min_ratio)
+        top = mu_max(prep.Ad, prep.bd) if gw is None else mu_max(prep.Ad, prep.bd, gw[0], gw[1])
+        mus = mu_grid(top, n_mus, mu_min_ratio)
     out = []
     xd = None
     for mu in mus:

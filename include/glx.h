@@ -727,6 +727,96 @@ int glx_certified_solve(const glx_problem* prob, double t, double tol, int64_t m
                         int32_t* kept_rows_dev, void* workspace, size_t workspace_bytes,
                         glx_certified_info* info, void* stream);
 
+/* ---- feature groups and weights (DESIGN.md "Feature groups and weights"; additive entries, the ABI
+ * version stays 2) ----
+ * The classical group lasso  P(x) = 1/2 ||A x - b||_F^2 + mu sum_g w_g ||x_[g]||_F : group g is the
+ * contiguous row range group_ptr[g] .. group_ptr[g + 1] - 1 of the n x l iterate (the same columns of
+ * A), w_g > 0 its weight. group_ptr (G + 1 int32) and weights (G doubles) are HOST arrays in every
+ * entry below except glx_group_expand; they are checked before anything is launched and copied into
+ * the workspace (the copy is complete on return). GLX_E_INVALID, with a message, for G < 1,
+ * group_ptr[0] != 0, group_ptr[G] != n, offsets that are not strictly increasing, a weight that is
+ * <= 0, NaN or infinite, l > 128, a communicator, and the row entries' pointer and workspace checks.
+ * Labels that are not contiguous are the caller's to sort (glx.group_order); A is never gathered
+ * for that here.
+ *
+ * The certificate: out = [||r||^2, <r, b>, sum_g w_g ||x_[g]||, max_g ||g_[g]|| / w_g, kkt_max,
+ * sum_g kkt_g^2, nonzero groups, 0] with kkt_g = ||g_[g] + mu w_g x_[g] / ||x_[g]|| || where x_[g] != 0
+ * and max(||g_[g]|| - mu w_g, 0) where it is 0; the caller composes primal, dual and gap exactly as
+ * for glx_certificate (s = min(1, mu / out[3])). The A^T pass is the plain product and the group
+ * terms run behind it (k_group_cert). G_out (n x l) and groupnorm_out (G doubles: ||g_[g]|| / w_g)
+ * are device pointers, or NULL. */
+int glx_group_certificate_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, size_t* bytes);
+/* One line: the tiles of the two passes and the lane layout of the group kernel for runs of up to
+ * max_run rows. Resolved on the host; needs no device. */
+int glx_group_certificate_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, char* out,
+                                   size_t cap);
+int glx_group_certificate(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                          double mu, int64_t G, const int32_t* group_ptr, const double* weights, void* G_out,
+                          double* groupnorm_out, double out[8], void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* The certified solve on groups: glx_certified_solve's loop, schedule and arguments. The step is the
+ * plain A^T r followed by k_group_fista; with screen != 0 the test runs on groups,
+ *   s ||g_[g]|| / w_g + (||A_[g]||_F / w_g) rho < mu  =>  x*_[g] = 0
+ * (||A_[g]||_F bounds the spectral norm of the group's columns from above), all columns of a
+ * screened group leave A at once, and the compaction rule (padded kept rows <= 0.9 of the width)
+ * is the row solve's. base.kept and base.kept_hist count groups. kept_rows_dev (room for n rounded
+ * up to 64 ints) and kept_groups_dev (room for G ints), either may be NULL: the rows and the groups
+ * of the full problem not proven zero, ascending; base.listed / listed_groups entries are written. */
+typedef struct glx_group_certified_info {
+  glx_certified_info base;
+  int64_t kept_groups;     /* groups the last screening test did not prove zero (G with screen = 0) */
+  int64_t listed_groups;   /* entries written to kept_groups_dev (0: none)                          */
+  int64_t max_run;         /* rows of the largest group                                             */
+  int64_t reserved;
+} glx_group_certified_info;
+int glx_group_certified_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, int screen,
+                                        size_t* bytes);
+int glx_group_certified_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, int screen,
+                                 char* out, size_t cap);
+int glx_group_certified_solve(const glx_problem* prob, int64_t G, const int32_t* group_ptr, const double* weights,
+                              double t, double tol, int64_t maxit, int screen, int check_every,
+                              const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev,
+                              int32_t* kept_groups_dev, void* workspace, size_t workspace_bytes,
+                              glx_group_certified_info* info, void* stream);
+/* The grouped rounding guard (host only, needs no device): glx_screen_guard's three outputs from the
+ * group certificate's record, with max_g ||A_[g]||_F / w_g (gcol_max, glx_group_cnorm's maximum) in
+ * place of the largest column norm, ||x||_F <= rec[2] / w_min, and the roundings of a max_run * l
+ * term norm and of the stored group figures. */
+int glx_group_screen_guard(const double rec[8], double mu, int dtype, int64_t m, int64_t n, int64_t l,
+                           int64_t max_run, double w_min, double gcol_max, double col_sumsq, double b_norm,
+                           double out[3]);
+/* The group kernels one launch at a time (test surface). Workspace: glx_group_workspace_bytes(G).
+ * glx_group_step: the FISTA step on S >= 1 slabs g of rows * l values (rows = n .. n + 63, the padded
+ *   width; rows from n on belong to no group and come back 0 in xc, vnext, ynext): w = y - t g,
+ *   xc_[g] = w_[g] max(||w_[g]|| - t mu w_g, 0) / ((||w_[g]|| < thres) + ||w_[g]||), then per element
+ *   the momentum of glx_trial_fista; sums_dev = [sum g (xc - y), sum (xc - y)^2, sum_g w_g ||xc_[g]||,
+ *   max |xc|] (4 device doubles).
+ * glx_group_certificate_step: the group terms on a given g: sums_dev = out[2..6] of
+ *   glx_group_certificate (5 device doubles); gout, groupnorm_out may be NULL.
+ * glx_group_cnorm: gcn_dev[g] = sqrt(sum_{i in [g]} col_norms_dev[i]^2) / w_g in double, max_dev[0]
+ *   their maximum.
+ * glx_group_expand (device arrays only): kept_dev = kept_count_dev[0] groups of the current problem,
+ *   ascending (glx_screen_step's list and count) -> rows_out (their rows, ascending, then -1 up to
+ *   count_out[1]), the reduced problem's group_ptr_out (kept + 1), weights_out, gcn_out, and map_out =
+ *   map_dev composed (map_dev NULL: identity), so it names groups of the full problem;
+ *   count_out = [rows, rows rounded up to 64]. An ordered integer scan, identical from run to run. */
+int glx_group_workspace_bytes(int64_t G, size_t* bytes);
+int glx_group_step(int dtype, int64_t n, int64_t rows, int64_t l, int64_t G, const int32_t* group_ptr,
+                   const double* weights, const void* y, const void* g, int S, const void* xk, double t, double mu,
+                   double thres, double theta, double theta_next, void* xc, void* vnext, void* ynext,
+                   void* sums_dev, void* workspace, size_t workspace_bytes, void* stream);
+int glx_group_certificate_step(int dtype, int64_t n, int64_t l, int64_t G, const int32_t* group_ptr,
+                               const double* weights, const void* x, const void* g, int S, double mu, void* gout,
+                               double* groupnorm_out, void* sums_dev, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int glx_group_cnorm(int64_t n, int64_t G, const int32_t* group_ptr, const double* weights,
+                    const double* col_norms_dev, double* gcn_dev, double* max_dev, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int glx_group_expand(const int32_t* kept_dev, const int32_t* kept_count_dev, const int32_t* group_ptr_dev,
+                     const double* weights_dev, const double* gcn_dev, const int32_t* map_dev, int32_t* rows_out,
+                     int32_t* group_ptr_out, double* weights_out, double* gcn_out, int32_t* map_out,
+                     int32_t* count_out, void* stream);
+
 /* ---- multi-GPU (row-sharded A; A^T r all-reduced, or reduce-scattered with the row-sharded step) ---- */
 #define GLX_COMM_ID_BYTES 128
 int  glx_comm_unique_id(uint8_t id[GLX_COMM_ID_BYTES]);
