@@ -128,7 +128,7 @@ void cert_rows(const CertPlan& pl, bool fused, const T* A, const T* R, const T* 
 template <typename T>
 void certificate(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const T* A, const T* X, const T* b,
                  double mu, int fused_opt, T* G, double* rn, double* out, void* ws, hipStream_t st,
-                 const GroupView* grp) {
+                 const GroupView* grp, const SampleView* sw, double* holdout_sum) {
   CertWs w;
   cert_carve(pl, m, n, l, ws, &w);
   const bool fused = grp == nullptr && use_fused(pl, fused_opt);
@@ -139,7 +139,15 @@ void certificate(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const T* A
   GLX_HIP(hipMemsetAsync(w.rec, 0, sizeof(double) * kCertRec, st));
   const T* xs[3] = {X, nullptr, nullptr};
   launch_ax<T>(pl.a, 1, A, xs, pa, nullptr, 0, st);
-  launch_cert_fin<T>(pa, ax_split(pl.a, 1), b, r, ml, Red{w.part, w.ticket, w.rec}, st);
+  const bool hold = sw != nullptr && sw->hold != nullptr;
+  if (sw != nullptr) {
+    // r = w (A x - b), the operand of the A^T pass. Two sums go where k_cert_fin's go; with hold-out
+    // weights there are three, which rec + 2 has no room for: they go to sw->sums
+    launch_cert_fin_w<T>(pa, ax_split(pl.a, 1), b, static_cast<const T*>(sw->w), static_cast<const T*>(sw->hold),
+                         nullptr, r, ml, l, Red{w.part, w.ticket, hold ? sw->sums : w.rec}, st);
+  } else {
+    launch_cert_fin<T>(pa, ax_split(pl.a, 1), b, r, ml, Red{w.part, w.ticket, w.rec}, st);
+  }
   if (grp != nullptr) {   // the group terms on the slabs of the plain product
     launch_atr<T>(pl.a, A, r, static_cast<T*>(w.gp), st);
     launch_group_cert<T>(X, static_cast<const T*>(w.gp), pl.a.atr_S, G, rn, grp->ptr, grp->wts, grp->G, n, l,
@@ -148,18 +156,26 @@ void certificate(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const T* A
     cert_rows<T>(pl, fused, A, r, X, mu, G, rn, w, Red{w.part, w.ticket, w.rec + 2}, st);
   }
   check_launch();
+  double hs[3] = {0.0, 0.0, 0.0};
   GLX_HIP(hipMemcpyAsync(out, w.rec, sizeof(double) * kCertRec, hipMemcpyDeviceToHost, st));
+  if (hold) GLX_HIP(hipMemcpyAsync(hs, sw->sums, sizeof hs, hipMemcpyDeviceToHost, st));
   GLX_HIP(hipStreamSynchronize(st));
   out[7] = fused ? 1.0 : 0.0;
+  if (hold) {
+    out[0] = hs[0];
+    out[1] = hs[1];
+  }
+  if (holdout_sum != nullptr) *holdout_sum = hs[2];
 }
 
 }  // namespace
 
 void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
                      double mu, int fused, void* G_out, double* rownorm_out, double* out, void* ws, size_t wsb,
-                     void* stream, const GroupView* grp) {
+                     void* stream, const GroupView* grp, const SampleView* sw, double* holdout_sum) {
   const CertPlan pl = cert_plan(dtype, m, n, l);
   check_fused(fused);
+  if (sw != nullptr && (!sw->w || !sw->sums)) throw Error{GLX_E_INVALID, "sample weights: null vector or sums"};
   if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
   if (!A || !X || !b) throw Error{GLX_E_INVALID, "A, X and b must be device pointers"};
   if (!out) throw Error{GLX_E_INVALID, "null out"};
@@ -170,10 +186,17 @@ void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, 
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (dtype == GLX_F64)
     certificate<double>(pl, m, n, l, (const double*)A, (const double*)X, (const double*)b, mu, fused,
-                        (double*)G_out, rownorm_out, out, ws, st, grp);
+                        (double*)G_out, rownorm_out, out, ws, st, grp, sw, holdout_sum);
   else
     certificate<float>(pl, m, n, l, (const float*)A, (const float*)X, (const float*)b, mu, fused,
-                       (float*)G_out, rownorm_out, out, ws, st, grp);
+                       (float*)G_out, rownorm_out, out, ws, st, grp, sw, holdout_sum);
+}
+
+void check_sample(const void* sample_w, const void* holdout_w) {
+  if (holdout_w != nullptr && sample_w == nullptr)
+    throw Error{GLX_E_INVALID, "holdout_w goes with sample_w (pass ones for an unweighted fit)"};
+  if ((reinterpret_cast<uintptr_t>(sample_w) | reinterpret_cast<uintptr_t>(holdout_w)) & 15)
+    throw Error{GLX_E_INVALID, "sample_w and holdout_w must be 16-byte aligned"};
 }
 
 }  // namespace glx
@@ -181,6 +204,45 @@ void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, 
 using namespace glx;
 
 extern "C" {
+
+int glx_certificate_sw_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    *bytes = sample_bytes(cert_carve(cert_plan(dtype, m, n, l), m, n, l, nullptr, nullptr));
+  });
+}
+
+int glx_certificate_sw_describe(int dtype, int64_t m, int64_t n, int64_t l, int fused, char* out, size_t cap) {
+  return guarded([&] {
+    if (!out || cap == 0) throw Error{GLX_E_INVALID, "null out"};
+    check_fused(fused);
+    std::snprintf(out, cap, "%s; residual=weighted finalize (k_cert_fin_w)",
+                  describe_cert(cert_plan(dtype, m, n, l), fused).c_str());
+  });
+}
+
+int glx_certificate_sw(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                       double mu, int fused, const void* sample_w, const void* holdout_w, void* G_out,
+                       double* rownorm_out, double* out, double* holdout_sum, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_sample(sample_w, holdout_w);
+    const size_t head = cert_carve(cert_plan(dtype, m, n, l), m, n, l, nullptr, nullptr);
+    if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
+    if (wsb < sample_bytes(head))
+      throw Error{GLX_E_INVALID, "workspace too small (glx_certificate_sw_workspace_bytes)"};
+    if (holdout_sum != nullptr) *holdout_sum = 0.0;
+    if (sample_w == nullptr) {   // today's entry, call for call
+      certificate_run(dtype, m, n, l, A, X, b, mu, fused, G_out, rownorm_out, out, ws, head, stream, nullptr);
+      return;
+    }
+    SampleView sw;
+    sw.w = sample_w;
+    sw.hold = holdout_w;
+    sw.sums = reinterpret_cast<double*>(static_cast<char*>(ws) + sample_off(head));
+    certificate_run(dtype, m, n, l, A, X, b, mu, fused, G_out, rownorm_out, out, ws, head, stream, nullptr, &sw,
+                    holdout_sum);
+  });
+}
 
 int glx_certificate_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes) {
   return guarded([&] {

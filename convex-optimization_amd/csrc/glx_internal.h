@@ -476,6 +476,13 @@ void launch_cert_row(const T* x, const T* g, int S, T* gout, double* rn, int64_t
 // out: [sum r^2, sum r b] (accumulated in double)
 template <typename T>
 void launch_cert_fin(const T* P, int S, const T* b, T* r, int64_t ml, Red red, hipStream_t st);
+// The same with one weight per row of A (w: m values of T; element idx is of row idx / l): r (may be
+// NULL) = the unweighted residual, rw = fl(w r), out: [sum w r^2, sum w r b] and, with hold-out
+// weights hv (may be NULL), a third value sum hv r^2. With w = 1 the two sums and rw are
+// launch_cert_fin's bits.
+template <typename T>
+void launch_cert_fin_w(const T* P, int S, const T* b, const T* w, const T* hv, T* r, T* rw, int64_t ml, int64_t l,
+                       Red red, hipStream_t st);
 
 // ---- gap-safe screening (kernels_screen.hip; DESIGN.md "Certified solve and screening") ----
 // norms[j] = ||A[:, j]||_2 (n doubles), accumulated in double over col_norm_slabs(m) fixed row slabs
@@ -487,6 +494,10 @@ size_t col_norms_count_bytes(int64_t n);
 template <typename T>
 void launch_col_norms(const T* A, int64_t m, int64_t n, double* norms, double* part, unsigned* ccnt, Red red,
                       hipStream_t st);
+// norms[j] = sqrt(sum_i w[i] A[i, j]^2) (w: m values of T, >= 0): the same slabs, combine and stats
+template <typename T>
+void launch_col_norms_w(const T* A, const T* w, int64_t m, int64_t n, double* norms, double* part, unsigned* ccnt,
+                        Red red, hipStream_t st);
 // keep[i] = !(s rn[i] + cn[i] rho < mu_lo) (a NaN keeps the row); list = the kept rows, ascending,
 // then -1 up to cnt[1]; cnt = [kept, kept rounded up to 64]. mask (n bytes) may be NULL; list holds n
 // rounded up to 64 ints; bal: screen_words_bytes(n); ticket: one zeroed word (reset by the kernel).
@@ -548,24 +559,48 @@ struct GroupView {
 // glx_certificate's body (certificate.cpp): grp == NULL is the row certificate; with groups the
 // A^T pass is launch_atr and the group terms follow (launch_group_cert), rownorm_out then takes G
 // doubles ||g_[g]|| / w_g and fused is ignored. Throws Error.
+// Sample weights as the drivers pass them on (DESIGN.md "Sample weights and cross-validation"):
+// w = m device values of A's dtype, >= 0 (validated by the caller of the C entry); hold (may be
+// NULL) = the hold-out weights of the same kind; sums = 3 device doubles the weighted finalize
+// reduces into, carved behind the callee's workspace.
+struct SampleView {
+  const void* w = nullptr;
+  const void* hold = nullptr;
+  double* sums = nullptr;
+};
+// SampleView::sums behind `head` bytes of a callee's workspace: its offset and the bytes of both
+inline size_t sample_off(size_t head) { return (head + 255) & ~size_t(255); }
+inline size_t sample_bytes(size_t head) { return sample_off(head) + 256; }
+// sw (NULL: every call and byte above): the certificate of 1/2 sum_j w_j ||(A x - b)_j||^2 + mu Omega(x):
+// out[0] = sum w r^2, out[1] = sum w r b, the A^T pass runs on w r; *holdout_sum (where sw->hold)
+// = sum_j hold_j ||(A x - b)_j||^2 from the same launch.
 void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
                      double mu, int fused, void* G_out, double* rownorm_out, double* out, void* ws, size_t wsb,
-                     void* stream, const GroupView* grp);
+                     void* stream, const GroupView* grp, const SampleView* sw = nullptr,
+                     double* holdout_sum = nullptr);
 // The certified solve (screen.cpp), rows (grp == NULL) or groups: one loop, glx_certified_solve's
 // arguments and checks. With groups the step is launch_atr + launch_group_fista, the screen runs on
 // the G "rows" ||g_[g]|| / w_g against gcn (launch_group_cnorm, computed here) and
 // launch_group_expand turns its list into rows; info->kept and kept_hist then count groups.
 // kept_groups_dev (may be NULL): as kept_rows_dev, for groups; *listed_groups = the entries written.
-size_t certified_bytes(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t G);
+// With sample weights (sw; its `sums` is ignored: the solve carves its own) both residual finalizes,
+// ||b~||, the column figures and every certificate are the weighted problem's; col_norms_dev then
+// holds the weighted norms. The final full-problem certificate takes sw->hold: *holdout_sum.
+size_t certified_bytes(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t G, bool weighted = false);
 std::string certified_describe(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run);
 void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit, int screen, int check_every,
                    const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev, void* ws,
                    size_t wsb, glx_certified_info* info, void* stream, const GroupView* grp,
-                   int32_t* kept_groups_dev, int64_t* listed_groups);
-// The rounding guards, host only (screen.cpp / group.cpp); out = [s_safe, gap+, rho+]
+                   int32_t* kept_groups_dev, int64_t* listed_groups, const SampleView* sw = nullptr,
+                   double* holdout_sum = nullptr);
+// The rounding guards, host only (screen.cpp / group.cpp); out = [s_safe, gap+, rho+]. weighted: the
+// record, the column figures and bn are the sample-weighted problem's, and the roundings of w r and
+// w r^2 are counted (DESIGN.md "Sample weights and cross-validation", "The guard").
 double gamma_k(double k, double u);
 void group_screen_guard(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run,
-                        double w_min, double gcol_max, double csq, double bn, double* out);
+                        double w_min, double gcol_max, double csq, double bn, double* out, bool weighted = false);
+// the checks every weighted C entry makes of its two vectors: 16-byte aligned, hold only with w
+void check_sample(const void* sample_w, const void* holdout_w);
 
 // ---- shared by the two ADMM drivers (defined in admm.cpp) ----
 namespace admm {

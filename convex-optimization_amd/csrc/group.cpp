@@ -157,24 +157,28 @@ StepWs step_head(void* head) {
 // certificate's record of the stored r^ and g^ = A^T r^ in dtype arithmetic. Every quantity is an
 // upper bound; NaN propagates (and then keeps every group in k_screen).
 void group_screen_guard(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run,
-                        double w_min, double gcol_max, double csq, double bn, double* out) {
+                        double w_min, double gcol_max, double csq, double bn_in, double* out, bool weighted) {
+  // weighted (sample weights): one more rounding in w r^, in the two fp64 sums and in the column norms,
+  // exactly as in screen_guard (DESIGN.md "Sample weights and cross-validation", "The guard")
+  const double k = weighted ? 3.0 : 2.0;
   const double u = dtype == GLX_F64 ? DBL_EPSILON : (double)FLT_EPSILON;   // eps of A's dtype
   const double u64 = DBL_EPSILON;
   const double rr = rec[0], rb = rec[1], sxw = rec[2], gmax = rec[3];
   const double rn = std::sqrt(rr);
   const double K = (double)max_run * (double)l;   // terms of a group's norm
-  const double gm = gamma_k((double)m + 2.0, u), gn = gamma_k((double)n + 2.0, u);
+  const double gm = gamma_k((double)m + k, u), gn = gamma_k((double)n + 2.0, u);
   const double gK = gamma_k(K + 3.0, u);          // the norm in A's dtype, then the weight's rounding
+  const double ml = (double)m * (double)l;
+  const double g_ml = gamma_k(ml + k, u64);
+  const double bn = weighted ? bn_in * (1.0 + g_ml) : bn_in;
   // the stored gcn are low by the column norms' gamma64_{m+2} and their own root and division
-  const double up = (1.0 + gamma_k((double)m + 2.0, u64)) * (1.0 + gamma_k((double)max_run + 3.0, u64));
+  const double up = (1.0 + gamma_k((double)m + k, u64)) * (1.0 + gamma_k((double)max_run + 3.0, u64));
   // 1. dual feasibility: ||A_[g]^T r^|| / w_g <= ||g^_[g]|| / w_g + gm (||A_[g]||_F / w_g) ||r^||, the
   //    per-column bounds summed in squares; the stored maximum may be low by its own gK
   const double den = gmax * (1.0 + gK) + gm * gcol_max * up * rn;
   const double s = den > mu ? mu / den : (den <= mu ? 1.0 : den);   // (NaN den: NaN)
   // 2. the primal value: ||x||_F <= sum_g ||x_[g]|| <= rec[2] / w_min
   const double dr = gn * std::sqrt(csq) * (sxw / w_min) + u * (rn + 2.0 * bn);
-  const double ml = (double)m * (double)l;
-  const double g_ml = gamma_k(ml + 2.0, u64);
   const double bar_rr = g_ml * rr;
   const double bar_rb = g_ml * rn * bn;
   const double bar_sx = (gK + gamma_k((double)n + 2.0, u64)) * sxw;   // at most n groups in the fp64 sum
@@ -287,6 +291,116 @@ int glx_group_certified_solve(const glx_problem* prob, int64_t G, const int32_t*
     int64_t listed_groups = 0;
     certified_run(prob, t, tol, maxit, screen, check_every, col_norms_dev, col_stats, kept_rows_dev, d.head, head,
                   &info->base, stream, &v, kept_groups_dev, &listed_groups);
+    info->kept_groups = screen != 0 ? info->base.kept : G;
+    info->listed_groups = listed_groups;
+    info->max_run = f.max_run;
+  });
+}
+
+/* ---- sample weights (DESIGN.md "Sample weights and cross-validation"): the grouped entries with a
+ * weight per row of A; the sums of the weighted finalize sit behind the grouped workspace ---- */
+
+int glx_group_screen_guard_sw(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l,
+                              int64_t max_run, double w_min, double gcol_max, double col_sumsq, double b_norm,
+                              double* out) {
+  return guarded([&] {
+    if (!rec || !out) throw Error{GLX_E_INVALID, "null argument"};
+    check_dims(dtype, n, l);
+    if (m <= 0) throw Error{GLX_E_INVALID, "m must be positive"};
+    if (max_run < 1 || max_run > n) throw Error{GLX_E_INVALID, "max_run must be in 1 .. n"};
+    if (!(w_min > 0.0) || !std::isfinite(w_min)) throw Error{GLX_E_INVALID, "w_min must be positive and finite"};
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    group_screen_guard(rec, mu, dtype, m, n, l, max_run, w_min, gcol_max, col_sumsq, b_norm, out, true);
+  });
+}
+
+int glx_group_certificate_sw_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    if (G < 1 || G > n) throw Error{GLX_E_INVALID, "groups: G must be in 1 .. n"};
+    *bytes = sample_bytes(group_carve(cert_bytes(dtype, m, n, l), G, nullptr, nullptr));
+  });
+}
+
+int glx_group_certificate_sw_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, char* out,
+                                      size_t cap) {
+  const int rc = glx_group_certificate_describe(dtype, m, n, l, max_run, out, cap);
+  if (rc != GLX_OK) return rc;
+  const size_t used = std::strlen(out);
+  std::snprintf(out + used, cap - used, "; residual=weighted finalize (k_cert_fin_w)");
+  return GLX_OK;
+}
+
+int glx_group_certificate_sw(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X,
+                             const void* b, double mu, int64_t G, const int32_t* group_ptr, const double* weights,
+                             const void* sample_w, const void* holdout_w, void* G_out, double* groupnorm_out,
+                             double* out, double* holdout_sum, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_dims(dtype, n, l);
+    const GroupFacts f = check_groups(n, G, group_ptr, weights);
+    check_sample(sample_w, holdout_w);
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    if (!A || !X || !b) throw Error{GLX_E_INVALID, "A, X and b must be device pointers"};
+    if (!out) throw Error{GLX_E_INVALID, "null out"};
+    const size_t head = cert_bytes(dtype, m, n, l);
+    const size_t grouped = group_carve(head, G, nullptr, nullptr);
+    check_ws(sample_bytes(grouped), ws, wsb, "glx_group_certificate_sw_workspace_bytes");
+    GroupDev d;
+    group_carve(head, G, ws, &d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const GroupView v = upload(dtype, d, G, group_ptr, weights, f, st);
+    if (holdout_sum != nullptr) *holdout_sum = 0.0;
+    if (sample_w == nullptr) {   // today's entry, call for call
+      certificate_run(dtype, m, n, l, A, X, b, mu, 0, G_out, groupnorm_out, out, d.head, head, stream, &v);
+      return;
+    }
+    const SampleView sw{sample_w, holdout_w, reinterpret_cast<double*>(static_cast<char*>(ws) + sample_off(grouped))};
+    certificate_run(dtype, m, n, l, A, X, b, mu, 0, G_out, groupnorm_out, out, d.head, head, stream, &v, &sw,
+                    holdout_sum);
+  });
+}
+
+int glx_group_certified_sw_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, int screen,
+                                           size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    if (G < 1 || G > n) throw Error{GLX_E_INVALID, "groups: G must be in 1 .. n"};
+    *bytes = group_carve(certified_bytes(dtype, m, n, l, screen != 0, G, true), G, nullptr, nullptr);
+  });
+}
+
+int glx_group_certified_sw_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, int screen,
+                                    char* out, size_t cap) {
+  const int rc = glx_group_certified_describe(dtype, m, n, l, max_run, screen, out, cap);
+  if (rc != GLX_OK) return rc;
+  const size_t used = std::strlen(out);
+  std::snprintf(out + used, cap - used, "; residual=weighted finalize (k_cert_fin_w)");
+  return GLX_OK;
+}
+
+int glx_group_certified_solve_sw(const glx_problem* prob, int64_t G, const int32_t* group_ptr, const double* weights,
+                                 const void* sample_w, const void* holdout_w, double t, double tol, int64_t maxit,
+                                 int screen, int check_every, const double* col_norms_dev, const double* col_stats,
+                                 int32_t* kept_rows_dev, int32_t* kept_groups_dev, void* ws, size_t wsb,
+                                 glx_group_certified_info* info, double* holdout_sum, void* stream) {
+  return guarded([&] {
+    if (!prob || !info) throw Error{GLX_E_INVALID, "null problem/info"};
+    if (prob->comm != nullptr) throw Error{GLX_E_INVALID, "the certified solve is single-GPU: comm must be NULL"};
+    check_dims(prob->dtype, prob->n, prob->l);
+    const GroupFacts f = check_groups(prob->n, G, group_ptr, weights);
+    check_sample(sample_w, holdout_w);
+    const bool weighted = sample_w != nullptr;   // (NULL: the grouped entry's own layout and calls)
+    const size_t head = certified_bytes(prob->dtype, prob->m, prob->n, prob->l, screen != 0, G, weighted);
+    check_ws(group_carve(head, G, nullptr, nullptr), ws, wsb, "glx_group_certified_sw_workspace_bytes");
+    if (!prob->A || !prob->b || !prob->x) throw Error{GLX_E_INVALID, "A, b and x must be device pointers"};
+    GroupDev d;
+    group_carve(head, G, ws, &d);
+    const GroupView v = upload(prob->dtype, d, G, group_ptr, weights, f, static_cast<hipStream_t>(stream));
+    std::memset(info, 0, sizeof *info);
+    int64_t listed_groups = 0;
+    const SampleView sw{sample_w, holdout_w, nullptr};
+    certified_run(prob, t, tol, maxit, screen, check_every, col_norms_dev, col_stats, kept_rows_dev, d.head, head,
+                  &info->base, stream, &v, kept_groups_dev, &listed_groups, weighted ? &sw : nullptr, holdout_sum);
     info->kept_groups = screen != 0 ? info->base.kept : G;
     info->listed_groups = listed_groups;
     info->max_run = f.max_run;

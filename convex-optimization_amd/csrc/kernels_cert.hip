@@ -1,6 +1,7 @@
 // kernels_cert.hip — the kernels of the optimality certificate (DESIGN.md "Certificate") around
 // its two dense products A x and g = A^T r:
 //   k_cert_fin  sums the slabs of A x in slab order into r = A x - b and reduces ||r||^2, <r, b>
+//   k_cert_fin_w  the same with one weight per row of A: r, w r and the weighted sums
 //   k_cert_row  the row terms (cert_row, glx_device.h) on a given g, any n and l <= kMaxL (their
 //               fused form is k_atr_cert and its panel counterpart k_cert_panel, kernels_atr.hip)
 // mu is rounded to T first, as in kernels_elem.hip; reductions are deterministic (grid_reduce,
@@ -34,6 +35,39 @@ __global__ __launch_bounds__(256) void k_cert_fin(const T* __restrict__ P, int S
     v[1] += (double)rv * (double)bv;
   }
   grid_reduce<2, 0u>(v, red);
+}
+
+// The finalize of the sample-weighted problem (DESIGN.md "Sample weights and cross-validation"):
+// k_cert_fin's thread-to-element map and accumulation order with one weight per row of A (element
+// idx belongs to row idx / l; w holds m values of T, >= 0). r (may be NULL) receives the unweighted
+// r^ = fl(A x) - b, rw = fl(w r^) is the operand of the A^T pass, and the sums are
+//   [sum w r^2, sum w r^ b, sum v r^2 (HOLD: v = the hold-out weights)]
+// with every product formed as ((double)w r^) r^, which is exact for w = 1: the first two sums and rw
+// are then k_cert_fin's bits. The row comes from a plain division, 32-bit where m l allows it: at one
+// element per thread it is noise beside the loads (the launch is a few microseconds between two
+// passes over A).
+template <typename T, bool HOLD>
+__global__ __launch_bounds__(256) void k_cert_fin_w(const T* __restrict__ P, int S, const T* __restrict__ b,
+                                                    const T* __restrict__ w, const T* __restrict__ hv,
+                                                    T* __restrict__ r, T* __restrict__ rw, int64_t ml, int64_t l,
+                                                    Red red) {
+  double v[HOLD ? 3 : 2] = {};
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  const bool narrow = ml <= (int64_t)0xffffffffll;   // uniform: l <= ml
+  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < ml; idx += stride) {
+    const int64_t row = narrow ? (int64_t)((unsigned)idx / (unsigned)l) : idx / l;
+    const T ax = S > 0 ? slab_sum(P, S, ml, idx) : T(0);
+    const T bv = b[idx];
+    const T wv = w[row];
+    const T rv = ax - bv;
+    if (r != nullptr) r[idx] = rv;
+    rw[idx] = wv * rv;
+    const double wr = (double)wv * (double)rv;
+    v[0] += wr * (double)rv;
+    v[1] += wr * (double)bv;
+    if constexpr (HOLD) v[2] += ((double)hv[row] * (double)rv) * (double)rv;
+  }
+  grid_reduce<HOLD ? 3 : 2, 0u>(v, red);
 }
 
 // Rows of x are owned by LPR lanes holding EPL elements strided by LPR (kernels_elem.hip's layout)
@@ -76,6 +110,16 @@ void launch_cert_fin(const T* P, int S, const T* b, T* r, int64_t ml, Red red, h
   hipLaunchKernelGGL(k_cert_fin<T>, dim3(cert_grid_for(ml, 256)), dim3(256), 0, st, P, S, b, r, ml, red);
 }
 
+template <typename T>
+void launch_cert_fin_w(const T* P, int S, const T* b, const T* w, const T* hv, T* r, T* rw, int64_t ml, int64_t l,
+                       Red red, hipStream_t st) {
+  const dim3 grid(cert_grid_for(ml, 256));   // (k_cert_fin's grid: the same partials, the same order)
+  if (hv != nullptr)
+    hipLaunchKernelGGL((k_cert_fin_w<T, true>), grid, dim3(256), 0, st, P, S, b, w, hv, r, rw, ml, l, red);
+  else
+    hipLaunchKernelGGL((k_cert_fin_w<T, false>), grid, dim3(256), 0, st, P, S, b, w, hv, r, rw, ml, l, red);
+}
+
 template <typename T, int LPR, int EPL>
 static void cert_row_go(const T* x, const T* g, int S, T* gout, double* rn, int64_t n, int64_t l, double mu,
                         Red red, hipStream_t st) {
@@ -113,6 +157,8 @@ void launch_cert_row(const T* x, const T* g, int S, T* gout, double* rn, int64_t
 
 #define GLX_CERT_INST(T)                                                                              \
   template void launch_cert_fin<T>(const T*, int, const T*, T*, int64_t, Red, hipStream_t);           \
+  template void launch_cert_fin_w<T>(const T*, int, const T*, const T*, const T*, T*, T*, int64_t,    \
+                                     int64_t, Red, hipStream_t);                                      \
   template void launch_cert_row<T>(const T*, const T*, int, T*, double*, int64_t, int64_t, double, Red, \
                                    hipStream_t);
 

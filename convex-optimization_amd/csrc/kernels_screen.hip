@@ -2,6 +2,7 @@
 //   k_col_norms    ||a_i||_2 of every column of row-major A in one coalesced pass, accumulated in
 //                  double over fixed row slabs; the last workgroup of a column block sums the slabs in
 //                  slab order and the grid reduction gives max_i ||a_i|| and sum_i ||a_i||^2
+//   k_col_norms_w  the same walk with a weight per row of A: sqrt(sum_j w_j A_ji^2)
 //   k_screen       the test  s ||g_i|| + ||a_i|| rho < mu  per row, the keep mask, and the ascending
 //                  list of kept rows by an ordered scan: wave ballots, their popcounts, block offsets
 //   k_gather_cols  dst[r, j] = src[r, idx[j]] (0 where idx[j] < 0), 16-byte stores
@@ -85,11 +86,74 @@ __global__ __launch_bounds__(256) void k_col_norms(const T* __restrict__ A, int6
   grid_reduce<2, 0x1u>(v, red, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// The weighted norms sqrt(sum_j w_j A_ji^2) of the sample-weighted problem (DESIGN.md "Sample weights
+// and cross-validation"): k_col_norms' walk, slabs and last-block combine, kept as a sibling so that
+// k_col_norms stays instruction for instruction (a shared inlined body did not compile to the same
+// code). w_j is uniform over a wave (a lane owns a column): one broadcast load per row. The term is
+// (w a) a, which is a a exactly for w = 1 and 0 for w = 0.
+template <typename T>
+__global__ __launch_bounds__(256) void k_col_norms_w(const T* __restrict__ A, const T* __restrict__ w, int64_t m,
+                                                     int64_t n, int64_t rps, double* __restrict__ part,
+                                                     unsigned* __restrict__ ccnt, double* __restrict__ norms,
+                                                     Red red) {
+  __shared__ int last;
+  const int64_t r0 = (int64_t)blockIdx.y * rps;
+  const int64_t r1 = r0 + rps < m ? r0 + rps : m;
+  const int64_t cstride = (int64_t)gridDim.x * 256;
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += cstride) {
+    const T* p = A + r0 * n + j;
+    double acc = 0.0;
+    int64_t r = r0;
+    for (; r + 4 <= r1; r += 4) {
+      const double a0 = (double)p[0], a1 = (double)p[n], a2 = (double)p[2 * n], a3 = (double)p[3 * n];
+      acc += ((double)w[r] * a0) * a0;
+      acc += ((double)w[r + 1] * a1) * a1;
+      acc += ((double)w[r + 2] * a2) * a2;
+      acc += ((double)w[r + 3] * a3) * a3;
+      p += 4 * n;
+    }
+    for (; r < r1; ++r) {
+      const double a0 = (double)p[0];
+      acc += ((double)w[r] * a0) * a0;
+      p += n;
+    }
+    __hip_atomic_store(part + (int64_t)blockIdx.y * n + j, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned arrival = __hip_atomic_fetch_add(ccnt + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = arrival == gridDim.y - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  double v[2] = {-__builtin_inf(), 0.0};
+  const int S = (int)gridDim.y;
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += cstride) {
+    double s = 0.0;
+    for (int k = 0; k < S; ++k)
+      s += __hip_atomic_load(part + (int64_t)k * n + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double nrm = __builtin_sqrt(s);
+    norms[j] = nrm;
+    v[0] = nan_max(v[0], nrm);
+    v[1] += s;
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(ccnt + blockIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  grid_reduce<2, 0x1u>(v, red, (int)blockIdx.x, (int)gridDim.x);
+}
+
 template <typename T>
 void launch_col_norms(const T* A, int64_t m, int64_t n, double* norms, double* part, unsigned* ccnt, Red red,
                       hipStream_t st) {
   const dim3 grid(col_norm_blocks(n), (unsigned)col_norm_slabs(m));
   hipLaunchKernelGGL(k_col_norms<T>, grid, dim3(256), 0, st, A, m, n, col_norm_rows_per_slab(m), part, ccnt,
+                     norms, red);
+}
+template <typename T>
+void launch_col_norms_w(const T* A, const T* w, int64_t m, int64_t n, double* norms, double* part, unsigned* ccnt,
+                        Red red, hipStream_t st) {
+  const dim3 grid(col_norm_blocks(n), (unsigned)col_norm_slabs(m));
+  hipLaunchKernelGGL(k_col_norms_w<T>, grid, dim3(256), 0, st, A, w, m, n, col_norm_rows_per_slab(m), part, ccnt,
                      norms, red);
 }
 
@@ -274,6 +338,8 @@ void launch_compose_list(const int* map, const int* idx, int64_t wp, int* out, h
 
 #define GLX_SCREEN_INST(T)                                                                                  \
   template void launch_col_norms<T>(const T*, int64_t, int64_t, double*, double*, unsigned*, Red, hipStream_t); \
+  template void launch_col_norms_w<T>(const T*, const T*, int64_t, int64_t, double*, double*, unsigned*, Red, \
+                                      hipStream_t);                                                         \
   template void launch_gather_cols<T>(const T*, int64_t, int64_t, const int*, int64_t, T*, hipStream_t);     \
   template void launch_gather_rows<T>(const T*, const int*, int64_t, int64_t, T*, hipStream_t);             \
   template void launch_scatter_rows<T>(const T*, const int*, int64_t, int64_t, T*, hipStream_t);

@@ -16,6 +16,11 @@
 // certificate takes the view, the screen runs on the G "rows" ||g_[g]|| / w_g against
 // ||A_[g]||_F / w_g under group_screen_guard, and launch_group_expand turns the kept groups into the
 // row list a compaction gathers with. Without a view every call and every byte is the row solve's.
+// With a SampleView (DESIGN.md "Sample weights and cross-validation") the loop solves
+// 1/2 sum_j w_j ||(A x - b)_j||^2 + mu Omega(x): the two residual finalizes become launch_cert_fin_w
+// (r = w (A y - b) is the R every step already takes), ||b~|| and the column figures are the weighted
+// ones, every certificate takes the weights and the guards count their roundings; the final
+// certificate also reduces the hold-out sum. Without one, again, nothing differs.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -79,20 +84,25 @@ inline int64_t pad64(int64_t v) { return (v + 63) / 64 * 64; }
 // rec: the certificate's record of the stored residual r^ and g^ = A^T r^ in dtype arithmetic.
 // out = [s_safe, gap+, rho+]. Every quantity below is an upper bound; NaN propagates (and then
 // keeps every row in k_screen).
+// weighted: the sample-weighted problem's record and figures (cmax, csq of the weighted column norms,
+// bn = ||b~||); k counts the one more rounding of w r^ before the A^T pass, of (w r^) r^ and (w r^) b in
+// the fp64 sums, and of (w a) a in the column norms (DESIGN.md "Sample weights and cross-validation").
 void screen_guard(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, double cmax,
-                  double csq, double bn, double* out) {
+                  double csq, double bn_in, double* out, bool weighted = false) {
+  const double k = weighted ? 3.0 : 2.0;
   const double u = dtype == GLX_F64 ? DBL_EPSILON : (double)FLT_EPSILON;   // eps of A's dtype
   const double u64 = DBL_EPSILON;
   const double rr = rec[0], rb = rec[1], sx = rec[2], gmax = rec[3];
   const double rn = std::sqrt(rr);
-  const double gm = gamma_k((double)m + 2.0, u), gn = gamma_k((double)n + 2.0, u);
+  const double gm = gamma_k((double)m + k, u), gn = gamma_k((double)n + 2.0, u);
+  const double ml = (double)m * (double)l;
+  const double g_ml = gamma_k(ml + k, u64);
+  const double bn = weighted ? bn_in * (1.0 + g_ml) : bn_in;   // (the weighted ||b~|| is itself such a sum)
   // 1. dual feasibility: ||a_i^T r^|| <= ||g^_i|| + gm ||a_i|| ||r^||
   const double den = gmax + gm * cmax * rn;
   const double s = den > mu ? mu / den : (den <= mu ? 1.0 : den);   // (NaN den: NaN)
   // 2. the primal value: ||r^ - (A x - b)|| <= dr
   const double dr = gn * std::sqrt(csq) * sx + u * (rn + 2.0 * bn);
-  const double ml = (double)m * (double)l;
-  const double g_ml = gamma_k(ml + 2.0, u64);
   const double bar_rr = g_ml * rr;                      // the fp64 sum ||r^||^2
   const double bar_rb = g_ml * rn * bn;                 // the fp64 sum <r^, b> (Cauchy-Schwarz on sum |r b|)
   const double bar_sx = (gamma_k((double)l + 2.0, u) + gamma_k((double)n + 2.0, u64)) * sx;   // sum_i ||x_i||
@@ -104,7 +114,7 @@ void screen_guard(const double* rec, double mu, int dtype, int64_t m, int64_t n,
   //    norms themselves are low by at most gamma64_{m+2}
   const double gl = gamma_k((double)l + 2.0, u);
   double rho = std::sqrt(2.0 * gap_p) + s * gm * rn + s * gl * (1.0 + gm) * rn;
-  rho *= 1.0 + gamma_k((double)m + 2.0, u64);
+  rho *= 1.0 + gamma_k((double)m + k, u64);
   out[0] = s;
   out[1] = gap_p;
   out[2] = rho;
@@ -173,9 +183,10 @@ struct Ws {
   // problem's gcn, and the screen's list of kept groups
   int *gptr[2], *gmap[2], *glist;
   double *gw[2], *ggcn[2], *gcn_full;
+  double* ssums;   // sample weights: the weighted finalize's sums of a certificate (SampleView::sums)
 };
 size_t carve(int dtype, int64_t m, int64_t n, int64_t l, bool screen, bool own_norms, void* base, Ws* out,
-             int64_t G = 0) {
+             int64_t G = 0, bool weighted = false) {
   const size_t es = dtype == GLX_F64 ? 8 : 4;
   const Extent e = extent(dtype, m, n, l, screen);
   const int64_t np = pad64(n);
@@ -212,6 +223,7 @@ size_t carve(int dtype, int64_t m, int64_t n, int64_t l, bool screen, bool own_n
   }
   w.gcn_full = static_cast<double*>(c.take(sizeof(double) * (size_t)G));
   w.glist = static_cast<int*>(c.take(G > 0 ? sizeof(int) * (size_t)pad64(G) : 0));
+  w.ssums = static_cast<double*>(c.take(weighted ? 256 : 0));   // (behind the grouped pieces in turn)
   if (out) *out = w;
   return c.off + 256;
 }
@@ -242,7 +254,13 @@ Composed compose(const double* rec, double mu) {
 }
 
 void cert_call(int dtype, int64_t m, int64_t w, int64_t l, const void* A, const void* x, const void* b, double mu,
-               double* rn, double* rec, const Ws& ws, hipStream_t st, const GroupView* grp = nullptr) {
+               double* rn, double* rec, const Ws& ws, hipStream_t st, const GroupView* grp = nullptr,
+               const SampleView* sw = nullptr, double* holdout_sum = nullptr) {
+  if (sw != nullptr) {   // the weighted problem's certificate, rows or groups
+    certificate_run(dtype, m, w, l, A, x, b, mu, 0, nullptr, rn, rec, ws.cert, ws.cert_bytes, st, grp, sw,
+                    holdout_sum);
+    return;
+  }
   if (grp != nullptr) {   // (rn: ||g_[g]|| / w_g of the grp->G groups)
     certificate_run(dtype, m, w, l, A, x, b, mu, 0, nullptr, rn, rec, ws.cert, ws.cert_bytes, st, grp);
     return;
@@ -255,9 +273,13 @@ template <typename T>
 void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T* X, double mu, double t,
            double tol, int64_t maxit, bool screen, int check_every, const double* cn_in, const double* cstats_in,
            int32_t* kept_rows, void* wsp, glx_certified_info* info, hipStream_t st, const GroupView* grp,
-           int32_t* kept_groups, int64_t* listed_groups) {
+           int32_t* kept_groups, int64_t* listed_groups, const SampleView* sw, double* holdout_sum) {
   Ws w;
-  carve(dtype, m, n, l, screen, cn_in == nullptr, wsp, &w, grp != nullptr ? grp->G : 0);
+  carve(dtype, m, n, l, screen, cn_in == nullptr, wsp, &w, grp != nullptr ? grp->G : 0, sw != nullptr);
+  // sample weights: the loop's certificates take the weights alone, the final one the hold-out too
+  const T* sww = sw != nullptr ? static_cast<const T*>(sw->w) : nullptr;
+  const SampleView sw_in{sw != nullptr ? sw->w : nullptr, nullptr, w.ssums};
+  const SampleView sw_out{sw != nullptr ? sw->w : nullptr, sw != nullptr ? sw->hold : nullptr, w.ssums};
   const size_t es = sizeof(T);
   const double thres = std::is_same<T, double>::value ? DBL_MIN : (double)FLT_MIN;
   const int64_t ml = m * l;
@@ -280,12 +302,17 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
       cmax = cstats_in[0];
       csq = cstats_in[1];
     } else {
-      launch_col_norms<T>(A, m, n, w.cn[1], w.cpart, w.ccnt, red2, st);
+      if (sww != nullptr) launch_col_norms_w<T>(A, sww, m, n, w.cn[1], w.cpart, w.ccnt, red2, st);
+      else launch_col_norms<T>(A, m, n, w.cn[1], w.cpart, w.ccnt, red2, st);
       check_launch();
       cn = w.cn[1];
       info->passes += 1.0;
     }
-    launch_cert_fin<T>(nullptr, 0, b, static_cast<T*>(w.r), ml, red0, st);   // r = -b: red0 = [||b||^2, .]
+    // r = -b: red0 = [||b||^2, .] (weighted: sum w b^2 = ||b~||^2, the null product of k_cert_fin_w)
+    if (sww != nullptr)
+      launch_cert_fin_w<T>(nullptr, 0, b, sww, nullptr, nullptr, static_cast<T*>(w.r), ml, l, red0, st);
+    else
+      launch_cert_fin<T>(nullptr, 0, b, static_cast<T*>(w.r), ml, red0, st);
     check_launch();
     double h[4];
     GLX_HIP(hipMemcpyAsync(h, w.red, sizeof(double), hipMemcpyDeviceToHost, st));
@@ -342,7 +369,8 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
       launch_scatter_rows<T>(x, map, wc, l, X, st);
       check_launch();
     }
-    cert_call(dtype, m, n, l, A, X, b, mu, nullptr, info->cert, w, st, grp);
+    cert_call(dtype, m, n, l, A, X, b, mu, nullptr, info->cert, w, st, grp, sw != nullptr ? &sw_out : nullptr,
+              holdout_sum);
     info->passes += 2.0;
     return compose(info->cert, mu);
   };
@@ -351,7 +379,8 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
   // where it pays, a compaction. Returns true when the reduced problem meets `target`.
   auto check = [&]() -> bool {
     ++info->checks;
-    cert_call(dtype, m, wc, l, Ac, x, b, mu, w.rn, rec, w, st, grp != nullptr ? &gcur : nullptr);
+    cert_call(dtype, m, wc, l, Ac, x, b, mu, w.rn, rec, w, st, grp != nullptr ? &gcur : nullptr,
+              sw != nullptr ? &sw_in : nullptr);
     info->passes += 2.0 * (double)wc / (double)n;
     const Composed c = compose(rec, mu);
     info->inner_rel_gap = c.rel;
@@ -361,14 +390,14 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     const double mu_lo = mu * (1.0 - 4.0 * DBL_EPSILON);   // the test's own three roundings in fp64
     int hc[4] = {0, 0, 0, 0};
     if (grp != nullptr) {   // the same test on the G "rows" of groups, then their rows
-      group_screen_guard(rec, mu, dtype, m, wc, l, grp->max_run, grp->w_min, gcol_max, csq, bn, gd);
+      group_screen_guard(rec, mu, dtype, m, wc, l, grp->max_run, grp->w_min, gcol_max, csq, bn, gd, sw != nullptr);
       launch_screen(w.rn, gcn, gcur.G, gd[0], gd[2], mu_lo, nullptr, w.glist, w.cnt, w.bal, w.sticket, st);
       launch_group_expand(w.glist, w.cnt, gcur.ptr, gcur.wts, gcn, gmap, w.list, w.gptr[gside], w.gw[gside],
                           w.ggcn[gside], w.gmap[gside], w.cnt + 2, st);
       check_launch();
       GLX_HIP(hipMemcpyAsync(hc, w.cnt, sizeof hc, hipMemcpyDeviceToHost, st));
     } else {
-      screen_guard(rec, mu, dtype, m, wc, l, cmax, csq, bn, gd);
+      screen_guard(rec, mu, dtype, m, wc, l, cmax, csq, bn, gd, sw != nullptr);
       launch_screen(w.rn, cn, wc, gd[0], gd[2], mu_lo, nullptr, w.list, w.cnt, w.bal, w.sticket, st);
       check_launch();
       GLX_HIP(hipMemcpyAsync(hc, w.cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -426,7 +455,10 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     const T* xs[3] = {y, nullptr, nullptr};
     T* r = static_cast<T*>(w.r);
     launch_ax<T>(pl.a, 1, Ac, xs, static_cast<T*>(w.pa), nullptr, 0, st);
-    launch_cert_fin<T>(static_cast<T*>(w.pa), ax_split(pl.a, 1), b, r, ml, red0, st);
+    if (sww != nullptr)   // r = w (A y - b): every step below takes it as the R it already takes
+      launch_cert_fin_w<T>(static_cast<T*>(w.pa), ax_split(pl.a, 1), b, sww, nullptr, nullptr, r, ml, l, red0, st);
+    else
+      launch_cert_fin<T>(static_cast<T*>(w.pa), ax_split(pl.a, 1), b, r, ml, red0, st);
     T* gp = static_cast<T*>(w.gp);
     if (grp != nullptr) {   // the grouped step is never fused: A^T r, then the group kernel on its slabs
       launch_atr<T>(pl.a, Ac, r, gp, st);
@@ -515,9 +547,9 @@ size_t step_carve(int64_t m, int64_t n, void* base, StepWs* out) {
 
 }  // namespace
 
-size_t certified_bytes(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t G) {
+size_t certified_bytes(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t G, bool weighted) {
   check_shape(dtype, m, n, l);
-  return carve(dtype, m, n, l, screen, true, nullptr, nullptr, G);
+  return carve(dtype, m, n, l, screen, true, nullptr, nullptr, G, weighted);
 }
 
 std::string certified_describe(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run) {
@@ -528,8 +560,10 @@ std::string certified_describe(int dtype, int64_t m, int64_t n, int64_t l, bool 
 void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit, int screen, int check_every,
                    const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev, void* ws,
                    size_t wsb, glx_certified_info* info, void* stream, const GroupView* grp,
-                   int32_t* kept_groups_dev, int64_t* listed_groups) {
+                   int32_t* kept_groups_dev, int64_t* listed_groups, const SampleView* sw, double* holdout_sum) {
   if (!prob || !info) throw Error{GLX_E_INVALID, "null problem/info"};
+  if (sw != nullptr) check_sample(sw->w, sw->hold);
+  if (sw != nullptr && sw->w == nullptr) throw Error{GLX_E_INVALID, "sample weights: null vector"};
   if (prob->comm != nullptr) throw Error{GLX_E_INVALID, "the certified solve is single-GPU: comm must be NULL"};
   check_shape(prob->dtype, prob->m, prob->n, prob->l);
   if (!(prob->mu0 >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
@@ -544,17 +578,18 @@ void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit,
   if ((col_norms_dev != nullptr) != (col_stats != nullptr))
     throw Error{GLX_E_INVALID, "col_norms_dev and col_stats go together"};
   check_ws(carve(prob->dtype, prob->m, prob->n, prob->l, screen != 0, true, nullptr, nullptr,
-                 grp != nullptr ? grp->G : 0),
+                 grp != nullptr ? grp->G : 0, sw != nullptr),
            ws, wsb, grp != nullptr ? "glx_group_certified_workspace_bytes" : "glx_certified_workspace_bytes");
+  if (holdout_sum != nullptr) *holdout_sum = 0.0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (prob->dtype == GLX_F64)
     solve<double>(prob->dtype, prob->m, prob->n, prob->l, (const double*)prob->A, (const double*)prob->b,
                   (double*)prob->x, prob->mu0, t, tol, maxit, screen != 0, check_every, col_norms_dev, col_stats,
-                  kept_rows_dev, ws, info, st, grp, kept_groups_dev, listed_groups);
+                  kept_rows_dev, ws, info, st, grp, kept_groups_dev, listed_groups, sw, holdout_sum);
   else
     solve<float>(prob->dtype, prob->m, prob->n, prob->l, (const float*)prob->A, (const float*)prob->b,
                  (float*)prob->x, prob->mu0, t, tol, maxit, screen != 0, check_every, col_norms_dev, col_stats,
-                 kept_rows_dev, ws, info, st, grp, kept_groups_dev, listed_groups);
+                 kept_rows_dev, ws, info, st, grp, kept_groups_dev, listed_groups, sw, holdout_sum);
 }
 
 }  // namespace glx
@@ -651,6 +686,104 @@ int glx_certified_solve(const glx_problem* prob, double t, double tol, int64_t m
   return guarded([&] {
     certified_run(prob, t, tol, maxit, screen, check_every, col_norms_dev, col_stats, kept_rows_dev, ws, wsb, info,
                   stream, nullptr, nullptr, nullptr);
+  });
+}
+
+/* ---- sample weights (DESIGN.md "Sample weights and cross-validation") ---- */
+
+int glx_screen_guard_sw(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, double col_max,
+                        double col_sumsq, double b_norm, double* out) {
+  return guarded([&] {
+    if (!rec || !out) throw Error{GLX_E_INVALID, "null argument"};
+    check_shape(dtype, m, n, l);
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    screen_guard(rec, mu, dtype, m, n, l, col_max, col_sumsq, b_norm, out, true);
+  });
+}
+
+int glx_col_norms_sw(int dtype, int64_t m, int64_t n, const void* A, const void* sample_w, double* norms_dev,
+                     double* stats_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_shape(dtype, m, n, 1);
+    if (!A || !sample_w || !norms_dev || !stats_dev) throw Error{GLX_E_INVALID, "null argument"};
+    check_sample(sample_w, nullptr);
+    check_ws(step_carve(m, n, nullptr, nullptr), ws, wsb, "glx_screen_workspace_bytes");
+    StepWs w;
+    step_carve(m, n, ws, &w);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    GLX_HIP(hipMemsetAsync(w.ccnt, 0, col_norms_count_bytes(n), st));
+    const Red red{w.part, w.ticket, stats_dev};
+    if (dtype == GLX_F64)
+      launch_col_norms_w<double>((const double*)A, (const double*)sample_w, m, n, norms_dev, w.cpart, w.ccnt, red, st);
+    else
+      launch_col_norms_w<float>((const float*)A, (const float*)sample_w, m, n, norms_dev, w.cpart, w.ccnt, red, st);
+    check_launch();
+  });
+}
+
+int glx_cert_fin_sw(int dtype, int64_t m, int64_t l, const void* P, int S, const void* b, const void* sample_w,
+                    const void* holdout_w, void* r_out, void* rw_out, double* sums_dev, void* ws, size_t wsb,
+                    void* stream) {
+  return guarded([&] {
+    check_shape(dtype, m, 1, l);
+    if (S < 0 || S > kMaxSplit) throw Error{GLX_E_INVALID, "S must be in 0 .. 64"};
+    if ((S > 0) != (P != nullptr)) throw Error{GLX_E_INVALID, "P goes with S > 0"};
+    if (!b || !rw_out || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
+    check_sample(sample_w, holdout_w);
+    check_ws(step_carve(1, 1, nullptr, nullptr), ws, wsb, "glx_screen_workspace_bytes");
+    StepWs w;
+    step_carve(1, 1, ws, &w);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    const Red red{w.part, w.ticket, sums_dev};
+    const int64_t ml = m * l;
+    auto go = [&](auto* tag) {
+      typedef std::remove_pointer_t<decltype(tag)> T;
+      if (sample_w != nullptr)
+        launch_cert_fin_w<T>((const T*)P, S, (const T*)b, (const T*)sample_w, (const T*)holdout_w, (T*)r_out,
+                             (T*)rw_out, ml, l, red, st);
+      else   // the unweighted finalize, for the bit comparison: rw_out = r, two sums
+        launch_cert_fin<T>((const T*)P, S, (const T*)b, (T*)rw_out, ml, red, st);
+    };
+    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
+    else go(static_cast<float*>(nullptr));
+    check_launch();
+  });
+}
+
+int glx_certified_sw_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int screen, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    check_shape(dtype, m, n, l);
+    *bytes = carve(dtype, m, n, l, screen != 0, true, nullptr, nullptr, 0, true);
+  });
+}
+
+int glx_certified_sw_describe(int dtype, int64_t m, int64_t n, int64_t l, int screen, char* out, size_t cap) {
+  return guarded([&] {
+    if (!out || cap == 0) throw Error{GLX_E_INVALID, "null out"};
+    check_shape(dtype, m, n, l);
+    std::snprintf(out, cap, "%s; residual=weighted finalize (k_cert_fin_w)",
+                  describe_certified(dtype, m, n, l, screen != 0).c_str());
+  });
+}
+
+int glx_certified_solve_sw(const glx_problem* prob, const void* sample_w, const void* holdout_w, double t, double tol,
+                           int64_t maxit, int screen, int check_every, const double* col_norms_dev,
+                           const double* col_stats, int32_t* kept_rows_dev, void* ws, size_t wsb,
+                           glx_certified_info* info, double* holdout_sum, void* stream) {
+  return guarded([&] {
+    check_sample(sample_w, holdout_w);
+    if (holdout_sum != nullptr) *holdout_sum = 0.0;
+    if (sample_w == nullptr) {   // today's entry, call for call (its workspace is a prefix of this one's)
+      certified_run(prob, t, tol, maxit, screen, check_every, col_norms_dev, col_stats, kept_rows_dev, ws, wsb, info,
+                    stream, nullptr, nullptr, nullptr);
+      return;
+    }
+    const SampleView sw{sample_w, holdout_w, nullptr};
+    certified_run(prob, t, tol, maxit, screen, check_every, col_norms_dev, col_stats, kept_rows_dev, ws, wsb, info,
+                  stream, nullptr, nullptr, nullptr, &sw, holdout_sum);
   });
 }
 

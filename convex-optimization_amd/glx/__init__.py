@@ -18,12 +18,16 @@ Public surface:
   * ``groups=`` / ``weights=`` on ``certificate``, ``mu_max``, ``solve_certified`` and ``path`` — the
     classical group lasso over contiguous feature groups with weights, and ``group_order(labels)``,
     the host-only helper that sorts arbitrary labels into such groups;
+  * ``sample_weight=`` on the same four (and ``holdout_weight=`` on the two solves) — observation
+    weights on the caller's A: weighted least squares, row subsets as 0/1 vectors, case weights; and
+    ``cv_path(A, b, folds=5)`` — K-fold cross-validation over the mu path built on them (``glx/cv.py``);
   * ``dist`` — row sharding + RCCL communicator.
 """
 from ._lib import LIB_PATH, GlxError, lib  # noqa: F401
 from .solver import Session, solve  # noqa: F401
 from .certificate import certificate, group_order, mu_max  # noqa: F401
 from .screen import path, solve_certified  # noqa: F401
+from .cv import cv_path  # noqa: F401
 
 __all__ = ["solve", "Session", "lib", "LIB_PATH", "GlxError", "certificate", "mu_max",
-           "solve_certified", "path", "group_order"]
+           "solve_certified", "path", "group_order", "cv_path"]

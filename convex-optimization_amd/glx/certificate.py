@@ -107,6 +107,38 @@ def check_groups(groups, weights, n: int, l: int = 1):
     return np.ascontiguousarray(ptr, dtype=np.int32), np.ascontiguousarray(w)
 
 
+def check_sample_weight(sample_weight, m: int, dtype=np.float64, name: str = "sample_weight"):
+    """The host-side check of observation weights for an m-row A, before any device work. None stays
+    None (the unweighted problem, today's path and bits); anything else must be m finite values >= 0
+    with at least one > 0 and comes back as a contiguous NumPy array rounded ONCE to ``dtype`` (A's), so
+    that every kernel and the guard see the same problem. ValueError for a wrong length, a negative,
+    NaN or infinite weight (also one that rounding to float32 makes infinite) and all-zero weights."""
+    if sample_weight is None:
+        return None
+    if isinstance(sample_weight, torch.Tensor):
+        sample_weight = sample_weight.detach().cpu().numpy()
+    w = np.asarray(sample_weight, dtype=np.float64)
+    if w.ndim != 1 or w.size != int(m):
+        raise ValueError("%s must have one entry per row of A (%d), got shape %s" % (name, int(m), tuple(w.shape)))
+    with np.errstate(over="ignore"):
+        w = np.ascontiguousarray(w.astype(np.float32 if np.dtype(dtype) == np.float32 else np.float64))
+    if not np.all(np.isfinite(w)):
+        raise ValueError("every %s must be finite" % name)
+    if np.any(w < 0.0):
+        raise ValueError("every %s must be >= 0" % name)
+    if not np.any(w > 0.0):
+        raise ValueError("%s: at least one weight must be > 0" % name)
+    return w
+
+
+def _np_dtype(A):
+    return np.float32 if _dtype_of(A) == torch.float32 else np.float64
+
+
+def _rows_of(A) -> int:
+    return int(np.shape(A)[0]) if len(np.shape(A)) == 2 else -1
+
+
 def compose(rec, mu: float) -> Dict[str, Any]:
     """The certificate's figures from the record [||r||^2, <r, b>, sum_i ||x_i||, gmax, kkt_max,
     sum_i kkt_i^2, nonzero rows, fused was used] and mu, in float64."""
@@ -119,6 +151,11 @@ def compose(rec, mu: float) -> Dict[str, Any]:
     return {"primal": primal, "dual": dual, "gap": gap, "rel_gap": gap / max(abs(primal), _TINY),
             "scale": scale, "gmax": gmax, "kkt_max": kmax, "kkt_fro": math.sqrt(ksq),
             "nonzero_rows": nz if math.isnan(nz) else int(nz), "fused": bool(fused)}
+
+
+def _sw_device(w, device):
+    """The checked host weights (check_sample_weight) as a device tensor of their own dtype; None stays None."""
+    return None if w is None else torch.from_numpy(w).to(device)
 
 
 def _record(xd: torch.Tensor, Ad: torch.Tensor, bd: torch.Tensor, mu: float, fused: int, row_norms: bool):
@@ -135,6 +172,53 @@ def _record(xd: torch.Tensor, Ad: torch.Tensor, bd: torch.Tensor, mu: float, fus
                                     ws.data_ptr(), ws.numel(),
                                     ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
     return list(rec), rn, _lib.certificate_describe(gdt, m, n, l, fused)
+
+
+def _record_sw(xd, Ad, bd, mu: float, fused: int, row_norms: bool, sw, hw=None):
+    m, n = Ad.shape
+    l = xd.shape[1]
+    device = Ad.device
+    gdt = _lib.GLX_F64 if Ad.dtype == torch.float64 else _lib.GLX_F32
+    rec = (ctypes.c_double * 8)()
+    hs = ctypes.c_double(0.0)
+    with torch.cuda.device(device):
+        nb = ctypes.c_size_t(0)
+        check(lib().glx_certificate_sw_workspace_bytes(gdt, m, n, l, ctypes.byref(nb)))
+        ws = torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+        rn = torch.empty(n, dtype=torch.float64, device=device) if row_norms else None
+        check(lib().glx_certificate_sw(gdt, m, n, l, Ad.data_ptr(), xd.data_ptr(), bd.data_ptr(), float(mu),
+                                       int(fused), sw.data_ptr(), None if hw is None else hw.data_ptr(), None,
+                                       None if rn is None else rn.data_ptr(), rec, ctypes.byref(hs),
+                                       ws.data_ptr(), ws.numel(),
+                                       ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    buf = ctypes.create_string_buffer(2048)
+    check(lib().glx_certificate_sw_describe(gdt, m, n, l, int(fused), buf, len(buf)))
+    return list(rec), rn, buf.value.decode(), float(hs.value)
+
+
+def _group_record_sw(xd, Ad, bd, mu: float, gw, norms: bool, sw, hw=None):
+    ptr, w = gw
+    m, n = Ad.shape
+    l = xd.shape[1]
+    G = int(w.size)
+    device = Ad.device
+    gdt = _lib.GLX_F64 if Ad.dtype == torch.float64 else _lib.GLX_F32
+    rec = (ctypes.c_double * 8)()
+    hs = ctypes.c_double(0.0)
+    with torch.cuda.device(device):
+        nb = ctypes.c_size_t(0)
+        check(lib().glx_group_certificate_sw_workspace_bytes(gdt, m, n, l, G, ctypes.byref(nb)))
+        ws = torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+        gn = torch.empty(G, dtype=torch.float64, device=device) if norms else None
+        check(lib().glx_group_certificate_sw(gdt, m, n, l, Ad.data_ptr(), xd.data_ptr(), bd.data_ptr(), float(mu),
+                                             G, ptr.ctypes.data, w.ctypes.data, sw.data_ptr(),
+                                             None if hw is None else hw.data_ptr(), None,
+                                             None if gn is None else gn.data_ptr(), rec, ctypes.byref(hs),
+                                             ws.data_ptr(), ws.numel(),
+                                             ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    buf = ctypes.create_string_buffer(2048)
+    check(lib().glx_group_certificate_sw_describe(gdt, m, n, l, int(np.diff(ptr).max()), buf, len(buf)))
+    return list(rec), gn, buf.value.decode(), float(hs.value)
 
 
 def compose_groups(rec, mu: float) -> Dict[str, Any]:
@@ -195,7 +279,8 @@ def record(x, A, b, mu, *, fused: int = 0) -> np.ndarray:
     return np.asarray(_record(xd, Ad, bd, float(mu), fused, False)[0], dtype=np.float64)
 
 
-def certificate(x, A, b, mu, groups=None, weights=None, *, fused: int = 0, row_norms: bool = False) -> Dict[str, Any]:
+def certificate(x, A, b, mu, groups=None, weights=None, *, fused: int = 0, row_norms: bool = False,
+                sample_weight=None) -> Dict[str, Any]:
     """The duality gap and KKT violation of the iterate ``x`` at ``mu`` (module docstring).
 
     ``x`` (n x l), ``A`` (m x n) and ``b`` (m x l) are NumPy arrays or torch tensors and are not
@@ -210,21 +295,33 @@ def certificate(x, A, b, mu, groups=None, weights=None, *, fused: int = 0, row_n
     ``groups`` / ``weights`` (module docstring; both None: the row problem, today's path and bits):
     the certificate of ``mu sum_g w_g ||x_[g]||_F``. ``nonzero_groups`` replaces ``nonzero_rows``,
     ``gmax`` is ``max_g ||g_[g]|| / w_g``, ``fused`` is False (the group terms run behind the plain
-    product) and ``row_norms=True`` returns ``group_norms``: ``||g_[g]|| / w_g``, length G."""
+    product) and ``row_norms=True`` returns ``group_norms``: ``||g_[g]|| / w_g``, length G.
+
+    ``sample_weight`` (None: today's path, bit for bit): m observation weights ``w_j >= 0``, the
+    certificate of ``1/2 sum_j w_j ||(A x - b)_j||^2 + mu Omega(x)`` (:func:`check_sample_weight`; it
+    composes with ``groups`` / ``weights``, which weigh features). A is neither copied nor scaled."""
     mu = float(mu)
     if not mu >= 0.0:
         raise ValueError("mu must be >= 0")
     gw = check_groups(groups, weights, np.shape(A)[1] if len(np.shape(A)) == 2 else -1,
                       np.shape(b)[1] if len(np.shape(b)) == 2 else 1)
+    sw = check_sample_weight(sample_weight, _rows_of(A), _np_dtype(A))
     xd, Ad, bd = _inputs(x, A, b)
+    swd = _sw_device(sw, Ad.device)
     if gw is not None:
-        rec, gn, plan = _group_record(xd, Ad, bd, mu, gw, row_norms)
+        if swd is not None:
+            rec, gn, plan, _ = _group_record_sw(xd, Ad, bd, mu, gw, row_norms, swd)
+        else:
+            rec, gn, plan = _group_record(xd, Ad, bd, mu, gw, row_norms)
         out = compose_groups(rec, mu)
         out["plan"] = plan
         if row_norms:
             out["group_norms"] = gn if isinstance(A, torch.Tensor) else gn.cpu().numpy()
         return out
-    rec, rn, plan = _record(xd, Ad, bd, mu, fused, row_norms)
+    if swd is not None:
+        rec, rn, plan, _ = _record_sw(xd, Ad, bd, mu, fused, row_norms, swd)
+    else:
+        rec, rn, plan = _record(xd, Ad, bd, mu, fused, row_norms)
     out = compose(rec, mu)
     out["plan"] = plan
     if row_norms:
@@ -232,12 +329,19 @@ def certificate(x, A, b, mu, groups=None, weights=None, *, fused: int = 0, row_n
     return out
 
 
-def mu_max(A, b, groups=None, weights=None) -> float:
+def mu_max(A, b, groups=None, weights=None, sample_weight=None) -> float:
     """The smallest mu for which x = 0 is optimal, max_i ||(A^T b)_i||_2: the certificate's gmax at
-    x = 0, where r = -b. With ``groups`` / ``weights``: max_g ||(A^T b)_[g]||_F / w_g."""
+    x = 0, where r = -b. With ``groups`` / ``weights``: max_g ||(A^T b)_[g]||_F / w_g. With
+    ``sample_weight``: of A^T W b."""
     gw = check_groups(groups, weights, np.shape(A)[1] if len(np.shape(A)) == 2 else -1,
                       np.shape(b)[1] if len(np.shape(b)) == 2 else 1)
+    sw = check_sample_weight(sample_weight, _rows_of(A), _np_dtype(A))
     xd, Ad, bd = _inputs(None, A, b)
+    if sw is not None:
+        swd = _sw_device(sw, Ad.device)
+        if gw is not None:
+            return float(_group_record_sw(xd, Ad, bd, 0.0, gw, False, swd)[0][3])
+        return float(_record_sw(xd, Ad, bd, 0.0, 0, False, swd)[0][3])
     if gw is not None:
         return float(_group_record(xd, Ad, bd, 0.0, gw, False)[0][3])
     rec, _, _ = _record(xd, Ad, bd, 0.0, 0, False)

@@ -194,14 +194,17 @@ def setup_logger(log_file: Optional[str], level=logging.INFO) -> logging.Logger:
 def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Dict[str, dict]] = None,
         xstar: Optional[np.ndarray] = None, dest_dir: Optional[str] = None, seed: int = SEED,
         size=(256, 512, 2), stream: TextIO = sys.stdout, certify: bool = False,
-        certified: Optional[str] = None) -> Dict[str, Any]:
+        certified: Optional[str] = None, cv: int = 0) -> Dict[str, Any]:
     """The body of main.py's __main__ block (main.py:141-235) without the CVX solvers and plots.
 
     ``solvers`` defaults to the GPU solvers; tests pass other callables with the same signature.
     ``certify`` appends the ``gap`` and ``kkt`` columns (solve_routine); without it the log lines,
     the table and f_hist.npz are what they were before the flag existed. ``certified``: "solve" or
-    "path" appends certified_rows' rows to the table (they have no objective history).
-    Returns {"log_dicts", "f_hists", "f_star", "xs"}.
+    "path" appends certified_rows' rows to the table (they have no objective history). ``cv`` = K >= 2
+    appends the K-fold cross-validation table of glx.cv_path behind the Statistics output: one line
+    per mu with the mean validation loss, its standard error and a marker on the best and on the
+    one-standard-error choice.
+    Returns {"log_dicts", "f_hists", "f_star", "xs"} (and "cv": glx.cv_path's dict with ``cv``).
     """
     m, n, l = size
     n, m, l, mu, A, b, u, x0, errfun, errfun_exact, sparsity = gen_data(seed, m, n, l)
@@ -222,12 +225,20 @@ def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Di
                                       certify).items():
             log_dicts[mode] = d
     write_to_table(log_dicts, stream)
+    cv_out = None
+    if cv:
+        from glx.cv import cv_path, format_table
+        cv_out = cv_path(A, b, folds=int(cv))
+        stream.write("# Cross-validation (%d folds)\n%s\n" % (int(cv), format_table(cv_out)))
     f_star = obj_func(A, b, mu, u)
     if dest_dir:
         os.makedirs(dest_dir, exist_ok=True)
         np.savez(os.path.join(dest_dir, "f_hist.npz"), f_star=f_star,
                  **{k.replace(" ", "_"): v for k, v in f_hists.items()})
-    return {"log_dicts": log_dicts, "f_hists": f_hists, "f_star": f_star, "xs": xs}
+    res = {"log_dicts": log_dicts, "f_hists": f_hists, "f_star": f_star, "xs": xs}
+    if cv_out is not None:
+        res["cv"] = cv_out
+    return res
 
 
 def main(argv=None) -> int:
@@ -246,6 +257,9 @@ def main(argv=None) -> int:
     p.add_argument("--certified", nargs="?", const="solve", default=None, choices=["solve", "path"],
                    help="Append a 'Certified' row (glx.solve_certified to rel. gap 1e-6 with gap-safe "
                         "screening), or with 'path' the rows of glx.path over ten values of mu.")
+    p.add_argument("--cv", type=int, default=0, metavar="K",
+                   help="Append the K-fold cross-validation table of glx.cv_path over ten values of mu "
+                        "(mu, mean, se, best and 1-SE markers).")
     a = p.parse_args(argv)
     setup_logger(a.log)
     size = tuple(int(v) for v in a.size.split(","))
@@ -258,7 +272,7 @@ def main(argv=None) -> int:
             p.error(f"unknown solver(s) {unknown}; choose from {list(solvers)}")
         solvers = {k: solvers[k] for k in keep}
     run(solvers, xstar=xstar, dest_dir=a.dest_dir, seed=a.seed, size=size, stream=sys.stdout,
-        certify=a.certify, certified=a.certified)
+        certify=a.certify, certified=a.certified, cv=a.cv)
     return 0
 
 

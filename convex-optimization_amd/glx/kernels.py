@@ -627,6 +627,47 @@ def col_norms(A: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return norms, stats
 
 
+def col_norms_sw(A: torch.Tensor, sample_weight: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The weighted column norms sqrt(sum_j w_j A_ji^2) (glx_col_norms_sw): :func:`col_norms`' slabs and
+    combine with one weight per row of A (``sample_weight``: m values of A's dtype on A's device). Returns
+    (norms (n,), stats = [max, sum of squares]), float64 device tensors."""
+    m, n = A.shape
+    dev = A.device
+    assert sample_weight.dtype == A.dtype and sample_weight.shape == (m,) and sample_weight.is_contiguous()
+    norms = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    stats = torch.full((2,), float("nan"), dtype=torch.float64, device=dev)
+    ws = _screen_ws(m, n, dev)
+    check(lib().glx_col_norms_sw(_dt(A), m, n, A.data_ptr(), sample_weight.data_ptr(), norms.data_ptr(),
+                                 stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return norms, stats
+
+
+def cert_fin_sw(P: Optional[torch.Tensor], b: torch.Tensor, sample_weight: Optional[torch.Tensor],
+                holdout_weight: Optional[torch.Tensor] = None, want_r: bool = True) -> Dict[str, torch.Tensor]:
+    """The weighted residual finalize, one launch (glx_cert_fin_sw). ``P``: (S, m, l) slabs of A x, or
+    None for the null product; ``b`` (m, l); the weights m values of b's dtype. Returns {"r": fl(sum of
+    the slabs) - b (None without ``want_r``), "rw": fl(w r), "sums": float64 [sum w r^2, sum w r b,
+    sum v r^2 (NaN without hold-out weights)]}. ``sample_weight=None`` runs the unweighted finalize
+    (k_cert_fin) instead: "rw" is then r itself and "sums" its two values."""
+    m, l = b.shape
+    dev = b.device
+    S = 0 if P is None else int(P.shape[0])
+    if P is not None:
+        assert P.shape == (S, m, l) and P.is_contiguous() and P.dtype == b.dtype
+    for v in (sample_weight, holdout_weight):
+        assert v is None or (v.dtype == b.dtype and v.shape == (m,) and v.is_contiguous())
+    r = torch.full((m, l), float("nan"), dtype=b.dtype, device=dev) if want_r and sample_weight is not None else None
+    rw = torch.full((m, l), float("nan"), dtype=b.dtype, device=dev)
+    sums = torch.full((3,), float("nan"), dtype=torch.float64, device=dev)
+    ws = _screen_ws(1, 1, dev)
+    check(lib().glx_cert_fin_sw(_dt(b), m, l, None if P is None else P.data_ptr(), S, b.data_ptr(),
+                                None if sample_weight is None else sample_weight.data_ptr(),
+                                None if holdout_weight is None else holdout_weight.data_ptr(),
+                                None if r is None else r.data_ptr(), rw.data_ptr(), sums.data_ptr(), ws.data_ptr(),
+                                ws.numel(), _stream(dev)))
+    return {"r": r, "rw": rw, "sums": sums}
+
+
 def screen_step(row_norms: torch.Tensor, col_norms: torch.Tensor, s: float, rho: float,
                 mu: float) -> Dict[str, torch.Tensor]:
     """The gap-safe test on n rows (glx_screen_step): row i is kept unless
@@ -789,4 +830,27 @@ def group_screen_guard(rec, mu: float, dtype: int, m: int, n: int, l: int, max_r
     out = (ctypes.c_double * 3)()
     check(lib().glx_group_screen_guard(r, float(mu), int(dtype), int(m), int(n), int(l), int(max_run), float(w_min),
                                        float(gcol_max), float(col_sumsq), float(b_norm), out))
+    return float(out[0]), float(out[1]), float(out[2])
+
+
+# ---- sample weights (glx.h "sample weights"; the weighted guards, host only) ----
+def screen_guard_sw(rec, mu: float, dtype: int, m: int, n: int, l: int, col_max: float, col_sumsq: float,
+                    b_norm: float) -> Tuple[float, float, float]:
+    """The rounding guard of the sample-weighted problem (glx_screen_guard_sw, host only): ``rec`` is
+    the weighted certificate's record, the column figures are :func:`col_norms_sw`'s and ``b_norm`` is
+    sqrt(sum w b^2)."""
+    r = (ctypes.c_double * 8)(*[float(v) for v in rec])
+    out = (ctypes.c_double * 3)()
+    check(lib().glx_screen_guard_sw(r, float(mu), int(dtype), int(m), int(n), int(l), float(col_max),
+                                    float(col_sumsq), float(b_norm), out))
+    return float(out[0]), float(out[1]), float(out[2])
+
+
+def group_screen_guard_sw(rec, mu: float, dtype: int, m: int, n: int, l: int, max_run: int, w_min: float,
+                          gcol_max: float, col_sumsq: float, b_norm: float) -> Tuple[float, float, float]:
+    """The grouped guard of the sample-weighted problem (glx_group_screen_guard_sw, host only)."""
+    r = (ctypes.c_double * 8)(*[float(v) for v in rec])
+    out = (ctypes.c_double * 3)()
+    check(lib().glx_group_screen_guard_sw(r, float(mu), int(dtype), int(m), int(n), int(l), int(max_run),
+                                          float(w_min), float(gcol_max), float(col_sumsq), float(b_norm), out))
     return float(out[0]), float(out[1]), float(out[2])

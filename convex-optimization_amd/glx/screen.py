@@ -32,7 +32,8 @@ import torch
 
 from . import _lib
 from ._lib import GlxCertifiedInfo, GlxGroupCertifiedInfo, GlxProblem, check, lib
-from .certificate import _inputs, check_groups, compose, compose_groups, mu_max
+from .certificate import (_inputs, _np_dtype, _rows_of, _sw_device, check_groups, check_sample_weight, compose,
+                          compose_groups, mu_max)
 
 DEFAULT_MAXIT = 100000
 
@@ -84,13 +85,38 @@ def _check_args(A, b, x0, tol, maxit, check_every, groups=None, weights=None):
     return check_groups(groups, weights, sa[1], sb[1])
 
 
+def _check_sample(A, sample_weight, holdout_weight):
+    """The host checks of the two observation-weight vectors (glx.certificate.check_sample_weight),
+    before any device work: ``(sw, hw)`` in A's dtype, None where not given. Hold-out weights without
+    sample weights are held out of the unweighted fit: sw = ones."""
+    m, dt = _rows_of(A), _np_dtype(A)
+    sw = check_sample_weight(sample_weight, m, dt)
+    hw = check_sample_weight(holdout_weight, m, dt, "holdout_weight")
+    if hw is not None and sw is None:
+        sw = np.ones(m, dtype=dt)
+    return sw, hw
+
+
+def _describe(fn, *args) -> str:
+    """The line of one of libglx's host-only ``*_describe`` entries."""
+    buf = ctypes.create_string_buffer(2048)
+    check(fn(*args, buf, len(buf)))
+    return buf.value.decode()
+
+
+def _holdout_info(info: Dict[str, Any], hw) -> None:
+    """holdout_loss = 1/2 sum_j v_j ||(A x - b)_j||^2 / sum_j v_j from the solve's holdout_sum."""
+    if hw is not None:
+        info["holdout_loss"] = 0.5 * info["holdout_sum"] / float(np.sum(hw, dtype=np.float64))
+
+
 class _Prepared:
     """What a sequence of solves on one (A, b) shares: the device copies, the step, the column norms
     and the workspace."""
 
-    def __init__(self, A, b, screen: bool, comm=None, gw=None):
-        from . import kernels
-        from .solver import _lambda_max
+    def __init__(self, A, b, screen: bool, comm=None, gw=None, sw=None, weighted: bool = False):
+        """``sw``: the checked host sample weights (None: the unweighted problem). ``weighted=True``
+        sizes the workspace for weights that arrive later (:meth:`set_weights`, one per fold)."""
         if comm is not None:
             raise ValueError("the certified solve is single-GPU: it takes no communicator")
         _, self.Ad, self.bd = _inputs(None, A, b)
@@ -103,23 +129,39 @@ class _Prepared:
         self.gw = gw   # (group_ptr, weights) on the host, or None: rows
         self.G = 0 if gw is None else int(gw[1].size)
         self.max_run = 0 if gw is None else int(np.diff(gw[0]).max())
+        self.weighted = bool(weighted) or sw is not None
         with torch.cuda.device(self.device):
             nb = ctypes.c_size_t(0)   # (first: it refuses what the solve would, before any launch)
+            suffix = "_sw" if self.weighted else ""
             if gw is None:
-                check(lib().glx_certified_workspace_bytes(self.gdt, self.m, self.n, self.l, int(self.screen),
-                                                          ctypes.byref(nb)))
+                check(getattr(lib(), "glx_certified%s_workspace_bytes" % suffix)(
+                    self.gdt, self.m, self.n, self.l, int(self.screen), ctypes.byref(nb)))
             else:
-                check(lib().glx_group_certified_workspace_bytes(self.gdt, self.m, self.n, self.l, self.G,
-                                                                int(self.screen), ctypes.byref(nb)))
-            self.lam = float(_lambda_max(self.Ad))
+                check(getattr(lib(), "glx_group_certified%s_workspace_bytes" % suffix)(
+                    self.gdt, self.m, self.n, self.l, self.G, int(self.screen), ctypes.byref(nb)))
+            self.set_weights(sw)
+            self.ws = torch.empty(int(nb.value), dtype=torch.uint8, device=self.device)
+
+    def set_weights(self, sw):
+        """The figures that depend on the sample weights (host array of A's dtype, or None): the step
+        1 / lambda_max(A^T W A) and the (weighted) column norms. A, b and the workspace stay."""
+        from . import kernels
+        from .solver import _lambda_max
+        if sw is not None and not self.weighted:
+            raise ValueError("this preparation was sized for the unweighted problem")
+        with torch.cuda.device(self.device):
+            self.sw = _sw_device(sw, self.device)
+            self.lam = float(_lambda_max(self.Ad, sample_weight=self.sw))
             self.t = 1.0 / self.lam
             self.cn = self.cstats = None
             if self.screen:
-                self.cn, st = kernels.col_norms(self.Ad)
+                self.cn, st = (kernels.col_norms(self.Ad) if self.sw is None
+                               else kernels.col_norms_sw(self.Ad, self.sw))
                 self.cstats = (ctypes.c_double * 2)(*st.cpu().tolist())
-            self.ws = torch.empty(int(nb.value), dtype=torch.uint8, device=self.device)
 
-    def solve(self, mu: float, x0, tol: float, maxit: int, check_every: int):
+    def solve(self, mu: float, x0, tol: float, maxit: int, check_every: int, hold=None):
+        """``hold``: hold-out weights (a device tensor of A's dtype, m values) for the final certificate;
+        ``info`` then carries ``holdout_sum`` = sum_j hold_j ||(A x - b)_j||^2."""
         mu = float(mu)
         if not mu >= 0.0:
             raise ValueError("mu must be >= 0")
@@ -129,17 +171,31 @@ class _Prepared:
         p = GlxProblem(dtype=self.gdt, method=0, m=self.m, n=self.n, l=self.l, A=self.Ad.data_ptr(),
                        b=self.bd.data_ptr(), x=xd.data_ptr(), mu0=mu, comm=None)
         rows = torch.full(((self.n + 63) // 64 * 64,), -1, dtype=torch.int32, device=self.device)
+        if hold is not None and self.sw is None:
+            raise ValueError("hold-out weights go with sample weights")
         if self.gw is not None:
-            return self._solve_groups(mu, xd, p, rows, tol, maxit, check_every)
+            return self._solve_groups(mu, xd, p, rows, tol, maxit, check_every, hold)
         info = GlxCertifiedInfo()
+        hs = ctypes.c_double(0.0)
         with torch.cuda.device(self.device):
-            check(lib().glx_certified_solve(ctypes.byref(p), self.t, float(tol), int(maxit), int(self.screen),
-                                            int(check_every), None if self.cn is None else self.cn.data_ptr(),
-                                            self.cstats, rows.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
-                                            ctypes.byref(info),
-                                            ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            cn = None if self.cn is None else self.cn.data_ptr()
+            if self.sw is None:
+                check(lib().glx_certified_solve(ctypes.byref(p), self.t, float(tol), int(maxit), int(self.screen),
+                                                int(check_every), cn, self.cstats, rows.data_ptr(),
+                                                self.ws.data_ptr(), self.ws.numel(), ctypes.byref(info), stream))
+            else:
+                check(lib().glx_certified_solve_sw(ctypes.byref(p), self.sw.data_ptr(),
+                                                   None if hold is None else hold.data_ptr(), self.t, float(tol),
+                                                   int(maxit), int(self.screen), int(check_every), cn, self.cstats,
+                                                   rows.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
+                                                   ctypes.byref(info), ctypes.byref(hs), stream))
         out: Dict[str, Any] = compose(list(info.cert), mu)
-        out["plan"] = _lib.certified_describe(self.gdt, self.m, self.n, self.l, self.screen)
+        out["plan"] = (_lib.certified_describe(self.gdt, self.m, self.n, self.l, self.screen) if self.sw is None
+                       else _describe(lib().glx_certified_sw_describe, self.gdt, self.m, self.n, self.l,
+                                      int(self.screen)))
+        if hold is not None:
+            out["holdout_sum"] = float(hs.value)
         nc = int(info.compactions)
         if int(info.listed) > 0:
             kept_rows = rows[:int(info.listed)].cpu().numpy().astype(np.int64)
@@ -155,19 +211,34 @@ class _Prepared:
                    step_fused=bool(info.fused), screen=self.screen, tol=float(tol), step=self.t, mu=mu)
         return xd, out
 
-    def _solve_groups(self, mu, xd, p, rows, tol, maxit, check_every):
+    def _solve_groups(self, mu, xd, p, rows, tol, maxit, check_every, hold=None):
         ptr, w = self.gw
         ginfo = GlxGroupCertifiedInfo()
+        hs = ctypes.c_double(0.0)
         grps = torch.full((self.G,), -1, dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            check(lib().glx_group_certified_solve(
-                ctypes.byref(p), self.G, ptr.ctypes.data, w.ctypes.data, self.t, float(tol), int(maxit),
-                int(self.screen), int(check_every), None if self.cn is None else self.cn.data_ptr(), self.cstats,
-                rows.data_ptr(), grps.data_ptr(), self.ws.data_ptr(), self.ws.numel(), ctypes.byref(ginfo),
-                ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            cn = None if self.cn is None else self.cn.data_ptr()
+            if self.sw is None:
+                check(lib().glx_group_certified_solve(
+                    ctypes.byref(p), self.G, ptr.ctypes.data, w.ctypes.data, self.t, float(tol), int(maxit),
+                    int(self.screen), int(check_every), cn, self.cstats,
+                    rows.data_ptr(), grps.data_ptr(), self.ws.data_ptr(), self.ws.numel(), ctypes.byref(ginfo),
+                    stream))
+            else:
+                check(lib().glx_group_certified_solve_sw(
+                    ctypes.byref(p), self.G, ptr.ctypes.data, w.ctypes.data, self.sw.data_ptr(),
+                    None if hold is None else hold.data_ptr(), self.t, float(tol), int(maxit), int(self.screen),
+                    int(check_every), cn, self.cstats, rows.data_ptr(), grps.data_ptr(), self.ws.data_ptr(),
+                    self.ws.numel(), ctypes.byref(ginfo), ctypes.byref(hs), stream))
         info = ginfo.base
         out: Dict[str, Any] = compose_groups(list(info.cert), mu)
-        out["plan"] = _lib.group_certified_describe(self.gdt, self.m, self.n, self.l, self.max_run, self.screen)
+        out["plan"] = (_lib.group_certified_describe(self.gdt, self.m, self.n, self.l, self.max_run, self.screen)
+                       if self.sw is None else
+                       _describe(lib().glx_group_certified_sw_describe, self.gdt, self.m, self.n, self.l,
+                                 self.max_run, int(self.screen)))
+        if hold is not None:
+            out["holdout_sum"] = float(hs.value)
         nc = int(info.compactions)
         if int(ginfo.listed_groups) > 0:
             kept_groups = grps[:int(ginfo.listed_groups)].cpu().numpy().astype(np.int64)
@@ -192,7 +263,8 @@ class _Prepared:
 
 
 def solve_certified(A, b, mu, x0=None, tol: float = 1e-6, maxit: int = DEFAULT_MAXIT, screen: bool = True,
-                    check_every: int = 10, comm=None, groups=None, weights=None) -> Tuple[Any, Dict[str, Any]]:
+                    check_every: int = 10, comm=None, groups=None, weights=None, sample_weight=None,
+                    holdout_weight=None) -> Tuple[Any, Dict[str, Any]]:
     """Solve min_x 1/2 ||A x - b||_F^2 + mu sum_i ||x_i||_2 until the duality gap is at most ``tol``
     of the primal objective (or ``maxit`` iterations in total).
 
@@ -211,12 +283,22 @@ def solve_certified(A, b, mu, x0=None, tol: float = 1e-6, maxit: int = DEFAULT_M
     ``mu sum_g w_g ||x_[g]||_F`` over contiguous row ranges (``group_ptr`` array; ``weights`` alone:
     single rows). ``info`` then carries ``nonzero_groups`` in place of ``nonzero_rows``, ``kept`` and
     ``kept_history`` count groups, and ``kept_groups`` (ascending) stands next to ``kept_rows`` (the
-    rows of those groups)."""
+    rows of those groups).
+
+    ``sample_weight`` (None: today's path, bit for bit): m observation weights ``w_j >= 0``, at least one
+    > 0, rounded once to A's dtype: solve ``1/2 sum_j w_j ||(A x - b)_j||^2 + mu Omega(x)`` on the
+    caller's A (no copy, no scaling; a 0/1 vector solves the row-subset problem, integer weights the
+    row-duplicated one). The step is 1 / lambda_max(A^T W A), screening runs on the weighted column
+    norms under the weighted guard, and ``info`` speaks of the weighted problem. ``holdout_weight``
+    (m values >= 0): ``info["holdout_loss"]`` = 1/2 sum_j v_j ||(A x - b)_j||^2 / sum_j v_j of the
+    returned x, from the final certificate's own launch (``holdout_sum`` is the numerator's sum)."""
     gw = _check_args(A, b, x0, tol, maxit, check_every, groups, weights)
+    sw, hw = _check_sample(A, sample_weight, holdout_weight)
     if not float(mu) >= 0.0:
         raise ValueError("mu must be >= 0")
-    prep = _Prepared(A, b, screen, comm, gw)
-    xd, info = prep.solve(mu, x0, tol, maxit, check_every)
+    prep = _Prepared(A, b, screen, comm, gw, sw)
+    xd, info = prep.solve(mu, x0, tol, maxit, check_every, _sw_device(hw, prep.device))
+    _holdout_info(info, hw)
     return prep.result(xd), info
 
 
@@ -225,26 +307,41 @@ def path(A, b, mus: Optional[Sequence[float]] = None, n_mus: int = 10, mu_min_ra
     """Certified solves over a decreasing sequence of mu: ``mus``, or the geometric grid of ``n_mus``
     values from ``glx.mu_max(A, b)`` down to ``mu_min_ratio`` of it (:func:`mu_grid`). Each solve is
     warm-started from the one before; the column norms and lambda_max are computed once. ``kw``:
-    ``tol``, ``maxit``, ``screen``, ``check_every``, ``groups``, ``weights`` of :func:`solve_certified`
-    (with groups the grid starts at the grouped ``mu_max``). Returns the list of
-    ``(mu, x, info)``; at mu = mu_max the entry is x = 0 with gap 0 and no iterations."""
-    unknown = set(kw) - {"tol", "maxit", "screen", "check_every", "comm", "groups", "weights"}
+    ``tol``, ``maxit``, ``screen``, ``check_every``, ``groups``, ``weights``, ``sample_weight``,
+    ``holdout_weight`` of :func:`solve_certified` (with groups or sample weights the grid starts at
+    their ``mu_max``). Returns the list of ``(mu, x, info)``; at mu = mu_max the entry is x = 0 with
+    gap 0 and no iterations."""
+    unknown = set(kw) - {"tol", "maxit", "screen", "check_every", "comm", "groups", "weights", "sample_weight",
+                         "holdout_weight"}
     if unknown:
         raise TypeError("path() got unexpected keyword arguments %s" % sorted(unknown))
     tol, maxit = kw.get("tol", 1e-6), kw.get("maxit", DEFAULT_MAXIT)
     check_every = kw.get("check_every", 10)
     gw = _check_args(A, b, None, tol, maxit, check_every, kw.get("groups"), kw.get("weights"))
+    sw, hw = _check_sample(A, kw.get("sample_weight"), kw.get("holdout_weight"))
     if mus is not None:
         mus = _check_mus(mus)
     else:
         mu_grid(1.0, n_mus, mu_min_ratio)   # the grid's own checks, before any device work
-    prep = _Prepared(A, b, kw.get("screen", True), kw.get("comm"), gw)
+    prep = _Prepared(A, b, kw.get("screen", True), kw.get("comm"), gw, sw)
     if mus is None:
-        top = mu_max(prep.Ad, prep.bd) if gw is None else mu_max(prep.Ad, prep.bd, gw[0], gw[1])
-        mus = mu_grid(top, n_mus, mu_min_ratio)
+        mus = mu_grid(_top(prep, gw, sw), n_mus, mu_min_ratio)
+    return _run_path(prep, mus, tol, maxit, check_every, hw)
+
+
+def _top(prep: "_Prepared", gw, sw) -> float:
+    if sw is not None:
+        return mu_max(prep.Ad, prep.bd, None if gw is None else gw[0], None if gw is None else gw[1], sample_weight=sw)
+    return mu_max(prep.Ad, prep.bd) if gw is None else mu_max(prep.Ad, prep.bd, gw[0], gw[1])
+
+
+def _run_path(prep: "_Prepared", mus, tol, maxit, check_every, hw=None):
+    """The warm-started solves of :func:`path` on a prepared problem (its current weights)."""
+    hold = _sw_device(hw, prep.device)
     out = []
     xd = None
     for mu in mus:
-        xd, info = prep.solve(mu, xd, tol, maxit, check_every)
+        xd, info = prep.solve(mu, xd, tol, maxit, check_every, hold)
+        _holdout_info(info, hw)
         out.append((mu, prep.result(xd.clone()), info))
     return out

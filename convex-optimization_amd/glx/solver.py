@@ -92,7 +92,7 @@ def workspace(problem: GlxProblem, o: GlxOpts, device) -> torch.Tensor:
     return torch.empty(int(nbytes.value), dtype=torch.uint8, device=device)
 
 
-def _lambda_max(A: torch.Tensor, comm=None, max_steps: int = 400) -> float:
+def _lambda_max(A: torch.Tensor, comm=None, max_steps: int = 400, sample_weight=None) -> float:
     """``np.max(LA.eigvals(A.T @ A))`` (gl_SGD_primal.py:35-37, gl_GD_primal.py:43-45) for the
     optional continuous_subgradient_flag, without forming the n x n Gram matrix and without a
     library eigensolver on the device: Lanczos on the operator v -> A^T (A v), whose two products
@@ -102,7 +102,9 @@ def _lambda_max(A: torch.Tensor, comm=None, max_steps: int = 400) -> float:
     largest eigenvalue of the k x k tridiagonal matrix is taken once its Ritz residual
     beta_k |s_k| is below 1e-13 of it (the eigenvalue itself is then accurate to ~1e-16 relative),
     or when the Krylov space is all of R^n (k = n: exact). A fixed start vector (seeded), so the
-    result is the same on every rank and from run to run."""
+    result is the same on every rank and from run to run. ``sample_weight`` (a device tensor of m
+    weights, or None): lambda_max(A^T W A), the intermediate A q times w between the two products
+    (a torch elementwise op, in setup only)."""
     import numpy as np
     from . import kernels
     a = A if A.dtype == torch.float64 else A.to(torch.float64)
@@ -118,6 +120,8 @@ def _lambda_max(A: torch.Tensor, comm=None, max_steps: int = 400) -> float:
     for k in range(min(n, max_steps)):
         Q[k] = q
         r, _ = kernels.residual(a, torch.from_numpy(np.ascontiguousarray(q[:, None])).to(a.device), zero)   # A q
+        if sample_weight is not None:
+            r = r * sample_weight.to(torch.float64)[:, None]                           # W A q
         w_t = kernels.gradient(a, r)                                                   # A^T A q
         if comm is not None:
             comm.allreduce_(w_t)

@@ -817,6 +817,80 @@ int glx_group_expand(const int32_t* kept_dev, const int32_t* kept_count_dev, con
                      int32_t* group_ptr_out, double* weights_out, double* gcn_out, int32_t* map_out,
                      int32_t* count_out, void* stream);
 
+/* ---- sample weights (DESIGN.md "Sample weights and cross-validation"; additive entries, the ABI
+ * version stays 2) ----
+ * Observation weights:  P_w(x) = 1/2 sum_j w_j ||(A x - b)_j||^2 + mu Omega(x),  w_j >= 0, one per row
+ * j of A; Omega is the row penalty or the grouped, weighted one. Everything above carries over with
+ * A~ = W^(1/2) A and b~ = W^(1/2) b in place of A and b, and neither is ever formed: A is not copied
+ * and not written. The residual finalize between the two dense passes keeps the unweighted
+ * r = A x - b, hands w r to the A^T pass and reduces sum w r^2 and sum w r b (k_cert_fin_w); the
+ * column norms are sqrt(sum_j w_j A_ji^2) (k_col_norms_w). A 0/1 vector solves the row-subset
+ * problem (a cross-validation fold), integer weights the row-duplicated one.
+ *   sample_w  (device, m values of A's dtype, 16-byte aligned; may be NULL): the weights, finite and
+ *             >= 0 with one > 0: the CALLER's check (glx/certificate.py check_sample_weight makes it
+ *             on the host before anything is uploaded). NULL runs the sibling entry, call for call.
+ *   holdout_w (the same kind of vector; may be NULL; only with sample_w): *holdout_sum receives
+ *             sum_j holdout_w_j ||(A x - b)_j||^2 from the finalize's own launch (0 without it).
+ * The certificate's out[0], out[1] are sum w r^2 and sum w r b; every other value and the host's
+ * arithmetic are as documented for the sibling. The certified solve's final certificate of the full
+ * problem is the one that takes holdout_w, so a fold's validation loss costs no pass over A.
+ * col_norms_dev / col_stats of the solves are glx_col_norms_sw's. Each entry validates before any
+ * launch (GLX_E_INVALID): its sibling's checks, the alignment of the two vectors, holdout_w without
+ * sample_w. Workspaces: the sibling's layout with the new pieces behind it. */
+int glx_certificate_sw_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes);
+int glx_certificate_sw_describe(int dtype, int64_t m, int64_t n, int64_t l, int fused, char* out, size_t cap);
+int glx_certificate_sw(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                       double mu, int fused, const void* sample_w, const void* holdout_w, void* G_out,
+                       double* rownorm_out, double out[8], double* holdout_sum, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int glx_group_certificate_sw_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, size_t* bytes);
+int glx_group_certificate_sw_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, char* out,
+                                      size_t cap);
+int glx_group_certificate_sw(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X,
+                             const void* b, double mu, int64_t G, const int32_t* group_ptr, const double* weights,
+                             const void* sample_w, const void* holdout_w, void* G_out, double* groupnorm_out,
+                             double out[8], double* holdout_sum, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int glx_certified_sw_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int screen, size_t* bytes);
+int glx_certified_sw_describe(int dtype, int64_t m, int64_t n, int64_t l, int screen, char* out, size_t cap);
+int glx_certified_solve_sw(const glx_problem* prob, const void* sample_w, const void* holdout_w, double t,
+                           double tol, int64_t maxit, int screen, int check_every, const double* col_norms_dev,
+                           const double* col_stats, int32_t* kept_rows_dev, void* workspace,
+                           size_t workspace_bytes, glx_certified_info* info, double* holdout_sum, void* stream);
+int glx_group_certified_sw_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, int screen,
+                                           size_t* bytes);
+int glx_group_certified_sw_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, int screen,
+                                    char* out, size_t cap);
+int glx_group_certified_solve_sw(const glx_problem* prob, int64_t G, const int32_t* group_ptr,
+                                 const double* weights, const void* sample_w, const void* holdout_w, double t,
+                                 double tol, int64_t maxit, int screen, int check_every,
+                                 const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev,
+                                 int32_t* kept_groups_dev, void* workspace, size_t workspace_bytes,
+                                 glx_group_certified_info* info, double* holdout_sum, void* stream);
+/* The weighted rounding guards (host only, need no device): glx_screen_guard / glx_group_screen_guard
+ * with the weighted problem's record, column figures (glx_col_norms_sw) and b_norm = ||b~|| =
+ * sqrt(sum w b^2), and one more rounding counted where w r, (w r) r, (w r) b and (w a) a are formed.
+ * The unweighted guards are unchanged. */
+int glx_screen_guard_sw(const double rec[8], double mu, int dtype, int64_t m, int64_t n, int64_t l,
+                        double col_max, double col_sumsq, double b_norm, double out[3]);
+int glx_group_screen_guard_sw(const double rec[8], double mu, int dtype, int64_t m, int64_t n, int64_t l,
+                              int64_t max_run, double w_min, double gcol_max, double col_sumsq, double b_norm,
+                              double out[3]);
+/* The two kernels one launch at a time (test surface). Workspace: glx_screen_workspace_bytes(m, n)
+ * for the column norms, (1, 1) for the finalize.
+ * glx_col_norms_sw: glx_col_norms with norms_dev[i] = sqrt(sum_j sample_w_j A_ji^2); a column whose
+ *   rows all weigh 0 gives exactly 0, all-ones weights give glx_col_norms' bits.
+ * glx_cert_fin_sw: P = S slabs of m * l values (S = 0, P = NULL: the null product), b (m x l);
+ *   r_out (may be NULL) = fl(sum of the slabs in slab order) - b, rw_out = fl(sample_w_j r),
+ *   sums_dev = [sum w r^2, sum w r b, sum holdout_w r^2 (written only with holdout_w)], device
+ *   doubles, each product formed as ((double) w r) r. sample_w = NULL runs the unweighted finalize
+ *   instead (rw_out = r, two sums), for bit comparisons. */
+int glx_col_norms_sw(int dtype, int64_t m, int64_t n, const void* A, const void* sample_w, double* norms_dev,
+                     double* stats_dev, void* workspace, size_t workspace_bytes, void* stream);
+int glx_cert_fin_sw(int dtype, int64_t m, int64_t l, const void* P, int S, const void* b, const void* sample_w,
+                    const void* holdout_w, void* r_out, void* rw_out, double* sums_dev, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* ---- multi-GPU (row-sharded A; A^T r all-reduced, or reduce-scattered with the row-sharded step) ---- */
 #define GLX_COMM_ID_BYTES 128
 int  glx_comm_unique_id(uint8_t id[GLX_COMM_ID_BYTES]);
