@@ -358,10 +358,19 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
   int64_t listed = -1;   // >= 0: entries of w.list from the last screen, valid for the current problem
   double rec[8];
 
-  // x (reduced) -> X (n x l); then the certificate of the full problem on the caller's A
+  // x (reduced) -> X (n x l); then the certificate of the full problem on the caller's A. Where the
+  // last check screened without compacting, only the rows it listed travel: a row proven zero is
+  // returned as +0 whether a compaction dropped it or not (xc and the idle map are free here)
   auto full_certificate = [&]() {
     if (all_zero) {
       GLX_HIP(hipMemsetAsync(X, 0, es * n * l, st));
+    } else if (listed >= 0) {   // (<= pad64(wc) entries, -1 behind the kept rows; none: X = 0)
+      int* rows = w.map[mapi ^ 1];
+      GLX_HIP(hipMemsetAsync(X, 0, es * n * l, st));
+      launch_gather_rows<T>(x, w.list, listed, l, xc, st);
+      launch_compose_list(map, w.list, listed, rows, st);
+      launch_scatter_rows<T>(xc, rows, listed, l, X, st);
+      check_launch();
     } else if (map == nullptr) {
       GLX_HIP(hipMemcpyAsync(X, x, es * n * l, hipMemcpyDeviceToDevice, st));
     } else {

@@ -274,7 +274,8 @@ def solve_certified(A, b, mu, x0=None, tol: float = 1e-6, maxit: int = DEFAULT_M
     problem (``primal``, ``dual``, ``gap``, ``rel_gap``, ``scale``, ``gmax``, ``kkt_max``, ``kkt_fro``,
     ``nonzero_rows``, ``fused``, ``plan``) plus ``converged`` (rel_gap <= tol), ``iterations``,
     ``checks``, ``compactions``, ``kept_history`` (rows kept after each compaction), ``kept`` (rows the last screening test did not
-    prove zero), ``kept_rows`` (their indices, ascending: every other row is zero at the optimum),
+    prove zero), ``kept_rows`` (their indices, ascending: every other row is zero at the optimum, and +0
+    in the returned x),
     ``width`` (columns of the last reduced problem), ``rounds``, ``passes`` (passes over A, each
     weighted by its width / n), ``tt`` (seconds inside the native call) and ``step``. Single GPU: a
     communicator is refused.

@@ -104,7 +104,14 @@ def _lambda_max(A: torch.Tensor, comm=None, max_steps: int = 400, sample_weight=
     or when the Krylov space is all of R^n (k = n: exact). A fixed start vector (seeded), so the
     result is the same on every rank and from run to run. ``sample_weight`` (a device tensor of m
     weights, or None): lambda_max(A^T W A), the intermediate A q times w between the two products
-    (a torch elementwise op, in setup only)."""
+    (a torch elementwise op, in setup only).
+
+    Leaving the loop because ``max_steps`` < n ran out is not silent: the Ritz value is then a lower
+    bound of lambda_max that has not met the test above (a flat top of the spectrum does this), its
+    reciprocal a step above 1 / L, and a ``RuntimeWarning`` names the steps taken and the Ritz
+    residual beta_k |s_k| / theta (some eigenvalue lies within that of the returned value, relatively)."""
+    import warnings
+
     import numpy as np
     from . import kernels
     a = A if A.dtype == torch.float64 else A.to(torch.float64)
@@ -117,7 +124,8 @@ def _lambda_max(A: torch.Tensor, comm=None, max_steps: int = 400, sample_weight=
     alphas, betas = [], []
     q_prev, beta = np.zeros(n), 0.0
     theta = 0.0
-    for k in range(min(n, max_steps)):
+    steps, resid, settled = min(n, max_steps), 0.0, False
+    for k in range(steps):
         Q[k] = q
         r, _ = kernels.residual(a, torch.from_numpy(np.ascontiguousarray(q[:, None])).to(a.device), zero)   # A q
         if sample_weight is not None:
@@ -136,10 +144,18 @@ def _lambda_max(A: torch.Tensor, comm=None, max_steps: int = 400, sample_weight=
         ev, evec = np.linalg.eigh(T)
         theta = float(ev[-1])
         # an invariant subspace (beta ~ 0), or the Ritz pair of theta converged
-        if beta <= 1e-14 * abs(theta) or (k >= 4 and abs(beta * evec[-1, -1]) <= 1e-13 * abs(theta)):
+        resid = abs(beta * evec[-1, -1])
+        if beta <= 1e-14 * abs(theta) or (k >= 4 and resid <= 1e-13 * abs(theta)):
+            settled = True
             break
         betas.append(beta)
         q_prev, q = q, w / beta
+    if not settled and steps < n:   # (steps = n: the Krylov space is all of R^n)
+        warnings.warn("lambda_max: the Lanczos recurrence took all %d steps (n = %d) without settling; the Ritz "
+                      "value %.17g has the relative residual beta |s_k| / theta = %.3e and may lie below "
+                      "lambda_max, so a step 1 / lambda_max taken from it may exceed 1 / L"
+                      % (steps, n, theta, resid / max(abs(theta), np.finfo(np.float64).tiny)), RuntimeWarning,
+                      stacklevel=2)
     return theta
 
 
