@@ -429,8 +429,8 @@ def prox(W: torch.Tensor, t: float, mu: float, thres: float = 1e-3
     """Group prox with the reference's denominator quirk; returns (X, [sum ||x_i||, max|x|])."""
     n, l = W.shape
     dt = _dt(W)
-    X = torch.empty_like(W)
-    sums = torch.empty(2, dtype=torch.float64, device=W.device)
+    X = torch.full_like(W, float("nan"))
+    sums = _nan_sums(2, W.device)
     ws = _ws(dt, 1, n, l, W.device)
     check(lib().glx_prox(dt, n, l, W.data_ptr(), float(t), float(mu), float(thres), X.data_ptr(),
                          sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream(W.device)))

@@ -24,13 +24,21 @@ roundoff); per row, a_j = |x_j| / rho + |g_j| and N = ||a||_2 >= ||w||. Term by 
          dx_j <= tr dr_j + eps / 2 (tr |r_j| + |x+_j|).
   sum_i ||x+_i||  per row ||dx_i||_2 + (l / 2 + 2) eps ||x+_i|| (as nrm), + CSUM eps64 sum |term|
        for the fp64 accumulation (CSUM = 32 additions deep: a few per thread, 8 levels in the
-       workgroup, 12 over the workgroup partials).
+       workgroup, 12 over the workgroup partials). A thread adds one more row norm in every further
+       trip of its workgroup: the several-trip cases take CSUM + trips - 1 (33 at their two trips).
   max |x+|        max_j dx_j (max is 1-Lipschitz in every element).
 Each bar is doubled (C = 2) for the second-order terms dropped above. The inputs hold, where n
 allows, rows outside the ball, rows strictly inside it (u+ = w up to rounding), an all-zero row, a
 row with ||w|| within a few ulp of mu and one NaN row. The NaN turns both sums into NaN, so each
 case runs twice: without the NaN row (all the bars above) and with it (every other row
 bit-identical to the first run, the row itself NaN, both sums NaN).
+A row of l values is held by LPR lanes with EPL values each; the l of test 1 select (LPR, EPL) =
+1 (1, 1), 2 (2, 1), 3 (4, 1), 5 and 8 (8, 1), 16 (16, 1), 17 and 32 (16, 2): every instantiation of
+k_admm_dual, with a ragged row at LPR 4, LPR 8 and EPL 2, each in one trip of at most 17 workgroups.
+test_row_kernel_several_trips runs (l, n) = (1, 131077), (2, 65541), (3, 32771), (8, 16389),
+(16, 8200), (17, 8200), (32, 8200): each 5 to 8 rows past the 512 * 256 / LPR rows the capped grid of
+512 workgroups takes in one trip, so two trips, the second ragged; u+, x+ and r of the rows on both
+sides of the boundary are bit-identical to those of a launch of their own.
 
 2. The fused form (form 1, k_atr_admm) against form 0 on the G it wrote: every bit of u+, x+, r
 and of both sums, at the shapes whose plan fuses (asserted from glx_admm_describe). Form 0 is
@@ -45,14 +53,16 @@ takes splits; the tile and S are asserted from the describe string) at (64, 64, 
 3. k_gram against float64 NumPy: the inputs are rounded to T first, the products of doubles are
 rounded once each and every entry is a sum of `rows` terms, so
   |gram - ref|_ij <= rows eps64 sum_k |a_ki| |a_kj|   (the bar the issue sets).
+rows = 70000 (l = 3 and 32) is past the 65536 rows at which the grid stops growing: 256 workgroups
+of 273 or 274 rows each.
 
 4.-6. Whole solves: see each test.
 
 Measured on an MI355X, worst error / bound over all cases (f64, f32); the module prints this table
 when its tests are over (pytest -s):
-  test 1   u+ 0.114 0.135   r 0.124 0.177   x+ 0.185 0.180   sum ||x+_i|| 0.0067 0.029
+  test 1   u+ 0.255 0.256   r 0.277 0.255   x+ 0.198 0.252   sum ||x+_i|| 0.011 0.029
            max |x+| 0.099 0.080   rows at the switch: 1 per case with n > 3 (the constructed one)
-  test 2   (panel layout) u+ 0.016 0.011   r 0.138 0.137   x+ 0.201 0.205
+  test 2   (panel layout) u+ 0.016 0.019   r 0.141 0.137   x+ 0.218 0.211
   test 3   gram 0.021 0.030
   test 4   fp64: k identical in all six cases, f_hist within 3.2e-12 relative (the m > n case; the
            others <= 1.1e-13), x within 4.4e-13 of max |x|; fp32: k identical, fval within 2.6e-7.
@@ -121,8 +131,28 @@ def _row_inputs(n, l, dt, seed):
     return x, g
 
 
-def _row_reference(x, g, dt):
-    """The row step in the wider type from the T inputs and T-rounded scalars, and the bars."""
+def _row_inputs_large(n, l, dt, seed):
+    """_row_inputs for the several-trip cases, drawn in whole arrays (the same row kinds)."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((n, l)).astype(dt)
+    g = (rng.standard_normal((n, l)) * 0.05).astype(dt)
+    inside = rng.random(n) < 0.4
+    inside[:4] = [False, True, False, False]
+    w = rng.standard_normal((n, l))
+    w *= 0.3 * MU / np.linalg.norm(w, axis=1, keepdims=True)
+    x = np.where(inside[:, None], ((g.astype(np.float64) + w) * RHO).astype(dt), x)
+    x[2] = 0
+    g[2] = 0
+    w3 = rng.standard_normal(l)
+    w3 *= MU * (1 + 2 * np.finfo(dt).eps) / np.linalg.norm(w3)
+    g[3] = 0
+    x[3] = (w3 * RHO).astype(dt)
+    return x, g
+
+
+def _row_reference(x, g, dt, csum=CSUM):
+    """The row step in the wider type from the T inputs and T-rounded scalars, and the bars. csum:
+    the depth of the fp64 accumulation (CSUM at one trip)."""
     W = _wide(dt)
     eps = float(np.finfo(dt).eps)
     rho, mu, tr = W(dt(RHO)), W(dt(MU)), W(dt(TAU * RHO))
@@ -142,21 +172,20 @@ def _row_reference(x, g, dt):
     dx = tr * dr + eps / 2 * (tr * np.abs(r) + np.abs(xn))
     xnorm = np.sqrt(np.sum(xn * xn, axis=1))
     dsum = np.sum(np.sqrt(np.sum(dx * dx, axis=1)) + (l / 2 + 2) * eps * xnorm) \
-        + CSUM * np.finfo(np.float64).eps * np.sum(xnorm)
+        + csum * np.finfo(np.float64).eps * np.sum(xnorm)
     amb = int(np.sum(np.abs(nrm - mu) <= dn))
     return {"u": u, "r": r, "x": xn, "sum": np.sum(xnorm), "max": np.max(np.abs(xn)),
             "bu": C * du, "br": C * dr, "bx": C * dx, "bsum": C * dsum, "bmax": C * np.max(dx),
             "amb": amb}
 
 
-@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
-@pytest.mark.parametrize("l", [1, 2, 3, 16, 32])
-@pytest.mark.parametrize("n", [1, 15, 64, 130, 257])
-def test_row_kernel_against_wider_type(n, l, dt):
+def _row_kernel_case(x, g, dt, csum=CSUM):
+    """One launch of the row kernel on (x, g) against the wider type, then the same inputs with a
+    NaN in the last row; returns the first run's u+, x+, r."""
     torch = _torch()
     from glx import kernels
-    x, g = _row_inputs(n, l, dt, seed=1000 * n + l)
-    ref = _row_reference(x, g, dt)
+    n, l = x.shape
+    ref = _row_reference(x, g, dt, csum=csum)
     assert ref["amb"] <= 4
     _note("rows at the switch", ref["amb"])
     tag = "f64" if dt == np.float64 else "f32"
@@ -185,6 +214,50 @@ def test_row_kernel_against_wider_type(n, l, dt):
         assert np.isnan(v[n - 1]).all()
         assert np.array_equal(v[:n - 1], got[key][:n - 1])
     assert np.isnan(out2["sums"].cpu().numpy()).all()
+    return got
+
+
+# l -> (LPR, EPL) of launch_admm_dual: 1 (1, 1), 2 (2, 1), 3 (4, 1), 5 and 8 (8, 1), 16 (16, 1),
+# 17 and 32 (16, 2); 3, 5 and 17 leave lanes or a row's tail elements without a value
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("l", [1, 2, 3, 5, 8, 16, 17, 32])
+@pytest.mark.parametrize("n", [1, 15, 64, 130, 257])
+def test_row_kernel_against_wider_type(n, l, dt):
+    x, g = _row_inputs(n, l, dt, seed=1000 * n + l)
+    _row_kernel_case(x, g, dt)
+
+
+# one n past a single trip of the 512-workgroup grid (512 * 256 / LPR rows) per layout: LPR 1, 2, 4,
+# 8, then LPR 16 with EPL 1, a ragged EPL 2 and a full EPL 2; two trips each, the second of 5 to 8 rows
+SEVERAL_TRIPS = [(1, 131077), (2, 65541), (3, 32771), (8, 16389), (16, 8200), (17, 8200), (32, 8200)]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == np.float64 else np.uint32)
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("l,n", SEVERAL_TRIPS)
+def test_row_kernel_several_trips(l, n, dt):
+    """Test 1 past one trip (generic layout, m = 1). The sum's bar is test 1's with CSUM + 1 per
+    further trip: a thread adds one more row norm to its partial in each. Then the rows on both sides
+    of the trip boundary run again as an input of their own, in one trip: u+, x+ and r of a row depend
+    on neither n nor the trip, so they come back bit for bit (the wrapper pre-fills them with NaN)."""
+    torch = _torch()
+    from glx import kernels
+    lpr = 1
+    while lpr < min(l, 16):
+        lpr *= 2
+    per_trip = 512 * 256 // lpr
+    trips = -(-n // per_trip)
+    assert trips == 2 and 0 < n - per_trip < 256 // lpr
+    x, g = _row_inputs_large(n, l, dt, seed=1000 * n + l)
+    got = _row_kernel_case(x, g, dt, csum=CSUM + trips - 1)
+    rows = slice(per_trip - 251, n)
+    part = kernels.admm_dual_step(torch.from_numpy(x[rows].copy()).cuda(), RHO, TAU, MU,
+                                  G=torch.from_numpy(g[rows].copy()).cuda(), form=0)
+    for key in ("u", "x", "r"):
+        assert np.array_equal(_bits(part[key].cpu().numpy()), _bits(got[key][rows])), key
 
 
 FUSED_CASES = [(64, 64, 16, np.float64, None, None), (128, 128, 32, np.float64, None, None),
@@ -259,8 +332,9 @@ def test_fused_form_refuses_small_l():
 
 
 @pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
-@pytest.mark.parametrize("l", [1, 2, 3, 16, 32])
-@pytest.mark.parametrize("rows", [1, 63, 1000, 4097])
+# (70000 rows: past 65536 the grid stays at 256 workgroups, which own 273 or 274 rows each)
+@pytest.mark.parametrize("rows,l", [(r, l) for r in (1, 63, 1000, 4097) for l in (1, 2, 3, 16, 32)]
+                         + [(70000, 3), (70000, 32)])
 def test_gram(rows, l, dt):
     torch = _torch()
     from glx import kernels

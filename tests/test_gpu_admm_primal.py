@@ -34,7 +34,8 @@ thres. eps = T's machine epsilon, u = eps / 2 the unit roundoff. Term by term, f
   w+   a1 = ATb - z+, a2 = rho x+, a1 + a2: dw_j <= dz_j + rho dx_j + u (|a1| + |a2| + |w+_j|).
   sum_i ||x+_i||  per row ||dx_i||_2 + (l / 2 + 2) eps ||x+_i|| (as nr), + CSUM eps64 sum |term|
        for the fp64 accumulation (CSUM = 32 additions deep: a few per thread, 8 levels in the
-       workgroup, 12 over the workgroup partials).
+       workgroup, 12 over the workgroup partials). A thread adds one more row norm in every further
+       trip of its workgroup: the several-trip cases take CSUM + trips - 1 (33 at their two trips).
   max |x+|        max_j dx_j (max is 1-Lipschitz in every element).
 Each bar is doubled (C = 2) for the second-order terms dropped above. Two parameter sets: the
 defaults (eta = 100: er = 1, em = 1) and eta = 1e-2 (em = 1e-4 < thres): only the second lets a row
@@ -42,6 +43,14 @@ with 1e-4 < ||p|| < 1e-3 come out non-zero through the 1 + nr denominator. The i
 allows, rows above the threshold em, rows below it (exact zeros), an all-zero row, a row with ||p||
 within a few ulp of em, one row in the nr < thres regime and, in a second run, one NaN row: that
 row comes out NaN, every other row bit-identical to the first run, both sums NaN.
+A row of l values is held by LPR lanes with EPL values each; the l of test 1 select (LPR, EPL) =
+1 (1, 1), 2 (2, 1), 3 (4, 1), 5 and 8 (8, 1), 16 (16, 1), 17 and 32 (16, 2): every instantiation of
+k_admm_primal, with a ragged row at LPR 4, LPR 8 and EPL 2, each in one trip of at most 17
+workgroups. test_row_kernel_several_trips runs (l, n) = (1, 131077), (2, 65541), (3, 32771),
+(8, 16389), (16, 8200), (17, 8200), (32, 8200), the direct form on one slab with the defaults and the
+Woodbury form on three slabs with eta = 1e-2: each 5 to 8 rows past the 512 * 256 / LPR rows the
+capped grid of 512 workgroups takes in one trip, so two trips, the second ragged; the six outputs of
+the rows on both sides of the boundary are bit-identical to those of a launch of their own.
 
 2. Slab order: S = 3 slabs give the bits of the same product summed in slab order beforehand.
 
@@ -49,9 +58,10 @@ row comes out NaN, every other row bit-identical to the first run, both sums NaN
 
 Measured on an MI355X, worst error / bound over all cases (f64, f32); the module prints this table
 when its tests are over (pytest -s):
-  test 1   x+ 0.255 0.236   y+ 0.395 0.388   z+ 0.444 0.462   r 0.467 0.484   s 0.500 0.500
-           w+ 0.447 0.437   sum ||x+_i|| 0.012 0.033   max |x+| 0.055 0.051
-           rows at the switch: 1 per case with n > 3 (the constructed one); rows at thres: 0
+  test 1   x+ 0.288 0.301   y+ 0.395 0.388   z+ 0.444 0.462   r 0.469 0.484   s 0.500 0.500
+           w+ 0.462 0.463   sum ||x+_i|| 0.013 0.033   max |x+| 0.055 0.051
+           rows at the switch: the constructed one per case with n > 3, and one more in two of the
+           several-trip cases in f32; rows at thres: 0
            (s is one rounding of an exact difference where S = 1, bar 2 u |s|: 0.5 is its ceiling)
   test 3   k identical in all 22 solves; f_hist within 1.5e-9 relative (direct) and 1.9e-9
            (Woodbury), both at (96, 192, 1); x within 8.6e-11 / 1.7e-10 of max |x|
@@ -150,8 +160,9 @@ def _row_inputs(n, l, dt, form, S, eta, seed):
     return tuple(np.ascontiguousarray(a.astype(dt)) for a in (slabs, x, y, z, w, atb))
 
 
-def _row_reference(slabs, x, y, z, w, atb, dt, form, eta):
-    """The row step in the wider type from the T inputs and T-rounded scalars, and the bars."""
+def _row_reference(slabs, x, y, z, w, atb, dt, form, eta, csum=CSUM):
+    """The row step in the wider type from the T inputs and T-rounded scalars, and the bars. csum:
+    the depth of the fp64 accumulation (CSUM at one trip)."""
     W = _wide(dt)
     eps = float(np.finfo(dt).eps)
     u = eps / 2
@@ -190,7 +201,7 @@ def _row_reference(slabs, x, y, z, w, atb, dt, form, eta):
     dw = dz + rho * dx + u * (np.abs(a1) + np.abs(a2) + np.abs(wn))
     xnorm = np.sqrt(np.sum(xn * xn, axis=1))
     dsum = np.sum(np.sqrt(np.sum(dx * dx, axis=1)) + (l / 2 + 2) * eps * xnorm) \
-        + CSUM * np.finfo(np.float64).eps * np.sum(xnorm)
+        + csum * np.finfo(np.float64).eps * np.sum(xnorm)
     return {"x": xn, "y": yn, "z": zn, "r": r, "s": s, "w": wn, "sum": np.sum(xnorm), "max": np.max(np.abs(xn)),
             "bx": C * dx, "by": C * dy, "bz": C * dz, "br": C * dr, "bs": C * ds, "bw": C * dw,
             "bsum": C * dsum, "bmax": C * np.max(dx),
@@ -204,56 +215,143 @@ def _step(torch, kernels, inp, form, eta):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
-@pytest.mark.parametrize("l", [1, 2, 3, 16, 32])
-@pytest.mark.parametrize("n", [1, 15, 64, 130, 257])
-def test_row_kernel_against_wider_type(n, l, dt):
+def _row_case(inp, dt, form, eta, pname, csum=CSUM):
+    """One launch of the row kernel on ``inp`` against the wider type, then the same inputs with a
+    NaN in the last row; returns the first run's outputs and the reference."""
     torch = _torch()
     from glx import kernels
     tag = "f64" if dt == np.float64 else "f32"
+    S, n, l = inp[0].shape
+    ref = _row_reference(*inp, dt, form, eta, csum=csum)
+    where = (form, S, pname)
+    assert ref["at_thres"] == 0, where      # no row at the reference's own jump
+    assert ref["amb"] <= 4, where
+    _note("rows at the switch", ref["amb"])
+    got = _step(torch, kernels, inp, form, eta)
+    for key in OUTS:
+        err = np.abs(got[key].astype(_wide(dt)) - ref[key])
+        bar = ref["b" + key]
+        ratio = np.max(err / np.maximum(bar, np.finfo(np.float64).tiny))
+        _note("%s %s" % (key, tag), ratio)
+        assert np.all(err <= bar), (where, key, float(ratio))
+    assert not got["x"][ref["zero_rows"]].any(), where    # rows below em: exact zeros
+    if n > 1:
+        assert ref["zero_rows"][1], where
+    if n > 2:   # the all-zero row stays zero
+        assert not any(got[key][2].any() for key in OUTS), where
+    if n > 4:
+        if pname == "small_eta":   # em < ||p|| < thres: non-zero through 1 + nr
+            assert ref["small_rows"][4] and got["x"][4].all(), where
+        else:
+            assert ref["zero_rows"][4], where
+    rs = abs(float(got["sums"][0]) - float(ref["sum"])) / max(float(ref["bsum"]), np.finfo(np.float64).tiny)
+    rm = abs(float(got["sums"][1]) - float(ref["max"])) / max(float(ref["bmax"]), np.finfo(np.float64).tiny)
+    _note("sum " + tag, rs)
+    _note("max " + tag, rm)
+    assert rs <= 1 and rm <= 1, (where, rs, rm)
+    # the same inputs with a NaN in the last row: that row NaN, the others untouched, sums NaN
+    x2 = inp[1].copy()
+    x2[n - 1, l // 2] = np.nan
+    got2 = _step(torch, kernels, (inp[0], x2) + inp[2:], form, eta)
+    for key in ("x", "z", "r", "w"):
+        assert np.isnan(got2[key][n - 1]).all(), (where, key)
+    for key in OUTS:
+        assert np.array_equal(got2[key][:n - 1], got[key][:n - 1]), (where, key)
+    assert np.isnan(got2["sums"]).all(), where
+    return got, ref
+
+
+# l -> (LPR, EPL) of launch_admm_primal: 1 (1, 1), 2 (2, 1), 3 (4, 1), 5 and 8 (8, 1), 16 (16, 1),
+# 17 and 32 (16, 2); 3, 5 and 17 leave lanes or a row's tail elements without a value
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("l", [1, 2, 3, 5, 8, 16, 17, 32])
+@pytest.mark.parametrize("n", [1, 15, 64, 130, 257])
+def test_row_kernel_against_wider_type(n, l, dt):
     small_seen = 0
     for form in (1, 2):
         for S in (1, 3):
             for pname, eta in ETAS.items():
                 inp = _row_inputs(n, l, dt, form, S, eta, seed=1000 * n + 10 * l + form + S)
-                ref = _row_reference(*inp, dt, form, eta)
-                where = (form, S, pname)
-                assert ref["at_thres"] == 0, where      # no row at the reference's own jump
-                assert ref["amb"] <= 4, where
-                _note("rows at the switch", ref["amb"])
-                got = _step(torch, kernels, inp, form, eta)
-                for key in OUTS:
-                    err = np.abs(got[key].astype(_wide(dt)) - ref[key])
-                    bar = ref["b" + key]
-                    ratio = np.max(err / np.maximum(bar, np.finfo(np.float64).tiny))
-                    _note("%s %s" % (key, tag), ratio)
-                    assert np.all(err <= bar), (where, key, float(ratio))
-                assert not got["x"][ref["zero_rows"]].any(), where    # rows below em: exact zeros
-                if n > 1:
-                    assert ref["zero_rows"][1], where
-                if n > 2:   # the all-zero row stays zero
-                    assert not any(got[key][2].any() for key in OUTS), where
-                if n > 4:
-                    if pname == "small_eta":   # em < ||p|| < thres: non-zero through 1 + nr
-                        assert ref["small_rows"][4] and got["x"][4].all(), where
-                        small_seen += 1
-                    else:
-                        assert ref["zero_rows"][4], where
-                rs = abs(float(got["sums"][0]) - float(ref["sum"])) / max(float(ref["bsum"]), np.finfo(np.float64).tiny)
-                rm = abs(float(got["sums"][1]) - float(ref["max"])) / max(float(ref["bmax"]), np.finfo(np.float64).tiny)
-                _note("sum " + tag, rs)
-                _note("max " + tag, rm)
-                assert rs <= 1 and rm <= 1, (where, rs, rm)
-                # the same inputs with a NaN in the last row: that row NaN, the others untouched, sums NaN
-                x2 = inp[1].copy()
-                x2[n - 1, l // 2] = np.nan
-                got2 = _step(torch, kernels, (inp[0], x2) + inp[2:], form, eta)
-                for key in ("x", "z", "r", "w"):
-                    assert np.isnan(got2[key][n - 1]).all(), (where, key)
-                for key in OUTS:
-                    assert np.array_equal(got2[key][:n - 1], got[key][:n - 1]), (where, key)
-                assert np.isnan(got2["sums"]).all(), where
+                _row_case(inp, dt, form, eta, pname)
+                small_seen += n > 4 and pname == "small_eta"
     assert small_seen == (4 if n > 4 else 0)
+
+
+def _row_inputs_large(n, l, dt, form, S, eta, seed):
+    """_row_inputs for the several-trip cases, drawn in whole arrays (the same row kinds; n > 4)."""
+    rng = np.random.default_rng(seed)
+    er, em = eta * RHO, eta * MU
+    x = rng.standard_normal((n, l))
+    y = rng.standard_normal((n, l))
+    z = rng.standard_normal((n, l)) * 1e-2
+    w = rng.standard_normal((n, l))
+    atb = rng.standard_normal((n, l))
+    yn = rng.standard_normal((n, l))
+    below = rng.random(n) < 0.3
+    below[:5] = [False, True, False, False, False]
+    below = below[:, None]
+    zb = rng.standard_normal((n, l)) * 1e-4
+    pt = rng.standard_normal((n, l))
+    pt *= em * rng.uniform(0.15, 0.45, (n, 1)) / np.linalg.norm(pt, axis=1, keepdims=True)
+    z = np.where(below, zb, z)
+    if er == 1.0:
+        yn = np.where(below, pt - zb / RHO, yn)
+    else:
+        yb = rng.standard_normal((n, l)) * 1e-2
+        yn = np.where(below, yb, yn)
+        x = np.where(below, (pt - er * (yb + zb / RHO)) / (1 - er), x)
+    special = {2: np.zeros(l), 3: _unit(rng, l) * em * (1 + 2 * np.finfo(dt).eps), 4: _unit(rng, l) * 0.5 * THRES}
+    for i, p in special.items():
+        x[i] = yn[i] = p
+        z[i] = 0
+        w[i] = 0
+    y[2] = atb[2] = 0
+    prod = (w - RHO * yn) if form == 2 else yn
+    shares = np.array([1.0])[:, None, None] if S == 1 else np.array([0.5, 0.25, 0.25])[:, None, None]
+    slabs = shares * prod[None]
+    if S > 1:
+        noise = rng.standard_normal((n, l))
+        noise[2:5] = 0
+        slabs[0] += noise
+        slabs[1] -= noise
+    return tuple(np.ascontiguousarray(a.astype(dt)) for a in (slabs, x, y, z, w, atb))
+
+
+# one n past a single trip of the 512-workgroup grid (512 * 256 / LPR rows) per layout: LPR 1, 2, 4,
+# 8, then LPR 16 with EPL 1, a ragged EPL 2 and a full EPL 2; two trips each, the second of 5 to 8 rows
+SEVERAL_TRIPS = [(1, 131077), (2, 65541), (3, 32771), (8, 16389), (16, 8200), (17, 8200), (32, 8200)]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == np.float64 else np.uint32)
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("l,n", SEVERAL_TRIPS)
+def test_row_kernel_several_trips(l, n, dt):
+    """Test 1 past one trip: the direct form on one slab with the default parameters, and the
+    Woodbury form on three slabs with the small eta. The sum's bar is test 1's with CSUM + 1 per
+    further trip: a thread adds one more row norm to its partial in each. Then the rows on both sides
+    of the trip boundary run again as an input of their own, in one trip: the six outputs of a row
+    depend on neither n nor the trip, so they come back bit for bit (the wrapper pre-fills them with
+    NaN)."""
+    torch = _torch()
+    from glx import kernels
+    lpr = 1
+    while lpr < min(l, 16):
+        lpr *= 2
+    per_trip = 512 * 256 // lpr
+    trips = -(-n // per_trip)
+    assert trips == 2 and 0 < n - per_trip < 256 // lpr
+    rows = slice(per_trip - 251, n)
+    for form, S, pname in ((1, 1, "default"), (2, 3, "small_eta")):
+        eta = ETAS[pname]
+        inp = _row_inputs_large(n, l, dt, form, S, eta, seed=1000 * n + 10 * l + form + S)
+        got, _ = _row_case(inp, dt, form, eta, pname, csum=CSUM + trips - 1)
+        part = _step(torch, kernels, (np.ascontiguousarray(inp[0][:, rows]),) + tuple(a[rows].copy() for a in inp[1:]),
+                     form, eta)
+        for key in OUTS:
+            assert np.array_equal(_bits(part[key]), _bits(got[key][rows])), (form, key)
 
 
 @pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])

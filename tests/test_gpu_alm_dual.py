@@ -28,6 +28,15 @@ Each bar is doubled (C = 2, the only slack) for the second-order terms dropped a
 hold rows outside the ball, rows strictly inside it, an all-zero row (which stays zero), a row with
 ||w|| within a few ulp of mu and, in a second run, one NaN row: that row comes out NaN and every
 other row is bit-identical to the first run. gamma_next = 0 leaves a NaN-filled y_out untouched.
+A row of l values is held by LPR lanes with EPL values each. The generic shapes' l select
+(LPR, EPL) = 1 (1, 1), 2 (2, 1), 3 (4, 1), 8 (8, 1), 17 and 32 (16, 2) of k_alm_inner, and the fused
+shapes run the panel layout at l = 16 and 32; with (16, 1) of the several-trip cases that is every
+instantiation. All of those are one trip of a dozen workgroups at most. test_inner_step_several_trips
+runs form 0 at (l, n) = (1, 131077), (2, 65541), (3, 32771), (8, 16389), (16, 8200), (17, 8200),
+(32, 8200), on one slab and on three: each 5 to 8 rows past the 512 * 256 / LPR rows the capped grid
+of 512 workgroups takes in one trip, so two trips, the second ragged; u+ and y+ of the rows on both
+sides of the boundary are bit-identical to those of a launch of their own. The step has no sums,
+so its bars do not depend on the trips.
 
 2. The fused form (form 1, k_atr_alm) against form 0 (k_alm_inner_panel) on the product that
 kernels.gradient(Qn, y) wrote: every bit of u+ and y+, at the shapes whose plan fuses, and on every
@@ -45,7 +54,7 @@ own n-term dot products. fused = 1 and fused = 2 give the same bits, and so does
 
 Measured on an MI355X, worst error / bound over all cases (the module prints this table when its
 tests are over, pytest -s):
-  test 1   u+ 0.093 (generic) 0.121 (panel) 0.028 (fused)   y+ 0.105 0.138 0.138
+  test 1   u+ 0.161 (generic) 0.121 (panel) 0.028 (fused)   y+ 0.174 0.138 0.138
            rows at the switch: 1 per case (the constructed one)
   test 3   inner loop 6.9e-6 of its bar (6.9e-16 of max |u|, 500 steps included)
   test 4   k identical to the reference's in all 7 fixtures, with fused = 0 and fused = 2; f_hist
@@ -97,7 +106,9 @@ def _dev(a):
 
 
 FUSED_SHAPES = [(128, 16), (128, 32), (192, 32)]
-GENERIC_SHAPES = [(130, 3), (128, 1), (67, 32)]
+# l -> (LPR, EPL) of launch_alm_inner: 1 (1, 1), 2 (2, 1), 3 (4, 1), 8 (8, 1), 17 and 32 (16, 2); the
+# fused shapes run the panel layout (LPR 16; EPL 1 at l = 16, 2 at l = 32)
+GENERIC_SHAPES = [(130, 3), (128, 1), (67, 32), (130, 2), (130, 8), (131, 17)]
 
 
 def _step_inputs(n, l, S, seed):
@@ -119,6 +130,32 @@ def _step_inputs(n, l, S, seed):
     P[3] = J[3] = 0
     y[3] = ws * (MU * (1 + 2 * EPS) / np.linalg.norm(ws))
     if S > 1:   # slabs that add up to about P, with cancellation between them
+        parts = rng.standard_normal((S - 1, n, l))
+        parts[:, 2] = 0
+        parts[:, 3] = 0
+        P = np.concatenate([parts, (P - parts.sum(axis=0))[None]], axis=0)
+    else:
+        P = P[None]
+    return P, y, J, u
+
+
+def _step_inputs_large(n, l, S, seed):
+    """_step_inputs for the several-trip cases, drawn in whole arrays (the same row kinds)."""
+    rng = np.random.default_rng(seed)
+    P = rng.standard_normal((n, l))
+    J = rng.standard_normal((n, l)) * 0.5
+    u = rng.standard_normal((n, l)) * MU / math.sqrt(l)
+    w = rng.standard_normal((n, l)) * 0.05
+    inside = rng.random(n) < 0.4
+    inside[:4] = [False, True, False, False]
+    w[0] = 5 * MU * np.sign(w[0] + (w[0] == 0))
+    w = np.where(inside[:, None], w * (0.3 * MU / np.linalg.norm(w, axis=1, keepdims=True)), w)
+    y = w + T_STEP * (P + J)
+    P[2] = J[2] = u[2] = y[2] = 0
+    ws = rng.standard_normal(l)
+    P[3] = J[3] = 0
+    y[3] = ws * (MU * (1 + 2 * EPS) / np.linalg.norm(ws))
+    if S > 1:
         parts = rng.standard_normal((S - 1, n, l))
         parts[:, 2] = 0
         parts[:, 3] = 0
@@ -168,6 +205,33 @@ def _run_step(form, Pd, yd, Jd, ud, gamma, gnext, Qnd=None):
     return kernels.alm_inner_step(yd, ud, Jd, gamma, gnext, T_STEP, MU, P=Pd, form=0)
 
 
+def _step_case(form, P, y, J, u, Pw, dP, gamma, gnext, fuses, Qn=None):
+    """One launch against the longdouble step on the exact product Pw with its bar dP, then
+    gamma_next = 0 and the NaN row; returns the first run's u+, y+."""
+    torch = _torch()
+    n, l = y.shape
+    ref = _step_reference(Pw, dP, y, J, u, gamma, gnext)
+    Pd, yd, Jd, ud = _dev(P), _dev(y), _dev(J), _dev(u)
+    Qnd = _dev(Qn) if Qn is not None else None
+    out = _run_step(form, Pd, yd, Jd, ud, gamma, gnext, Qnd)
+    gu, gy = out["u"].cpu().numpy(), out["y"].cpu().numpy()
+    _check_step(gu, gy, ref, "panel" if fuses and form == 0 else ("fused" if form == 1 else "generic"))
+    # gamma_next = 0: the same u+, and a NaN-filled y_out is left as it was
+    last = _run_step(form, Pd, yd, Jd, ud, gamma, 0.0, Qnd)
+    assert np.array_equal(last["u"].cpu().numpy(), gu)
+    assert torch.isnan(last["y"]).all()
+    # one NaN in the last row (in J, which is row-local in every arm; a NaN in y would reach every
+    # row of Qn^T y): that row NaN, every other row bit-identical
+    J2 = J.copy()
+    J2[n - 1, l // 2] = np.nan
+    out2 = _run_step(form, Pd, yd, _dev(J2), ud, gamma, gnext, Qnd)
+    for key, first in (("u", gu), ("y", gy)):
+        v = out2[key].cpu().numpy()
+        assert np.isnan(v[n - 1]).all(), key
+        assert np.array_equal(v[:n - 1], first[:n - 1]), key
+    return gu, gy
+
+
 @pytest.mark.parametrize("gamma,gnext", [(1.0, 2 / 3), (2 / 8, 2 / 9)], ids=["first", "i7"])
 @pytest.mark.parametrize("arm", ["S1", "S3", "fused"])
 @pytest.mark.parametrize("n,l", FUSED_SHAPES + GENERIC_SHAPES)
@@ -203,26 +267,40 @@ def test_inner_step_against_longdouble(n, l, arm, gamma, gnext):
     else:
         Pw = P.astype(W).sum(axis=0)
         dP = (S - 1) * EPS / 2 * np.abs(P).astype(W).sum(axis=0)
-    ref = _step_reference(Pw, dP, y, J, u, gamma, gnext)
-    form = 1 if arm == "fused" else 0
-    Pd, yd, Jd, ud = _dev(P), _dev(y), _dev(J), _dev(u)
-    Qnd = _dev(Qn) if Qn is not None else None
-    out = _run_step(form, Pd, yd, Jd, ud, gamma, gnext, Qnd)
-    gu, gy = out["u"].cpu().numpy(), out["y"].cpu().numpy()
-    _check_step(gu, gy, ref, "panel" if fuses and form == 0 else ("fused" if form == 1 else "generic"))
-    # gamma_next = 0: the same u+, and a NaN-filled y_out is left as it was
-    last = _run_step(form, Pd, yd, Jd, ud, gamma, 0.0, Qnd)
-    assert np.array_equal(last["u"].cpu().numpy(), gu)
-    assert torch.isnan(last["y"]).all()
-    # one NaN in the last row (in J, which is row-local in every arm; a NaN in y would reach every
-    # row of Qn^T y): that row NaN, every other row bit-identical
-    J2 = J.copy()
-    J2[n - 1, l // 2] = np.nan
-    out2 = _run_step(form, Pd, yd, _dev(J2), ud, gamma, gnext, Qnd)
-    for key, first in (("u", gu), ("y", gy)):
-        v = out2[key].cpu().numpy()
-        assert np.isnan(v[n - 1]).all(), key
-        assert np.array_equal(v[:n - 1], first[:n - 1]), key
+    _step_case(1 if arm == "fused" else 0, P, y, J, u, Pw, dP, gamma, gnext, fuses, Qn)
+
+
+# one n past a single trip of the 512-workgroup grid (512 * 256 / LPR rows) per layout: LPR 1, 2, 4,
+# 8, then LPR 16 with EPL 1, a ragged EPL 2 and a full EPL 2; two trips each, the second of 5 to 8 rows
+SEVERAL_TRIPS = [(1, 131077), (2, 65541), (3, 32771), (8, 16389), (16, 8200), (17, 8200), (32, 8200)]
+
+
+@pytest.mark.parametrize("S", [1, 3])
+@pytest.mark.parametrize("l,n", SEVERAL_TRIPS)
+def test_inner_step_several_trips(l, n, S):
+    """Test 1's form 0 past one trip, on the generic layout (the plan of (n, n, l) does not fuse,
+    asserted from the describe string). The step has no sums, so the bars are test 1's as they stand.
+    Then the rows on both sides of the trip boundary run again as an input of their own, in one
+    trip: u+ and y+ of a row depend on neither n nor the trip, so they come back bit for bit (the
+    wrapper pre-fills them with NaN)."""
+    from glx import _lib
+    assert "inner step=fused" not in _lib.alm_describe(_lib.GLX_F64, n, n, l)
+    lpr = 1
+    while lpr < min(l, 16):
+        lpr *= 2
+    per_trip = 512 * 256 // lpr
+    assert -(-n // per_trip) == 2 and 0 < n - per_trip < 256 // lpr
+    gamma, gnext = ((1.0, 2 / 3), (2 / 8, 2 / 9))[(l + S) % 2]
+    P, y, J, u = _step_inputs_large(n, l, S, seed=1000 * n + l)
+    Pw = P.astype(W).sum(axis=0)
+    dP = (S - 1) * EPS / 2 * np.abs(P).astype(W).sum(axis=0)
+    gu, gy = _step_case(0, P, y, J, u, Pw, dP, gamma, gnext, False)
+    rows = slice(per_trip - 251, n)
+    ns = n - (per_trip - 251)
+    assert "inner step=fused" not in _lib.alm_describe(_lib.GLX_F64, ns, ns, l)   # the same layout
+    part = _run_step(0, _dev(P[:, rows]), _dev(y[rows]), _dev(J[rows]), _dev(u[rows]), gamma, gnext)
+    assert np.array_equal(part["u"].cpu().numpy().view(np.uint64), gu[rows].view(np.uint64))
+    assert np.array_equal(part["y"].cpu().numpy().view(np.uint64), gy[rows].view(np.uint64))
 
 
 # the planner's own tile and splits at FUSED_SHAPES, then every fused tile by name (GLX_ATR_VARIANT)

@@ -26,7 +26,9 @@ term, per row i:
          Which branch a row takes is decided by ||x_i|| == 0, exact for an all-zero row and for the
          O(1) entries used here (no underflow), so no row is ambiguous.
   sum_i ||x_i||   sum_i RN ||x_i|| + CSUM eps64 sum_i ||x_i|| for the fp64 accumulation (CSUM = 32
-         additions deep: a few per thread, 8 levels in the workgroup, 12 over the partials).
+         additions deep: a few per thread, 8 levels in the workgroup, 12 over the partials). A thread
+         adds one more term in every further trip of its workgroup: the several-trip cases take
+         CSUM + trips - 1 (33 at their two trips).
   max_i ||g_i||   max_i (||dg_i||_2 + RN ||g_i||): max is 1-Lipschitz in every element.
   max_i kkt_i     max_i dkkt_i, likewise.
   sum_i kkt_i^2   sum_i (2 kkt_i dkkt_i + dkkt_i^2) + (CSUM + 1) eps64 sum_i kkt_i^2 (the square is
@@ -39,6 +41,13 @@ its KKT condition (g = -mu x / ||x|| + 1e-3 mu noise), then random rows of those
 runs twice: as built, and with one NaN in the last row of x. ||g_i|| does not read x, so the row
 norms and max_i ||g_i|| of the second run are bit-identical to the first; the three sums and the
 max that the NaN row feeds (sum ||x_i||, max kkt, sum kkt^2, and the row count) are NaN.
+The l of test 1 select (LPR, EPL) = 1 (1, 1), 2 (2, 1), 3 (4, 1), 5 and 8 (8, 1), 16 (16, 1),
+32 (16, 2), 33 (16, 3), 64 (16, 4), 72 (16, 5), 88 (16, 6), 104 (16, 7), 128 (16, 8): every
+instantiation of k_cert_row, each in one trip of at most 17 workgroups. test_row_kernel_several_trips
+runs (l, n) = (1, 131077), (2, 65541), (3, 32771), (8, 16389), (16, 8200), (128, 8200): LPR 1, 2, 4, 8
+and LPR 16 at EPL 1 and 8, each 5 to 8 rows past the 512 * 256 / LPR rows the capped grid of 512
+workgroups takes in one trip, so two trips, the second ragged; the norms of the rows on both sides
+of the boundary are bit-identical to those of a launch of their own.
 
 2. Fused against unfused at the shapes whose plan fuses (asserted from glx_certificate_describe):
 the five sums and the row norms of form 1 (k_atr_cert) and of form 0 on the G it wrote, given m
@@ -63,10 +72,10 @@ its bar is gmax's with dr = 0.
 
 Measured on an MI355X, worst error / bound over all cases (f64, f32); the module prints this table
 when its tests are over (pytest -s):
-  test 1   sum ||x_i|| 0.014 0.11   max ||g_i|| 0.32 0.16   max kkt 0.25 0.25   sum kkt^2 0.013 0.22
-           row norms 0.50 0.39
-  test 2   (panel layout) sum ||x_i|| 0.012 0.002   max ||g_i|| <1e-4 0.061   max kkt 0.15 0.032
-           sum kkt^2 0.013 0.0015   G 0.024 0.0043; forms 0 / 1 and fused = 1 / 2 bit-identical
+  test 1   sum ||x_i|| 0.014 0.18   max ||g_i|| 0.32 0.17   max kkt 0.25 0.25   sum kkt^2 0.013 0.22
+           row norms 0.50 0.43
+  test 2   (panel layout) sum ||x_i|| 0.012 0.022   max ||g_i|| <1e-4 0.085   max kkt 0.15 0.090
+           sum kkt^2 0.013 0.028   G 0.024 0.011; forms 0 / 1 and fused = 1 / 2 bit-identical
   test 3   ||r||^2 1e-4 1e-4   <r, b> 2e-4 <1e-4   sum ||x_i|| <1e-4 8e-4   gmax 1e-4 1e-4
            kkt_max 2e-4 1e-4   sum kkt^2 <1e-4 <1e-4   gap <1e-4 1e-4   mu_max <1e-4 (its bars carry
            the worst-case dot-product terms); at x*: gap 1.14e-11 = 1.87e-11 of primal, kkt_max 2.5e-13;
@@ -131,9 +140,10 @@ def _rn(l, dt):
     return (epl + math.log2(lpr) + 2) / 4 * float(np.finfo(dt).eps)
 
 
-def _row_bars(x, g, mu, dt, dg=None):
+def _row_bars(x, g, mu, dt, dg=None, csum=CSUM):
     """The row terms of x, g (T values) in the wider type with mu = T(mu), and their bars (already
-    doubled). dg: the elementwise bar of g (None: g is exact)."""
+    doubled). dg: the elementwise bar of g (None: g is exact). csum: the depth of the fp64
+    accumulation (CSUM at one trip)."""
     W = _wide(dt)
     eps = float(np.finfo(dt).eps)
     l = x.shape[1]
@@ -152,10 +162,10 @@ def _row_bars(x, g, mu, dt, dg=None):
     dk_z = dgn + eps / 2 * np.abs(gn - float(muw))
     dkkt = np.where(nz, dk_nz, dk_z)
     bars = {
-        "sum_xnorm": C * (RN + CSUM * EPS64) * np.sum(xn),
+        "sum_xnorm": C * (RN + csum * EPS64) * np.sum(xn),
         "gmax": C * np.max(dgn),
         "kkt_max": C * np.max(dkkt),
-        "kkt_sq": C * (np.sum(2 * kkt * dkkt + dkkt * dkkt) + (CSUM + 1) * EPS64 * np.sum(kkt * kkt)),
+        "kkt_sq": C * (np.sum(2 * kkt * dkkt + dkkt * dkkt) + (csum + 1) * EPS64 * np.sum(kkt * kkt)),
         "gnorm": C * dgn,
     }
     return ref, bars
@@ -209,14 +219,34 @@ def _row_inputs(n, l, dt, seed):
     return x.astype(dt), g.astype(dt)
 
 
-@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
-@pytest.mark.parametrize("l", [1, 2, 3, 16, 32, 33, 64, 128])
-@pytest.mark.parametrize("n", [1, 15, 64, 130, 257])
-def test_row_kernel_against_wider_type(n, l, dt):
+def _row_inputs_large(n, l, dt, seed):
+    """_row_inputs' seven row kinds for the several-trip cases, drawn in whole arrays: the first seven
+    rows hold one kind each, the rest random kinds. The random values differ from row to row, so no
+    two rows agree except the all-zero ones."""
+    rng = np.random.default_rng(seed)
+    eps = float(np.finfo(dt).eps)
+    mu = float(dt(MU))
+    kinds = np.concatenate([np.arange(7), rng.integers(0, 7, size=max(0, n - 7))])[:n, None]
+    w = rng.standard_normal((n, l))
+    unit = w / np.linalg.norm(w, axis=1, keepdims=True)
+    xr = rng.standard_normal((n, l))
+    far = 1.5 + rng.random((n, 1)) * 5
+    noise = rng.standard_normal((n, l))
+    x = np.where((kinds == 0) | (kinds == 6), xr, 0.0)
+    near = -mu * xr / np.linalg.norm(xr, axis=1, keepdims=True) + 1e-3 * mu * noise
+    g = np.select([kinds == 0, kinds == 1, kinds == 2, kinds == 3, kinds == 4, kinds == 5],
+                  [noise * 0.05, unit * mu * far, 0.0 * unit, unit * mu * (1 + 2 * eps), unit * mu * (1 - 2 * eps),
+                   unit * mu * 0.3], near)
+    return x.astype(dt), g.astype(dt)
+
+
+def _row_kernel_case(x, g, dt, csum=CSUM):
+    """One launch of the row kernel on (x, g) against the wider type, then the same inputs with a
+    NaN in the last row of x; returns the first run's row norms."""
     torch = _torch()
     from glx import kernels
-    x, g = _row_inputs(n, l, dt, seed=1000 * n + l)
-    ref, bars = _row_bars(x, g, MU, dt)
+    n, l = x.shape
+    ref, bars = _row_bars(x, g, MU, dt, csum=csum)
     tag = _tag(dt)
     xd, gd = torch.from_numpy(x).cuda(), torch.from_numpy(g).cuda()
     out = kernels.certificate_step(xd, MU, G=gd, form=0)
@@ -236,6 +266,45 @@ def test_row_kernel_against_wider_type(n, l, dt):
     assert np.isnan(s2[[0, 2, 3, 4]]).all(), s2
     assert s2[1] == sums[1]
     assert np.array_equal(out2["row_norms"].cpu().numpy(), rn)
+    return rn
+
+
+# l -> (LPR, EPL) of cert_dispatch_row: 1 (1, 1), 2 (2, 1), 3 (4, 1), 5 and 8 (8, 1), 16 (16, 1),
+# 32 (16, 2), 33 (16, 3), 64 (16, 4), 72 (16, 5), 88 (16, 6), 104 (16, 7), 128 (16, 8)
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("l", [1, 2, 3, 5, 8, 16, 32, 33, 64, 72, 88, 104, 128])
+@pytest.mark.parametrize("n", [1, 15, 64, 130, 257])
+def test_row_kernel_against_wider_type(n, l, dt):
+    x, g = _row_inputs(n, l, dt, seed=1000 * n + l)
+    _row_kernel_case(x, g, dt)
+
+
+# one n past a single trip of the 512-workgroup grid (512 * 256 / LPR rows) per lanes-per-row layout:
+# LPR 1, 2, 4, 8, then LPR 16 with EPL 1 and EPL 8; two trips each, the second of 5 to 8 rows
+SEVERAL_TRIPS = [(1, 131077), (2, 65541), (3, 32771), (8, 16389), (16, 8200), (128, 8200)]
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("l,n", SEVERAL_TRIPS)
+def test_row_kernel_several_trips(l, n, dt):
+    """Test 1 past one trip (generic layout, m = 1). The bars are test 1's with CSUM + 1 per further
+    trip: a thread adds one more term to its partial sums in each. Then the rows on both sides of the
+    trip boundary run again as an input of their own, in one trip: a row's norm depends on neither n
+    nor the trip, so it comes back bit for bit (the wrapper pre-fills the norms with NaN)."""
+    torch = _torch()
+    from glx import kernels
+    lpr = 1
+    while lpr < min(l, 16):
+        lpr *= 2
+    per_trip = 512 * 256 // lpr
+    trips = -(-n // per_trip)
+    assert trips == 2 and 0 < n - per_trip < 256 // lpr
+    x, g = _row_inputs_large(n, l, dt, seed=1000 * n + l)
+    rn = _row_kernel_case(x, g, dt, csum=CSUM + trips - 1)
+    rows = slice(per_trip - 251, n)
+    part = kernels.certificate_step(torch.from_numpy(x[rows].copy()).cuda(), MU,
+                                    G=torch.from_numpy(g[rows].copy()).cuda(), form=0)
+    assert np.array_equal(part["row_norms"].cpu().numpy().view(np.uint64), rn[rows].view(np.uint64))
 
 
 FUSED_CASES = [(64, 64, 16, np.float64, None, None), (128, 128, 32, np.float64, None, None),

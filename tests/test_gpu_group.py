@@ -37,6 +37,21 @@ k = size_g l is the number of elements of a group; every bar below is first orde
    norms; kkt per row twice (l / 2 + 5) u (||g_i|| + 2 mu), item 2's worst case); weights on single
    rows against the row solve of A / w.
 5. The path on groups. 6. Refusals through the C ABI.
+
+Layouts and trips. A team of LPG lanes owns a group; group_dispatch picks LPG and the elements per
+lane from the longest run's max_run l elements: <= 4: 4 lanes, <= 16: 16, <= 32: 32, <= 64: a wave,
+one element per lane; <= 128, 256, 512: a wave with 2, 4, 8 per lane; longer: two sweeps. The grid
+is capped at 1024 workgroups, 1024 * 256 / LPG groups a trip. STEP_CASES and CERT_CASES hold one
+case per layout in one trip of at most 34 workgroups. SEVERAL_TRIPS holds one case per layout
+family with G five past one trip (two trips, the second ragged): (l, pool, G) = (2, (1, 2), 65541)
+at 4 lanes, (16, (3, 4), 4101) at a wave with one element per lane and (64, (2, 8, 9), 4101) at two
+sweeps, for group_step (rows = n + 63, the widest padding the entry takes, so the loop over the rows
+past group_ptr[G] stays within one trip there; the (200, 256, 128) case of STEP_CASES makes two
+trips of it on its 19 workgroups) and for group_certificate_step; group_cnorm runs G = 262149 with
+a lane per group (runs <= 8) and G = 4101 with a wave per group (runs of 9 .. 12). In each, the
+groups on both sides of the trip boundary, which hold one of the longest run, run again as a
+problem of their own and give the same bits. group_expand is one workgroup; its case with 573
+kept groups of 257 .. 260 rows fills the 512-entry list of long groups and reaches the fallback.
 """
 import ctypes
 import functools
@@ -84,10 +99,26 @@ STEP_CASES = [(475, 512, 16, gr.POOL_SMALL), (475, 512, 16, gr.POOL_LONG), (130,
 T_STEP, MU_STEP = 0.3, 0.7
 
 
-def _step_inputs(n, rows, l, pool, dt, seed):
+def _draw_groups_at_once(g, G, pool):
+    """G sizes from `pool` in one call (the several-trip cases): group_ptr, int32; n = group_ptr[G]."""
+    return np.concatenate(([0], np.cumsum(g.choice(pool, size=G)))).astype(np.int32)
+
+
+def _lpg(max_len):
+    """Lanes per group of group_dispatch for a longest run of max_len elements (EPL: 1 up to 64
+    elements, then 2, 4, 8 in registers up to 512, then the two-sweep form)."""
+    return 4 if max_len <= 4 else 16 if max_len <= 16 else 32 if max_len <= 32 else 64
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == np.float64 else np.uint32)
+
+
+def _step_inputs(n, rows, l, pool, dt, seed, ptr=None):
     """y, g, xk (rows x l, T) with every group's ||y - t g|| at t mu w_g (1 +- d); one group all zero."""
     g = np.random.default_rng(seed)
-    ptr = gr.draw_groups(g, n, pool)
+    if ptr is None:
+        ptr = gr.draw_groups(g, n, pool)
     G = ptr.size - 1
     w = np.sqrt(np.diff(ptr).astype(np.float64)) * g.uniform(0.5, 2.0, G)
     y = g.standard_normal((rows, l))
@@ -108,11 +139,17 @@ def _step_inputs(n, rows, l, pool, dt, seed):
 @pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
 @pytest.mark.parametrize("case", STEP_CASES, ids=lambda c: "%d(%d)x%d-%s" % (c[0], c[1], c[2], c[3][-1]))
 def test_group_step(case, dt):
+    _step_case(case, dt)
+
+
+def _step_case(case, dt, ptr=None):
+    """One group_step launch with all the checks of test 1; ptr: a description drawn beforehand.
+    Returns the description, the inputs and the outputs."""
     from glx import kernels
     torch = _torch()
     n, rows, l, pool = case
     u = _u(dt)
-    ptr, w, y, gv, xk, zero = _step_inputs(n, rows, l, pool, dt, 7 + n + l)
+    ptr, w, y, gv, xk, zero = _step_inputs(n, rows, l, pool, dt, 7 + n + l, ptr)
     thres = float(np.finfo(dt).tiny)
     theta, theta_next = 2.0 / 4, 2.0 / 5
     xc, vn, yn, sums, nrm, tmuw = gr.step_ref(y[:n], gv[:n], xk[:n], ptr, w, T_STEP, MU_STEP, thres, theta, theta_next)
@@ -182,6 +219,44 @@ def test_group_step(case, dt):
     if np.array_equal(summed, gv):
         for nm in ("xc", "v_next", "y_next", "sums"):
             assert torch.equal(r1[nm].reshape(-1), res[nm].reshape(-1)), nm
+    return ptr, w, y, gv, xk, res, (thres, theta, theta_next)
+
+
+# One case per layout family past one trip of the 1024-workgroup grid (1024 * 256 / LPG groups),
+# (l, pool, G): 4 lanes per group (65536 groups a trip), a wave per group with one element per lane in
+# registers (4096 a trip), the two-sweep form (4096 a trip; about 1.7 M elements). Two trips each, the
+# second of 5 groups. rows = n + 63, the widest padding the entry takes.
+SEVERAL_TRIPS = [(2, (1, 2), 65541), (16, (3, 4), 4101), (64, (2, 8, 9), 4101)]
+SEVERAL_IDS = ["4-lanes", "wave-1-per-lane", "two-sweeps"]
+
+
+def _trip_slice(ptr, l, pool):
+    """The groups on both sides of the trip boundary: (first group, its first row); they hold a
+    group of the longest run, so on their own they take the same layout."""
+    G = ptr.size - 1
+    per_trip = 1024 * 256 // _lpg(max(pool) * l)
+    assert -(-G // per_trip) == 2 and 0 < G - per_trip < 40     # a second trip of a few groups
+    g0 = per_trip - 40
+    assert np.diff(ptr[g0:]).max() == max(pool) == np.diff(ptr).max()
+    return g0, int(ptr[g0])
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("l,pool,G", SEVERAL_TRIPS, ids=SEVERAL_IDS)
+def test_group_step_several_trips(l, pool, G, dt):
+    """Test 1 past one trip. Its bars hold as they stand: the sums' accumulation term is the
+    worst case of an n l-term sum, whatever the trips. Then the groups on both sides of the trip
+    boundary run again as a problem of their own, in one trip: a group's outputs depend on neither
+    G nor the trip, so they come back bit for bit (NaN-filled by the wrapper before the launch)."""
+    from glx import kernels
+    ptr = _draw_groups_at_once(np.random.default_rng(1000 * l + G), G, pool)
+    n = int(ptr[-1])
+    g0, r0 = _trip_slice(ptr, l, pool)
+    ptr, w, y, gv, xk, res, (thres, theta, theta_next) = _step_case((n, n + 63, l, pool), dt, ptr=ptr)
+    part = kernels.group_step(_dev(y[r0:n]), _dev(gv[r0:n]), _dev(xk[r0:n]), ptr[g0:] - ptr[g0], w[g0:], T_STEP,
+                              MU_STEP, thres, theta, theta_next)
+    for nm in ("xc", "v_next", "y_next"):
+        assert np.array_equal(_bits(part[nm].cpu().numpy()), _bits(res[nm].cpu().numpy()[r0:n])), nm
 
 
 # ------------------------------------------------------------------------------------------ 2
@@ -192,12 +267,19 @@ CERT_CASES = [(512, 16, gr.POOL_SMALL), (512, 16, gr.POOL_LONG), (130, 3, gr.POO
 @pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
 @pytest.mark.parametrize("case", CERT_CASES, ids=lambda c: "%dx%d-%s" % (c[0], c[1], c[2][-1]))
 def test_group_certificate_step(case, dt):
+    _cert_case(case, dt)
+
+
+def _cert_case(case, dt, ptr=None):
+    """One group_certificate_step launch with all the checks of test 2; ptr: a description drawn
+    beforehand. Returns the description, the inputs and the outputs."""
     from glx import kernels
     torch = _torch()
     n, l, pool = case
     u = _u(dt)
     g = np.random.default_rng(31 + n + l)
-    ptr = gr.draw_groups(g, n, pool)
+    if ptr is None:
+        ptr = gr.draw_groups(g, n, pool)
     G = ptr.size - 1
     w = np.sqrt(np.diff(ptr).astype(np.float64)) * g.uniform(0.5, 2.0, G)
     mu = 0.8
@@ -243,27 +325,66 @@ def test_group_certificate_step(case, dt):
     xb[ptr[first], 0] = np.nan
     bad = kernels.group_certificate_step(_dev(xb), _dev(gv), ptr, w, mu)["sums"].cpu().numpy()
     assert np.isnan(bad[0]) and np.isnan(bad[2]) and np.isnan(bad[4]) and bad[1] == got[1]
+    return ptr, w, x, gv, mu, out
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("l,pool,G", SEVERAL_TRIPS, ids=SEVERAL_IDS)
+def test_group_certificate_step_several_trips(l, pool, G, dt):
+    """Test 2 past one trip, with its bars as they stand (the sums' accumulation term is the worst case
+    of a G-term sum), then the groups on both sides of the trip boundary as a problem of their own:
+    ||g_[g]|| / w_g and the summed gradient come back bit for bit."""
+    from glx import kernels
+    ptr = _draw_groups_at_once(np.random.default_rng(2000 * l + G), G, pool)
+    n = int(ptr[-1])
+    g0, r0 = _trip_slice(ptr, l, pool)
+    ptr, w, x, gv, mu, out = _cert_case((n, l, pool), dt, ptr=ptr)
+    part = kernels.group_certificate_step(_dev(x[r0:]), _dev(gv[r0:]), ptr[g0:] - ptr[g0], w[g0:], mu, want_g=True)
+    assert np.array_equal(_bits(part["group_norms"].cpu().numpy()), _bits(out["group_norms"].cpu().numpy()[g0:]))
+    assert np.array_equal(_bits(part["g"].cpu().numpy()), _bits(out["g"].cpu().numpy()[r0:]))
+
+
+def _cnorm_case(g, m, n, pool, ptr=None):
+    from glx import kernels
+    if ptr is None:
+        ptr = gr.draw_groups(g, n, pool)
+    w = g.uniform(0.5, 3.0, ptr.size - 1)
+    A = g.standard_normal((m, n))
+    want = gr.group_cnorms(A, ptr, w)
+    cn, _ = kernels.col_norms(_dev(A))
+    gcn, mx = kernels.group_cnorm(cn, ptr, w)
+    got = gcn.cpu().numpy()
+    max_run = int(np.diff(ptr).max())
+    bar = ((m + 2) + (max_run + 3)) * gr.EPS64 / 2 * want
+    err = np.abs(got.astype(LD) - want)
+    assert np.all(err <= bar), (m, n, pool, float(np.max(err / bar)))
+    assert mx.cpu().numpy()[0] == got.max()
+    again, mx2 = kernels.group_cnorm(cn, ptr, w)
+    assert np.array_equal(again.cpu().numpy(), got) and mx2.cpu().numpy()[0] == got.max()
+    return cn, w, got
 
 
 def test_group_cnorm():
-    from glx import kernels
     g = np.random.default_rng(3)
     for m, n, pool in ((96, 512, gr.POOL_SMALL), (96, 512, gr.POOL_LONG), (40, 130, gr.POOL_RAGGED), (5, 70, (1,)),
                        (7, 300, (300,))):
-        ptr = gr.draw_groups(g, n, pool)
-        w = g.uniform(0.5, 3.0, ptr.size - 1)
-        A = g.standard_normal((m, n))
-        want = gr.group_cnorms(A, ptr, w)
-        cn, _ = kernels.col_norms(_dev(A))
-        gcn, mx = kernels.group_cnorm(cn, ptr, w)
-        got = gcn.cpu().numpy()
-        max_run = int(np.diff(ptr).max())
-        bar = ((m + 2) + (max_run + 3)) * gr.EPS64 / 2 * want
-        err = np.abs(got.astype(LD) - want)
-        assert np.all(err <= bar), (m, n, pool, float(np.max(err / bar)))
-        assert mx.cpu().numpy()[0] == got.max()
-        again, mx2 = kernels.group_cnorm(cn, ptr, w)
-        assert np.array_equal(again.cpu().numpy(), got) and mx2.cpu().numpy()[0] == got.max()
+        _cnorm_case(g, m, n, pool)
+
+
+# a lane per group (runs of at most 8: 262144 groups a trip) and a wave per group (4096 a trip), each
+# 5 groups past one trip
+@pytest.mark.parametrize("m,pool,G", [(3, (1, 2, 3), 262149), (5, (9, 10, 11, 12), 4101)], ids=["lane", "wave"])
+def test_group_cnorm_several_trips(m, pool, G):
+    from glx import kernels
+    g = np.random.default_rng(5 + G)
+    ptr = _draw_groups_at_once(g, G, pool)
+    per_trip = 1024 * 256 // (1 if max(pool) <= 8 else 64)
+    assert -(-G // per_trip) == 2 and np.diff(ptr).max() == max(pool)
+    cn, w, got = _cnorm_case(g, m, int(ptr[-1]), pool, ptr=ptr)
+    g0 = per_trip - 40          # the groups on both sides of the trip boundary, on their own: the same bits
+    assert np.diff(ptr[g0:]).max() == max(pool)
+    part, _ = kernels.group_cnorm(cn[int(ptr[g0]):].clone(), ptr[g0:] - ptr[g0], w[g0:])
+    assert np.array_equal(_bits(part.cpu().numpy()), _bits(got[g0:]))
 
 
 def _expand(kept, ptr, w, gcn, gmap=None):
@@ -290,7 +411,20 @@ def _expand(kept, ptr, w, gcn, gmap=None):
 def test_group_expand(case):
     n, pool = case
     g = np.random.default_rng(17 + n)
-    ptr = gr.draw_groups(g, n, pool)
+    _expand_case(g, gr.draw_groups(g, n, pool))
+
+
+def test_group_expand_with_the_long_list_full():
+    """More than 512 kept groups of more than 256 rows: the workgroup's LDS list of long groups
+    fills up, and a thread that finds it full writes its group's rows itself. Which groups those
+    are differs from run to run; the lists do not."""
+    g = np.random.default_rng(23)
+    sizes = g.choice([257, 258, 259, 260, 1, 2, 3], size=1101, p=[0.13, 0.13, 0.13, 0.13, 0.16, 0.16, 0.16])
+    assert (sizes > 256).sum() >= 520
+    _expand_case(g, np.concatenate(([0], np.cumsum(sizes))).astype(np.int32))
+
+
+def _expand_case(g, ptr):
     G = ptr.size - 1
     assert G % 64 != 0
     w, gcn = g.uniform(0.5, 2.0, G), g.uniform(1.0, 9.0, G)

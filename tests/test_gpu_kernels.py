@@ -133,18 +133,18 @@ def test_deterministic_repeat():
     assert torch.equal(k.gradient(A, R1), k.gradient(A, R1))
 
 
-@pytest.mark.parametrize("l", [1, 2, 3, 8, 16, 17, 32, 64])
-@pytest.mark.parametrize("dtype", ["f64", "f32"])
-def test_prox_matches_reference_formula(l, dtype):
-    """prox_th of gl_ProxGD_primal.py:65-71 including the (||w||<thres)+||w|| denominator."""
-    k = _glx()
-    dt = torch.float64 if dtype == "f64" else torch.float32
+def _prox_inputs(n, l, dtype, seed):
     npdt = np.float64 if dtype == "f64" else np.float32
-    rng = np.random.default_rng(l)
-    n = 1000
+    rng = np.random.default_rng(seed)
     W = rng.standard_normal((n, l)).astype(npdt)
     W[::7] *= 1e-4            # rows below thres take the quirky denominator
     W[::11] = 0               # all-zero rows
+    return W
+
+
+def _prox_case(W, dtype):
+    """prox_th of gl_ProxGD_primal.py:65-71 including the (||w||<thres)+||w|| denominator."""
+    k = _glx()
     t, mu, thres = 0.37, 0.02, 1e-3
     nrm = np.linalg.norm(W, axis=1).reshape(-1, 1)
     ref = W * np.clip(nrm - t * mu, a_min=0, a_max=None) / ((nrm < thres) + nrm)
@@ -157,6 +157,81 @@ def test_prox_matches_reference_formula(l, dtype):
     s = sums.cpu().numpy()
     assert np.isclose(s[0], np.linalg.norm(ref.astype(np.float64), axis=1).sum(), rtol=1e-6 if dtype == "f32" else 1e-13)
     assert s[1] == np.abs(got).max()
+    return got
+
+
+# l -> (lanes per row, elements per lane) of k_prox_plain: 1 (1, 1), 2 (2, 1), 3 (4, 1), 8 (8, 1),
+# 16 (16, 1), 17 and 32 (16, 2), 40 (16, 3), 64 (16, 4), 72 (16, 5), 88 (16, 6), 104 (16, 7), 128 (16, 8)
+@pytest.mark.parametrize("l", [1, 2, 3, 8, 16, 17, 32, 40, 64, 72, 88, 104, 128])
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_prox_matches_reference_formula(l, dtype):
+    _prox_case(_prox_inputs(1000, l, dtype, l), dtype)
+
+
+def _prox_bars_case(W, dtype, lpr, epl, csum):
+    """k_prox_plain against the next wider type, term by term (eps = T's machine epsilon, u = eps / 2;
+    t mu, formed in double, and thres are rounded to T first, as the kernel does):
+      nrm  the l squares round once (u), a sum path has EPL - 1 additions in the lane and log2 LPR
+           shuffle levels, the root halves the relative error and rounds once:
+             dn <= RN nrm,  RN = (EPL + log2 LPR + 2) / 4 eps.
+      c    max(nrm - t mu, 0): one rounding, 1-Lipschitz: dc <= dn + u c, on both sides of the switch.
+      d    (nrm < thres) + nrm: the indicator is a jump in the reference itself, so no row may sit
+           within 2 dn of thres (asserted); then dd <= dn + u d.
+      p    (w c) / d, two roundings: dp_j <= |w_j| dc / d + |p_j| (eps + dd / d).
+      sum_i ||p_i||  per row ||dp_i||_2 + RN ||p_i||, + csum eps64 sum |term| for the fp64 accumulation
+           (32 additions deep at one trip: a few per thread, 8 levels in the workgroup, 12 over the
+           partials; one more per further trip).
+      max |p|        that of the returned p, bit for bit.
+    Each bar is doubled for the second-order terms dropped. Returns the returned p."""
+    npdt = np.float64 if dtype == "f64" else np.float32
+    wide = np.longdouble if dtype == "f64" else np.float64
+    eps = float(np.finfo(npdt).eps)
+    u = eps / 2
+    t, mu, thres = 0.37, 0.02, 1e-3
+    tmu, th = wide(npdt(t * mu)), wide(npdt(thres))
+    Ww = W.astype(wide)
+    nrm = np.sqrt(np.sum(Ww * Ww, axis=1, keepdims=True))
+    c = np.maximum(nrm - tmu, 0)
+    d = (nrm < th).astype(wide) + nrm
+    ref = Ww * c / d
+    RN = (epl + np.log2(lpr) + 2) / 4 * eps
+    dn = RN * nrm
+    assert not np.any(np.abs(nrm - th) <= 2 * dn)
+    dc, dd = dn + u * c, dn + u * d
+    bar = 2 * (np.abs(Ww) * dc / d + np.abs(ref) * (eps + dd / d))
+    X, sums = _glx().prox(torch.from_numpy(W).cuda(), t, mu, thres)
+    got = X.cpu().numpy()
+    err = np.abs(got.astype(wide) - ref)
+    assert np.all(err <= bar), float(np.max(err / np.maximum(bar, wide(1e-300))))
+    assert not got[np.sum(np.abs(W), axis=1) == 0].any()          # all-zero rows stay zero
+    pn = np.sqrt(np.sum(ref * ref, axis=1))
+    sbar = 2 * np.sum(np.sqrt(np.sum(bar * bar, axis=1)) / 2 + RN * pn) + csum * float(np.finfo(np.float64).eps) * np.sum(pn)
+    s = sums.cpu().numpy()
+    assert abs(wide(s[0]) - np.sum(pn)) <= sbar, (float(s[0]), float(np.sum(pn)), float(sbar))
+    assert s[1] == np.abs(got).max()
+    return got
+
+
+# one n past a single trip of the 512-workgroup grid (512 * 256 / LPR rows) per lanes-per-row layout
+@pytest.mark.parametrize("l,n", [(1, 131077), (2, 65541), (3, 32771), (8, 16389), (16, 8200), (128, 8200)])
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_prox_several_trips(l, n, dtype):
+    """The last workgroups make a second, ragged trip (5 to 8 rows). Then the rows on both sides of
+    the trip boundary run again as an input of their own, in one trip: a row's prox depends on neither
+    n nor the trip, so it comes back bit for bit (the wrapper pre-fills the output with NaN). With
+    10^5 rows some norm lies close to t mu, where a fixed relative tolerance on p cannot hold, so
+    these cases take the derived bars of _prox_bars_case."""
+    lpr = 1
+    while lpr < min(l, 16):
+        lpr *= 2
+    per_trip = 512 * 256 // lpr
+    assert -(-n // per_trip) == 2 and 0 < n - per_trip < 256 // lpr
+    W = _prox_inputs(n, l, dtype, 1000 * l + n)
+    got = _prox_bars_case(W, dtype, lpr, -(-l // lpr), 32 + 1)
+    rows = slice(per_trip - 251, n)
+    part, _ = _glx().prox(torch.from_numpy(W[rows].copy()).cuda(), 0.37, 0.02, 1e-3)
+    bits = np.uint64 if dtype == "f64" else np.uint32
+    assert np.array_equal(part.cpu().numpy().view(bits), got[rows].view(bits))
 
 
 def test_prox_nan_propagates():

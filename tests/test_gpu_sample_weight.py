@@ -6,11 +6,15 @@ Reference: tests/sw_ref.py, which reduces every weighted problem to the existing
    r_w = fl(w r^) are one rounded operation each on values the test holds exactly, so they are compared
    bit for bit with NumPy in the dtype. Each of the three sums adds m l terms that carry two roundings
    in double ((w r^) r^; for float32 inputs the first product is exact), and m l - 1 additions:
-   gamma_{ml+3}(eps64) sum |terms| against longdouble on the same r^.
+   gamma_{ml+3}(eps64) sum |terms| against longdouble on the same r^. The bar is a function of m l, so
+   it holds as it stands at (2050, 128) and (262147, 1), where the grid of 1024 workgroups is full and
+   256 and 3 threads take a second element (two trips, the second ragged; S = 0, 1, 3, with and
+   without hold-out weights, and the unweighted kernel on the same inputs).
 2. The weighted column norms (glx.kernels.col_norms_sw): test_gpu_screen's bar with one more
    rounding per term ((w a) a): (m + 3) eps64 / 2 relative (+ eps32 / 2 for float32 inputs, whose
    reference is longdouble on the float64 values they were rounded from; the weights are given in the
-   dtype and are exact).
+   dtype and are exact). (3, 262214) and (130, 262214) are past the cap of 1024 column blocks: 70
+   lanes walk a second column, in one slab and in three.
 3. Certificates. Ones against None bit for bit. Random weights against sw_ref in longdouble with
    test_gpu_certificate's bars, the weights carried through them: dr is the product's elementwise bar,
    d(w r) = w dr + eps / 2 |w r|, dg = (m + 2) eps |A|^T |w r| + |A|^T d(w r).
@@ -71,7 +75,10 @@ def _fin_weights(g, m, dt):
 
 @pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
 @pytest.mark.parametrize("S", [0, 1, 3])
-@pytest.mark.parametrize("shape", [(5, 3), (64, 16), (67, 1), (130, 128)], ids=lambda s: "%dx%d" % s)
+# (2050 x 128 and 262147 x 1: past the 1024-workgroup cap of 262144 elements, so the first 256 and the
+# first 3 threads take a second element; the row of an element comes from idx / l at both l)
+@pytest.mark.parametrize("shape", [(5, 3), (64, 16), (67, 1), (130, 128), (2050, 128), (262147, 1)],
+                         ids=lambda s: "%dx%d" % s)
 def test_weighted_finalize(shape, S, dt):
     from glx import kernels
     m, l = shape
@@ -115,7 +122,10 @@ def test_weighted_finalize(shape, S, dt):
 
 # ------------------------------------------------------------------------------------------ 2
 @pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
-@pytest.mark.parametrize("shape", [(1, 1), (63, 65), (130, 300), (4097, 70)], ids=lambda s: "%dx%d" % s)
+# (m x 262214: 70 columns past the 1024-workgroup cap, a second column for the first 70 lanes of
+# workgroup 0, in one slab and in three)
+@pytest.mark.parametrize("shape", [(1, 1), (63, 65), (130, 300), (4097, 70), (3, 262214), (130, 262214)],
+                         ids=lambda s: "%dx%d" % s)
 def test_weighted_col_norms(shape, dt):
     from glx import kernels
     m, n = shape
@@ -129,7 +139,8 @@ def test_weighted_col_norms(shape, dt):
     if m == 1:
         w[:] = 0 if n == 1 else w
     want = sw.col_norms(A64, w)
-    norms, stats = kernels.col_norms_sw(_dev(A64, dt), _dev(w))
+    Ad = _dev(A64, dt)
+    norms, stats = kernels.col_norms_sw(Ad, _dev(w))
     got, st = norms.cpu().numpy(), stats.cpu().numpy()
     bar = ((m + 3) * EPS64 / 2 + (sr.EPS32 / 2 if dt == np.float32 else 0.0)) * want
     err = np.abs(got.astype(LD) - want)
@@ -138,10 +149,10 @@ def test_weighted_col_norms(shape, dt):
     assert st[0] == got.max()
     sq = float(np.sum(got.astype(LD) ** 2))
     assert abs(st[1] - sq) <= (m + n + 2) * EPS64 * sq
-    norms2, stats2 = kernels.col_norms_sw(_dev(A64, dt), _dev(w))
+    norms2, stats2 = kernels.col_norms_sw(Ad, _dev(w))
     assert np.array_equal(norms2.cpu().numpy(), got) and np.array_equal(stats2.cpu().numpy(), st)
-    ones, so = kernels.col_norms_sw(_dev(A64, dt), _dev(np.ones(m, dtype=dt)))
-    base, sb = kernels.col_norms(_dev(A64, dt))
+    ones, so = kernels.col_norms_sw(Ad, _dev(np.ones(m, dtype=dt)))
+    base, sb = kernels.col_norms(Ad)
     assert np.array_equal(ones.cpu().numpy(), base.cpu().numpy()) and np.array_equal(so.cpu().numpy(), sb.cpu().numpy())
 
 

@@ -7,12 +7,18 @@ the path over mu and the refusals. Reference: tests/screen_ref.py.
    (m + 1) u64, the root halves it and rounds once: (m + 2) eps64 / 2 relative, u64 = eps64 / 2, so
    the bar has a factor 2 in hand; the input's rounding adds eps32 / 2 relative for float32. The
    maximum is that of the returned norms, bit for bit; the sum of squares is within
-   (m + n + 2) eps64 relative.
+   (m + n + 2) eps64 relative. Both bars are functions of the shape, so they hold as they stand past
+   the grid's cap of 1024 column blocks (n = 262214: a second column for 70 lanes, one trip more) and
+   at 64 slabs (m = 4097).
 2. The screen step (glx.kernels.screen_step) on synthetic norms with margins set by construction:
    row i sits at lhs_i = mu (1 + sign_i d_i), d_i in [1e-6, 0.5], so the GPU's three roundings in
    double (~4e-16 relative) cannot flip it; at most 8 rows are placed within one ulp of the
-   threshold and are exempt from the mask comparison (only they may differ).
+   threshold and are exempt from the mask comparison (only they may differ). n = 16385 and 16449
+   give the list builder's threads two ballot words each (the last ones one or none), n = 262209 a
+   second trip of two waves past the 1024-workgroup cap and 17 words a thread.
 3. The gather (glx.kernels.gather_cols): bit-equal to A[:, idx], pad columns exactly 0, canaries.
+   m = 1030 and 5123 at 64 destination columns make the 1024 row walkers read a second row and a
+   whole unrolled group of four; wp = 576 / 1088 give a second block of column groups.
 4. Whole solves against a reference solved to rel_gap <= 1e-12 (screen_ref.reference_solution).
    Slack of the objective comparisons: the reference's own gap plus screen_ref.primal_bar, the
    rounding of a primal value composed from a record in A's dtype (the guard's item 2).
@@ -47,28 +53,42 @@ def _dev(a, dtype=None):
 
 
 # ------------------------------------------------------------------------------------------ 1
+def _col_norms_case(dt, m, n, g):
+    from glx import kernels
+    A64 = g.standard_normal((m, n))
+    A64[:, n // 2] *= 1e-3
+    if n > 2:
+        A64[:, 1] = 0.0
+    want = sr.col_norms(A64)
+    Ad = _dev(A64, dt)
+    norms, stats = kernels.col_norms(Ad)
+    got = norms.cpu().numpy()
+    st = stats.cpu().numpy()
+    bar = ((m + 2) * EPS64 / 2 + (sr.EPS32 / 2 if dt == np.float32 else 0.0)) * want
+    err = np.abs(got.astype(sr.LD) - want)
+    assert np.all(err <= bar), (m, n, float(np.max(err / np.maximum(bar, 1e-300))))
+    assert st[0] == got.max()
+    sq = float(np.sum(got.astype(sr.LD) ** 2))
+    assert abs(st[1] - sq) <= (m + n + 2) * EPS64 * sq
+    norms2, stats2 = kernels.col_norms(Ad)
+    assert np.array_equal(norms2.cpu().numpy(), got) and np.array_equal(stats2.cpu().numpy(), st)
+
+
 @pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
 def test_col_norms(dt):
-    from glx import kernels
     g = np.random.default_rng(11)
     shapes = [(m, n) for m in (1, 63, 64, 257) for n in (1, 63, 64, 65, 200)] + [(130, 600)]
     for m, n in shapes:
-        A64 = g.standard_normal((m, n))
-        A64[:, n // 2] *= 1e-3
-        if n > 2:
-            A64[:, 1] = 0.0
-        want = sr.col_norms(A64)
-        norms, stats = kernels.col_norms(_dev(A64, dt))
-        got = norms.cpu().numpy()
-        st = stats.cpu().numpy()
-        bar = ((m + 2) * EPS64 / 2 + (sr.EPS32 / 2 if dt == np.float32 else 0.0)) * want
-        err = np.abs(got.astype(sr.LD) - want)
-        assert np.all(err <= bar), (m, n, float(np.max(err / np.maximum(bar, 1e-300))))
-        assert st[0] == got.max()
-        sq = float(np.sum(got.astype(sr.LD) ** 2))
-        assert abs(st[1] - sq) <= (m + n + 2) * EPS64 * sq
-        norms2, stats2 = kernels.col_norms(_dev(A64, dt))
-        assert np.array_equal(norms2.cpu().numpy(), got) and np.array_equal(stats2.cpu().numpy(), st)
+        _col_norms_case(dt, m, n, g)
+
+
+# (m, 262214): 70 columns past the 1024-workgroup cap, so the first 70 lanes of workgroup 0 walk a
+# second column, in one slab (m = 3) and in three (m = 130); (4097, 70): 64 slabs of 65 rows, the last
+# of two. The bars are those of test 1: they grow with m, and the stats' with m + n.
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
+@pytest.mark.parametrize("m,n", [(3, 262214), (130, 262214), (4097, 70)])
+def test_col_norms_several_trips(m, n, dt):
+    _col_norms_case(dt, m, n, np.random.default_rng(11 + m + n))
 
 
 def test_col_norms_nan_reaches_the_maximum():
@@ -126,7 +146,9 @@ def _check_list(out, n):
     return mask.astype(bool)
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 1000, 4097])
+# (16385 and 16449: the list builder's 256 threads take two ballot words each, the last ones one or
+# none; 262209: past the 1024-workgroup cap, two waves make a second trip, and 17 words a thread)
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1000, 4097, 16385, 16449, 262209])
 def test_screen_step(n):
     from glx import kernels
     for kind in ("random", "all", "none", "one"):
@@ -163,38 +185,55 @@ def _padded(idx):
     return out
 
 
+def _gather_case(g, dt, aligned, m, sw, kept):
+    from glx import kernels
+    torch = _torch()
+    tdt = torch.float64 if dt == np.float64 else torch.float32
+    canary = -7.25
+    A = g.standard_normal((m, sw)).astype(dt)
+    Ad = _dev(A)
+    idx = np.sort(g.choice(sw, size=kept, replace=False)).astype(np.int32)
+    pidx = _padded(idx)
+    wp = len(pidx)
+    off = 0 if aligned else 1
+    flat = torch.full((off + m * wp + 64,), canary, dtype=tdt, device="cuda")
+    out = flat[off: off + m * wp].view(m, wp)
+    kernels.gather_cols(Ad, _dev(pidx), out=out)
+    got = flat.cpu().numpy()
+    body = got[off: off + m * wp].reshape(m, wp)
+    assert np.array_equal(body[:, :kept], A[:, idx]), (m, sw, kept)
+    assert np.all(body[:, kept:] == 0) and not np.any(np.signbit(body[:, kept:]))
+    assert np.all(got[:off] == canary) and np.all(got[off + m * wp:] == canary)
+    if kept >= 63:   # second generation: buffer to buffer, a list of the first one's columns
+        idx2 = np.sort(g.choice(kept, size=kept // 2, replace=False)).astype(np.int32)
+        p2 = _padded(idx2)
+        src = out.contiguous()
+        got2 = kernels.gather_cols(src, _dev(p2)).cpu().numpy()
+        assert np.array_equal(got2[:, : len(idx2)], A[:, idx[idx2]])
+        assert np.all(got2[:, len(idx2):] == 0)
+
+
+# A row walk: wp = 64 is one block of column groups and 1024 row walkers, so at m = 1030 six of
+# them read a second row and at m = 5123 each reads five or six (one unrolled group of four, then the
+# rest). Two blocks of column groups: a thread stores 16 bytes where dst is aligned and one value
+# elsewhere, so wp = 576 (f64, 2 a thread) / 1088 (f32, 4 a thread; f64 unaligned: 5 blocks), the
+# second block partly past wp.
+GATHER_LARGE = {(np.float64, True): [(1030, 100, 60), (5123, 100, 60), (830, 1200, 570)],
+                (np.float64, False): [(1030, 100, 60), (5123, 100, 60), (830, 1200, 1080)],
+                (np.float32, True): [(1030, 100, 60), (5123, 100, 60), (830, 1200, 1080)],
+                (np.float32, False): [(1030, 100, 60), (5123, 100, 60)]}
+
+
 @pytest.mark.parametrize("dt", [np.float64, np.float32], ids=["f64", "f32"])
 @pytest.mark.parametrize("aligned", [True, False], ids=["16B", "unaligned"])
 def test_gather_cols(dt, aligned):
-    from glx import kernels
-    torch = _torch()
     g = np.random.default_rng(3)
-    tdt = torch.float64 if dt == np.float64 else torch.float32
-    canary = -7.25
     for m in (1, 17, 256):
         for sw in (65, 512):
-            A = g.standard_normal((m, sw)).astype(dt)
-            Ad = _dev(A)
             for kept in (0, 1, 63, 64, 65):
-                idx = np.sort(g.choice(sw, size=kept, replace=False)).astype(np.int32)
-                pidx = _padded(idx)
-                wp = len(pidx)
-                off = 0 if aligned else 1
-                flat = torch.full((off + m * wp + 64,), canary, dtype=tdt, device="cuda")
-                out = flat[off: off + m * wp].view(m, wp)
-                kernels.gather_cols(Ad, _dev(pidx), out=out)
-                got = flat.cpu().numpy()
-                body = got[off: off + m * wp].reshape(m, wp)
-                assert np.array_equal(body[:, :kept], A[:, idx]), (m, sw, kept)
-                assert np.all(body[:, kept:] == 0) and not np.any(np.signbit(body[:, kept:]))
-                assert np.all(got[:off] == canary) and np.all(got[off + m * wp:] == canary)
-                if kept >= 63:   # second generation: buffer to buffer, a list of the first one's columns
-                    idx2 = np.sort(g.choice(kept, size=kept // 2, replace=False)).astype(np.int32)
-                    p2 = _padded(idx2)
-                    src = out.contiguous()
-                    got2 = kernels.gather_cols(src, _dev(p2)).cpu().numpy()
-                    assert np.array_equal(got2[:, : len(idx2)], A[:, idx[idx2]])
-                    assert np.all(got2[:, len(idx2):] == 0)
+                _gather_case(g, dt, aligned, m, sw, kept)
+    for m, sw, kept in GATHER_LARGE[(dt, aligned)]:
+        _gather_case(g, dt, aligned, m, sw, kept)
 
 
 # ------------------------------------------------------------------------------------------ 4

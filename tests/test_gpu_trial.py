@@ -28,8 +28,9 @@ Bars, with eps = the kernel type's machine epsilon (none is fitted to the kernel
                squares, their <= 11 additions and the root); FISTA the same with xc - y for G_t
                (B_d = B + eps |xc - y|), FGD's smoothed norm with sqrt(||xc_i||^2 + delta^2) for
                ||p_i||. Each plus CSUM eps64 sum|term| for the fp64 accumulation (at most CSUM = 32
-               additions deep at these shapes: 8 per thread, 8 levels in the workgroup, 12 over the
-               workgroup partials).
+               additions deep at one trip: 8 per thread, 8 levels in the workgroup, 12 over the
+               workgroup partials). A thread adds up to 8 more terms in every further trip of its
+               workgroup, so the several-trip cases take CSUM + 8 (trips - 1): 40 at their two trips.
   max |p|      equal to the maximum of the returned p exactly; NaN when a NaN row is present.
 Discrete outputs (pthr, e / ec, the row masks, every column-bitmap word including the padding
 groups in [ceil16(n), npad), the two counts) are compared exactly outside an ambiguity set: the
@@ -44,15 +45,30 @@ NaN would turn three of the sums into NaN, so each case runs twice: with a finit
 the NaN (all the bars above), and with the NaN (every other row bit-identical to the first run,
 the row itself NaN, the sums NaN, the counts exact).
 
+The row kernels' cases by layout. A row of l values is held by LPR lanes with EPL values each
+(dispatch_row: LPR = the power of two >= l up to 16, then EPL = ceil(l / 16) at LPR 16), so the l of
+test_row_kernels select (LPR, EPL) =
+  l = 1 (1, 1)   2 (2, 1)   3 (4, 1)   5, 8 (8, 1)   16 (16, 1)   17, 32 (16, 2)   40 (16, 3)
+  64 (16, 4)   72 (16, 5)   88 (16, 6)   104 (16, 7)   128 (16, 8)
+which is every instantiation; 3, 5, 17, 40, 72, 88 and 104 leave lanes or a row's last elements
+without a value. test_replicated_halves_match_row_kernels runs k_trial_split at (4, 1) and at every
+(16, EPL). All of those are one trip of at most 63 workgroups. test_row_kernels_several_trips runs
+(l, n) = (1, 131077), (2, 65541), (3, 32771), (8, 16389), (16, 8200), (128, 8200): LPR 1, 2, 4, 8 and
+LPR 16 at EPL 1 and 8, each 5 to 8 rows past the 512 * 256 / LPR rows that the capped grid of 512
+workgroups takes in one trip, so two trips, the second ragged, and the rows on both sides of the
+boundary bit-identical to a launch of their own (test_split_candidate_outputs makes the same two
+trips at n = 8200 for the split outputs).
+
 Measured on an MI355X, worst error / bound over all cases of this file (f64, f32); the module
 prints the table and the ambiguity sets' sizes when its tests are over (pytest -s):
-  p            0.130  0.128      xc           0.130  0.128      z            0.131  0.131
-  vnext        0.421  0.425      ynext        0.301  0.296      G (form 1)   0.0044 0.0104
+  p            0.131  0.130      xc           0.136  0.130      z            0.140  0.140
+  vnext        0.432  0.427      ynext        0.301  0.296      G (form 1)   0.0044 0.0104
   sum g*Gt     0.0190 0.0283     sum Gt^2     0.0189 0.0271     sum |p_i|    0.0280 0.0176
   sum g*d      0.0286 0.0293     sum d^2      0.0239 0.0268     sum |xc_i|   0.0280 0.0168
-  sum smooth   0.0157 0.0094
+  sum smooth   0.0182 0.0094
 None is above 1 and none below 1e-3, so the constants stand as derived. Ambiguity sets: 0 members
-in every case (largest set 0 over all references built).
+in every case (largest set 0 over the 1248 references built; a several-trip case takes the first of
+its seeds whose set, counted on the CPU from the reference alone, is empty).
 
 What a one-line slip would trip (each tried on a NumPy model of the kernels' arithmetic put in
 place of the library, never as device code):
@@ -81,6 +97,12 @@ THETA, THETA_NEXT, DELTA = 2.0 / 7.0, 2.0 / 8.0, 1e-4
 CSUM = 32
 EPS64 = float(np.finfo(np.float64).eps)
 MAX_AMBIGUOUS = 4
+# l -> (lanes per row, elements per lane) of dispatch_row: 1 (1, 1), 2 (2, 1), 3 (4, 1), 5 and 8
+# (8, 1), 16 (16, 1), 17 and 32 (16, 2), 40 (16, 3), 64 (16, 4), 72 (16, 5), 88 (16, 6), 104 (16, 7),
+# 128 (16, 8); 3, 5, 17, 40, 72, 88 and 104 leave lanes or tail elements of a row without a value
+ROW_LS = [1, 2, 3, 5, 8, 16, 17, 32, 40, 64, 72, 88, 104, 128]
+# one n past a single trip of 512 workgroups (512 * 256 / LPR rows) per lanes-per-row layout
+MULTI_TRIP = [(1, 131077), (2, 65541), (3, 32771), (8, 16389), (16, 8200), (128, 8200)]
 
 # worst error / bound per (output, dtype) and the ambiguity sets' sizes, printed when the module's
 # tests are over (pytest -s)
@@ -175,7 +197,7 @@ def _ambiguous(p, w, nrm, mag, th, tmu, eps, prox=True):
     return amb_e, amb_r
 
 
-def ref_proxgd(x, g, t, mu, thres):
+def ref_proxgd(x, g, t, mu, thres, csum=CSUM):
     npdt = x.dtype.type
     C = np.longdouble if npdt is np.float64 else np.float64
     eps = C(np.finfo(npdt).eps)
@@ -201,12 +223,12 @@ def ref_proxgd(x, g, t, mu, thres):
     sums, sbnd = [], []
     for k in range(3):
         sums.append(terms[k].sum())
-        sbnd.append(bnds[k].sum() + CSUM * EPS64 * np.abs(terms[k]).sum() + slack[k][amb_r].sum())
+        sbnd.append(bnds[k].sum() + csum * EPS64 * np.abs(terms[k]).sum() + slack[k][amb_r].sum())
     return dict(p=p, z=z, small=small, ch=ch, B=B, Bz=B + 4 * eps * (np.abs(X) + np.abs(p)),
                 amb_e=amb_e, amb_r=amb_r, sums=sums, sbnd=sbnd, th=th, eps=eps)
 
 
-def ref_fista(y, g, xk, t, mu, thres, theta, theta_next, delta, prox):
+def ref_fista(y, g, xk, t, mu, thres, theta, theta_next, delta, prox, csum=CSUM):
     npdt = y.dtype.type
     C = np.longdouble if npdt is np.float64 else np.float64
     eps = C(np.finfo(npdt).eps)
@@ -249,7 +271,7 @@ def ref_fista(y, g, xk, t, mu, thres, theta, theta_next, delta, prox):
     sums, sbnd = [], []
     for k in range(len(terms)):
         sums.append(terms[k].sum())
-        sbnd.append(bnds[k].sum() + CSUM * EPS64 * np.abs(terms[k]).sum() + slack[k][amb_r].sum())
+        sbnd.append(bnds[k].sum() + csum * EPS64 * np.abs(terms[k]).sum() + slack[k][amb_r].sum())
     return dict(xc=xc, vn=vn, yn=yn, small=small, ch=ch, B=B, Bv=Bv, By=By, amb_e=amb_e, amb_r=amb_r,
                 sums=sums, sbnd=sbnd, th=th, eps=eps)
 
@@ -395,10 +417,12 @@ def run_fista(y, g, xk, mu, **kw):
     return _out_np(_k().trial_fista(_dev(y), _dev(g), _dev(xk), T_STEP, mu, THETA, THETA_NEXT, THRES, DELTA, **kw))
 
 
-def proxgd_case(dtype, x, g, mu, n, emode, nanpos, **kw):
-    """Both variants of one ProxGD case with all its checks; returns the clean run's outputs."""
+def proxgd_case(dtype, x, g, mu, n, emode, nanpos, ref=None, **kw):
+    """Both variants of one ProxGD case with all its checks; returns the clean run's outputs.
+    ref: the reference of (x, g), where the caller has built it already."""
     out = run_proxgd(x, g, mu, emode=emode, **kw)
-    ref = ref_proxgd(x, out["G"] if kw.get("form") == 1 else g, T_STEP, mu, THRES)
+    if ref is None:
+        ref = ref_proxgd(x, out["G"] if kw.get("form") == 1 else g, T_STEP, mu, THRES)
     check_proxgd(dtype, out, ref, n, emode)
     nan = run_proxgd(_with_nan(x, nanpos), g, mu, emode=emode, **kw)
     exact = _amb_count(ref) == 0
@@ -407,9 +431,11 @@ def proxgd_case(dtype, x, g, mu, n, emode, nanpos, **kw):
     return out, ref
 
 
-def fista_case(dtype, y, g, xk, mu, n, prox, split, nanpos, **kw):
+def fista_case(dtype, y, g, xk, mu, n, prox, split, nanpos, ref=None, **kw):
     out = run_fista(y, g, xk, mu, prox=prox, split=split, **kw)
-    ref = ref_fista(y, out["G"] if kw.get("form") == 1 else g, xk, T_STEP, mu, THRES, THETA, THETA_NEXT, DELTA, prox)
+    if ref is None:
+        ref = ref_fista(y, out["G"] if kw.get("form") == 1 else g, xk, T_STEP, mu, THRES, THETA, THETA_NEXT, DELTA,
+                        prox)
     check_fista(dtype, out, ref, n, prox, split)
     nan = run_fista(_with_nan(y, nanpos), g, xk, mu, prox=prox, split=split, **kw)
     nsum = 4 if prox else 5
@@ -429,7 +455,7 @@ def fista_case(dtype, y, g, xk, mu, n, prox, split, nanpos, **kw):
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mu", MUS)
 @pytest.mark.parametrize("n", [17, 1000])
-@pytest.mark.parametrize("l", [1, 2, 3, 8, 16, 17, 32, 64, 128])
+@pytest.mark.parametrize("l", ROW_LS)
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 @pytest.mark.parametrize("kind", ["proxgd", "fista", "fgd"])
 def test_row_kernels(kind, dtype, l, n, mu):
@@ -439,6 +465,56 @@ def test_row_kernels(kind, dtype, l, n, mu):
         proxgd_case(dtype, x, g, mu, n, False, nanpos)
     else:
         fista_case(dtype, x, g, xk, mu, n, kind == "fista", False, nanpos)
+
+
+def _lpr(l):
+    lpr = 1
+    while lpr < min(l, 16):
+        lpr *= 2
+    return lpr
+
+
+def _several_trip_inputs(kind, dtype, l, n, mu, csum):
+    """The case's inputs and reference: the first of the seeds 1000 l + n, + 100003, ... whose
+    ambiguity set, counted from the reference alone, is empty (with f32 and 10^5 .. 10^6 elements a
+    seed may leave an element within B of thres)."""
+    for k in range(16):
+        x, g, xk = _gen(n, l, dtype, seed=1000 * l + n + 100003 * k)
+        nanpos = _special_rows(x, g)
+        if kind == "proxgd":
+            ref = ref_proxgd(x, g, T_STEP, mu, THRES, csum=csum)
+        else:
+            ref = ref_fista(x, g, xk, T_STEP, mu, THRES, THETA, THETA_NEXT, DELTA, kind == "fista", csum=csum)
+        if not (ref["amb_e"].any() or ref["amb_r"].any()):
+            return x, g, xk, nanpos, ref
+    raise AssertionError("no seed with an empty ambiguity set")
+
+
+@pytest.mark.parametrize("l,n", MULTI_TRIP)
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("kind", ["proxgd", "fista", "fgd"])
+def test_row_kernels_several_trips(kind, dtype, l, n):
+    """One n past a single trip of the 512-workgroup grid per lanes-per-row layout: the last
+    workgroups make a second, ragged trip (5 to 8 rows). The sums' bars take CSUM + 8 per further
+    trip (a thread adds up to 8 more terms in each). Then the rows on both sides of the trip
+    boundary run again as a case of their own, in one trip: a row's outputs depend on neither n nor
+    the trip, so they come back bit for bit."""
+    per_trip = 512 * 256 // _lpr(l)
+    trips = -(-n // per_trip)
+    assert trips == 2 and 0 < n - per_trip < 256 // _lpr(l)
+    mu = MUS[(l + len(kind)) % 2]
+    x, g, xk, nanpos, ref = _several_trip_inputs(kind, dtype, l, n, mu, CSUM + 8 * (trips - 1))
+    rows = slice(per_trip - 251, n)
+    if kind == "proxgd":
+        out, _ = proxgd_case(dtype, x, g, mu, n, False, nanpos, ref=ref)
+        part = run_proxgd(x[rows].copy(), g[rows].copy(), mu, emode=False)
+        same = ("p", "pthr", "z")
+    else:
+        out, _ = fista_case(dtype, x, g, xk, mu, n, kind == "fista", False, nanpos, ref=ref)
+        part = run_fista(x[rows].copy(), g[rows].copy(), xk[rows].copy(), mu, prox=kind == "fista")
+        same = ("xc", "vnext", "ynext")
+    for key in same:
+        assert _same_bits(out[key][rows], part[key]), key
 
 
 # ---------------------------------------------------------------------------------------------
@@ -591,7 +667,7 @@ def test_fused_epilogue_refuses_inadmissible_plan():
 # replicated halves of the row-sharded schedules (form 2)
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [17, 1000])
-@pytest.mark.parametrize("l", [3, 16, 17, 32, 128])
+@pytest.mark.parametrize("l", [3, 16, 17, 32, 40, 64, 72, 88, 104, 128])
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_replicated_halves_match_row_kernels(dtype, l, n):
     x, g, xk = _gen(n, l, dtype, seed=31 * l + n)
