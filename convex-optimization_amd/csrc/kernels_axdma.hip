@@ -60,6 +60,14 @@ constexpr int dma_lds_bytes() {
 // block's walk are fetched with the default policy instead, about that many MiB of A over the
 // grid, so they stay in the 256 MiB Infinity Cache for the next pass (A^T R).
 
+// a wave-uniform pointer taken to SGPRs
+__device__ inline const char* sgpr_ptr(const char* p) {
+  const uint64_t v = reinterpret_cast<uint64_t>(p);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+  return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);
+}
+
 // A slot swizzle of row i for SLR 16-B slots per row piece
 template <int SLR>
 __device__ inline int dma_sw(int i) { return SLR >= 16 ? (i & 15) : ((i >> 1) & 7); }
@@ -132,27 +140,37 @@ __global__ __launch_bounds__(64 * WAVES) void k_ax_dma(const T* __restrict__ A,
   if (nch <= 0) return;   // block-uniform
 
   // A piece t of this wave: linear slot 64 t + lane of the [16][SLR] image
-  const T* asrc[NIA];
+  // Its source is a wave-uniform base (the wave's first row, the split's first chunk: SGPRs,
+  // advanced per chunk by scalar adds) plus a loop-invariant 32-bit byte offset per lane (the
+  // launcher checks that 16 MT rows fit one), the SGPR-base form of the global load: one VGPR per
+  // piece and no 64-bit vector add per chunk.
+  const int64_t rowb = row0 < m ? row0 : m - 1;
+  const char* const abase = sgpr_ptr(reinterpret_cast<const char*>(A + rowb * n + cb * KC));
+  unsigned aoffs[NIA];
 #pragma unroll
   for (int t = 0; t < NIA; ++t) {
     const int ls = 64 * t + lane, ri = ls / SLR, p = ls % SLR;
     int64_t r = row0 + ri;
     r = r < m ? r : m - 1;
-    asrc[t] = A + r * n + cb * KC + EV * (p ^ dma_sw<SLR>(ri & 15));
+    aoffs[t] = (unsigned)(((r - rowb) * n + EV * (p ^ dma_sw<SLR>(ri & 15))) * ES);
   }
   // X pieces: instruction tx = wave + WAVES r of the block covers the UPI units UPI tx ..
-  const T* xsrc[NIX];
+  // (an instruction lies within one source, so its base is wave-uniform too: as for A)
+  static_assert((KC * NT) % UPI == 0, "an X instruction within one source");
+  const char* xbase[NIX];
+  unsigned xoffs[NIX];
   int xdst[NIX];
 #pragma unroll
   for (int r = 0; r < NIX; ++r) {
     const int tx = wave + WAVES * r;
     const int txc = tx % NXT;                        // surplus: a real piece into the dummy
     const int pu = UPI * txc + lane / LPU;
-    const int src = pu / (KC * NT), u = pu % (KC * NT);
+    const int src = (UPI * txc) / (KC * NT), u = pu % (KC * NT);
     const int k = u / NT;
     const int us = u ^ ((k / EV) & (EV - 1));
     const T* xb = src == 0 ? X0 : (src == 1 ? X1 : X2);
-    xsrc[r] = xb + (cb * KC + us / NT) * L + (us % NT) * 16 + (lane % LPU) * EV;
+    xbase[r] = sgpr_ptr(reinterpret_cast<const char*>(xb + cb * KC * L));
+    xoffs[r] = (unsigned)(((us / NT) * L + (us % NT) * 16 + (lane % LPU) * EV) * ES);
     xdst[r] = tx < NXT ? WAVES * AW + tx * 1024 : -1;
   }
   const int64_t rot = ax_rot(xmap, bx, gx, nch);
@@ -161,22 +179,36 @@ __global__ __launch_bounds__(64 * WAVES) void k_ax_dma(const T* __restrict__ A,
     const int64_t kb = (int64_t)keep_mib << 20;
     if (kb > 0) kt = nch - kb / ((int64_t)gridDim.x * WAVES * AW);
   }
-  auto issue = [&](int64_t c, int slot) {
+  // walk step j loads A non-temporally while its (clamped) chunk lies below kt: block-uniform
+  auto step_nt = [&](int64_t j) -> bool { return NTL && (j < nch ? j : nch - 1) < kt; };
+  // the NI DMAs of walk step c into ring slot `slot`, A's policy a compile-time argument (one
+  // basic block: the pipelined loop's sched_group_barrier sequence places every one of them)
+  auto issue_as = [&](auto ntp, int64_t c, int slot) {
+    constexpr bool NTP = decltype(ntp)::value;
     c = c < nch ? c : nch - 1;
-    const bool nt = c < kt;
     c += rot;                            // the walk starts at chunk rot (mod nch)
     c = c >= nch ? c - nch : c;
+    c = __builtin_amdgcn_readfirstlane((int)c);   // a chunk index of the split: fits an int
     char* sb = lds + slot * SLOT;
-    if (NTL && nt) {
+    const char* const ab = abase + c * (KC * ES);
 #pragma unroll
-      for (int t = 0; t < NIA; ++t) glds16<NTL>(asrc[t] + c * KC, sb + wave * AW + t * 1024);
-    } else {
-#pragma unroll
-      for (int t = 0; t < NIA; ++t) glds16<false>(asrc[t] + c * KC, sb + wave * AW + t * 1024);
+    for (int t = 0; t < NIA; ++t) {
+      // (opaque here, so the zero extension stays next to the add and is matched as the load's
+      // 32-bit offset operand instead of being hoisted into a loop-invariant 64-bit pair)
+      unsigned off = aoffs[t];
+      asm("" : "+v"(off));
+      glds16<NTP>(ab + off, sb + wave * AW + t * 1024);
     }
 #pragma unroll
-    for (int r = 0; r < NIX; ++r)
-      glds16<false>(xsrc[r] + c * KC * L, XDUP && xdst[r] < 0 ? lds + NS * SLOT : sb + xdst[r]);
+    for (int r = 0; r < NIX; ++r) {
+      unsigned off = xoffs[r];
+      asm("" : "+v"(off));
+      glds16<false>(xbase[r] + c * (KC * L * ES) + off, XDUP && xdst[r] < 0 ? lds + NS * SLOT : sb + xdst[r]);
+    }
+  };
+  auto issue = [&](int64_t c, int slot) {   // the policy looked up at run time (prologue, flat loop)
+    if (step_nt(c)) issue_as(std::bool_constant<NTL>{}, c, slot);
+    else issue_as(std::false_type{}, c, slot);
   };
 
   C acc[MT][NC];
@@ -260,7 +292,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_ax_dma(const T* __restrict__ A,
   // entry (k, c) the wave issues one broadcast read of p[k][c] from the staged X chunk (source
   // 0 = p), RG ds_read_b64 of A[i + 64 g][k] (the lane's row base plus the uniform k under dma_sw,
   // the row groups 64 rows = an immediate offset apart: conflict-free over 16 rows, two-way over
-  // 32) and accE[g][c - v CPW] += A[i + 64 g][k] p[k][c] in all 64 lanes.
+  // 32) and accE[g][c - v CPW] += A[i + 64 g][k] p[k][c] in all 64 lanes. A chunk's walk runs
+  // inside the MFMA stream of the chunk before it, the two waves of a SIMD at different points
+  // (the pipelined loop below).
   // Order of summation of every (row, column) accumulator: (1) per K split, the block's (rotated)
   // chunk walk; (2) ascending k within a chunk; (3) one rounded multiply and one rounded add per
   // entry (-ffp-contract=off). The finalize sums the S slabs in order and forms
@@ -280,13 +314,15 @@ __global__ __launch_bounds__(64 * WAVES) void k_ax_dma(const T* __restrict__ A,
     if constexpr (!EG) {
       return 0u;
     } else {
-      if (c >= nch) return 0u;
+      const bool in = c < nch;           // branch-free: the clamped word is loaded, 0 selected
+      c = in ? c : nch - 1;
       c += rot;
       c = c >= nch ? c - nch : c;
-      return *reinterpret_cast<const unsigned*>(ecol + (cb + c) * (KC / 16));
+      const unsigned w = *reinterpret_cast<const unsigned*>(ecol + (cb + c) * (KC / 16));
+      return in ? w : 0u;
     }
   };
-  auto ework = [&](int slot, unsigned bits) {
+  auto ework = [&](int slot, unsigned bits) __attribute__((always_inline)) {
     if constexpr (EG) {
       unsigned wd[CPW], any = 0u;
 #pragma unroll
@@ -364,6 +400,16 @@ __global__ __launch_bounds__(64 * WAVES) void k_ax_dma(const T* __restrict__ A,
               for (int nt = 0; nt < NT; ++nt)
                 acc[mt][src * NT + nt] = M::mma(a[mt][j][e], x[j][e][src][nt], acc[mt][src * NT + nt]);
     };
+    // the MFMAs [lo, hi) of a chunk, in mma_ops' order
+    auto mma_range = [&](const V (&a)[MT][JN], const T (&x)[JN][EV][NSRC][NT], auto lo, auto hi) __attribute__((always_inline)) {
+#pragma unroll
+      for (int f = decltype(lo)::value; f < decltype(hi)::value; ++f) {
+        const int nt = f % NT, src = f / NT % NSRC, mt = f / (NT * NSRC) % MT;
+        const int e = f / (NT * NSRC * MT) % EV, j = f / (NT * NSRC * MT * EV);
+        acc[mt][src * NT + nt] = M::mma(a[mt][j][e], x[j][e][src][nt], acc[mt][src * NT + nt]);
+      }
+    };
+    const int epar = (wave >> 2) & 1;   // the two waves of a SIMD (w, w + 4) take the walk at different points
     GLX_CLK(1);
     if constexpr (EG) ebr[0] = ebits(0);
 #pragma unroll
@@ -377,54 +423,110 @@ __global__ __launch_bounds__(64 * WAVES) void k_ax_dma(const T* __restrict__ A,
     if constexpr (EG) ework(0, ebr[0]);   // chunk 0 before the loop's first barrier frees slot 0
     int cs = 1;           // slot of chunk c + 1
     int64_t c = 0;
-    // two chunks per trip so the register sets keep static indices
-    for (; c + 1 < nch; c += 2) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        // chunk c + h + 1 landed everywhere, chunk c + h no longer read by anyone. The builtin
-        // (not inline asm) so that the compiler's own wait insertion knows the operand reads of
-        // the previous iteration are complete and adds no lgkmcnt(0) in front of the MFMAs
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(kWaitVmLgkm0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        const int is = cs == 0 ? NS - 1 : cs - 1;   // slot of chunk c + h = slot of c + h + 1 + D
-        unsigned eb_use = 0u;
-        if constexpr (EG) {   // this step's word (chunk c + h + 1) out, the word of c + h + 2 in
-          eb_use = ebr[h ^ 1];
-          ebr[h] = ebits(c + h + 1 + D);
-        }
-        issue(c + h + 1 + D, is);
-        read_ops(cs, av[h ^ 1], xv[h ^ 1]);         // next chunk's operands ...
-        if constexpr (!HOIST) {
-          __builtin_amdgcn_sched_barrier(0);        // (DMA and reads issue before the MFMAs)
-          mma_ops(av[h], xv[h]);                    // ... in flight behind this chunk's MFMAs
-        } else {
-          // An LDS-DMA issue costs its wave ~60-185 cycles (MI355X_MICROARCH.md constants):
-          // spread the NI DMAs over the first MFMAs (one after each), then the operand reads two
-          // per MFMA, so the issue costs hide under the MFMA pipe instead of delaying it
-          mma_ops(av[h], xv[h]);
-          constexpr int NMF = MT * JN * EV * NSRC * NT;      // MFMAs per chunk and wave
-          constexpr int NRD = MT * JN + JN * EV * NSRC * NT; // operand reads per chunk and wave
-#pragma unroll
-          for (int g = 0; g < NI; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // 1 VMEM read (the DMA)
-          }
-#pragma unroll
-          for (int g = 0; g < (NRD + 1) / 2; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // 2 DS reads
-          }
-          __builtin_amdgcn_sched_group_barrier(0x008, NMF - NI - (NRD + 1) / 2, 0);
-        }
-        if constexpr (EG) {   // behind this chunk's MFMAs: chunk c + h + 1's A e (slot cs)
-          __builtin_amdgcn_sched_barrier(0);
-          if (c + h + 1 < nch) ework(cs, eb_use);
-        }
-        cs = cs + 1 == NS ? 0 : cs + 1;
+    // One step of the walk: chunk c + h in register set h, the DMAs of walk step c + h + 1 + D
+    // issued with A's load policy NTP. h and the policy are compile-time arguments, so the part
+    // from the barrier to the last MFMA is one basic block and HOIST's sched_group_barrier
+    // sequence reaches every DMA (a run-time policy test inside would split the block and leave
+    // all the A pieces in front of the first MFMA).
+    auto step = [&](auto hh, auto ntp, int64_t c) __attribute__((always_inline)) {
+      constexpr int h = decltype(hh)::value;
+      // chunk c + h + 1 landed everywhere, chunk c + h no longer read by anyone. The builtin
+      // (not inline asm) so that the compiler's own wait insertion knows the operand reads of
+      // the previous iteration are complete and adds no lgkmcnt(0) in front of the MFMAs
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_waitcnt(kWaitVmLgkm0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      const int is = cs == 0 ? NS - 1 : cs - 1;   // slot of chunk c + h = slot of c + h + 1 + D
+      unsigned eb_use = 0u;
+      if constexpr (EG) {   // this step's word (chunk c + h + 1) out, the word of c + h + 2 in
+        eb_use = ebr[h ^ 1];
+        ebr[h] = ebits(c + h + 1 + D);
       }
+      issue_as(ntp, c + h + 1 + D, is);
+      read_ops(cs, av[h ^ 1], xv[h ^ 1]);         // next chunk's operands ...
+      if constexpr (!HOIST) {
+        __builtin_amdgcn_sched_barrier(0);        // (DMA and reads issue before the MFMAs)
+        mma_ops(av[h], xv[h]);                    // ... in flight behind this chunk's MFMAs
+      } else if constexpr (EG) {
+        // As below, and chunk c + h + 1's A e (slot cs) goes INTO the MFMA stream, at a different
+        // point for each of the two waves of a SIMD (w and w + 4): while one walks its entries
+        // (LDS latency chains, the wave issues no MFMA) the other still has MFMAs to issue and the
+        // pipe stays busy. Behind the last MFMA both waves walked at once and the pipe idled for
+        // it. The points lie in the last quarter of the stream: the walk's registers (RG + 1
+        // values) then fit into operands of this chunk that are already dead (at l = 32: 256
+        // VGPRs, no scratch; at NMF * 5 / 8 and * 13 / 16 the kernel spilled four).
+        constexpr int NMF = MT * JN * EV * NSRC * NT;
+        constexpr int NRD = MT * JN + JN * EV * NSRC * NT;
+        constexpr int MA = NMF - NMF / 4, MB = NMF - NMF / 8;
+        static_assert(0 < MA && MA < MB && MB < NMF, "MFMAs left behind both walks");
+        const bool walk = c + h + 1 < nch;
+        mma_range(av[h], xv[h], std::integral_constant<int, 0>{}, std::integral_constant<int, MA>{});
+#pragma unroll
+        for (int g = 0; g < NI; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
+          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // 1 VMEM read (the DMA)
+        }
+#pragma unroll
+        for (int g = 0; g < (NRD + 1) / 2; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
+          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // 2 DS reads
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (walk && epar == 0) ework(cs, eb_use);
+        __builtin_amdgcn_sched_barrier(0);
+        mma_range(av[h], xv[h], std::integral_constant<int, MA>{}, std::integral_constant<int, MB>{});
+        __builtin_amdgcn_sched_barrier(0);
+        if (walk && epar != 0) ework(cs, eb_use);
+        __builtin_amdgcn_sched_barrier(0);
+        mma_range(av[h], xv[h], std::integral_constant<int, MB>{}, std::integral_constant<int, NMF>{});
+      } else {
+        // An LDS-DMA issue costs its wave ~60-185 cycles (MI355X_MICROARCH.md constants):
+        // spread the NI DMAs over the first MFMAs (one after each), then the operand reads two
+        // per MFMA, so the issue costs hide under the MFMA pipe instead of delaying it
+        mma_ops(av[h], xv[h]);
+        constexpr int NMF = MT * JN * EV * NSRC * NT;      // MFMAs per chunk and wave
+        constexpr int NRD = MT * JN + JN * EV * NSRC * NT; // operand reads per chunk and wave
+#pragma unroll
+        for (int g = 0; g < NI; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
+          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // 1 VMEM read (the DMA)
+        }
+#pragma unroll
+        for (int g = 0; g < (NRD + 1) / 2; ++g) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
+          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // 2 DS reads
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, NMF - NI - (NRD + 1) / 2, 0);
+      }
+      cs = cs + 1 == NS ? 0 : cs + 1;
+    };
+    // two chunks per trip so the register sets keep static indices
+    auto trip = [&](auto nt0, auto nt1, int64_t c) __attribute__((always_inline)) {
+      step(std::integral_constant<int, 0>{}, nt0, c);
+      step(std::integral_constant<int, 1>{}, nt1, c);
+    };
+    // The walk split by load policy (the hand-off above): trips whose two issues (walk steps
+    // c + 1 + D, c + 2 + D) are both non-temporal, at most one mixed trip, then trips that issue
+    // with the default policy. step_nt is monotone in the step, and c, nch, kt are block-uniform,
+    // so every wave of the block takes the same trips and meets the same barriers.
+    // The trip counts are formed once, on the scalar side: of the ntr = nch / 2 trips, trip i
+    // (c = 2 i) is all non-temporal while step_nt(2 i + 2 + D), i.e. for all of them where
+    // kt >= nch and else for the i with 2 i + 2 + D < kt, floor((kt - 1 - D) / 2) of them.
+    const int ntr = __builtin_amdgcn_readfirstlane((int)(nch >> 1));
+    int n1 = 0, nmix = 0;
+    if constexpr (NTL) {
+      const int64_t below = (kt - 1 - D) >> 1;
+      n1 = kt >= nch ? ntr : (int)(below < 0 ? 0 : (below < ntr ? below : ntr));
+      n1 = __builtin_amdgcn_readfirstlane(n1);
+      nmix = __builtin_amdgcn_readfirstlane(n1 < ntr && step_nt(2 * (int64_t)n1 + 1 + D) ? 1 : 0);
     }
+    for (int i = 0; i < n1; ++i, c += 2) trip(std::true_type{}, std::true_type{}, c);
+    if (nmix != 0) {
+      trip(std::true_type{}, std::false_type{}, c);
+      c += 2;
+    }
+    for (int i = n1 + nmix; i < ntr; ++i, c += 2) trip(std::false_type{}, std::false_type{}, c);
     if (c < nch) mma_ops(av[0], xv[0]);   // odd count: the last chunk is in set 0
     GLX_CLK(2);
   } else {
@@ -482,6 +584,9 @@ static void ax_dma_go(const GemmPlan& p, int S, const T* A, const T* const* X, T
   if constexpr (dma_lds_bytes<T, NT, NSRC, t.slots, t.kc, t.waves, t.mt>() > 160 * 1024) {
     throw Error{GLX_E_INVALID, "A@X: this LDS-DMA tile does not fit (160 KiB of LDS)"};
   } else {
+    // a lane's source offset from its wave's base (up to 16 MT rows of A) is a 32-bit value
+    if ((uint64_t)p.n * (16 * t.mt) * sizeof(T) >= (1ull << 32))
+      throw Error{GLX_E_INVALID, "A@X: rows of A too long for the LDS-DMA tile's 32-bit lane offsets"};
     const int gx = (int)cdiv(p.m, ax_tile_rows(t));
     const int xmap = ax_xmap_flags(p, S);
     const dim3 grid((unsigned)ax_grid(xmap, gx, S) + (pub.host ? 1u : 0u));

@@ -2691,6 +2691,41 @@ int glx_fused_ae_pass(int64_t m, int64_t n, int64_t l, const void* A, const void
   });
 }
 
+int glx_dense_pass_keep(int64_t m, int64_t n, int64_t l, const void* A, const void* p, const uint32_t* zf,
+                        void* P, void* Pe, int keep_mib, int* S_out, int* rotated, void* stream) {
+  return guarded([&] {
+    if (m <= 0 || n <= 0 || l <= 0 || l > kMaxL) throw Error{GLX_E_INVALID, "bad shape"};
+    if (keep_mib < 0) throw Error{GLX_E_INVALID, "keep_mib must be >= 0"};
+    GemmPlan plan = make_plan(8, m, n, l, 0);
+    if (!ax_egat_ok(plan, 8))
+      throw Error{GLX_E_INVALID, "the dense pass with a keep size needs the f64 LDS-DMA tile 92278 as this shape's "
+                                 "one-source plan (" + describe_plan(plan) + ")"};
+    plan.ax_keep_mib = keep_mib;
+    if (S_out) *S_out = ax_split(plan, 1);
+    if (rotated) *rotated = (plan.ax_xmap & 2) != 0 ? 1 : 0;
+    if (P == nullptr) return;   // the query
+    if (!A || !p) throw Error{GLX_E_INVALID, "null argument"};
+    if ((zf == nullptr) != (Pe == nullptr)) throw Error{GLX_E_INVALID, "zf and Pe go together"};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (Pe == nullptr) {   // the plain launch of the same tile
+      const double* xs[3] = {static_cast<const double*>(p), nullptr, nullptr};
+      if (!launch_ax_dma<double>(plan, ax_tile(92278), 1, plan.axb_S[1], static_cast<const double*>(A), xs,
+                                 static_cast<double*>(P), nullptr, 0, st, Pub{}))
+        throw Error{GLX_E_STATE, "dense pass: the plan does not take it"};
+    } else {
+      EGat eg;
+      const int64_t npad = (n + 63) / 64 * 64;   // glx_device.h zf_npad
+      eg.bm = reinterpret_cast<const unsigned short*>(zf + npad);
+      eg.bstride = npad / 16;
+      eg.Pe = Pe;
+      if (!launch_ax_egat<double>(plan, static_cast<const double*>(A), static_cast<const double*>(p),
+                                  static_cast<double*>(P), nullptr, 0, st, Pub{}, eg))
+        throw Error{GLX_E_STATE, "fused A e: the plan does not take it"};
+    }
+    check_launch();
+  });
+}
+
 int glx_trial_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes) {
   return guarded([&] {
     if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "bad dtype"};

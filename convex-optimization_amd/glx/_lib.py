@@ -133,6 +133,8 @@ _SIGS = {
                                          c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "glx_fused_ae_pass": (c_int, [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, POINTER(c_int), POINTER(c_int), c_void_p]),
+    "glx_dense_pass_keep": (c_int, [c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_int, POINTER(c_int), POINTER(c_int), c_void_p]),
     "glx_trial_mask_bytes": (c_int, [c_int64, POINTER(c_size_t)]),
     "glx_trial_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
     "glx_trial_proxgd": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,

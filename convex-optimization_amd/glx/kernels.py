@@ -11,7 +11,7 @@ launch at a time (``glx_descent_step``, ``glx_fgd_gradient``, ``glx_row_stats``,
 Gram kernel and host eigenvalue sweep (``glx_admm_dual_step``, ``glx_admm_primal_step``, ``glx_gram``,
 ``glx_sym_lambda_max``), and the dual ALM solver's inner step and inner loop (``glx_alm_inner_step``,
 ``glx_alm_inner_run``), and the optimality certificate's row terms (``glx_certificate_step``), and
-the split-candidate trial's dense pass with A e fused in, one launch (``glx_fused_ae_pass``), and
+the split-candidate trial's dense pass with A e fused in, one launch (``glx_fused_ae_pass``, ``glx_dense_pass_keep``), and
 the pieces of gap-safe screening (``glx_col_norms``, ``glx_screen_step``, ``glx_gather_cols`` and the
 host-only ``glx_screen_guard``). All
 tensors are contiguous device
@@ -174,6 +174,30 @@ def fused_ae_pass(A: torch.Tensor, p: torch.Tensor, thres: float = 1e-3) -> Dict
                                   _stream(A.device)))
     return {"P": P, "Pe": Pe, "S": int(S.value), "rotated": bool(rot.value), "e": tr["z"],
             "zf": tr["zf"]}
+
+
+def dense_pass_keep(A: torch.Tensor, p: torch.Tensor, keep_mib: int, fused: bool = True,
+                    thres: float = 1e-3) -> Dict[str, object]:
+    """The dense pass of :func:`fused_ae_pass` alone with a given Infinity-Cache keep size
+    (glx_dense_pass_keep): about ``keep_mib`` MiB of A, the last chunks of every block's walk, load
+    with the default policy, the rest non-temporally (0: all non-temporal, as fused_ae_pass).
+    ``fused``: the launch with A e fused in; else the plain launch of the same tile (Pe, e, zf are
+    None). Returns the dict of fused_ae_pass."""
+    m, n = A.shape
+    l = p.shape[1]
+    if A.dtype != torch.float64 or p.dtype != torch.float64:
+        raise ValueError("float64 required")
+    S, rot = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().glx_dense_pass_keep(m, n, l, None, None, None, None, None, int(keep_mib),
+                                    ctypes.byref(S), ctypes.byref(rot), None))
+    tr = trial_proxgd(p, None, 1.0, 0.0, thres=thres, form=2, emode=True, p=p) if fused else None
+    P = torch.full((S.value, m, l), float("nan"), dtype=A.dtype, device=A.device)
+    Pe = torch.full((S.value, m, l), float("nan"), dtype=A.dtype, device=A.device) if fused else None
+    check(lib().glx_dense_pass_keep(m, n, l, A.data_ptr(), p.data_ptr(),
+                                    tr["zf"].data_ptr() if fused else None, P.data_ptr(), _ptr(Pe),
+                                    int(keep_mib), ctypes.byref(S), ctypes.byref(rot), _stream(A.device)))
+    return {"P": P, "Pe": Pe, "S": int(S.value), "rotated": bool(rot.value),
+            "e": tr["z"] if fused else None, "zf": tr["zf"] if fused else None}
 
 
 def trial_mask_words(n: int) -> int:

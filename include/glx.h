@@ -274,6 +274,15 @@ int glx_flagged_rows_product(int dtype, int64_t m, int64_t n, int64_t l, const v
  * per entry. */
 int glx_fused_ae_pass(int64_t m, int64_t n, int64_t l, const void* A, const void* p,
                       const uint32_t* zf, void* P, void* Pe, int* S, int* rotated, void* stream);
+/* The same dense pass alone with a given Infinity-Cache keep size (test surface): the arguments of
+ * glx_fused_ae_pass plus keep_mib >= 0, the plan's ax_keep_mib (the solver's GLX_AX_KEEP_MIB; 0 = every
+ * chunk of A non-temporal, as glx_fused_ae_pass plans). About keep_mib MiB of A over the grid, the
+ * last chunks of every block's walk, load with the default policy; the results do not depend on it.
+ * zf and Pe may both be NULL: the plain launch of the same tile (A p only). With P NULL nothing is
+ * launched and only *S and *rotated are set. */
+int glx_dense_pass_keep(int64_t m, int64_t n, int64_t l, const void* A, const void* p,
+                        const uint32_t* zf, void* P, void* Pe, int keep_mib, int* S, int* rotated,
+                        void* stream);
 /* ---- the line-search trial, one kernel at a time (test surface) ----
  * The other half of an iteration: prox, hard threshold, the Armijo / backtracking sums, and in
  * the split-candidate form the masks of e and the column bitmaps the A e gather walks. Both
