@@ -244,6 +244,23 @@ void admm_solve(const glx_problem& P, const T* K, const glx_admm_opts& O, void* 
   res->stats[1] = fused ? 1.0 : 0.0;     // the row step ran in the A^T z epilogue
 }
 
+
+// the workspace of the glue-kernel entries: the reduction's partials and its arrival tickets
+Red glue_red(void* ws, size_t wsb, void* sums_dev, hipStream_t st) {
+  Carver c(ws);
+  double* part = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals * kMaxBlocks));
+  unsigned* ticket = static_cast<unsigned*>(c.take(kTicketBytes));
+  if (!ws || wsb < c.off) throw Error{GLX_E_WORKSPACE, "workspace too small"};
+  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_WORKSPACE, "workspace must be 256-byte aligned"};
+  GLX_HIP(hipMemsetAsync(ticket, 0, kTicketBytes, st));
+  return Red{part, ticket, static_cast<double*>(sums_dev)};
+}
+void check_glue(int dtype, int64_t count, int S) {
+  if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+  if (count <= 0) throw Error{GLX_E_INVALID, "needs a positive element count"};
+  if (S < 1) throw Error{GLX_E_INVALID, "needs S >= 1 slabs"};
+}
+
 }  // namespace
 
 // ---- shared with admm_primal.cpp (glx_internal.h, namespace admm) ----
@@ -429,6 +446,31 @@ int glx_admm_dual_step(int dtype, int64_t m, int64_t n, int64_t l, const void* A
     };
     if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
     else go(static_cast<float*>(nullptr));
+    check_launch();
+  });
+}
+
+int glx_admm_rhs(int dtype, int64_t ml, const void* Ax, const void* Au, const void* b, double rho, void* v_out,
+                 void* stream) {
+  return guarded([&] {
+    check_glue(dtype, ml, 1);
+    if (!Ax || !Au || !b || !v_out) throw Error{GLX_E_INVALID, "null argument"};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == GLX_F64) launch_admm_v<double>((const double*)Ax, (const double*)Au, (const double*)b, (double*)v_out, ml, rho, st);
+    else launch_admm_v<float>((const float*)Ax, (const float*)Au, (const float*)b, (float*)v_out, ml, rho, st);
+    check_launch();
+  });
+}
+
+int glx_admm_fin(int dtype, int64_t ml, int S, const void* P, const void* b, void* Ax, void* Au, void* s,
+                 void* sums_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_glue(dtype, ml, S);
+    if (!P || !b || !Ax || !Au || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const Red red = glue_red(ws, wsb, sums_dev, st);
+    if (dtype == GLX_F64) launch_admm_fin<double>((const double*)P, S, (const double*)b, (double*)Ax, (double*)Au, (double*)s, ml, red, st);
+    else launch_admm_fin<float>((const float*)P, S, (const float*)b, (float*)Ax, (float*)Au, (float*)s, ml, red, st);
     check_launch();
   });
 }

@@ -256,6 +256,23 @@ void primal_solve(const glx_problem& P, const T* K, const T* ATb, const T* AATb,
   res->stats[1] = wb ? 2.0 : 1.0;        // the resolved form
 }
 
+
+// the workspace of the glue-kernel entries: the reduction's partials and its arrival tickets
+Red glue_red(void* ws, size_t wsb, void* sums_dev, hipStream_t st) {
+  Carver c(ws);
+  double* part = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals * kMaxBlocks));
+  unsigned* ticket = static_cast<unsigned*>(c.take(kTicketBytes));
+  if (!ws || wsb < c.off) throw Error{GLX_E_WORKSPACE, "workspace too small"};
+  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_WORKSPACE, "workspace must be 256-byte aligned"};
+  GLX_HIP(hipMemsetAsync(ticket, 0, kTicketBytes, st));
+  return Red{part, ticket, static_cast<double*>(sums_dev)};
+}
+void check_glue(int dtype, int64_t count, int S) {
+  if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+  if (count <= 0) throw Error{GLX_E_INVALID, "needs a positive element count"};
+  if (S < 1) throw Error{GLX_E_INVALID, "needs S >= 1 slabs"};
+}
+
 }  // namespace
 }  // namespace glx
 
@@ -353,6 +370,34 @@ int glx_admm_primal_step(int dtype, int64_t n, int64_t l, int form, int S, const
     };
     if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
     else go(static_cast<float*>(nullptr));
+    check_launch();
+  });
+}
+
+int glx_admm_primal_rhs(int dtype, int64_t nl, const void* ATb, const void* x, const void* z, double rho,
+                        void* w_out, void* stream) {
+  return guarded([&] {
+    check_glue(dtype, nl, 1);
+    if (!ATb || !x || !z || !w_out) throw Error{GLX_E_INVALID, "null argument"};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (dtype == GLX_F64) launch_admm_primal_w<double>((const double*)ATb, (const double*)x, (const double*)z, (double*)w_out, nl, rho, st);
+    else launch_admm_primal_w<float>((const float*)ATb, (const float*)x, (const float*)z, (float*)w_out, nl, rho, st);
+    check_launch();
+  });
+}
+
+int glx_admm_primal_fin(int dtype, int64_t ml, int S, const void* P, const void* b, const void* AATb, double rho,
+                        void* Ax, void* Az, void* v, void* sums_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_glue(dtype, ml, S);
+    if (!P || !b || !Ax || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
+    if (AATb && (!Az || !v)) throw Error{GLX_E_INVALID, "the Woodbury half (AATb given) writes Az and v"};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const Red red = glue_red(ws, wsb, sums_dev, st);
+    if (dtype == GLX_F64)
+      launch_admm_primal_fin<double>((const double*)P, S, (const double*)b, (const double*)AATb, (double*)Ax, (double*)Az, (double*)v, ml, rho, red, st);
+    else
+      launch_admm_primal_fin<float>((const float*)P, S, (const float*)b, (const float*)AATb, (float*)Ax, (float*)Az, (float*)v, ml, rho, red, st);
     check_launch();
   });
 }

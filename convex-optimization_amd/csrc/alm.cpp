@@ -314,6 +314,23 @@ size_t inner_ws(const InnerPlan& p, int64_t n, int64_t l, void* base, InnerWs* o
   return c.off + 256;
 }
 
+
+// the workspace of the glue-kernel entries: the reduction's partials and its arrival tickets
+Red glue_red(void* ws, size_t wsb, void* sums_dev, hipStream_t st) {
+  Carver c(ws);
+  double* part = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals * kMaxBlocks));
+  unsigned* ticket = static_cast<unsigned*>(c.take(kTicketBytes));
+  if (!ws || wsb < c.off) throw Error{GLX_E_WORKSPACE, "workspace too small"};
+  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_WORKSPACE, "workspace must be 256-byte aligned"};
+  GLX_HIP(hipMemsetAsync(ticket, 0, kTicketBytes, st));
+  return Red{part, ticket, static_cast<double*>(sums_dev)};
+}
+void check_glue(int dtype, int64_t count, int S) {
+  check_f64(dtype);
+  if (count <= 0) throw Error{GLX_E_INVALID, "needs a positive element count"};
+  if (S < 1) throw Error{GLX_E_INVALID, "needs S >= 1 slabs"};
+}
+
 }  // namespace
 }  // namespace glx
 
@@ -425,6 +442,30 @@ int glx_alm_inner_run(int dtype, int64_t n, int64_t l, const void* Qn, const voi
     hipStream_t st = static_cast<hipStream_t>(stream);
     GLX_HIP(hipMemsetAsync(w.pcnt, 0, sizeof(unsigned) * (n / 64 + 64), st));
     inner_loop(pl, use_fused(pl, fused), (const double*)Qn, (const double*)J, (double*)u_out, w, n, l, iters, t, mu, st);
+    check_launch();
+  });
+}
+
+int glx_alm_j(int dtype, int64_t nl, int S, const void* h, const void* x, double rho, void* J_out, void* stream) {
+  return guarded([&] {
+    check_glue(dtype, nl, S);
+    if (!h || !x || !J_out) throw Error{GLX_E_INVALID, "null argument"};
+    if (!(rho > 0.0)) throw Error{GLX_E_INVALID, "rho must be positive"};
+    launch_alm_j<double>((const double*)h, S, (const double*)x, (double*)J_out, nl, rho, static_cast<hipStream_t>(stream));
+    check_launch();
+  });
+}
+
+int glx_alm_x(int dtype, int64_t n, int64_t l, int S, const void* x, const void* u, const void* g, double taurho,
+              void* x_out, void* r_out, void* sums_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_glue(dtype, n, S);
+    if (l < 1 || l > admm::kMaxL) throw Error{GLX_E_INVALID, "the dual ALM x update takes 1 <= l <= 32"};
+    if (!x || !u || !g || !x_out || !r_out || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const Red red = glue_red(ws, wsb, sums_dev, st);
+    launch_alm_x<double>((const double*)x, (const double*)u, (const double*)g, S, (double*)x_out, (double*)r_out, n, l,
+                         taurho, red, st);
     check_launch();
   });
 }

@@ -207,6 +207,16 @@ _SIGS = {
                                    c_void_p, c_void_p, c_size_t, c_void_p]),
     "glx_alm_inner_run": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_double, c_double,
                                   c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_admm_rhs": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
+    "glx_admm_fin": (c_int, [c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_admm_primal_rhs": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
+                                    c_void_p]),
+    "glx_admm_primal_fin": (c_int, [c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_alm_j": (c_int, [c_int, c_int64, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p]),
+    "glx_alm_x": (c_int, [c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
+                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "glx_certificate_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
     "glx_certificate_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_char_p, c_size_t]),
     "glx_certificate": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double,

@@ -10,7 +10,8 @@ launch at a time (``glx_descent_step``, ``glx_fgd_gradient``, ``glx_row_stats``,
 ``glx_threshold``, ``glx_thr_combine``, ``glx_descent_pass``), and the dual ADMM solver's row step,
 Gram kernel and host eigenvalue sweep (``glx_admm_dual_step``, ``glx_admm_primal_step``, ``glx_gram``,
 ``glx_sym_lambda_max``), and the dual ALM solver's inner step and inner loop (``glx_alm_inner_step``,
-``glx_alm_inner_run``), and the optimality certificate's row terms (``glx_certificate_step``), and
+``glx_alm_inner_run``), and the three splitting solvers' glue kernels (``glx_admm_rhs``, ``glx_admm_fin``,
+``glx_admm_primal_rhs``, ``glx_admm_primal_fin``, ``glx_alm_j``, ``glx_alm_x``), and the optimality certificate's row terms (``glx_certificate_step``), and
 the split-candidate trial's dense pass with A e fused in, one launch (``glx_fused_ae_pass``, ``glx_dense_pass_keep``), and
 the pieces of gap-safe screening (``glx_col_norms``, ``glx_screen_step``, ``glx_gather_cols`` and the
 host-only ``glx_screen_guard``). All
@@ -608,6 +609,106 @@ def alm_inner_run(Qn: torch.Tensor, J: torch.Tensor, iters: int, t: float, mu: f
     check(lib().glx_alm_inner_run(dt, n, l, Qn.data_ptr(), J.data_ptr(), int(iters), float(t), float(mu),
                                   int(fused), u.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
     return u
+
+
+def _flat_slabs(P: torch.Tensor, count: int, sources: int = 1) -> int:
+    """S of a contiguous tensor of sources * S slabs of ``count`` values each."""
+    if not P.is_contiguous() or P.numel() % (sources * count) != 0 or P.numel() == 0:
+        raise ValueError("slabs must be contiguous, %d x S x %d values" % (sources, count))
+    return P.numel() // (sources * count)
+
+
+def admm_rhs(Ax: torch.Tensor, Au: torch.Tensor, b: torch.Tensor, rho: float) -> torch.Tensor:
+    """v = (Ax - rho Au) - b in one launch (glx_admm_rhs, k_admm_v). ``Au`` may be ``Ax`` itself."""
+    v = torch.full_like(b, float("nan"))
+    check(lib().glx_admm_rhs(_dt(b), b.numel(), Ax.data_ptr(), Au.data_ptr(), b.data_ptr(), float(rho),
+                             v.data_ptr(), _stream(b.device)))
+    return v
+
+
+def admm_fin(P: torch.Tensor, b: torch.Tensor, Au: torch.Tensor, s: "Optional[torch.Tensor] | bool" = True
+             ) -> Dict[str, Optional[torch.Tensor]]:
+    """The dual ADMM finalize in one launch (glx_admm_fin, k_admm_fin). ``P`` holds 2 S slabs of
+    b.numel() values, the first source's S then the second's; ``Au`` is the previous A u (read, not
+    modified: the kernel works on a copy). ``s``: True allocates it (NaN-filled), None / False passes
+    NULL, a tensor is written in place. Returns {"Ax", "Au", "s", "sums"} with
+    sums = [sum (Ax - b)^2] (float64)."""
+    ml = b.numel()
+    S = _flat_slabs(P, ml, 2)
+    dev = b.device
+    Ax = torch.full_like(b, float("nan"))
+    Au_io = Au.clone()
+    if s is True:
+        s = torch.full_like(b, float("nan"))
+    elif s is False:
+        s = None
+    sums = _nan_sums(1, dev)
+    ws = _ws(_dt(b), 1, 1, 1, dev)
+    check(lib().glx_admm_fin(_dt(b), ml, S, P.data_ptr(), b.data_ptr(), Ax.data_ptr(), Au_io.data_ptr(), _ptr(s),
+                             sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return {"Ax": Ax, "Au": Au_io, "s": s, "sums": sums}
+
+
+def admm_primal_rhs(ATb: torch.Tensor, x: torch.Tensor, z: torch.Tensor, rho: float) -> torch.Tensor:
+    """w = (ATb - z) + rho x in one launch (glx_admm_primal_rhs, k_admm_primal_w)."""
+    w = torch.full_like(x, float("nan"))
+    check(lib().glx_admm_primal_rhs(_dt(x), x.numel(), ATb.data_ptr(), x.data_ptr(), z.data_ptr(), float(rho),
+                                    w.data_ptr(), _stream(x.device)))
+    return w
+
+
+def admm_primal_fin(P: torch.Tensor, b: torch.Tensor, rho: float, AATb: Optional[torch.Tensor] = None,
+                    Az: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None
+                    ) -> Dict[str, Optional[torch.Tensor]]:
+    """The primal ADMM finalize in one launch (glx_admm_primal_fin, k_admm_primal_fin). ``P`` holds
+    S slabs of b.numel() values (direct: ``AATb`` None) or 2 S (Woodbury: ``AATb`` given, the slabs
+    of A x then those of A z). ``Az`` and ``v`` are NaN-filled unless passed in; without AATb the
+    kernel leaves them as they are. Returns {"Ax", "Az", "v", "sums"}, sums = [sum (Ax - b)^2]."""
+    ml = b.numel()
+    S = _flat_slabs(P, ml, 2 if AATb is not None else 1)
+    dev = b.device
+    Ax = torch.full_like(b, float("nan"))
+    Az = torch.full_like(b, float("nan")) if Az is None else Az
+    v = torch.full_like(b, float("nan")) if v is None else v
+    sums = _nan_sums(1, dev)
+    ws = _ws(_dt(b), 1, 1, 1, dev)
+    check(lib().glx_admm_primal_fin(_dt(b), ml, S, P.data_ptr(), b.data_ptr(), _ptr(AATb), float(rho),
+                                    Ax.data_ptr(), Az.data_ptr(), v.data_ptr(), sums.data_ptr(), ws.data_ptr(),
+                                    ws.numel(), _stream(dev)))
+    return {"Ax": Ax, "Az": Az, "v": v, "sums": sums}
+
+
+def alm_j(h: torch.Tensor, x: torch.Tensor, rho: float) -> torch.Tensor:
+    """J = rho (h - x / rho) in one launch (glx_alm_j, k_alm_j); ``h`` holds S slabs of x.numel()
+    values summed in slab order. float64 only."""
+    S = _flat_slabs(h, x.numel())
+    J = torch.full_like(x, float("nan"))
+    check(lib().glx_alm_j(_dt(x), x.numel(), S, h.data_ptr(), x.data_ptr(), float(rho), J.data_ptr(),
+                          _stream(x.device)))
+    return J
+
+
+def alm_x(x: torch.Tensor, u: torch.Tensor, g: torch.Tensor, taurho: float, in_place: bool = False,
+          x_out: Optional[torch.Tensor] = None, r_out: Optional[torch.Tensor] = None
+          ) -> Dict[str, torch.Tensor]:
+    """The dual ALM x update in one launch (glx_alm_x, k_alm_x): r = u + g, x+ = x - taurho r with
+    ``g`` S slabs of (n, l) summed in slab order. in_place: x+ overwrites a copy of ``x`` handed to
+    the kernel as both x and x_out (the solver's call). Returns {"x", "r", "sums"} with
+    sums = [sum_i ||x+_i||, max |x+|] (float64). float64 only, l <= 32."""
+    n, l = x.shape
+    S = _flat_slabs(g, n * l)
+    dev = x.device
+    if in_place:
+        x = x.clone()
+        xn = x
+    else:
+        xn = torch.full_like(x, float("nan")) if x_out is None else x_out
+    r = torch.full_like(x, float("nan")) if r_out is None else r_out
+    sums = _nan_sums(2, dev)
+    ws = _ws(_dt(x), 1, 1, 1, dev)
+    check(lib().glx_alm_x(_dt(x), n, l, S, x.data_ptr(), u.data_ptr(), g.data_ptr(), float(taurho),
+                          xn.data_ptr(), r.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return {"x": xn, "r": r, "sums": sums}
 
 
 def gram(R: torch.Tensor) -> torch.Tensor:

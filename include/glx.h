@@ -613,6 +613,42 @@ int glx_alm_inner_run(int dtype, int64_t n, int64_t l, const void* Qn, const voi
                       double mu, int fused, void* u_out, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* ---- the glue kernels of the three splitting solvers, one launch each (test surface) ----
+ * The elementwise and finalize kernels between the dense products of glx_admm_dual_solve,
+ * glx_admm_primal_solve and glx_alm_dual_solve. "S slabs" are S arrays of the element count laid end
+ * to end and summed in ascending slab order from slab 0. Scalars are rounded to the dtype first.
+ * The reducing entries take a workspace of glx_kernel_workspace_bytes(dtype, 1, 1, 1) bytes, 256-byte
+ * aligned (GLX_E_WORKSPACE otherwise); sums_dev receives device doubles.
+ *
+ * glx_admm_rhs: v_out = (Ax - rho Au) - b over ml elements (k_admm_v). Ax may be Au (the dual ALM
+ * solver passes Ax twice with rho = 0). */
+int glx_admm_rhs(int dtype, int64_t ml, const void* Ax, const void* Au, const void* b, double rho, void* v_out,
+                 void* stream);
+/* glx_admm_fin (k_admm_fin): P = 2 S slabs of ml values, the first source's S then the second's.
+ * au = the second source's sum; s[i] = Au[i] - au (Au as it was on entry; s may be NULL: not
+ * written), then Ax[i] = the first source's sum, Au[i] = au; sums_dev[0] = sum_i (Ax[i] - b[i])^2,
+ * each square rounded to the dtype and accumulated in double. */
+int glx_admm_fin(int dtype, int64_t ml, int S, const void* P, const void* b, void* Ax, void* Au, void* s,
+                 void* sums_dev, void* workspace, size_t workspace_bytes, void* stream);
+/* glx_admm_primal_rhs: w_out = (ATb - z) + rho x over nl elements (k_admm_primal_w). */
+int glx_admm_primal_rhs(int dtype, int64_t nl, const void* ATb, const void* x, const void* z, double rho,
+                        void* w_out, void* stream);
+/* glx_admm_primal_fin (k_admm_primal_fin): Ax[i] = the sum of the first S slabs of P and
+ * sums_dev[0] = sum_i (Ax[i] - b[i])^2 as above. With AATb given (the Woodbury form) P holds S more
+ * slabs: Az[i] = their sum and v[i] = (AATb[i] - Az[i]) + rho Ax[i]. AATb == NULL: Az and v are not
+ * written (and may be NULL) and P holds S slabs only. */
+int glx_admm_primal_fin(int dtype, int64_t ml, int S, const void* P, const void* b, const void* AATb, double rho,
+                        void* Ax, void* Az, void* v, void* sums_dev, void* workspace, size_t workspace_bytes,
+                        void* stream);
+/* glx_alm_j: J_out = rho (h - x / rho) with h the sum of S slabs of nl values (k_alm_j). GLX_F64 only
+ * (GLX_E_INVALID for GLX_F32), rho > 0. */
+int glx_alm_j(int dtype, int64_t nl, int S, const void* h, const void* x, double rho, void* J_out, void* stream);
+/* glx_alm_x (k_alm_x): r_out = u + g with g the sum of S slabs of n * l values,
+ * x_out = x - taurho r_out (x_out may be x), sums_dev = [sum_i ||x_out_i||, max |x_out|
+ * (NaN-propagating)]. GLX_F64 only; GLX_E_INVALID for l > 32, before anything is written. */
+int glx_alm_x(int dtype, int64_t n, int64_t l, int S, const void* x, const void* u, const void* g, double taurho,
+              void* x_out, void* r_out, void* sums_dev, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- optimality certificate of any iterate (DESIGN.md "Certificate") ----
  * For P(x) = 1/2 ||A x - b||_F^2 + mu sum_i ||x_i||_2 (x_i the rows of the n x l iterate) and its
  * dual D(theta) = -1/2 ||theta||_F^2 - <theta, b> over ||(A^T theta)_i||_2 <= mu: with r = A x - b,
