@@ -128,7 +128,7 @@ void cert_rows(const CertPlan& pl, bool fused, const T* A, const T* R, const T* 
 template <typename T>
 void certificate(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const T* A, const T* X, const T* b,
                  double mu, int fused_opt, T* G, double* rn, double* out, void* ws, hipStream_t st,
-                 const GroupView* grp, const SampleView* sw, double* holdout_sum) {
+                 const GroupView* grp, const SampleView* sw, double* holdout_sum, const InterceptView* ic) {
   CertWs w;
   cert_carve(pl, m, n, l, ws, &w);
   const bool fused = grp == nullptr && use_fused(pl, fused_opt);
@@ -140,7 +140,16 @@ void certificate(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const T* A
   const T* xs[3] = {X, nullptr, nullptr};
   launch_ax<T>(pl.a, 1, A, xs, pa, nullptr, 0, st);
   const bool hold = sw != nullptr && sw->hold != nullptr;
-  if (sw != nullptr) {
+  if (ic != nullptr) {
+    // the intercept eliminated: r^ and its weighted column means, then r = w (r^ - 1 mean^T), the
+    // operand of the A^T pass, and the sums on the centred residual (DESIGN.md "Intercept")
+    const T* wv = sw != nullptr ? static_cast<const T*>(sw->w) : nullptr;
+    T* rh = static_cast<T*>(ic->rhat);
+    GLX_HIP(hipMemsetAsync(ic->cnt, 0, 256, st));
+    launch_cert_csum<T>(pa, ax_split(pl.a, 1), b, wv, rh, m, l, ic->sigma, ic->part, ic->cnt, ic->mean, st);
+    launch_cert_fin_c<T>(rh, b, wv, hold ? static_cast<const T*>(sw->hold) : nullptr, ic->mean, nullptr, r, ml, l,
+                         Red{w.part, w.ticket, hold ? sw->sums : w.rec}, st);
+  } else if (sw != nullptr) {
     // r = w (A x - b), the operand of the A^T pass. Two sums go where k_cert_fin's go; with hold-out
     // weights there are three, which rec + 2 has no room for: they go to sw->sums
     launch_cert_fin_w<T>(pa, ax_split(pl.a, 1), b, static_cast<const T*>(sw->w), static_cast<const T*>(sw->hold),
@@ -159,6 +168,8 @@ void certificate(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const T* A
   double hs[3] = {0.0, 0.0, 0.0};
   GLX_HIP(hipMemcpyAsync(out, w.rec, sizeof(double) * kCertRec, hipMemcpyDeviceToHost, st));
   if (hold) GLX_HIP(hipMemcpyAsync(hs, sw->sums, sizeof hs, hipMemcpyDeviceToHost, st));
+  if (ic != nullptr)
+    GLX_HIP(hipMemcpyAsync(ic->mean_host, ic->mean, sizeof(double) * l, hipMemcpyDeviceToHost, st));
   GLX_HIP(hipStreamSynchronize(st));
   out[7] = fused ? 1.0 : 0.0;
   if (hold) {
@@ -172,10 +183,15 @@ void certificate(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const T* A
 
 void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
                      double mu, int fused, void* G_out, double* rownorm_out, double* out, void* ws, size_t wsb,
-                     void* stream, const GroupView* grp, const SampleView* sw, double* holdout_sum) {
+                     void* stream, const GroupView* grp, const SampleView* sw, double* holdout_sum,
+                     const InterceptView* ic) {
   const CertPlan pl = cert_plan(dtype, m, n, l);
   check_fused(fused);
   if (sw != nullptr && (!sw->w || !sw->sums)) throw Error{GLX_E_INVALID, "sample weights: null vector or sums"};
+  if (ic != nullptr) {
+    check_intercept(ic->sigma, ic->mean_host);
+    if (!ic->rhat || !ic->mean || !ic->part || !ic->cnt) throw Error{GLX_E_INVALID, "intercept: null workspace piece"};
+  }
   if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
   if (!A || !X || !b) throw Error{GLX_E_INVALID, "A, X and b must be device pointers"};
   if (!out) throw Error{GLX_E_INVALID, "null out"};
@@ -186,10 +202,33 @@ void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, 
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (dtype == GLX_F64)
     certificate<double>(pl, m, n, l, (const double*)A, (const double*)X, (const double*)b, mu, fused,
-                        (double*)G_out, rownorm_out, out, ws, st, grp, sw, holdout_sum);
+                        (double*)G_out, rownorm_out, out, ws, st, grp, sw, holdout_sum, ic);
   else
     certificate<float>(pl, m, n, l, (const float*)A, (const float*)X, (const float*)b, mu, fused,
-                       (float*)G_out, rownorm_out, out, ws, st, grp, sw, holdout_sum);
+                       (float*)G_out, rownorm_out, out, ws, st, grp, sw, holdout_sum, ic);
+}
+
+size_t intercept_carve(size_t head, int es, int64_t m, int64_t l, void* base, InterceptView* out) {
+  Carver c(base);
+  InterceptView v;
+  c.take(head);
+  v.rhat = c.take((size_t)es * (size_t)m * (size_t)l);
+  v.mean = static_cast<double*>(c.take(sizeof(double) * (size_t)l));
+  v.part = static_cast<double*>(c.take(cert_csum_part_bytes()));
+  v.cnt = static_cast<unsigned*>(c.take(256));
+  if (out) {
+    out->rhat = v.rhat;
+    out->mean = v.mean;
+    out->part = v.part;
+    out->cnt = v.cnt;
+  }
+  return c.off + 256;
+}
+
+void check_intercept(double weight_sum, const double* intercept_out) {
+  if (!(weight_sum > 0.0) || !std::isfinite(weight_sum))
+    throw Error{GLX_E_INVALID, "intercept: weight_sum must be positive and finite"};
+  if (!intercept_out) throw Error{GLX_E_INVALID, "intercept: null intercept_out"};
 }
 
 void check_sample(const void* sample_w, const void* holdout_w) {
@@ -241,6 +280,54 @@ int glx_certificate_sw(int dtype, int64_t m, int64_t n, int64_t l, const void* A
     sw.sums = reinterpret_cast<double*>(static_cast<char*>(ws) + sample_off(head));
     certificate_run(dtype, m, n, l, A, X, b, mu, fused, G_out, rownorm_out, out, ws, head, stream, nullptr, &sw,
                     holdout_sum);
+  });
+}
+
+/* ---- the unpenalised intercept (DESIGN.md "Intercept"): [the _sw entry's workspace | the centring
+ * finalize's pieces] ---- */
+
+int glx_certificate_ic_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    const CertPlan pl = cert_plan(dtype, m, n, l);
+    *bytes = intercept_carve(sample_bytes(cert_carve(pl, m, n, l, nullptr, nullptr)), pl.es, m, l, nullptr, nullptr);
+  });
+}
+
+int glx_certificate_ic_describe(int dtype, int64_t m, int64_t n, int64_t l, int fused, char* out, size_t cap) {
+  return guarded([&] {
+    if (!out || cap == 0) throw Error{GLX_E_INVALID, "null out"};
+    check_fused(fused);
+    std::snprintf(out, cap, "%s; residual=centring finalize (k_cert_csum, k_cert_fin_c)",
+                  describe_cert(cert_plan(dtype, m, n, l), fused).c_str());
+  });
+}
+
+int glx_certificate_ic(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                       double mu, int fused, const void* sample_w, const void* holdout_w, double weight_sum,
+                       void* G_out, double* rownorm_out, double* out, double* holdout_sum, double* intercept_out,
+                       void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_sample(sample_w, holdout_w);
+    check_intercept(weight_sum, intercept_out);
+    const CertPlan pl = cert_plan(dtype, m, n, l);
+    const size_t head = cert_carve(pl, m, n, l, nullptr, nullptr);
+    if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
+    if (wsb < intercept_carve(sample_bytes(head), pl.es, m, l, nullptr, nullptr))
+      throw Error{GLX_E_INVALID, "workspace too small (glx_certificate_ic_workspace_bytes)"};
+    if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
+    if (holdout_sum != nullptr) *holdout_sum = 0.0;
+    InterceptView ic;
+    ic.sigma = weight_sum;
+    ic.mean_host = intercept_out;
+    intercept_carve(sample_bytes(head), pl.es, m, l, ws, &ic);
+    SampleView sw;
+    sw.w = sample_w;
+    sw.hold = holdout_w;
+    sw.sums = reinterpret_cast<double*>(static_cast<char*>(ws) + sample_off(head));
+    certificate_run(dtype, m, n, l, A, X, b, mu, fused, G_out, rownorm_out, out, ws, head, stream, nullptr,
+                    sample_w != nullptr ? &sw : nullptr, holdout_sum, &ic);
+    for (int64_t c = 0; c < l; ++c) intercept_out[c] = -intercept_out[c];   // c = -r-bar
   });
 }
 

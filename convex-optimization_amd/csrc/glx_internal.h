@@ -483,6 +483,19 @@ void launch_cert_fin(const T* P, int S, const T* b, T* r, int64_t ml, Red red, h
 template <typename T>
 void launch_cert_fin_w(const T* P, int S, const T* b, const T* w, const T* hv, T* r, T* rw, int64_t ml, int64_t l,
                        Red red, hipStream_t st);
+// The centring finalize of the problem with an intercept (DESIGN.md "Intercept"), two launches:
+//   launch_cert_csum:  rh = (the sum of the S slabs at P) - b (S = 0: -b) and mean[c] =
+//       sum_j w_j rh[j, c] / sigma, l doubles (w may be NULL: unit weights, the bits of all-ones).
+//       part: cert_csum_part_bytes(); cnt: one zeroed word (reset by the kernel)
+//   launch_cert_fin_c: rc (may be NULL, may be rh) = (T)((double)rh - mean[c]), rw = fl(w rc), out:
+//       launch_cert_fin_w's sums on rc
+size_t cert_csum_part_bytes();
+template <typename T>
+void launch_cert_csum(const T* P, int S, const T* b, const T* w, T* rh, int64_t m, int64_t l, double sigma,
+                      double* part, unsigned* cnt, double* mean, hipStream_t st);
+template <typename T>
+void launch_cert_fin_c(const T* rh, const T* b, const T* w, const T* hv, const double* mean, T* rc, T* rw,
+                       int64_t ml, int64_t l, Red red, hipStream_t st);
 
 // ---- gap-safe screening (kernels_screen.hip; DESIGN.md "Certified solve and screening") ----
 // norms[j] = ||A[:, j]||_2 (n doubles), accumulated in double over col_norm_slabs(m) fixed row slabs
@@ -498,6 +511,12 @@ void launch_col_norms(const T* A, int64_t m, int64_t n, double* norms, double* p
 template <typename T>
 void launch_col_norms_w(const T* A, const T* w, int64_t m, int64_t n, double* norms, double* part, unsigned* ccnt,
                         Red red, hipStream_t st);
+// The centred norms of the problem with an intercept, two launches on the same slabs (w may be NULL):
+// mean[j] = sum_i w[i] A[i, j] / sigma (n doubles; red_mean.out = [max_j |mean[j]|, sum_j mean[j]^2]),
+// then norms[j] = sqrt(sum_i w[i] (A[i, j] - mean[j])^2) with red.out as launch_col_norms'
+template <typename T>
+void launch_col_norms_c(const T* A, const T* w, double sigma, int64_t m, int64_t n, double* norms, double* mean,
+                        double* part, unsigned* ccnt, Red red_mean, Red red, hipStream_t st);
 // keep[i] = !(s rn[i] + cn[i] rho < mu_lo) (a NaN keeps the row); list = the kept rows, ascending,
 // then -1 up to cnt[1]; cnt = [kept, kept rounded up to 64]. mask (n bytes) may be NULL; list holds n
 // rounded up to 64 ints; bal: screen_words_bytes(n); ticket: one zeroed word (reset by the kernel).
@@ -574,10 +593,29 @@ inline size_t sample_bytes(size_t head) { return sample_off(head) + 256; }
 // sw (NULL: every call and byte above): the certificate of 1/2 sum_j w_j ||(A x - b)_j||^2 + mu Omega(x):
 // out[0] = sum w r^2, out[1] = sum w r b, the A^T pass runs on w r; *holdout_sum (where sw->hold)
 // = sum_j hold_j ||(A x - b)_j||^2 from the same launch.
+// The unpenalised intercept as the drivers pass it on (DESIGN.md "Intercept"): sigma = sum_j w_j (m
+// without sample weights), mean_host = l host doubles that receive the weighted column means r-bar of
+// r^ = fl(A x) - b at every certificate (the intercept is c = -r-bar), and the device pieces of the
+// centring finalize, carved behind the callee's workspace (intercept_carve).
+struct InterceptView {
+  double sigma = 0.0;
+  double* mean_host = nullptr;
+  void* rhat = nullptr;       // m * l values of A's dtype
+  double* mean = nullptr;     // l doubles
+  double* part = nullptr;     // cert_csum_part_bytes()
+  unsigned* cnt = nullptr;    // 256 bytes, zeroed by the launching driver
+};
+// [head | rhat | mean | part | cnt] (base == NULL: the size only); returns the bytes of all of it
+size_t intercept_carve(size_t head, int es, int64_t m, int64_t l, void* base, InterceptView* out);
+// the checks every intercept entry makes: weight_sum finite and > 0, intercept_out not NULL
+void check_intercept(double weight_sum, const double* intercept_out);
+// ic (NULL: every call and byte above): the certificate of min_c 1/2 sum_j w_j ||(A x + 1 c^T - b)_j||^2
+// + mu Omega(x): the finalize is the two centring launches, out[0], out[1] are the sums on the centred
+// residual r_c, the A^T pass runs on w r_c (sw == NULL: on r_c), *holdout_sum is taken on r_c.
 void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
                      double mu, int fused, void* G_out, double* rownorm_out, double* out, void* ws, size_t wsb,
                      void* stream, const GroupView* grp, const SampleView* sw = nullptr,
-                     double* holdout_sum = nullptr);
+                     double* holdout_sum = nullptr, const InterceptView* ic = nullptr);
 // The certified solve (screen.cpp), rows (grp == NULL) or groups: one loop, glx_certified_solve's
 // arguments and checks. With groups the step is launch_atr + launch_group_fista, the screen runs on
 // the G "rows" ||g_[g]|| / w_g against gcn (launch_group_cnorm, computed here) and
@@ -586,19 +624,34 @@ void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, 
 // With sample weights (sw; its `sums` is ignored: the solve carves its own) both residual finalizes,
 // ||b~||, the column figures and every certificate are the weighted problem's; col_norms_dev then
 // holds the weighted norms. The final full-problem certificate takes sw->hold: *holdout_sum.
-size_t certified_bytes(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t G, bool weighted = false);
+// With an intercept (ic: its sigma and mean_host; the device pieces are carved here, `intercept` sizes
+// them) the finalize of an iteration and the null product's are the two centring launches, the column
+// figures are the centred ones (col_stats then holds four values: launch_col_norms_c's two pairs),
+// every certificate centres and the screen runs under screen_guard_ic; ic->mean_host holds the means
+// of the final certificate on return.
+size_t certified_bytes(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t G, bool weighted = false,
+                       bool intercept = false);
 std::string certified_describe(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run);
 void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit, int screen, int check_every,
                    const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev, void* ws,
                    size_t wsb, glx_certified_info* info, void* stream, const GroupView* grp,
                    int32_t* kept_groups_dev, int64_t* listed_groups, const SampleView* sw = nullptr,
-                   double* holdout_sum = nullptr);
+                   double* holdout_sum = nullptr, const InterceptView* ic = nullptr);
 // The rounding guards, host only (screen.cpp / group.cpp); out = [s_safe, gap+, rho+]. weighted: the
 // record, the column figures and bn are the sample-weighted problem's, and the roundings of w r and
 // w r^2 are counted (DESIGN.md "Sample weights and cross-validation", "The guard").
 double gamma_k(double k, double u);
 void group_screen_guard(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run,
                         double w_min, double gcol_max, double csq, double bn, double* out, bool weighted = false);
+// The guards of the problem with an intercept (DESIGN.md "Intercept", "The guard"); out = [s_safe, gap+,
+// rho+, slack]: a row is screened when s rn + cn rho+ < mu - slack with cn the CENTRED norm. rec: the
+// centred record; cstats = [max centred norm, sum centred norm^2, max |column mean|, sum column mean^2];
+// bn = sqrt(sum w b^2) (uncentred); sigma = sum w; mean_sq = sum_c r-bar_c^2 of the record's certificate.
+void screen_guard_ic(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, const double* cstats,
+                     double bn, double sigma, double mean_sq, double* out);
+void group_screen_guard_ic(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run,
+                           double w_min, double gcol_max, const double* cstats, double bn, double sigma,
+                           double mean_sq, double* out);
 // the checks every weighted C entry makes of its two vectors: 16-byte aligned, hold only with w
 void check_sample(const void* sample_w, const void* holdout_w);
 

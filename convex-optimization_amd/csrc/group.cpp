@@ -194,6 +194,49 @@ void group_screen_guard(const double* rec, double mu, int dtype, int64_t m, int6
   out[2] = rho;
 }
 
+// The grouped guard of the problem with an intercept: screen_guard_ic's substitutions (screen.cpp; DESIGN.md
+// "Intercept", "The guard") in group_screen_guard. A group's uncentred figure is at most
+// sqrt(gcn_c^2 + sigma max_run amax^2 / w_min^2) and its share of the departure from 1~^T theta = 0 at
+// most sqrt(max_run sigma) amax eps / w_min.
+void group_screen_guard_ic(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run,
+                           double w_min, double gcol_max, const double* cs, double bn_in, double sigma,
+                           double mean_sq, double* out) {
+  const double k = 3.0;
+  const double u = dtype == GLX_F64 ? DBL_EPSILON : (double)FLT_EPSILON;
+  const double u64 = DBL_EPSILON;
+  const double rr = rec[0], rb = rec[1], sxw = rec[2], gmax = rec[3];
+  const double rn = std::sqrt(rr);
+  const double K = (double)max_run * (double)l;
+  const double gm = gamma_k((double)m + k, u), gn = gamma_k((double)n + 2.0, u);
+  const double gK = gamma_k(K + 3.0, u);
+  const double ml = (double)m * (double)l;
+  const double g_ml = gamma_k(ml + k, u64);
+  const double bn = bn_in * (1.0 + g_ml);
+  const double up = (1.0 + gamma_k((double)m + 5.0, u64)) * (1.0 + gamma_k((double)max_run + 3.0, u64));
+  const double py = 1.0 + 3.0 * gamma_k((double)m + (double)n + 8.0, u64);
+  const double csq = cs[1], amax = cs[2], asq = cs[3];
+  const double ga = std::sqrt((double)max_run * sigma) * amax / w_min;   // a group's mean part / w_g
+  const double gcu = std::sqrt((gcol_max * gcol_max * up * up + ga * ga) * py);
+  const double csq_u = (csq + sigma * asq) * py;
+  const double rhn = std::sqrt((rr + sigma * mean_sq) * py * (1.0 + 4.0 * u));
+  const double eps = gamma_k(2.0, u) * rn + gamma_k((double)m + 3.0, u64) * rhn;
+  const double dep = ga * eps * (1.0 + 4.0 * u64);
+  const double den = gmax * (1.0 + gK) + gm * gcu * rn + dep;
+  const double s = den > mu ? mu / den : (den <= mu ? 1.0 : den);
+  const double dr = gn * std::sqrt(csq_u) * (sxw / w_min) + u * (rhn + 2.0 * bn) + u * rn;
+  const double bar_rr = g_ml * rr;
+  const double bar_rb = g_ml * rn * bn;
+  const double bar_sx = (gK + gamma_k((double)n + 2.0, u64)) * sxw;
+  const double gap = 0.5 * (1.0 + s * s) * rr + s * rb + mu * sxw;
+  const double bars = rn * dr + 0.5 * dr * dr + 0.5 * (1.0 + s * s) * bar_rr + s * bar_rb + mu * bar_sx +
+                      s * eps * bn + 0.5 * s * s * eps * eps;
+  const double gap_p = (gap > 0.0 ? gap : (gap <= 0.0 ? 0.0 : gap)) + bars;
+  out[0] = s;
+  out[1] = gap_p;
+  out[2] = (std::sqrt(2.0 * gap_p) + s * eps) * up;
+  out[3] = s * (gm * gcu * rn + gK * (1.0 + gm) * gcu * rn + dep) * (1.0 + 8.0 * u64);
+}
+
 }  // namespace glx
 
 using namespace glx;
@@ -401,6 +444,131 @@ int glx_group_certified_solve_sw(const glx_problem* prob, int64_t G, const int32
     const SampleView sw{sample_w, holdout_w, nullptr};
     certified_run(prob, t, tol, maxit, screen, check_every, col_norms_dev, col_stats, kept_rows_dev, d.head, head,
                   &info->base, stream, &v, kept_groups_dev, &listed_groups, weighted ? &sw : nullptr, holdout_sum);
+    info->kept_groups = screen != 0 ? info->base.kept : G;
+    info->listed_groups = listed_groups;
+    info->max_run = f.max_run;
+  });
+}
+
+/* ---- the unpenalised intercept (DESIGN.md "Intercept"): the grouped entries; the centring finalize's
+ * pieces sit behind the _sw entries' workspaces ---- */
+
+int glx_group_screen_guard_ic(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l,
+                              int64_t max_run, double w_min, double gcol_max, const double* col_stats, double b_norm,
+                              double weight_sum, double mean_sq, double* out) {
+  return guarded([&] {
+    if (!rec || !out || !col_stats) throw Error{GLX_E_INVALID, "null argument"};
+    check_dims(dtype, n, l);
+    if (m <= 0) throw Error{GLX_E_INVALID, "m must be positive"};
+    if (max_run < 1 || max_run > n) throw Error{GLX_E_INVALID, "max_run must be in 1 .. n"};
+    if (!(w_min > 0.0) || !std::isfinite(w_min)) throw Error{GLX_E_INVALID, "w_min must be positive and finite"};
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    if (!(weight_sum > 0.0) || !std::isfinite(weight_sum))
+      throw Error{GLX_E_INVALID, "intercept: weight_sum must be positive and finite"};
+    group_screen_guard_ic(rec, mu, dtype, m, n, l, max_run, w_min, gcol_max, col_stats, b_norm, weight_sum, mean_sq,
+                          out);
+  });
+}
+
+int glx_group_certificate_ic_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    if (G < 1 || G > n) throw Error{GLX_E_INVALID, "groups: G must be in 1 .. n"};
+    *bytes = intercept_carve(sample_bytes(group_carve(cert_bytes(dtype, m, n, l), G, nullptr, nullptr)),
+                             dtype == GLX_F64 ? 8 : 4, m, l, nullptr, nullptr);
+  });
+}
+
+int glx_group_certificate_ic_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, char* out,
+                                      size_t cap) {
+  const int rc = glx_group_certificate_describe(dtype, m, n, l, max_run, out, cap);
+  if (rc != GLX_OK) return rc;
+  const size_t used = std::strlen(out);
+  std::snprintf(out + used, cap - used, "; residual=centring finalize (k_cert_csum, k_cert_fin_c)");
+  return GLX_OK;
+}
+
+int glx_group_certificate_ic(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X,
+                             const void* b, double mu, int64_t G, const int32_t* group_ptr, const double* weights,
+                             const void* sample_w, const void* holdout_w, double weight_sum, void* G_out,
+                             double* groupnorm_out, double* out, double* holdout_sum, double* intercept_out, void* ws,
+                             size_t wsb, void* stream) {
+  return guarded([&] {
+    check_dims(dtype, n, l);
+    const GroupFacts f = check_groups(n, G, group_ptr, weights);
+    check_sample(sample_w, holdout_w);
+    check_intercept(weight_sum, intercept_out);
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    if (!A || !X || !b) throw Error{GLX_E_INVALID, "A, X and b must be device pointers"};
+    if (!out) throw Error{GLX_E_INVALID, "null out"};
+    const int es = dtype == GLX_F64 ? 8 : 4;
+    const size_t head = cert_bytes(dtype, m, n, l);
+    const size_t grouped = group_carve(head, G, nullptr, nullptr);
+    check_ws(intercept_carve(sample_bytes(grouped), es, m, l, nullptr, nullptr), ws, wsb,
+             "glx_group_certificate_ic_workspace_bytes");
+    GroupDev d;
+    group_carve(head, G, ws, &d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const GroupView v = upload(dtype, d, G, group_ptr, weights, f, st);
+    if (holdout_sum != nullptr) *holdout_sum = 0.0;
+    InterceptView ic;
+    ic.sigma = weight_sum;
+    ic.mean_host = intercept_out;
+    intercept_carve(sample_bytes(grouped), es, m, l, ws, &ic);
+    const SampleView sw{sample_w, holdout_w, reinterpret_cast<double*>(static_cast<char*>(ws) + sample_off(grouped))};
+    certificate_run(dtype, m, n, l, A, X, b, mu, 0, G_out, groupnorm_out, out, d.head, head, stream, &v,
+                    sample_w != nullptr ? &sw : nullptr, holdout_sum, &ic);
+    for (int64_t c = 0; c < l; ++c) intercept_out[c] = -intercept_out[c];   // c = -r-bar
+  });
+}
+
+int glx_group_certified_ic_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, int screen,
+                                           size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    if (G < 1 || G > n) throw Error{GLX_E_INVALID, "groups: G must be in 1 .. n"};
+    *bytes = group_carve(certified_bytes(dtype, m, n, l, screen != 0, G, true, true), G, nullptr, nullptr);
+  });
+}
+
+int glx_group_certified_ic_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, int screen,
+                                    char* out, size_t cap) {
+  const int rc = glx_group_certified_describe(dtype, m, n, l, max_run, screen, out, cap);
+  if (rc != GLX_OK) return rc;
+  const size_t used = std::strlen(out);
+  std::snprintf(out + used, cap - used, "; residual=centring finalize (k_cert_csum, k_cert_fin_c)");
+  return GLX_OK;
+}
+
+int glx_group_certified_solve_ic(const glx_problem* prob, int64_t G, const int32_t* group_ptr, const double* weights,
+                                 const void* sample_w, const void* holdout_w, double weight_sum, double t, double tol,
+                                 int64_t maxit, int screen, int check_every, const double* col_norms_dev,
+                                 const double* col_stats, int32_t* kept_rows_dev, int32_t* kept_groups_dev, void* ws,
+                                 size_t wsb, glx_group_certified_info* info, double* holdout_sum,
+                                 double* intercept_out, void* stream) {
+  return guarded([&] {
+    if (!prob || !info) throw Error{GLX_E_INVALID, "null problem/info"};
+    if (prob->comm != nullptr) throw Error{GLX_E_INVALID, "the certified solve is single-GPU: comm must be NULL"};
+    check_dims(prob->dtype, prob->n, prob->l);
+    const GroupFacts f = check_groups(prob->n, G, group_ptr, weights);
+    check_sample(sample_w, holdout_w);
+    check_intercept(weight_sum, intercept_out);
+    const size_t head = certified_bytes(prob->dtype, prob->m, prob->n, prob->l, screen != 0, G, true, true);
+    check_ws(group_carve(head, G, nullptr, nullptr), ws, wsb, "glx_group_certified_ic_workspace_bytes");
+    if (!prob->A || !prob->b || !prob->x) throw Error{GLX_E_INVALID, "A, b and x must be device pointers"};
+    GroupDev d;
+    group_carve(head, G, ws, &d);
+    const GroupView v = upload(prob->dtype, d, G, group_ptr, weights, f, static_cast<hipStream_t>(stream));
+    std::memset(info, 0, sizeof *info);
+    int64_t listed_groups = 0;
+    const SampleView sw{sample_w, holdout_w, nullptr};
+    InterceptView ic;
+    ic.sigma = weight_sum;
+    ic.mean_host = intercept_out;
+    certified_run(prob, t, tol, maxit, screen, check_every, col_norms_dev, col_stats, kept_rows_dev, d.head, head,
+                  &info->base, stream, &v, kept_groups_dev, &listed_groups, sample_w != nullptr ? &sw : nullptr,
+                  holdout_sum, &ic);
+    for (int64_t c = 0; c < prob->l; ++c) intercept_out[c] = -intercept_out[c];   // c = -r-bar
     info->kept_groups = screen != 0 ? info->base.kept : G;
     info->listed_groups = listed_groups;
     info->max_run = f.max_run;

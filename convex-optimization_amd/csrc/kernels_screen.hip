@@ -142,6 +142,127 @@ __global__ __launch_bounds__(256) void k_col_norms_w(const T* __restrict__ A, co
   grid_reduce<2, 0x1u>(v, red, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// The centred weighted column norms of the problem with an intercept (DESIGN.md "Intercept"), two
+// launches on k_col_norms' walk, slabs and last-block combine, siblings again (w == NULL: unit weights):
+//   k_col_means    mean[i] = sum_j w_j A_ji / sigma; the grid reduction gives max_i |mean[i]| and
+//                  sum_i mean[i]^2 (the guard recovers the uncentred norms from them)
+//   k_col_norms_c  sqrt(sum_j w_j (A_ji - mean[i])^2), the difference taken in double, the term formed
+//                  as (w d) d; max and sum of squares as k_col_norms
+// Any mean other than the exact one only enlarges the second sum, so its rounding errs on the safe side.
+template <typename T>
+__global__ __launch_bounds__(256) void k_col_means(const T* __restrict__ A, const T* __restrict__ w, int64_t m,
+                                                   int64_t n, int64_t rps, double sigma, double* __restrict__ part,
+                                                   unsigned* __restrict__ ccnt, double* __restrict__ mean, Red red) {
+  __shared__ int last;
+  const int64_t r0 = (int64_t)blockIdx.y * rps;
+  const int64_t r1 = r0 + rps < m ? r0 + rps : m;
+  const int64_t cstride = (int64_t)gridDim.x * 256;
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += cstride) {
+    const T* p = A + r0 * n + j;
+    double acc = 0.0;
+    int64_t r = r0;
+    for (; r + 4 <= r1; r += 4) {
+      const double a0 = (double)p[0], a1 = (double)p[n], a2 = (double)p[2 * n], a3 = (double)p[3 * n];
+      acc += (w != nullptr ? (double)w[r] : 1.0) * a0;
+      acc += (w != nullptr ? (double)w[r + 1] : 1.0) * a1;
+      acc += (w != nullptr ? (double)w[r + 2] : 1.0) * a2;
+      acc += (w != nullptr ? (double)w[r + 3] : 1.0) * a3;
+      p += 4 * n;
+    }
+    for (; r < r1; ++r) {
+      acc += (w != nullptr ? (double)w[r] : 1.0) * (double)p[0];
+      p += n;
+    }
+    __hip_atomic_store(part + (int64_t)blockIdx.y * n + j, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned arrival = __hip_atomic_fetch_add(ccnt + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = arrival == gridDim.y - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  double v[2] = {-__builtin_inf(), 0.0};
+  const int S = (int)gridDim.y;
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += cstride) {
+    double s = 0.0;
+    for (int k = 0; k < S; ++k)
+      s += __hip_atomic_load(part + (int64_t)k * n + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double mu = s / sigma;
+    mean[j] = mu;
+    v[0] = nan_max(v[0], mu < 0.0 ? -mu : mu);
+    v[1] += mu * mu;
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(ccnt + blockIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  grid_reduce<2, 0x1u>(v, red, (int)blockIdx.x, (int)gridDim.x);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_col_norms_c(const T* __restrict__ A, const T* __restrict__ w,
+                                                     const double* __restrict__ mean, int64_t m, int64_t n,
+                                                     int64_t rps, double* __restrict__ part,
+                                                     unsigned* __restrict__ ccnt, double* __restrict__ norms,
+                                                     Red red) {
+  __shared__ int last;
+  const int64_t r0 = (int64_t)blockIdx.y * rps;
+  const int64_t r1 = r0 + rps < m ? r0 + rps : m;
+  const int64_t cstride = (int64_t)gridDim.x * 256;
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += cstride) {
+    const T* p = A + r0 * n + j;
+    const double mj = mean[j];
+    double acc = 0.0;
+    int64_t r = r0;
+    for (; r + 4 <= r1; r += 4) {
+      const double d0 = (double)p[0] - mj, d1 = (double)p[n] - mj, d2 = (double)p[2 * n] - mj,
+                   d3 = (double)p[3 * n] - mj;
+      acc += ((w != nullptr ? (double)w[r] : 1.0) * d0) * d0;
+      acc += ((w != nullptr ? (double)w[r + 1] : 1.0) * d1) * d1;
+      acc += ((w != nullptr ? (double)w[r + 2] : 1.0) * d2) * d2;
+      acc += ((w != nullptr ? (double)w[r + 3] : 1.0) * d3) * d3;
+      p += 4 * n;
+    }
+    for (; r < r1; ++r) {
+      const double d0 = (double)p[0] - mj;
+      acc += ((w != nullptr ? (double)w[r] : 1.0) * d0) * d0;
+      p += n;
+    }
+    __hip_atomic_store(part + (int64_t)blockIdx.y * n + j, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned arrival = __hip_atomic_fetch_add(ccnt + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last = arrival == gridDim.y - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  double v[2] = {-__builtin_inf(), 0.0};
+  const int S = (int)gridDim.y;
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += cstride) {
+    double s = 0.0;
+    for (int k = 0; k < S; ++k)
+      s += __hip_atomic_load(part + (int64_t)k * n + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const double nrm = __builtin_sqrt(s);
+    norms[j] = nrm;
+    v[0] = nan_max(v[0], nrm);
+    v[1] += s;
+  }
+  if (threadIdx.x == 0) __hip_atomic_store(ccnt + blockIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  grid_reduce<2, 0x1u>(v, red, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// mean: n doubles; red_mean.out = [max_i |mean[i]|, sum_i mean[i]^2]; red.out as launch_col_norms'
+template <typename T>
+void launch_col_norms_c(const T* A, const T* w, double sigma, int64_t m, int64_t n, double* norms, double* mean,
+                        double* part, unsigned* ccnt, Red red_mean, Red red, hipStream_t st) {
+  const dim3 grid(col_norm_blocks(n), (unsigned)col_norm_slabs(m));
+  hipLaunchKernelGGL(k_col_means<T>, grid, dim3(256), 0, st, A, w, m, n, col_norm_rows_per_slab(m), sigma, part, ccnt,
+                     mean, red_mean);
+  hipLaunchKernelGGL(k_col_norms_c<T>, grid, dim3(256), 0, st, A, w, mean, m, n, col_norm_rows_per_slab(m), part, ccnt,
+                     norms, red);
+}
+
 template <typename T>
 void launch_col_norms(const T* A, int64_t m, int64_t n, double* norms, double* part, unsigned* ccnt, Red red,
                       hipStream_t st) {
@@ -340,6 +461,8 @@ void launch_compose_list(const int* map, const int* idx, int64_t wp, int* out, h
   template void launch_col_norms<T>(const T*, int64_t, int64_t, double*, double*, unsigned*, Red, hipStream_t); \
   template void launch_col_norms_w<T>(const T*, const T*, int64_t, int64_t, double*, double*, unsigned*, Red, \
                                       hipStream_t);                                                         \
+  template void launch_col_norms_c<T>(const T*, const T*, double, int64_t, int64_t, double*, double*, double*, \
+                                      unsigned*, Red, Red, hipStream_t);                                    \
   template void launch_gather_cols<T>(const T*, int64_t, int64_t, const int*, int64_t, T*, hipStream_t);     \
   template void launch_gather_rows<T>(const T*, const int*, int64_t, int64_t, T*, hipStream_t);             \
   template void launch_scatter_rows<T>(const T*, const int*, int64_t, int64_t, T*, hipStream_t);

@@ -21,6 +21,10 @@
 // (r = w (A y - b) is the R every step already takes), ||b~|| and the column figures are the weighted
 // ones, every certificate takes the weights and the guards count their roundings; the final
 // certificate also reduces the hold-out sum. Without one, again, nothing differs.
+// With an InterceptView (DESIGN.md "Intercept") the loop solves min_c 1/2 sum_j w_j ||(A x + 1 c^T - b)_j||^2
+// + mu Omega(x) with c eliminated exactly: the residual finalizes become the two centring launches
+// (launch_cert_csum, launch_cert_fin_c: r = w (A y - b - 1 mean^T)), the column figures are the centred
+// ones, every certificate centres and the screen runs under screen_guard_ic with its slack off mu.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -184,9 +188,11 @@ struct Ws {
   int *gptr[2], *gmap[2], *glist;
   double *gw[2], *ggcn[2], *gcn_full;
   double* ssums;   // sample weights: the weighted finalize's sums of a certificate (SampleView::sums)
+  InterceptView ic;   // intercept: the centring finalize's device pieces
+  double* cmean;      // intercept: the column means of A
 };
 size_t carve(int dtype, int64_t m, int64_t n, int64_t l, bool screen, bool own_norms, void* base, Ws* out,
-             int64_t G = 0, bool weighted = false) {
+             int64_t G = 0, bool weighted = false, bool intercept = false) {
   const size_t es = dtype == GLX_F64 ? 8 : 4;
   const Extent e = extent(dtype, m, n, l, screen);
   const int64_t np = pad64(n);
@@ -224,6 +230,11 @@ size_t carve(int dtype, int64_t m, int64_t n, int64_t l, bool screen, bool own_n
   w.gcn_full = static_cast<double*>(c.take(sizeof(double) * (size_t)G));
   w.glist = static_cast<int*>(c.take(G > 0 ? sizeof(int) * (size_t)pad64(G) : 0));
   w.ssums = static_cast<double*>(c.take(weighted ? 256 : 0));   // (behind the grouped pieces in turn)
+  w.cmean = nullptr;
+  if (intercept) {   // (and the intercept's behind those)
+    w.cmean = static_cast<double*>(c.take(sizeof(double) * np));
+    c.off = intercept_carve(c.off, (int)es, m, l, base, &w.ic) - 256;
+  }
   if (out) *out = w;
   return c.off + 256;
 }
@@ -255,10 +266,10 @@ Composed compose(const double* rec, double mu) {
 
 void cert_call(int dtype, int64_t m, int64_t w, int64_t l, const void* A, const void* x, const void* b, double mu,
                double* rn, double* rec, const Ws& ws, hipStream_t st, const GroupView* grp = nullptr,
-               const SampleView* sw = nullptr, double* holdout_sum = nullptr) {
-  if (sw != nullptr) {   // the weighted problem's certificate, rows or groups
+               const SampleView* sw = nullptr, double* holdout_sum = nullptr, const InterceptView* ic = nullptr) {
+  if (sw != nullptr || ic != nullptr) {   // the weighted problem's certificate, rows or groups; the intercept's
     certificate_run(dtype, m, w, l, A, x, b, mu, 0, nullptr, rn, rec, ws.cert, ws.cert_bytes, st, grp, sw,
-                    holdout_sum);
+                    holdout_sum, ic);
     return;
   }
   if (grp != nullptr) {   // (rn: ||g_[g]|| / w_g of the grp->G groups)
@@ -273,9 +284,24 @@ template <typename T>
 void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T* X, double mu, double t,
            double tol, int64_t maxit, bool screen, int check_every, const double* cn_in, const double* cstats_in,
            int32_t* kept_rows, void* wsp, glx_certified_info* info, hipStream_t st, const GroupView* grp,
-           int32_t* kept_groups, int64_t* listed_groups, const SampleView* sw, double* holdout_sum) {
+           int32_t* kept_groups, int64_t* listed_groups, const SampleView* sw, double* holdout_sum,
+           const InterceptView* icv) {
   Ws w;
-  carve(dtype, m, n, l, screen, cn_in == nullptr, wsp, &w, grp != nullptr ? grp->G : 0, sw != nullptr);
+  carve(dtype, m, n, l, screen, cn_in == nullptr, wsp, &w, grp != nullptr ? grp->G : 0,
+        sw != nullptr || icv != nullptr, icv != nullptr);
+  // the intercept (DESIGN.md "Intercept"): the caller's sigma and host means, this workspace's device pieces
+  InterceptView icw = w.ic;
+  if (icv != nullptr) {
+    icw.sigma = icv->sigma;
+    icw.mean_host = icv->mean_host;
+  }
+  const InterceptView* ic = icv != nullptr ? &icw : nullptr;
+  double amax = 0.0, asq = 0.0;   // max |column mean| and the sum of their squares
+  auto mean_sq = [&]() {          // sum_c r-bar_c^2 of the last certificate (or finalize read back)
+    double q = 0.0;
+    for (int64_t c = 0; c < l; ++c) q += icw.mean_host[c] * icw.mean_host[c];
+    return q;
+  };
   // sample weights: the loop's certificates take the weights alone, the final one the hold-out too
   const T* sww = sw != nullptr ? static_cast<const T*>(sw->w) : nullptr;
   const SampleView sw_in{sw != nullptr ? sw->w : nullptr, nullptr, w.ssums};
@@ -291,6 +317,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
   GLX_HIP(hipMemsetAsync(w.ccnt, 0, col_norms_count_bytes(n), st));
   GLX_HIP(hipMemsetAsync(w.sticket, 0, 256, st));
   GLX_HIP(hipMemsetAsync(w.red, 0, sizeof(double) * kRedOut, st));
+  if (ic != nullptr) GLX_HIP(hipMemsetAsync(ic->cnt, 0, 256, st));
   const Red red0{w.part, w.ticket, w.red}, red1{w.part, w.ticket, w.red + 4}, red2{w.part, w.ticket, w.red + 10};
 
   // the column figures and ||b||_F (screening only)
@@ -301,27 +328,48 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
       cn = cn_in;
       cmax = cstats_in[0];
       csq = cstats_in[1];
+      if (ic != nullptr) {
+        amax = cstats_in[2];
+        asq = cstats_in[3];
+      }
     } else {
-      if (sww != nullptr) launch_col_norms_w<T>(A, sww, m, n, w.cn[1], w.cpart, w.ccnt, red2, st);
+      if (ic != nullptr)
+        launch_col_norms_c<T>(A, sww, ic->sigma, m, n, w.cn[1], w.cmean, w.cpart, w.ccnt,
+                              Red{w.part, w.ticket, w.red + 13}, red2, st);
+      else if (sww != nullptr) launch_col_norms_w<T>(A, sww, m, n, w.cn[1], w.cpart, w.ccnt, red2, st);
       else launch_col_norms<T>(A, m, n, w.cn[1], w.cpart, w.ccnt, red2, st);
       check_launch();
       cn = w.cn[1];
-      info->passes += 1.0;
+      info->passes += ic != nullptr ? 2.0 : 1.0;
     }
     // r = -b: red0 = [||b||^2, .] (weighted: sum w b^2 = ||b~||^2, the null product of k_cert_fin_w)
-    if (sww != nullptr)
+    // (intercept: the centring finalize of the null product gives ||P~ b~||^2 and -b-bar; the guard
+    // takes the uncentred ||b~||^2 = ||P~ b~||^2 + sigma ||b-bar||^2)
+    if (ic != nullptr) {
+      GLX_HIP(hipMemsetAsync(ic->cnt, 0, 256, st));
+      launch_cert_csum<T>(nullptr, 0, b, sww, static_cast<T*>(ic->rhat), m, l, ic->sigma, ic->part, ic->cnt,
+                          ic->mean, st);
+      launch_cert_fin_c<T>(static_cast<const T*>(ic->rhat), b, sww, nullptr, ic->mean, nullptr,
+                           static_cast<T*>(w.r), ml, l, red0, st);
+      GLX_HIP(hipMemcpyAsync(ic->mean_host, ic->mean, sizeof(double) * l, hipMemcpyDeviceToHost, st));
+    } else if (sww != nullptr)
       launch_cert_fin_w<T>(nullptr, 0, b, sww, nullptr, nullptr, static_cast<T*>(w.r), ml, l, red0, st);
     else
       launch_cert_fin<T>(nullptr, 0, b, static_cast<T*>(w.r), ml, red0, st);
     check_launch();
-    double h[4];
+    double h[6] = {};
     GLX_HIP(hipMemcpyAsync(h, w.red, sizeof(double), hipMemcpyDeviceToHost, st));
     GLX_HIP(hipMemcpyAsync(h + 1, w.red + 10, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (ic != nullptr) GLX_HIP(hipMemcpyAsync(h + 3, w.red + 13, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
     GLX_HIP(hipStreamSynchronize(st));
-    bn = std::sqrt(h[0]);
+    bn = std::sqrt(ic != nullptr ? (h[0] + ic->sigma * mean_sq()) * (1.0 + 8.0 * DBL_EPSILON) : h[0]);
     if (cn_in == nullptr) {
       cmax = h[1];
       csq = h[2];
+      if (ic != nullptr) {
+        amax = h[3];
+        asq = h[4];
+      }
     }
     if (grp != nullptr) {   // gcn[g] = ||A_[g]||_F / w_g and its maximum, which stands in for cmax
       launch_group_cnorm(cn, grp->ptr, grp->wts, grp->G, grp->max_run, w.gcn_full,
@@ -379,7 +427,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
       check_launch();
     }
     cert_call(dtype, m, n, l, A, X, b, mu, nullptr, info->cert, w, st, grp, sw != nullptr ? &sw_out : nullptr,
-              holdout_sum);
+              holdout_sum, ic);
     info->passes += 2.0;
     return compose(info->cert, mu);
   };
@@ -389,24 +437,32 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
   auto check = [&]() -> bool {
     ++info->checks;
     cert_call(dtype, m, wc, l, Ac, x, b, mu, w.rn, rec, w, st, grp != nullptr ? &gcur : nullptr,
-              sw != nullptr ? &sw_in : nullptr);
+              sw != nullptr ? &sw_in : nullptr, nullptr, ic);
     info->passes += 2.0 * (double)wc / (double)n;
     const Composed c = compose(rec, mu);
     info->inner_rel_gap = c.rel;
     const bool met = c.rel <= target;
     if (!screen) return met;
-    double gd[3];
-    const double mu_lo = mu * (1.0 - 4.0 * DBL_EPSILON);   // the test's own three roundings in fp64
+    double gd[4] = {0.0, 0.0, 0.0, 0.0};
+    const double cst[4] = {cmax, csq, amax, asq};
+    if (ic != nullptr && grp != nullptr)
+      group_screen_guard_ic(rec, mu, dtype, m, wc, l, grp->max_run, grp->w_min, gcol_max, cst, bn, ic->sigma, mean_sq(),
+                            gd);
+    else if (ic != nullptr)
+      screen_guard_ic(rec, mu, dtype, m, wc, l, cst, bn, ic->sigma, mean_sq(), gd);
+    // the test's own three roundings in fp64 (intercept: and the guard's slack, gd[3], off mu)
+    const double mu_lo = (mu - gd[3]) * (1.0 - 4.0 * DBL_EPSILON);
     int hc[4] = {0, 0, 0, 0};
     if (grp != nullptr) {   // the same test on the G "rows" of groups, then their rows
-      group_screen_guard(rec, mu, dtype, m, wc, l, grp->max_run, grp->w_min, gcol_max, csq, bn, gd, sw != nullptr);
+      if (ic == nullptr)
+        group_screen_guard(rec, mu, dtype, m, wc, l, grp->max_run, grp->w_min, gcol_max, csq, bn, gd, sw != nullptr);
       launch_screen(w.rn, gcn, gcur.G, gd[0], gd[2], mu_lo, nullptr, w.glist, w.cnt, w.bal, w.sticket, st);
       launch_group_expand(w.glist, w.cnt, gcur.ptr, gcur.wts, gcn, gmap, w.list, w.gptr[gside], w.gw[gside],
                           w.ggcn[gside], w.gmap[gside], w.cnt + 2, st);
       check_launch();
       GLX_HIP(hipMemcpyAsync(hc, w.cnt, sizeof hc, hipMemcpyDeviceToHost, st));
     } else {
-      screen_guard(rec, mu, dtype, m, wc, l, cmax, csq, bn, gd, sw != nullptr);
+      if (ic == nullptr) screen_guard(rec, mu, dtype, m, wc, l, cmax, csq, bn, gd, sw != nullptr);
       launch_screen(w.rn, cn, wc, gd[0], gd[2], mu_lo, nullptr, w.list, w.cnt, w.bal, w.sticket, st);
       check_launch();
       GLX_HIP(hipMemcpyAsync(hc, w.cnt, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -464,7 +520,11 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     const T* xs[3] = {y, nullptr, nullptr};
     T* r = static_cast<T*>(w.r);
     launch_ax<T>(pl.a, 1, Ac, xs, static_cast<T*>(w.pa), nullptr, 0, st);
-    if (sww != nullptr)   // r = w (A y - b): every step below takes it as the R it already takes
+    if (ic != nullptr) {   // r = w (A y - b - 1 mean^T): the two centring launches, no readback
+      launch_cert_csum<T>(static_cast<T*>(w.pa), ax_split(pl.a, 1), b, sww, static_cast<T*>(ic->rhat), m, l, ic->sigma,
+                          ic->part, ic->cnt, ic->mean, st);
+      launch_cert_fin_c<T>(static_cast<const T*>(ic->rhat), b, sww, nullptr, ic->mean, nullptr, r, ml, l, red0, st);
+    } else if (sww != nullptr)   // r = w (A y - b): every step below takes it as the R it already takes
       launch_cert_fin_w<T>(static_cast<T*>(w.pa), ax_split(pl.a, 1), b, sww, nullptr, nullptr, r, ml, l, red0, st);
     else
       launch_cert_fin<T>(static_cast<T*>(w.pa), ax_split(pl.a, 1), b, r, ml, red0, st);
@@ -556,9 +616,60 @@ size_t step_carve(int64_t m, int64_t n, void* base, StepWs* out) {
 
 }  // namespace
 
-size_t certified_bytes(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t G, bool weighted) {
+// The guard of the problem with an intercept (DESIGN.md "Intercept", "The guard, term by term"): the
+// weighted guard on the centred record with
+//   - the uncentred figures, which the roundings of A y and of A^T (w r_c) still see, recovered by
+//     Pythagoras from the centred ones and the column means: max ||a~_i||^2 <= cmax^2 + sigma amax^2,
+//     ||A~||_F^2 = csq + sigma asq, ||r~^||^2 = rec[0] + sigma mean_sq (py covers their own roundings);
+//   - eps >= ||1~^T r~_c|| / sqrt(sigma), the departure of theta from the dual's equality: projecting
+//     theta onto it moves it by s eps, costs the dual value s eps ||b~|| + 1/2 s^2 eps^2, adds s eps to
+//     the radius and |a-bar_i| sqrt(sigma) s eps to a row's ||a~_i^T theta||;
+//   - one more rounding of the residual (r_c in A's dtype) in dr;
+//   - out[3], the slack: the terms that scale with the UNcentred norm of a column cannot ride on its
+//     centred norm in  s rn + cn rho < mu  and are taken off mu instead.
+void screen_guard_ic(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, const double* cs,
+                     double bn_in, double sigma, double mean_sq, double* out) {
+  const double k = 3.0;
+  const double u = dtype == GLX_F64 ? DBL_EPSILON : (double)FLT_EPSILON;
+  const double u64 = DBL_EPSILON;
+  const double rr = rec[0], rb = rec[1], sx = rec[2], gmax = rec[3];
+  const double rn = std::sqrt(rr);
+  const double gm = gamma_k((double)m + k, u), gn = gamma_k((double)n + 2.0, u);
+  const double ml = (double)m * (double)l;
+  const double g_ml = gamma_k(ml + k, u64);
+  const double bn = bn_in * (1.0 + g_ml);
+  const double up = 1.0 + gamma_k((double)m + 5.0, u64);   // the centred norms are low by at most this
+  const double py = 1.0 + 3.0 * gamma_k((double)m + (double)n + 8.0, u64);
+  const double cmax = cs[0], csq = cs[1], amax = cs[2], asq = cs[3];
+  const double cu = std::sqrt((cmax * cmax * up * up + sigma * amax * amax) * py);
+  const double csq_u = (csq + sigma * asq) * py;
+  const double rhn = std::sqrt((rr + sigma * mean_sq) * py * (1.0 + 4.0 * u));
+  const double eps = gamma_k(2.0, u) * rn + gamma_k((double)m + 3.0, u64) * rhn;
+  const double dep = amax * std::sqrt(sigma) * eps * (1.0 + 4.0 * u64);
+  // 1. dual feasibility of the projected point
+  const double den = gmax + gm * cu * rn + dep;
+  const double s = den > mu ? mu / den : (den <= mu ? 1.0 : den);   // (NaN den: NaN)
+  // 2. the primal value, for the intercept the record's means give (any other only raises it)
+  const double dr = gn * std::sqrt(csq_u) * sx + u * (rhn + 2.0 * bn) + u * rn;
+  const double bar_rr = g_ml * rr;
+  const double bar_rb = g_ml * rn * bn;
+  const double bar_sx = (gamma_k((double)l + 2.0, u) + gamma_k((double)n + 2.0, u64)) * sx;
+  const double gap = 0.5 * (1.0 + s * s) * rr + s * rb + mu * sx;
+  const double bars = rn * dr + 0.5 * dr * dr + 0.5 * (1.0 + s * s) * bar_rr + s * bar_rb + mu * bar_sx +
+                      s * eps * bn + 0.5 * s * s * eps * eps;
+  const double gap_p = (gap > 0.0 ? gap : (gap <= 0.0 ? 0.0 : gap)) + bars;
+  // 3. the radius on the centred norms, and the slack
+  const double gl = gamma_k((double)l + 2.0, u);
+  out[0] = s;
+  out[1] = gap_p;
+  out[2] = (std::sqrt(2.0 * gap_p) + s * eps) * up;
+  out[3] = s * (gm * cu * rn + gl * (1.0 + gm) * cu * rn + dep) * (1.0 + 8.0 * u64);
+}
+
+size_t certified_bytes(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t G, bool weighted,
+                       bool intercept) {
   check_shape(dtype, m, n, l);
-  return carve(dtype, m, n, l, screen, true, nullptr, nullptr, G, weighted);
+  return carve(dtype, m, n, l, screen, true, nullptr, nullptr, G, weighted, intercept);
 }
 
 std::string certified_describe(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run) {
@@ -569,8 +680,10 @@ std::string certified_describe(int dtype, int64_t m, int64_t n, int64_t l, bool 
 void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit, int screen, int check_every,
                    const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev, void* ws,
                    size_t wsb, glx_certified_info* info, void* stream, const GroupView* grp,
-                   int32_t* kept_groups_dev, int64_t* listed_groups, const SampleView* sw, double* holdout_sum) {
+                   int32_t* kept_groups_dev, int64_t* listed_groups, const SampleView* sw, double* holdout_sum,
+                   const InterceptView* ic) {
   if (!prob || !info) throw Error{GLX_E_INVALID, "null problem/info"};
+  if (ic != nullptr) check_intercept(ic->sigma, ic->mean_host);
   if (sw != nullptr) check_sample(sw->w, sw->hold);
   if (sw != nullptr && sw->w == nullptr) throw Error{GLX_E_INVALID, "sample weights: null vector"};
   if (prob->comm != nullptr) throw Error{GLX_E_INVALID, "the certified solve is single-GPU: comm must be NULL"};
@@ -587,18 +700,18 @@ void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit,
   if ((col_norms_dev != nullptr) != (col_stats != nullptr))
     throw Error{GLX_E_INVALID, "col_norms_dev and col_stats go together"};
   check_ws(carve(prob->dtype, prob->m, prob->n, prob->l, screen != 0, true, nullptr, nullptr,
-                 grp != nullptr ? grp->G : 0, sw != nullptr),
+                 grp != nullptr ? grp->G : 0, sw != nullptr || ic != nullptr, ic != nullptr),
            ws, wsb, grp != nullptr ? "glx_group_certified_workspace_bytes" : "glx_certified_workspace_bytes");
   if (holdout_sum != nullptr) *holdout_sum = 0.0;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (prob->dtype == GLX_F64)
     solve<double>(prob->dtype, prob->m, prob->n, prob->l, (const double*)prob->A, (const double*)prob->b,
                   (double*)prob->x, prob->mu0, t, tol, maxit, screen != 0, check_every, col_norms_dev, col_stats,
-                  kept_rows_dev, ws, info, st, grp, kept_groups_dev, listed_groups, sw, holdout_sum);
+                  kept_rows_dev, ws, info, st, grp, kept_groups_dev, listed_groups, sw, holdout_sum, ic);
   else
     solve<float>(prob->dtype, prob->m, prob->n, prob->l, (const float*)prob->A, (const float*)prob->b,
                  (float*)prob->x, prob->mu0, t, tol, maxit, screen != 0, check_every, col_norms_dev, col_stats,
-                 kept_rows_dev, ws, info, st, grp, kept_groups_dev, listed_groups, sw, holdout_sum);
+                 kept_rows_dev, ws, info, st, grp, kept_groups_dev, listed_groups, sw, holdout_sum, ic);
 }
 
 }  // namespace glx
@@ -793,6 +906,142 @@ int glx_certified_solve_sw(const glx_problem* prob, const void* sample_w, const 
     const SampleView sw{sample_w, holdout_w, nullptr};
     certified_run(prob, t, tol, maxit, screen, check_every, col_norms_dev, col_stats, kept_rows_dev, ws, wsb, info,
                   stream, nullptr, nullptr, nullptr, &sw, holdout_sum);
+  });
+}
+
+/* ---- the unpenalised intercept (DESIGN.md "Intercept") ---- */
+
+int glx_screen_guard_ic(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l,
+                        const double* col_stats, double b_norm, double weight_sum, double mean_sq, double* out) {
+  return guarded([&] {
+    if (!rec || !out || !col_stats) throw Error{GLX_E_INVALID, "null argument"};
+    check_shape(dtype, m, n, l);
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    if (!(weight_sum > 0.0) || !std::isfinite(weight_sum))
+      throw Error{GLX_E_INVALID, "intercept: weight_sum must be positive and finite"};
+    screen_guard_ic(rec, mu, dtype, m, n, l, col_stats, b_norm, weight_sum, mean_sq, out);
+  });
+}
+
+namespace {
+// the one-launch intercept entries' workspace: [glx_screen_workspace_bytes(m, n) | column means |
+// the centring finalize's partials | its counter]
+struct IcStepWs {
+  double* cmean;
+  double* part;
+  unsigned* cnt;
+};
+size_t ic_step_carve(int64_t m, int64_t n, void* base, StepWs* head, IcStepWs* out) {
+  Carver c(base);
+  c.take(step_carve(m, n, base, head) - 256);
+  IcStepWs w;
+  w.cmean = static_cast<double*>(c.take(sizeof(double) * (size_t)n));
+  w.part = static_cast<double*>(c.take(cert_csum_part_bytes()));
+  w.cnt = static_cast<unsigned*>(c.take(256));
+  if (out) *out = w;
+  return c.off + 256;
+}
+}  // namespace
+
+int glx_intercept_workspace_bytes(int64_t m, int64_t n, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    if (m <= 0 || n <= 0) throw Error{GLX_E_INVALID, "m, n must be positive"};
+    *bytes = ic_step_carve(m, n, nullptr, nullptr, nullptr);
+  });
+}
+
+int glx_col_norms_ic(int dtype, int64_t m, int64_t n, const void* A, const void* sample_w, double weight_sum,
+                     double* norms_dev, double* means_dev, double* stats_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_shape(dtype, m, n, 1);
+    if (!A || !norms_dev || !means_dev || !stats_dev) throw Error{GLX_E_INVALID, "null argument"};
+    check_sample(sample_w, nullptr);
+    if (!(weight_sum > 0.0) || !std::isfinite(weight_sum))
+      throw Error{GLX_E_INVALID, "intercept: weight_sum must be positive and finite"};
+    check_ws(ic_step_carve(m, n, nullptr, nullptr, nullptr), ws, wsb, "glx_intercept_workspace_bytes");
+    StepWs w;
+    ic_step_carve(m, n, ws, &w, nullptr);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    GLX_HIP(hipMemsetAsync(w.ccnt, 0, col_norms_count_bytes(n), st));
+    const Red red{w.part, w.ticket, stats_dev}, red_mean{w.part, w.ticket, stats_dev + 2};
+    if (dtype == GLX_F64)
+      launch_col_norms_c<double>((const double*)A, (const double*)sample_w, weight_sum, m, n, norms_dev, means_dev,
+                                 w.cpart, w.ccnt, red_mean, red, st);
+    else
+      launch_col_norms_c<float>((const float*)A, (const float*)sample_w, weight_sum, m, n, norms_dev, means_dev,
+                                w.cpart, w.ccnt, red_mean, red, st);
+    check_launch();
+  });
+}
+
+int glx_cert_fin_ic(int dtype, int64_t m, int64_t l, const void* P, int S, const void* b, const void* sample_w,
+                    const void* holdout_w, double weight_sum, void* rhat_out, double* means_dev, void* rc_out,
+                    void* rw_out, double* sums_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_shape(dtype, m, 1, l);
+    if (S < 0 || S > kMaxSplit) throw Error{GLX_E_INVALID, "S must be in 0 .. 64"};
+    if ((S > 0) != (P != nullptr)) throw Error{GLX_E_INVALID, "P goes with S > 0"};
+    if (!b || !rhat_out || !means_dev || !rw_out || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
+    if ((reinterpret_cast<uintptr_t>(sample_w) | reinterpret_cast<uintptr_t>(holdout_w)) & 15)
+      throw Error{GLX_E_INVALID, "sample_w and holdout_w must be 16-byte aligned"};
+    if (!(weight_sum > 0.0) || !std::isfinite(weight_sum))
+      throw Error{GLX_E_INVALID, "intercept: weight_sum must be positive and finite"};
+    check_ws(ic_step_carve(1, 1, nullptr, nullptr, nullptr), ws, wsb, "glx_intercept_workspace_bytes");
+    StepWs w;
+    IcStepWs iw;
+    ic_step_carve(1, 1, ws, &w, &iw);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    GLX_HIP(hipMemsetAsync(iw.cnt, 0, 256, st));
+    const Red red{w.part, w.ticket, sums_dev};
+    auto go = [&](auto* tag) {
+      typedef std::remove_pointer_t<decltype(tag)> T;
+      launch_cert_csum<T>((const T*)P, S, (const T*)b, (const T*)sample_w, (T*)rhat_out, m, l, weight_sum, iw.part,
+                          iw.cnt, means_dev, st);
+      launch_cert_fin_c<T>((const T*)rhat_out, (const T*)b, (const T*)sample_w, (const T*)holdout_w, means_dev,
+                           (T*)rc_out, (T*)rw_out, m * l, l, red, st);
+    };
+    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
+    else go(static_cast<float*>(nullptr));
+    check_launch();
+  });
+}
+
+int glx_certified_ic_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int screen, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    check_shape(dtype, m, n, l);
+    *bytes = carve(dtype, m, n, l, screen != 0, true, nullptr, nullptr, 0, true, true);
+  });
+}
+
+int glx_certified_ic_describe(int dtype, int64_t m, int64_t n, int64_t l, int screen, char* out, size_t cap) {
+  return guarded([&] {
+    if (!out || cap == 0) throw Error{GLX_E_INVALID, "null out"};
+    check_shape(dtype, m, n, l);
+    std::snprintf(out, cap, "%s; residual=centring finalize (k_cert_csum, k_cert_fin_c)",
+                  describe_certified(dtype, m, n, l, screen != 0).c_str());
+  });
+}
+
+int glx_certified_solve_ic(const glx_problem* prob, const void* sample_w, const void* holdout_w, double weight_sum,
+                           double t, double tol, int64_t maxit, int screen, int check_every,
+                           const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev, void* ws,
+                           size_t wsb, glx_certified_info* info, double* holdout_sum, double* intercept_out,
+                           void* stream) {
+  return guarded([&] {
+    check_sample(sample_w, holdout_w);
+    check_intercept(weight_sum, intercept_out);
+    if (holdout_sum != nullptr) *holdout_sum = 0.0;
+    const SampleView sw{sample_w, holdout_w, nullptr};
+    InterceptView ic;
+    ic.sigma = weight_sum;
+    ic.mean_host = intercept_out;
+    certified_run(prob, t, tol, maxit, screen, check_every, col_norms_dev, col_stats, kept_rows_dev, ws, wsb, info,
+                  stream, nullptr, nullptr, nullptr, sample_w != nullptr ? &sw : nullptr, holdout_sum, &ic);
+    for (int64_t c = 0; c < prob->l; ++c) intercept_out[c] = -intercept_out[c];   // c = -r-bar
   });
 }
 

@@ -298,6 +298,44 @@ _SIGS = {
                                  c_size_t, c_void_p]),
     "glx_cert_fin_sw": (c_int, [c_int, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_certificate_ic_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "glx_certificate_ic_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_char_p, c_size_t]),
+    "glx_certificate_ic": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double,
+                                   c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p, POINTER(c_double),
+                                   POINTER(c_double), POINTER(c_double), c_void_p, c_size_t, c_void_p]),
+    "glx_group_certificate_ic_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64,
+                                                         POINTER(c_size_t)]),
+    "glx_group_certificate_ic_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_char_p,
+                                                  c_size_t]),
+    "glx_group_certificate_ic": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+                                         c_void_p, c_void_p, POINTER(c_double), POINTER(c_double),
+                                         POINTER(c_double), c_void_p, c_size_t, c_void_p]),
+    "glx_certified_ic_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, POINTER(c_size_t)]),
+    "glx_certified_ic_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_char_p, c_size_t]),
+    "glx_certified_solve_ic": (c_int, [POINTER(GlxProblem), c_void_p, c_void_p, c_double, c_double, c_double,
+                                       c_int64, c_int, c_int, c_void_p, POINTER(c_double), c_void_p, c_void_p,
+                                       c_size_t, POINTER(GlxCertifiedInfo), POINTER(c_double), POINTER(c_double),
+                                       c_void_p]),
+    "glx_group_certified_ic_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int,
+                                                       POINTER(c_size_t)]),
+    "glx_group_certified_ic_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_char_p,
+                                                c_size_t]),
+    "glx_group_certified_solve_ic": (c_int, [POINTER(GlxProblem), c_int64, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_double, c_double, c_double, c_int64, c_int, c_int,
+                                             c_void_p, POINTER(c_double), c_void_p, c_void_p, c_void_p, c_size_t,
+                                             POINTER(GlxGroupCertifiedInfo), POINTER(c_double),
+                                             POINTER(c_double), c_void_p]),
+    "glx_screen_guard_ic": (c_int, [POINTER(c_double), c_double, c_int, c_int64, c_int64, c_int64,
+                                    POINTER(c_double), c_double, c_double, c_double, POINTER(c_double)]),
+    "glx_group_screen_guard_ic": (c_int, [POINTER(c_double), c_double, c_int, c_int64, c_int64, c_int64,
+                                          c_int64, c_double, c_double, POINTER(c_double), c_double, c_double,
+                                          c_double, POINTER(c_double)]),
+    "glx_intercept_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
+    "glx_col_norms_ic": (c_int, [c_int, c_int64, c_int64, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_cert_fin_ic": (c_int, [c_int, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "glx_comm_unique_id": (c_int, [POINTER(c_uint8)]),
     "glx_comm_create": (c_int, [POINTER(c_void_p), POINTER(c_uint8), c_int, c_int]),
     "glx_comm_create_host": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),

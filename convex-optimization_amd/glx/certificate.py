@@ -221,6 +221,50 @@ def _group_record_sw(xd, Ad, bd, mu: float, gw, norms: bool, sw, hw=None):
     return list(rec), gn, buf.value.decode(), float(hs.value)
 
 
+def _sigma(sw, m: int) -> float:
+    """sigma = sum_j w_j on the host in float64, from the weights as rounded to A's dtype (m without)."""
+    return float(m) if sw is None else float(np.sum(sw, dtype=np.float64))
+
+
+def _record_ic(xd, Ad, bd, mu: float, fused: int, norms: bool, sw, sigma: float, hw=None, gw=None):
+    """glx_certificate_ic / glx_group_certificate_ic (``gw``): the record of the problem with an intercept,
+    (rec, norms, plan, holdout_sum, intercept (l float64))."""
+    m, n = Ad.shape
+    l = xd.shape[1]
+    device = Ad.device
+    gdt = _lib.GLX_F64 if Ad.dtype == torch.float64 else _lib.GLX_F32
+    rec = (ctypes.c_double * 8)()
+    hs = ctypes.c_double(0.0)
+    icpt = (ctypes.c_double * l)()
+    swp = None if sw is None else sw.data_ptr()
+    hwp = None if hw is None else hw.data_ptr()
+    buf = ctypes.create_string_buffer(2048)
+    with torch.cuda.device(device):
+        nb = ctypes.c_size_t(0)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        if gw is None:
+            check(lib().glx_certificate_ic_workspace_bytes(gdt, m, n, l, ctypes.byref(nb)))
+            ws = torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+            rn = torch.empty(n, dtype=torch.float64, device=device) if norms else None
+            check(lib().glx_certificate_ic(gdt, m, n, l, Ad.data_ptr(), xd.data_ptr(), bd.data_ptr(), float(mu),
+                                           int(fused), swp, hwp, float(sigma), None,
+                                           None if rn is None else rn.data_ptr(), rec, ctypes.byref(hs), icpt,
+                                           ws.data_ptr(), ws.numel(), stream))
+            check(lib().glx_certificate_ic_describe(gdt, m, n, l, int(fused), buf, len(buf)))
+        else:
+            ptr, w = gw
+            G = int(w.size)
+            check(lib().glx_group_certificate_ic_workspace_bytes(gdt, m, n, l, G, ctypes.byref(nb)))
+            ws = torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+            rn = torch.empty(G, dtype=torch.float64, device=device) if norms else None
+            check(lib().glx_group_certificate_ic(gdt, m, n, l, Ad.data_ptr(), xd.data_ptr(), bd.data_ptr(), float(mu),
+                                                 G, ptr.ctypes.data, w.ctypes.data, swp, hwp, float(sigma), None,
+                                                 None if rn is None else rn.data_ptr(), rec, ctypes.byref(hs), icpt,
+                                                 ws.data_ptr(), ws.numel(), stream))
+            check(lib().glx_group_certificate_ic_describe(gdt, m, n, l, int(np.diff(ptr).max()), buf, len(buf)))
+    return list(rec), rn, buf.value.decode(), float(hs.value), np.array(list(icpt), dtype=np.float64)
+
+
 def compose_groups(rec, mu: float) -> Dict[str, Any]:
     """:func:`compose` for the group certificate's record [||r||^2, <r, b>, sum_g w_g ||x_[g]||,
     max_g ||g_[g]|| / w_g, kkt_max, sum_g kkt_g^2, nonzero groups, 0]: the same arithmetic,
@@ -280,7 +324,7 @@ def record(x, A, b, mu, *, fused: int = 0) -> np.ndarray:
 
 
 def certificate(x, A, b, mu, groups=None, weights=None, *, fused: int = 0, row_norms: bool = False,
-                sample_weight=None) -> Dict[str, Any]:
+                sample_weight=None, fit_intercept: bool = False) -> Dict[str, Any]:
     """The duality gap and KKT violation of the iterate ``x`` at ``mu`` (module docstring).
 
     ``x`` (n x l), ``A`` (m x n) and ``b`` (m x l) are NumPy arrays or torch tensors and are not
@@ -299,7 +343,14 @@ def certificate(x, A, b, mu, groups=None, weights=None, *, fused: int = 0, row_n
 
     ``sample_weight`` (None: today's path, bit for bit): m observation weights ``w_j >= 0``, the
     certificate of ``1/2 sum_j w_j ||(A x - b)_j||^2 + mu Omega(x)`` (:func:`check_sample_weight`; it
-    composes with ``groups`` / ``weights``, which weigh features). A is neither copied nor scaled."""
+    composes with ``groups`` / ``weights``, which weigh features). A is neither copied nor scaled.
+
+    ``fit_intercept`` (False: today's path, call for call): the certificate of
+    ``min_c 1/2 sum_j w_j ||(A x + 1 c^T - b)_j||^2 + mu Omega(x)`` with an unpenalised intercept c in R^l
+    (DESIGN.md "Intercept"). c is eliminated exactly: ``intercept`` (l float64 values) is minus the
+    weighted column mean of A x - b, ``primal``, ``dual``, ``gap`` and ``rel_gap`` speak of the minimum
+    over c, and ``gmax`` / the row norms are those of A^T (w o r_c) with r_c the centred residual. It
+    composes with ``groups`` / ``weights`` and ``sample_weight``; A is not centred."""
     mu = float(mu)
     if not mu >= 0.0:
         raise ValueError("mu must be >= 0")
@@ -308,6 +359,15 @@ def certificate(x, A, b, mu, groups=None, weights=None, *, fused: int = 0, row_n
     sw = check_sample_weight(sample_weight, _rows_of(A), _np_dtype(A))
     xd, Ad, bd = _inputs(x, A, b)
     swd = _sw_device(sw, Ad.device)
+    if fit_intercept:
+        rec, nrm, plan, _, icpt = _record_ic(xd, Ad, bd, mu, fused, row_norms, swd, _sigma(sw, Ad.shape[0]), None, gw)
+        out = compose(rec, mu) if gw is None else compose_groups(rec, mu)
+        out["plan"] = plan
+        out["intercept"] = icpt
+        if row_norms:
+            key = "row_norms" if gw is None else "group_norms"
+            out[key] = nrm if isinstance(A, torch.Tensor) else nrm.cpu().numpy()
+        return out
     if gw is not None:
         if swd is not None:
             rec, gn, plan, _ = _group_record_sw(xd, Ad, bd, mu, gw, row_norms, swd)
@@ -329,14 +389,18 @@ def certificate(x, A, b, mu, groups=None, weights=None, *, fused: int = 0, row_n
     return out
 
 
-def mu_max(A, b, groups=None, weights=None, sample_weight=None) -> float:
+def mu_max(A, b, groups=None, weights=None, sample_weight=None, fit_intercept: bool = False) -> float:
     """The smallest mu for which x = 0 is optimal, max_i ||(A^T b)_i||_2: the certificate's gmax at
     x = 0, where r = -b. With ``groups`` / ``weights``: max_g ||(A^T b)_[g]||_F / w_g. With
-    ``sample_weight``: of A^T W b."""
+    ``sample_weight``: of A^T W b. With ``fit_intercept``: of A^T W (b - 1 b-bar^T), b-bar the weighted
+    column mean of b (at and above it the solution is x = 0 with the intercept b-bar)."""
     gw = check_groups(groups, weights, np.shape(A)[1] if len(np.shape(A)) == 2 else -1,
                       np.shape(b)[1] if len(np.shape(b)) == 2 else 1)
     sw = check_sample_weight(sample_weight, _rows_of(A), _np_dtype(A))
     xd, Ad, bd = _inputs(None, A, b)
+    if fit_intercept:
+        return float(_record_ic(xd, Ad, bd, 0.0, 0, False, _sw_device(sw, Ad.device), _sigma(sw, Ad.shape[0]), None,
+                                gw)[0][3])
     if sw is not None:
         swd = _sw_device(sw, Ad.device)
         if gw is not None:

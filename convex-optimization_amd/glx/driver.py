@@ -129,15 +129,18 @@ def solve_routine(mode: str, func: Callable, x0, A, b, mu, opts, errfun, errfun_
 
 
 def certified_rows(mode: str, x0, A, b, mu, errfun, errfun_exact, sparsity, xstar=None, certify=False,
-                   headers=None) -> Dict[str, Dict[str, str]]:
+                   headers=None, intercept: bool = False, intercepts=None) -> Dict[str, Dict[str, str]]:
     """The rows ``--certified`` appends: ``mode`` "solve" gives one row "Certified" (glx.solve_certified
-    at mu from x0), "path" one row per mu of glx.path's default grid. Same keys as solve_routine's."""
+    at mu from x0), "path" one row per mu of glx.path's default grid. Same keys as solve_routine's.
+    ``intercept``: the solves fit an unpenalised intercept (``fit_intercept=True``); ``intercepts`` (a
+    dict) then receives each row's intercept."""
     from glx.screen import path, solve_certified
+    kw = {"fit_intercept": True} if intercept else {}
     if mode == "solve":
-        x, info = solve_certified(A, b, mu, x0=x0)
+        x, info = solve_certified(A, b, mu, x0=x0, **kw)
         results = [("Certified", x, info)]
     elif mode == "path":
-        results = [("Certified mu=%.3E" % m_, x, info) for m_, x, info in path(A, b)]
+        results = [("Certified mu=%.3E" % m_, x, info) for m_, x, info in path(A, b, **kw)]
     else:
         raise ValueError("certified must be 'solve' or 'path'")
     rows = {}
@@ -156,6 +159,8 @@ def certified_rows(mode: str, x0, A, b, mu, errfun, errfun_exact, sparsity, xsta
         logging.getLogger(LOGGER).info(("[%-10s]: " % name) + ", ".join(k + ": " + v for k, v in d.items())
                                        + ", rel_gap: %3.2E, kept: %d" % (info["rel_gap"], info["kept"]))
         rows[name] = d
+        if intercept and intercepts is not None:
+            intercepts[name] = info["intercept"]
     return rows
 
 
@@ -194,7 +199,7 @@ def setup_logger(log_file: Optional[str], level=logging.INFO) -> logging.Logger:
 def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Dict[str, dict]] = None,
         xstar: Optional[np.ndarray] = None, dest_dir: Optional[str] = None, seed: int = SEED,
         size=(256, 512, 2), stream: TextIO = sys.stdout, certify: bool = False,
-        certified: Optional[str] = None, cv: int = 0) -> Dict[str, Any]:
+        certified: Optional[str] = None, cv: int = 0, intercept: bool = False) -> Dict[str, Any]:
     """The body of main.py's __main__ block (main.py:141-235) without the CVX solvers and plots.
 
     ``solvers`` defaults to the GPU solvers; tests pass other callables with the same signature.
@@ -203,7 +208,8 @@ def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Di
     "path" appends certified_rows' rows to the table (they have no objective history). ``cv`` = K >= 2
     appends the K-fold cross-validation table of glx.cv_path behind the Statistics output: one line
     per mu with the mean validation loss, its standard error and a marker on the best and on the
-    one-standard-error choice.
+    one-standard-error choice. ``intercept`` passes ``fit_intercept=True`` to the certified solves and to
+    cv_path and appends one line with the largest magnitude of the fitted intercepts behind each.
     Returns {"log_dicts", "f_hists", "f_star", "xs"} (and "cv": glx.cv_path's dict with ``cv``).
     """
     m, n, l = size
@@ -220,16 +226,23 @@ def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Di
             f_hists[mode] = np.asarray(out["f_hist"], dtype=np.float64)
         log_dicts[mode] = log_dict
         xs[mode] = x
+    icpts: Dict[str, Any] = {}
     if certified:
         for mode, d in certified_rows(certified, x0, A, b, mu, errfun, errfun_exact, sparsity, xstar,
-                                      certify).items():
+                                      certify, intercept=intercept, intercepts=icpts).items():
             log_dicts[mode] = d
     write_to_table(log_dicts, stream)
+    if certified and intercept:
+        stream.write("# Intercept (certified): max |c| = %.6e\n"
+                     % max(float(np.max(np.abs(c))) for c in icpts.values()))
     cv_out = None
     if cv:
         from glx.cv import cv_path, format_table
-        cv_out = cv_path(A, b, folds=int(cv))
+        cv_out = cv_path(A, b, folds=int(cv), fit_intercept=True) if intercept else cv_path(A, b, folds=int(cv))
         stream.write("# Cross-validation (%d folds)\n%s\n" % (int(cv), format_table(cv_out)))
+        if intercept:
+            stream.write("# Intercept (cross-validation): max |c| over folds and mu = %.6e\n"
+                         % max(float(np.max(np.abs(i["intercept"]))) for f in cv_out["info"] for i in f))
     f_star = obj_func(A, b, mu, u)
     if dest_dir:
         os.makedirs(dest_dir, exist_ok=True)
@@ -260,6 +273,9 @@ def main(argv=None) -> int:
     p.add_argument("--cv", type=int, default=0, metavar="K",
                    help="Append the K-fold cross-validation table of glx.cv_path over ten values of mu "
                         "(mu, mean, se, best and 1-SE markers).")
+    p.add_argument("--intercept", action="store_true",
+                   help="With --certified and --cv: fit an unpenalised intercept (fit_intercept=True) and "
+                        "print the largest magnitude of the fitted intercepts.")
     a = p.parse_args(argv)
     setup_logger(a.log)
     size = tuple(int(v) for v in a.size.split(","))
@@ -272,7 +288,7 @@ def main(argv=None) -> int:
             p.error(f"unknown solver(s) {unknown}; choose from {list(solvers)}")
         solvers = {k: solvers[k] for k in keep}
     run(solvers, xstar=xstar, dest_dir=a.dest_dir, seed=a.seed, size=size, stream=sys.stdout,
-        certify=a.certify, certified=a.certified, cv=a.cv)
+        certify=a.certify, certified=a.certified, cv=a.cv, intercept=a.intercept)
     return 0
 
 

@@ -979,3 +979,93 @@ def group_screen_guard_sw(rec, mu: float, dtype: int, m: int, n: int, l: int, ma
     check(lib().glx_group_screen_guard_sw(r, float(mu), int(dtype), int(m), int(n), int(l), int(max_run),
                                           float(w_min), float(gcol_max), float(col_sumsq), float(b_norm), out))
     return float(out[0]), float(out[1]), float(out[2])
+
+
+# ---- an unpenalised intercept (glx.h "an unpenalised intercept"; DESIGN.md "Intercept") ----
+def _ic_ws(m: int, n: int, device) -> torch.Tensor:
+    nb = ctypes.c_size_t(0)
+    check(lib().glx_intercept_workspace_bytes(int(m), int(n), ctypes.byref(nb)))
+    return torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+
+
+def weight_sum(sample_weight, m: int) -> float:
+    """sigma = sum_j w_j in float64 on the host, from the weights as they are stored (m without weights)."""
+    if sample_weight is None:
+        return float(m)
+    import numpy as np
+    w = sample_weight.detach().cpu().numpy() if isinstance(sample_weight, torch.Tensor) else np.asarray(sample_weight)
+    return float(np.sum(w, dtype=np.float64))
+
+
+def col_norms_ic(A: torch.Tensor, sample_weight: Optional[torch.Tensor] = None,
+                 sigma: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The centred weighted column norms sqrt(sum_j w_j (A_ji - a-bar_i)^2) with a-bar_i = sum_j w_j A_ji /
+    sigma (glx_col_norms_ic: two launches on :func:`col_norms`' slabs; ``sample_weight`` None: unit weights,
+    ``sigma`` None: their float64 sum). Returns (norms (n,), means (n,), stats = [max norm, sum norm^2,
+    max |mean|, sum mean^2]), float64 device tensors."""
+    m, n = A.shape
+    dev = A.device
+    if sample_weight is not None:
+        assert sample_weight.dtype == A.dtype and sample_weight.shape == (m,) and sample_weight.is_contiguous()
+    sigma = weight_sum(sample_weight, m) if sigma is None else float(sigma)
+    norms = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    means = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    stats = torch.full((4,), float("nan"), dtype=torch.float64, device=dev)
+    ws = _ic_ws(m, n, dev)
+    check(lib().glx_col_norms_ic(_dt(A), m, n, A.data_ptr(), _ptr(sample_weight), sigma, norms.data_ptr(),
+                                 means.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return norms, means, stats
+
+
+def cert_fin_ic(P: Optional[torch.Tensor], b: torch.Tensor, sample_weight: Optional[torch.Tensor] = None,
+                holdout_weight: Optional[torch.Tensor] = None, sigma: Optional[float] = None,
+                want_rc: bool = True) -> Dict[str, torch.Tensor]:
+    """The centring finalize, its two launches (glx_cert_fin_ic: k_cert_csum, k_cert_fin_c). ``P``: (S, m, l)
+    slabs of A x, or None for the null product; ``b`` (m, l); the weights m values of b's dtype or None
+    (unit weights). Returns {"rhat": fl(sum of the slabs) - b, "means": its l weighted column means
+    (float64), "rc": (T)((double)rhat - mean) (None without ``want_rc``), "rw": fl(w rc), "sums": float64
+    [sum w rc^2, sum w rc b, sum v rc^2 (NaN without hold-out weights)]}."""
+    m, l = b.shape
+    dev = b.device
+    S = 0 if P is None else int(P.shape[0])
+    if P is not None:
+        assert P.shape == (S, m, l) and P.is_contiguous() and P.dtype == b.dtype
+    for v in (sample_weight, holdout_weight):
+        assert v is None or (v.dtype == b.dtype and v.shape == (m,) and v.is_contiguous())
+    sigma = weight_sum(sample_weight, m) if sigma is None else float(sigma)
+    rhat = torch.full((m, l), float("nan"), dtype=b.dtype, device=dev)
+    rc = torch.full((m, l), float("nan"), dtype=b.dtype, device=dev) if want_rc else None
+    rw = torch.full((m, l), float("nan"), dtype=b.dtype, device=dev)
+    means = torch.full((l,), float("nan"), dtype=torch.float64, device=dev)
+    sums = torch.full((3,), float("nan"), dtype=torch.float64, device=dev)
+    ws = _ic_ws(1, 1, dev)
+    check(lib().glx_cert_fin_ic(_dt(b), m, l, _ptr(P), S, b.data_ptr(), _ptr(sample_weight), _ptr(holdout_weight),
+                                sigma, rhat.data_ptr(), means.data_ptr(), _ptr(rc), rw.data_ptr(), sums.data_ptr(),
+                                ws.data_ptr(), ws.numel(), _stream(dev)))
+    return {"rhat": rhat, "means": means, "rc": rc, "rw": rw, "sums": sums}
+
+
+def screen_guard_ic(rec, mu: float, dtype: int, m: int, n: int, l: int, col_stats, b_norm: float, sigma: float,
+                    mean_sq: float) -> Tuple[float, float, float, float]:
+    """The rounding guard of the problem with an intercept (glx_screen_guard_ic, host only): ``rec`` the
+    centred record, ``col_stats`` :func:`col_norms_ic`'s four values, ``b_norm`` = sqrt(sum w b^2),
+    ``mean_sq`` = the sum of the squares of the record's intercept. Returns (s_safe, gap+, rho+, slack)."""
+    r = (ctypes.c_double * 8)(*[float(v) for v in rec])
+    cs = (ctypes.c_double * 4)(*[float(v) for v in col_stats])
+    out = (ctypes.c_double * 4)()
+    check(lib().glx_screen_guard_ic(r, float(mu), int(dtype), int(m), int(n), int(l), cs, float(b_norm),
+                                    float(sigma), float(mean_sq), out))
+    return tuple(float(v) for v in out)
+
+
+def group_screen_guard_ic(rec, mu: float, dtype: int, m: int, n: int, l: int, max_run: int, w_min: float,
+                          gcol_max: float, col_stats, b_norm: float, sigma: float,
+                          mean_sq: float) -> Tuple[float, float, float, float]:
+    """The grouped guard of the problem with an intercept (glx_group_screen_guard_ic, host only)."""
+    r = (ctypes.c_double * 8)(*[float(v) for v in rec])
+    cs = (ctypes.c_double * 4)(*[float(v) for v in col_stats])
+    out = (ctypes.c_double * 4)()
+    check(lib().glx_group_screen_guard_ic(r, float(mu), int(dtype), int(m), int(n), int(l), int(max_run),
+                                          float(w_min), float(gcol_max), cs, float(b_norm), float(sigma),
+                                          float(mean_sq), out))
+    return tuple(float(v) for v in out)

@@ -20,6 +20,11 @@ the group kernel, and the test runs on groups,
 
 so that proving a group zero removes all its columns from A at once (``glx_group_certified_solve``;
 DESIGN.md "Feature groups and weights").
+
+With ``fit_intercept=True`` the loss carries an unpenalised intercept, ``1/2 sum_j w_j ||(A x + 1 c^T -
+b)_j||^2``, which is eliminated exactly: the residual is centred between the two dense passes, the step
+is 1 / lambda_max(A^T W P A) and the test uses the centred column norms (the ``_ic`` entries; DESIGN.md
+"Intercept"). A is never centred or copied.
 """
 from __future__ import annotations
 
@@ -32,8 +37,8 @@ import torch
 
 from . import _lib
 from ._lib import GlxCertifiedInfo, GlxGroupCertifiedInfo, GlxProblem, check, lib
-from .certificate import (_inputs, _np_dtype, _rows_of, _sw_device, check_groups, check_sample_weight, compose,
-                          compose_groups, mu_max)
+from .certificate import (_inputs, _np_dtype, _rows_of, _sigma, _sw_device, check_groups, check_sample_weight,
+                          compose, compose_groups, mu_max)
 
 DEFAULT_MAXIT = 100000
 
@@ -114,9 +119,12 @@ class _Prepared:
     """What a sequence of solves on one (A, b) shares: the device copies, the step, the column norms
     and the workspace."""
 
-    def __init__(self, A, b, screen: bool, comm=None, gw=None, sw=None, weighted: bool = False):
+    def __init__(self, A, b, screen: bool, comm=None, gw=None, sw=None, weighted: bool = False,
+                 intercept: bool = False):
         """``sw``: the checked host sample weights (None: the unweighted problem). ``weighted=True``
-        sizes the workspace for weights that arrive later (:meth:`set_weights`, one per fold)."""
+        sizes the workspace for weights that arrive later (:meth:`set_weights`, one per fold).
+        ``intercept=True``: the problem with an unpenalised intercept (libglx's ``_ic`` entries, which
+        take the weights or none)."""
         if comm is not None:
             raise ValueError("the certified solve is single-GPU: it takes no communicator")
         _, self.Ad, self.bd = _inputs(None, A, b)
@@ -129,10 +137,11 @@ class _Prepared:
         self.gw = gw   # (group_ptr, weights) on the host, or None: rows
         self.G = 0 if gw is None else int(gw[1].size)
         self.max_run = 0 if gw is None else int(np.diff(gw[0]).max())
-        self.weighted = bool(weighted) or sw is not None
+        self.intercept = bool(intercept)
+        self.weighted = bool(weighted) or sw is not None or self.intercept
         with torch.cuda.device(self.device):
             nb = ctypes.c_size_t(0)   # (first: it refuses what the solve would, before any launch)
-            suffix = "_sw" if self.weighted else ""
+            suffix = "_ic" if self.intercept else ("_sw" if self.weighted else "")
             if gw is None:
                 check(getattr(lib(), "glx_certified%s_workspace_bytes" % suffix)(
                     self.gdt, self.m, self.n, self.l, int(self.screen), ctypes.byref(nb)))
@@ -151,6 +160,17 @@ class _Prepared:
             raise ValueError("this preparation was sized for the unweighted problem")
         with torch.cuda.device(self.device):
             self.sw = _sw_device(sw, self.device)
+            if self.intercept:
+                # sigma on the host in float64 from the weights as rounded to A's dtype; the step is
+                # 1 / lambda_max(A^T W P A) and the column figures are the centred ones
+                self.sigma = _sigma(sw, self.m)
+                self.lam = float(_lambda_max(self.Ad, sample_weight=self.sw, center_sum=self.sigma))
+                self.t = 1.0 / self.lam
+                self.cn = self.cstats = None
+                if self.screen:
+                    self.cn, _, st = kernels.col_norms_ic(self.Ad, self.sw, self.sigma)
+                    self.cstats = (ctypes.c_double * 4)(*st.cpu().tolist())
+                return
             self.lam = float(_lambda_max(self.Ad, sample_weight=self.sw))
             self.t = 1.0 / self.lam
             self.cn = self.cstats = None
@@ -177,10 +197,17 @@ class _Prepared:
             return self._solve_groups(mu, xd, p, rows, tol, maxit, check_every, hold)
         info = GlxCertifiedInfo()
         hs = ctypes.c_double(0.0)
+        icpt = (ctypes.c_double * self.l)()
         with torch.cuda.device(self.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             cn = None if self.cn is None else self.cn.data_ptr()
-            if self.sw is None:
+            if self.intercept:
+                check(lib().glx_certified_solve_ic(ctypes.byref(p), None if self.sw is None else self.sw.data_ptr(),
+                                                   None if hold is None else hold.data_ptr(), self.sigma, self.t,
+                                                   float(tol), int(maxit), int(self.screen), int(check_every), cn,
+                                                   self.cstats, rows.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
+                                                   ctypes.byref(info), ctypes.byref(hs), icpt, stream))
+            elif self.sw is None:
                 check(lib().glx_certified_solve(ctypes.byref(p), self.t, float(tol), int(maxit), int(self.screen),
                                                 int(check_every), cn, self.cstats, rows.data_ptr(),
                                                 self.ws.data_ptr(), self.ws.numel(), ctypes.byref(info), stream))
@@ -191,9 +218,13 @@ class _Prepared:
                                                    rows.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
                                                    ctypes.byref(info), ctypes.byref(hs), stream))
         out: Dict[str, Any] = compose(list(info.cert), mu)
-        out["plan"] = (_lib.certified_describe(self.gdt, self.m, self.n, self.l, self.screen) if self.sw is None
-                       else _describe(lib().glx_certified_sw_describe, self.gdt, self.m, self.n, self.l,
-                                      int(self.screen)))
+        if self.intercept:
+            out["plan"] = _describe(lib().glx_certified_ic_describe, self.gdt, self.m, self.n, self.l, int(self.screen))
+            out["intercept"] = np.array(list(icpt), dtype=np.float64)
+        else:
+            out["plan"] = (_lib.certified_describe(self.gdt, self.m, self.n, self.l, self.screen) if self.sw is None
+                           else _describe(lib().glx_certified_sw_describe, self.gdt, self.m, self.n, self.l,
+                                          int(self.screen)))
         if hold is not None:
             out["holdout_sum"] = float(hs.value)
         nc = int(info.compactions)
@@ -216,10 +247,18 @@ class _Prepared:
         ginfo = GlxGroupCertifiedInfo()
         hs = ctypes.c_double(0.0)
         grps = torch.full((self.G,), -1, dtype=torch.int32, device=self.device)
+        icpt = (ctypes.c_double * self.l)()
         with torch.cuda.device(self.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             cn = None if self.cn is None else self.cn.data_ptr()
-            if self.sw is None:
+            if self.intercept:
+                check(lib().glx_group_certified_solve_ic(
+                    ctypes.byref(p), self.G, ptr.ctypes.data, w.ctypes.data,
+                    None if self.sw is None else self.sw.data_ptr(), None if hold is None else hold.data_ptr(),
+                    self.sigma, self.t, float(tol), int(maxit), int(self.screen), int(check_every), cn, self.cstats,
+                    rows.data_ptr(), grps.data_ptr(), self.ws.data_ptr(), self.ws.numel(), ctypes.byref(ginfo),
+                    ctypes.byref(hs), icpt, stream))
+            elif self.sw is None:
                 check(lib().glx_group_certified_solve(
                     ctypes.byref(p), self.G, ptr.ctypes.data, w.ctypes.data, self.t, float(tol), int(maxit),
                     int(self.screen), int(check_every), cn, self.cstats,
@@ -233,10 +272,15 @@ class _Prepared:
                     self.ws.numel(), ctypes.byref(ginfo), ctypes.byref(hs), stream))
         info = ginfo.base
         out: Dict[str, Any] = compose_groups(list(info.cert), mu)
-        out["plan"] = (_lib.group_certified_describe(self.gdt, self.m, self.n, self.l, self.max_run, self.screen)
-                       if self.sw is None else
-                       _describe(lib().glx_group_certified_sw_describe, self.gdt, self.m, self.n, self.l,
-                                 self.max_run, int(self.screen)))
+        if self.intercept:
+            out["plan"] = _describe(lib().glx_group_certified_ic_describe, self.gdt, self.m, self.n, self.l,
+                                    self.max_run, int(self.screen))
+            out["intercept"] = np.array(list(icpt), dtype=np.float64)
+        else:
+            out["plan"] = (_lib.group_certified_describe(self.gdt, self.m, self.n, self.l, self.max_run, self.screen)
+                           if self.sw is None else
+                           _describe(lib().glx_group_certified_sw_describe, self.gdt, self.m, self.n, self.l,
+                                     self.max_run, int(self.screen)))
         if hold is not None:
             out["holdout_sum"] = float(hs.value)
         nc = int(info.compactions)
@@ -264,7 +308,7 @@ class _Prepared:
 
 def solve_certified(A, b, mu, x0=None, tol: float = 1e-6, maxit: int = DEFAULT_MAXIT, screen: bool = True,
                     check_every: int = 10, comm=None, groups=None, weights=None, sample_weight=None,
-                    holdout_weight=None) -> Tuple[Any, Dict[str, Any]]:
+                    holdout_weight=None, fit_intercept: bool = False) -> Tuple[Any, Dict[str, Any]]:
     """Solve min_x 1/2 ||A x - b||_F^2 + mu sum_i ||x_i||_2 until the duality gap is at most ``tol``
     of the primal objective (or ``maxit`` iterations in total).
 
@@ -292,12 +336,21 @@ def solve_certified(A, b, mu, x0=None, tol: float = 1e-6, maxit: int = DEFAULT_M
     row-duplicated one). The step is 1 / lambda_max(A^T W A), screening runs on the weighted column
     norms under the weighted guard, and ``info`` speaks of the weighted problem. ``holdout_weight``
     (m values >= 0): ``info["holdout_loss"]`` = 1/2 sum_j v_j ||(A x - b)_j||^2 / sum_j v_j of the
-    returned x, from the final certificate's own launch (``holdout_sum`` is the numerator's sum)."""
+    returned x, from the final certificate's own launch (``holdout_sum`` is the numerator's sum).
+
+    ``fit_intercept`` (False: today's path, call for call and bit for bit): solve
+    ``min_{x, c} 1/2 sum_j w_j ||(A x + 1 c^T - b)_j||^2 + mu Omega(x)`` with an unpenalised intercept c in
+    R^l (DESIGN.md "Intercept"). c is eliminated exactly, so the iteration is the same FISTA with the
+    residual centred between the two dense passes, the step is 1 / lambda_max(A^T W P A) and screening
+    runs on the centred weighted column norms; A is not centred or copied. ``info["intercept"]`` holds c
+    (l float64 values), ``primal`` / ``dual`` / ``gap`` / ``rel_gap`` speak of the minimum over c, and
+    ``holdout_loss`` = 1/2 sum_j v_j ||(A x + c - b)_j||^2 / sum_j v_j. It composes with ``groups`` /
+    ``weights``, ``sample_weight`` and ``holdout_weight``."""
     gw = _check_args(A, b, x0, tol, maxit, check_every, groups, weights)
     sw, hw = _check_sample(A, sample_weight, holdout_weight)
     if not float(mu) >= 0.0:
         raise ValueError("mu must be >= 0")
-    prep = _Prepared(A, b, screen, comm, gw, sw)
+    prep = _Prepared(A, b, screen, comm, gw, sw, intercept=bool(fit_intercept))
     xd, info = prep.solve(mu, x0, tol, maxit, check_every, _sw_device(hw, prep.device))
     _holdout_info(info, hw)
     return prep.result(xd), info
@@ -309,11 +362,12 @@ def path(A, b, mus: Optional[Sequence[float]] = None, n_mus: int = 10, mu_min_ra
     values from ``glx.mu_max(A, b)`` down to ``mu_min_ratio`` of it (:func:`mu_grid`). Each solve is
     warm-started from the one before; the column norms and lambda_max are computed once. ``kw``:
     ``tol``, ``maxit``, ``screen``, ``check_every``, ``groups``, ``weights``, ``sample_weight``,
-    ``holdout_weight`` of :func:`solve_certified` (with groups or sample weights the grid starts at
-    their ``mu_max``). Returns the list of ``(mu, x, info)``; at mu = mu_max the entry is x = 0 with
-    gap 0 and no iterations."""
+    ``holdout_weight``, ``fit_intercept`` of :func:`solve_certified` (with groups, sample weights or an
+    intercept the grid starts at their ``mu_max``). Returns the list of ``(mu, x, info)``; at mu = mu_max
+    the entry is x = 0 with gap 0 and no iterations (with an intercept the gap there is rounding dust:
+    the centred residual sums to zero only up to its own rounding)."""
     unknown = set(kw) - {"tol", "maxit", "screen", "check_every", "comm", "groups", "weights", "sample_weight",
-                         "holdout_weight"}
+                         "holdout_weight", "fit_intercept"}
     if unknown:
         raise TypeError("path() got unexpected keyword arguments %s" % sorted(unknown))
     tol, maxit = kw.get("tol", 1e-6), kw.get("maxit", DEFAULT_MAXIT)
@@ -324,13 +378,17 @@ def path(A, b, mus: Optional[Sequence[float]] = None, n_mus: int = 10, mu_min_ra
         mus = _check_mus(mus)
     else:
         mu_grid(1.0, n_mus, mu_min_ratio)   # the grid's own checks, before any device work
-    prep = _Prepared(A, b, kw.get("screen", True), kw.get("comm"), gw, sw)
+    prep = _Prepared(A, b, kw.get("screen", True), kw.get("comm"), gw, sw,
+                     intercept=bool(kw.get("fit_intercept", False)))
     if mus is None:
         mus = mu_grid(_top(prep, gw, sw), n_mus, mu_min_ratio)
     return _run_path(prep, mus, tol, maxit, check_every, hw)
 
 
 def _top(prep: "_Prepared", gw, sw) -> float:
+    if prep.intercept:
+        return mu_max(prep.Ad, prep.bd, None if gw is None else gw[0], None if gw is None else gw[1],
+                      sample_weight=sw, fit_intercept=True)
     if sw is not None:
         return mu_max(prep.Ad, prep.bd, None if gw is None else gw[0], None if gw is None else gw[1], sample_weight=sw)
     return mu_max(prep.Ad, prep.bd) if gw is None else mu_max(prep.Ad, prep.bd, gw[0], gw[1])

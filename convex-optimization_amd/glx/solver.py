@@ -92,7 +92,7 @@ def workspace(problem: GlxProblem, o: GlxOpts, device) -> torch.Tensor:
     return torch.empty(int(nbytes.value), dtype=torch.uint8, device=device)
 
 
-def _lambda_max(A: torch.Tensor, comm=None, max_steps: int = 400, sample_weight=None) -> float:
+def _lambda_max(A: torch.Tensor, comm=None, max_steps: int = 400, sample_weight=None, center_sum=None) -> float:
     """``np.max(LA.eigvals(A.T @ A))`` (gl_SGD_primal.py:35-37, gl_GD_primal.py:43-45) for the
     optional continuous_subgradient_flag, without forming the n x n Gram matrix and without a
     library eigensolver on the device: Lanczos on the operator v -> A^T (A v), whose two products
@@ -104,7 +104,9 @@ def _lambda_max(A: torch.Tensor, comm=None, max_steps: int = 400, sample_weight=
     or when the Krylov space is all of R^n (k = n: exact). A fixed start vector (seeded), so the
     result is the same on every rank and from run to run. ``sample_weight`` (a device tensor of m
     weights, or None): lambda_max(A^T W A), the intermediate A q times w between the two products
-    (a torch elementwise op, in setup only).
+    (a torch elementwise op, in setup only). ``center_sum`` (sigma = the sum of the weights, m without
+    them): lambda_max(A^T W P A) with P = I - 1 w^T / sigma, the operator of the problem with an intercept:
+    the intermediate becomes w o (A q - (w^T A q) / sigma), again elementwise ops in setup only.
 
     Leaving the loop because ``max_steps`` < n ran out is not silent: the Ritz value is then a lower
     bound of lambda_max that has not met the test above (a flat top of the spectrum does this), its
@@ -128,7 +130,11 @@ def _lambda_max(A: torch.Tensor, comm=None, max_steps: int = 400, sample_weight=
     for k in range(steps):
         Q[k] = q
         r, _ = kernels.residual(a, torch.from_numpy(np.ascontiguousarray(q[:, None])).to(a.device), zero)   # A q
-        if sample_weight is not None:
+        if center_sum is not None:                                                     # W P A q
+            wv = None if sample_weight is None else sample_weight.to(torch.float64)[:, None]
+            r = r - (r.sum() if wv is None else (wv * r).sum()) / float(center_sum)
+            r = r if wv is None else wv * r
+        elif sample_weight is not None:
             r = r * sample_weight.to(torch.float64)[:, None]                           # W A q
         w_t = kernels.gradient(a, r)                                                   # A^T A q
         if comm is not None:

@@ -936,6 +936,78 @@ int glx_cert_fin_sw(int dtype, int64_t m, int64_t l, const void* P, int S, const
                     const void* holdout_w, void* r_out, void* rw_out, double* sums_dev, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ---- an unpenalised intercept (DESIGN.md "Intercept"; additive entries, the ABI version stays 2) ----
+ *   P(x, c) = 1/2 sum_j w_j ||(A x + 1 c^T - b)_j||^2 + mu Omega(x),   c in R^l unpenalised,
+ * with w = 1 where sample_w is NULL. c is eliminated exactly: for fixed x it is minus the weighted
+ * column mean of r = A x - b, so min_c P is the problem above on the centred residual
+ * r_c = r - 1 r-bar^T. Between the two dense passes the finalize becomes two launches: k_cert_csum
+ * (r and its l weighted column means, combined in a fixed order by the last workgroup to arrive) and
+ * k_cert_fin_c (r_c, w r_c for the A^T pass, the sums on r_c). theta = s W^(1/2) r_c satisfies the dual's
+ * extra equality 1~^T theta = 0 by construction; the record keeps its layout with r_c in place of r.
+ * A is neither copied nor centred.
+ *   weight_sum    sigma = sum_j sample_w_j (m without sample weights), finite and > 0
+ *   intercept_out l host doubles: c = -r-bar of the returned / given x
+ *   holdout_sum   sum_j holdout_w_j ||(A x + c - b)_j||^2, the hold-out loss WITH the training intercept
+ * The solves' col_norms_dev / col_stats are glx_col_norms_ic's: the CENTRED weighted norms and four
+ * statistics. Refusals (GLX_E_INVALID, before any launch): those of the _sw entries, weight_sum not
+ * finite or <= 0, intercept_out NULL. Workspaces: the _sw entry's layout with the new pieces behind it. */
+int glx_certificate_ic_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes);
+int glx_certificate_ic_describe(int dtype, int64_t m, int64_t n, int64_t l, int fused, char* out, size_t cap);
+int glx_certificate_ic(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                       double mu, int fused, const void* sample_w, const void* holdout_w, double weight_sum,
+                       void* G_out, double* rownorm_out, double out[8], double* holdout_sum, double* intercept_out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int glx_group_certificate_ic_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, size_t* bytes);
+int glx_group_certificate_ic_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, char* out,
+                                      size_t cap);
+int glx_group_certificate_ic(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X,
+                             const void* b, double mu, int64_t G, const int32_t* group_ptr, const double* weights,
+                             const void* sample_w, const void* holdout_w, double weight_sum, void* G_out,
+                             double* groupnorm_out, double out[8], double* holdout_sum, double* intercept_out,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int glx_certified_ic_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int screen, size_t* bytes);
+int glx_certified_ic_describe(int dtype, int64_t m, int64_t n, int64_t l, int screen, char* out, size_t cap);
+int glx_certified_solve_ic(const glx_problem* prob, const void* sample_w, const void* holdout_w, double weight_sum,
+                           double t, double tol, int64_t maxit, int screen, int check_every,
+                           const double* col_norms_dev, const double col_stats[4], int32_t* kept_rows_dev,
+                           void* workspace, size_t workspace_bytes, glx_certified_info* info, double* holdout_sum,
+                           double* intercept_out, void* stream);
+int glx_group_certified_ic_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, int screen,
+                                           size_t* bytes);
+int glx_group_certified_ic_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, int screen,
+                                    char* out, size_t cap);
+int glx_group_certified_solve_ic(const glx_problem* prob, int64_t G, const int32_t* group_ptr,
+                                 const double* weights, const void* sample_w, const void* holdout_w,
+                                 double weight_sum, double t, double tol, int64_t maxit, int screen, int check_every,
+                                 const double* col_norms_dev, const double col_stats[4], int32_t* kept_rows_dev,
+                                 int32_t* kept_groups_dev, void* workspace, size_t workspace_bytes,
+                                 glx_group_certified_info* info, double* holdout_sum, double* intercept_out,
+                                 void* stream);
+/* The guards of the problem with an intercept (host only). col_stats = glx_col_norms_ic's four values,
+ * b_norm = sqrt(sum w b^2) (uncentred), mean_sq = sum_c r-bar_c^2 of the record's certificate (the
+ * squares of its intercept). out = [s_safe, gap+, rho+, slack]: row i is proven zero when
+ * s_safe rn_i + cn_i rho+ < mu - slack with cn_i the centred norm. */
+int glx_screen_guard_ic(const double rec[8], double mu, int dtype, int64_t m, int64_t n, int64_t l,
+                        const double col_stats[4], double b_norm, double weight_sum, double mean_sq, double out[4]);
+int glx_group_screen_guard_ic(const double rec[8], double mu, int dtype, int64_t m, int64_t n, int64_t l,
+                              int64_t max_run, double w_min, double gcol_max, const double col_stats[4],
+                              double b_norm, double weight_sum, double mean_sq, double out[4]);
+/* The new kernels by themselves (test surface). Workspace: glx_intercept_workspace_bytes(m, n) for the
+ * column norms, (1, 1) for the finalize.
+ * glx_col_norms_ic: means_dev[i] = sum_j w_j A_ji / sigma, norms_dev[i] = sqrt(sum_j w_j (A_ji - mean_i)^2)
+ *   (two launches on glx_col_norms' slabs), stats_dev = [max norm, sum norm^2, max |mean|, sum mean^2].
+ * glx_cert_fin_ic: the two launches of the centring finalize on S slabs P (S = 0: the null product):
+ *   rhat_out = fl(sum of the slabs) - b, means_dev = its l weighted column means, rc_out (may be NULL) =
+ *   the centred residual, rw_out = fl(w rc), sums_dev = [sum w rc^2, sum w rc b, sum holdout_w rc^2 (only
+ *   with holdout_w)]. sample_w = NULL: unit weights, the bits of all-ones. */
+int glx_intercept_workspace_bytes(int64_t m, int64_t n, size_t* bytes);
+int glx_col_norms_ic(int dtype, int64_t m, int64_t n, const void* A, const void* sample_w, double weight_sum,
+                     double* norms_dev, double* means_dev, double* stats_dev, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int glx_cert_fin_ic(int dtype, int64_t m, int64_t l, const void* P, int S, const void* b, const void* sample_w,
+                    const void* holdout_w, double weight_sum, void* rhat_out, double* means_dev, void* rc_out,
+                    void* rw_out, double* sums_dev, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- multi-GPU (row-sharded A; A^T r all-reduced, or reduce-scattered with the row-sharded step) ---- */
 #define GLX_COMM_ID_BYTES 128
 int  glx_comm_unique_id(uint8_t id[GLX_COMM_ID_BYTES]);
