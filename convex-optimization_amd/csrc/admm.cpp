@@ -10,76 +10,36 @@
 // a small record: the objective's two sums, the count for the logged sparsity and the two l x l
 // Gram matrices r^T r, s^T s, whose largest eigenvalues (a cyclic Jacobi sweep on the host) give
 // the spectral norms of the stop rule (:85-93).
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <limits>
 #include <string>
-#include <type_traits>
-#include <vector>
 
-#include "glx.h"
-#include "glx_internal.h"
+#include "glx_host.h"
 
 namespace glx {
 namespace {
 
-#define GLX_HIP(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) throw Error{GLX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
+// the Jacobi sweep, the trace and the stop rule are split_loop.h's (namespace split), shared with
+// admm_primal.cpp and alm.cpp; the carver, the pinned record and A's plan are glx_host.h's
+using namespace split;
+constexpr int kAdmmMaxL = split::kMaxL;
 
-inline void check_launch() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw Error{GLX_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)};
-}
-
-template <typename F>
-int guarded(F&& f) {
-  try {
-    f();
-    return GLX_OK;
-  } catch (const Error& e) {
-    g_last_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return GLX_E_STATE;
-  } catch (...) {
-    g_last_error = "unknown error";
-    return GLX_E_STATE;
-  }
-}
-
-// the carver, the pinned record, the Jacobi sweep and the trace are shared with admm_primal.cpp
-// (glx_internal.h, namespace admm; defined at the end of this file)
-using namespace admm;
-constexpr int kAdmmMaxL = admm::kMaxL;
-
-// The launch plans of a solve: A's is the session plan of a one-GPU line-search ProxGD at this
-// shape, i.e. the A^T R tile and split measured best for a fused epilogue where one fuses (both
-// forms of the row step run on it, so they see the same bits of g); K's is the planner's choice
-// for an m x m matrix. fuse_ok: the plan takes a fused epilogue and its tile is built for it.
-struct AdmmPlan {
-  int es = 8;
-  GemmPlan a{}, k{};
-  bool fuse_ok = false;
+// The launch plans of a solve: A's with its fuse condition (glx_host.h FusePlan); K's is the
+// planner's choice for an m x m matrix.
+struct AdmmPlan : FusePlan {
+  GemmPlan k{};
 };
 AdmmPlan admm_plan(int dtype, int64_t m, int64_t n, int64_t l, bool with_k = true) {
-  if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+  check_dtype(dtype);
   if (m <= 0 || n <= 0 || l <= 0) throw Error{GLX_E_INVALID, "m, n, l must be positive"};
   if (l > kAdmmMaxL) throw Error{GLX_E_INVALID, "the dual ADMM solver takes l <= 32"};
   AdmmPlan p;
-  p.es = dtype == GLX_F64 ? 8 : 4;
-  p.a = admm::a_plan(dtype, m, n, l);
+  static_cast<FusePlan&>(p) = fuse_plan(dtype, m, n, l);
   p.k = with_k ? make_plan(p.es, m, m, l, 0) : p.a;   // (the row step alone plans no K product
   if (!with_k) p.k.ax_S = 1;                            //  and carves one slab for it)
-  p.fuse_ok = atr_prox_ok(p.a) && (p.a.atr->fused & dtype_bit(p.es)) != 0;
   return p;
 }
 // opts.fused: 0 auto, 1 on (where admitted), 2 off. Auto = on: the A/B at (8192, 16384, 32) fp64
@@ -135,10 +95,9 @@ template <typename T>
 void admm_solve(const glx_problem& P, const T* K, const glx_admm_opts& O, void* ws, size_t wsb,
                 glx_result* res, hipStream_t st) {
   const int64_t m = P.m, n = P.n, l = P.l, nl = n * l, ml = m * l;
-  const int ll = (int)(l * l), nrec = kRecHead + 2 * ll;
+  const int ll = (int)(l * l);
   const AdmmPlan pl = admm_plan(P.dtype, m, n, l);
-  if (wsb < admm_carve(pl, m, n, l, nullptr, nullptr)) throw Error{GLX_E_INVALID, "workspace too small (glx_admm_workspace_bytes)"};
-  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
+  check_workspace(admm_carve(pl, m, n, l, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_admm_workspace_bytes");
   AdmmWs w;
   admm_carve(pl, m, n, l, ws, &w);
   const bool fused = use_fused(pl, O.fused);
@@ -151,15 +110,15 @@ void admm_solve(const glx_problem& P, const T* K, const glx_admm_opts& O, void* 
   T *s = static_cast<T*>(w.s), *v = static_cast<T*>(w.v), *z = static_cast<T*>(w.z);
   T *pa = static_cast<T*>(w.pa), *pk = static_cast<T*>(w.pk), *g = static_cast<T*>(w.g), *gp = static_cast<T*>(w.gp);
   double* rec = w.rec;
-  HostRec host((size_t)nrec);
+  const double mu = P.mu0, rho = O.rho, taurho = O.tau * O.rho;
+  SplitLoop loop(rec, l, nl, mu, O.thres, O.converge_len, res);
   int64_t maxit = O.maxit;
   if (O.max_total_iters > 0) maxit = std::min<int64_t>(maxit, O.max_total_iters);
-  const double mu = P.mu0, rho = O.rho, taurho = O.tau * O.rho;
 
   const auto t0 = std::chrono::steady_clock::now();
   GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
   GLX_HIP(hipMemsetAsync(w.pcnt, 0, sizeof(unsigned) * (n / 64 + 64), st));
-  GLX_HIP(hipMemsetAsync(rec, 0, sizeof(double) * nrec, st));
+  GLX_HIP(hipMemsetAsync(rec, 0, sizeof(double) * loop.nrec, st));
   GLX_HIP(hipMemsetAsync(ub[0], 0, sizeof(T) * nl, st));   // u = 0 (:50)
   auto red = [&](int slot) { return Red{w.part, w.ticket, rec + slot}; };
   auto batched_pass = [&](const T* x, const T* u, T* sout) {
@@ -170,12 +129,10 @@ void admm_solve(const glx_problem& P, const T* K, const glx_admm_opts& O, void* 
   batched_pass(xb[0], ub[0], nullptr);
   launch_rownorm_max<T>(xb[0], n, l, red(1), st);   // the objective of x0, returned when maxit = 0
   check_launch();
-  int64_t ax_calls = 1, atr_calls = 0, k_calls = 0, syncs = 0;
-  int64_t k = 0, length = 0;
+  int64_t ax_calls = 1, atr_calls = 0, k_calls = 0;
+  int64_t k = 0;
   int cur = 0;
-  double f_best = std::numeric_limits<double>::infinity(), f_now = 0.0;
-  admm::trace().clear();
-  res->n_fhist = 0;
+  loop.begin();
   while (k < maxit) {
     ++k;
     const int nxt = cur ^ 1;
@@ -204,149 +161,20 @@ void admm_solve(const glx_problem& P, const T* K, const glx_admm_opts& O, void* 
     launch_count_above<T>(xb[nxt], nl, rec + 2, red(3), st);
     launch_gram<T>(r, n, l, w.gram_part, rec + kRecHead, st);
     launch_gram<T>(s, m, l, w.gram_part, rec + kRecHead + ll, st);
-    check_launch();
-    GLX_HIP(hipMemcpyAsync(host.p, rec, sizeof(double) * nrec, hipMemcpyDeviceToHost, st));
-    GLX_HIP(hipStreamSynchronize(st));
-    ++syncs;
+    const bool stop = loop.end_iteration(st);
     cur = nxt;
-    const double* h = host.p;
-    f_now = 0.5 * h[0] + mu * h[1];
-    f_best = f_now < f_best ? f_now : f_best;   // min(f_best, f_now): a NaN f_now is not taken
-    if (res->f_hist && res->n_fhist < res->f_cap) {
-      res->f_hist[res->n_fhist] = f_now;
-      if (res->f_hist_best) res->f_hist_best[res->n_fhist] = f_best;
-      ++res->n_fhist;
-    }
-    admm::trace().push_back(h[3] / (double)nl);
-    const double rn = spectral_norm(h + kRecHead, (int)l), sn = spectral_norm(h + kRecHead + ll, (int)l);
-    if (rn < O.thres && sn < O.thres) ++length;
-    else length = 0;
-    if (length >= O.converge_len) break;
-  }
-  if (k == 0) {
-    GLX_HIP(hipMemcpyAsync(host.p, rec, sizeof(double) * kRecHead, hipMemcpyDeviceToHost, st));
-    GLX_HIP(hipStreamSynchronize(st));
-    ++syncs;
-    f_now = 0.5 * host.p[0] + mu * host.p[1];
+    if (stop) break;
   }
   if (cur != 0) GLX_HIP(hipMemcpyAsync(xb[0], xb[1], sizeof(T) * nl, hipMemcpyDeviceToDevice, st));
-  GLX_HIP(hipStreamSynchronize(st));
-  res->iters = k;
-  res->fval = f_now;
-  res->tt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  loop.finish(k, t0, st, /*count_maxit0_sync=*/true);
   res->ax_calls = ax_calls;
   res->ax_sources = 2 * ax_calls;
   res->atr_calls = atr_calls;
-  res->syncs = syncs;
-  res->record_waits = 0;
-  for (double& sv : res->stats) sv = 0.0;
   res->stats[0] = (double)k_calls;       // passes over K
   res->stats[1] = fused ? 1.0 : 0.0;     // the row step ran in the A^T z epilogue
 }
 
-
-// the workspace of the glue-kernel entries: the reduction's partials and its arrival tickets
-Red glue_red(void* ws, size_t wsb, void* sums_dev, hipStream_t st) {
-  Carver c(ws);
-  double* part = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals * kMaxBlocks));
-  unsigned* ticket = static_cast<unsigned*>(c.take(kTicketBytes));
-  if (!ws || wsb < c.off) throw Error{GLX_E_WORKSPACE, "workspace too small"};
-  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_WORKSPACE, "workspace must be 256-byte aligned"};
-  GLX_HIP(hipMemsetAsync(ticket, 0, kTicketBytes, st));
-  return Red{part, ticket, static_cast<double*>(sums_dev)};
-}
-void check_glue(int dtype, int64_t count, int S) {
-  if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
-  if (count <= 0) throw Error{GLX_E_INVALID, "needs a positive element count"};
-  if (S < 1) throw Error{GLX_E_INVALID, "needs S >= 1 slabs"};
-}
-
 }  // namespace
-
-// ---- shared with admm_primal.cpp (glx_internal.h, namespace admm) ----
-namespace admm {
-
-// Largest eigenvalue of the symmetric l x l matrix G (row-major) by cyclic Jacobi sweeps
-// (Golub & Van Loan, Alg. 8.5.3); NaN where G holds one. The Gram matrices of the stop rule are
-// at most 32 x 32, so a sweep is a few thousand flops on the host.
-double sym_lambda_max(const double* G, int l) {
-  double a[kMaxL][kMaxL];
-  double tr = 0.0;
-  for (int i = 0; i < l; ++i)
-    for (int j = 0; j < l; ++j) {
-      const double v = G[i * l + j];
-      if (v != v) return std::numeric_limits<double>::quiet_NaN();
-      a[i][j] = v;
-      if (i == j) tr += std::fabs(v);
-    }
-  for (int sweep = 0; sweep < 64; ++sweep) {
-    double off = 0.0;
-    for (int p = 0; p < l; ++p)
-      for (int q = p + 1; q < l; ++q) off += a[p][q] * a[p][q];
-    if (!(std::sqrt(off) > 1e-18 * tr)) break;
-    for (int p = 0; p < l; ++p)
-      for (int q = p + 1; q < l; ++q) {
-        const double apq = a[p][q];
-        if (apq == 0.0) continue;
-        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-        const double cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
-        for (int k = 0; k < l; ++k) {
-          if (k == p || k == q) continue;
-          const double akp = a[k][p], akq = a[k][q];
-          a[k][p] = a[p][k] = cs * akp - sn * akq;
-          a[k][q] = a[q][k] = sn * akp + cs * akq;
-        }
-        a[p][p] -= t * apq;
-        a[q][q] += t * apq;
-        a[p][q] = a[q][p] = 0.0;
-      }
-  }
-  double mx = a[0][0];
-  for (int i = 1; i < l; ++i) mx = a[i][i] > mx ? a[i][i] : mx;
-  return mx;
-}
-// the spectral norm of R from R^T R (a tiny negative eigenvalue of a rounded Gram matrix is 0)
-double spectral_norm(const double* gram, int l) {
-  const double lm = sym_lambda_max(gram, l);
-  return lm != lm ? lm : std::sqrt(lm > 0.0 ? lm : 0.0);
-}
-
-std::vector<double>& trace() {
-  thread_local std::vector<double> sparsity;
-  return sparsity;
-}
-
-HostRec::HostRec(size_t n) { GLX_HIP(hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(double) * n, hipHostMallocDefault)); }
-HostRec::~HostRec() { if (p) (void)hipHostFree(p); }
-
-GemmPlan a_plan(int dtype, int64_t m, int64_t n, int64_t l) {
-  glx_problem P;
-  glx_opts O;
-  std::memset(&P, 0, sizeof P);
-  std::memset(&O, 0, sizeof O);
-  P.dtype = dtype;
-  P.method = GLX_PROXGD;
-  P.m = m;
-  P.n = n;
-  P.l = l;
-  O.step_type = GLX_STEP_LINE_SEARCH;
-  return session_plan(P, O);
-}
-
-std::string plan_field(const GemmPlan& p, int idx) {
-  std::string d = describe_plan(p);
-  for (int i = 0; i < idx; ++i) {
-    const size_t at = d.find("; ");
-    d = at == std::string::npos ? std::string() : d.substr(at + 2);
-  }
-  d = d.substr(0, d.find("; "));
-  const size_t eq = d.find('=');
-  return eq == std::string::npos ? d : d.substr(eq + 1);
-}
-
-}  // namespace admm
-
 }  // namespace glx
 
 using namespace glx;
@@ -396,18 +224,19 @@ int glx_admm_dual_solve(const glx_problem* prob, const void* K_device, const glx
          reinterpret_cast<uintptr_t>(prob->x) | reinterpret_cast<uintptr_t>(K_device)) & 15)
       throw Error{GLX_E_INVALID, "A, b, x, K must be 16-byte aligned"};
     admm_plan(prob->dtype, prob->m, prob->n, prob->l);   // validates dtype and shape
-    if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (prob->dtype == GLX_F64) admm_solve<double>(*prob, static_cast<const double*>(K_device), *opts, ws, wsb, res, st);
-    else admm_solve<float>(*prob, static_cast<const float*>(K_device), *opts, ws, wsb, res, st);
+    by_dtype(prob->dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      admm_solve<T>(*prob, static_cast<const T*>(K_device), *opts, ws, wsb, res, st);
+    });
   });
 }
 
 int glx_admm_trace(double* sparsity_after, int64_t cap, int64_t* n) {
   return guarded([&] {
-    const int64_t have = (int64_t)admm::trace().size();
+    const int64_t have = (int64_t)split::trace().size();
     const int64_t k = sparsity_after ? std::min(cap, have) : have;
-    for (int64_t i = 0; sparsity_after && i < k; ++i) sparsity_after[i] = admm::trace()[(size_t)i];
+    for (int64_t i = 0; sparsity_after && i < k; ++i) sparsity_after[i] = split::trace()[(size_t)i];
     if (n) *n = k;
   });
 }
@@ -424,16 +253,15 @@ int glx_admm_dual_step(int dtype, int64_t m, int64_t n, int64_t l, const void* A
       if (!pl.fuse_ok)
         throw Error{GLX_E_INVALID, "form 1: this shape's A^T R plan takes no fused epilogue (" + describe_plan(pl.a) + ")"};
     }
-    if (!ws || wsb < admm_carve(pl, pl.a.m, n, l, nullptr, nullptr)) throw Error{GLX_E_WORKSPACE, "workspace too small"};
-    if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_WORKSPACE, "workspace must be 256-byte aligned"};
+    check_workspace(admm_carve(pl, pl.a.m, n, l, nullptr, nullptr), ws, wsb, GLX_E_WORKSPACE, nullptr);
     AdmmWs w;
     admm_carve(pl, pl.a.m, n, l, ws, &w);
     hipStream_t st = static_cast<hipStream_t>(stream);
     GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
     GLX_HIP(hipMemsetAsync(w.pcnt, 0, sizeof(unsigned) * (n / 64 + 64), st));
     Red red{w.part, w.ticket, static_cast<double*>(sums_dev)};
-    auto go = [&](auto* tag) {
-      typedef std::remove_pointer_t<decltype(tag)> T;
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
       if (form == 0 && pl.fuse_ok)   // the layout the driver's unfused arm takes at this (m, n, l)
         launch_admm_dual_panel<T>(pl.a, (const T*)x, (const T*)G, 1, nullptr, (T*)u_out, (T*)x_out,
                                   (T*)r_out, rho, tau * rho, mu, red, st);
@@ -443,9 +271,7 @@ int glx_admm_dual_step(int dtype, int64_t m, int64_t n, int64_t l, const void* A
       else
         launch_atr_admm<T>(pl.a, (const T*)A, (const T*)Z, (T*)G, (const T*)x, (T*)u_out, (T*)x_out, (T*)r_out,
                            rho, tau * rho, mu, red, st, pl.a.atr_S > 1 ? (T*)w.gp : nullptr, w.pcnt);
-    };
-    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
-    else go(static_cast<float*>(nullptr));
+    });
     check_launch();
   });
 }
@@ -456,8 +282,10 @@ int glx_admm_rhs(int dtype, int64_t ml, const void* Ax, const void* Au, const vo
     check_glue(dtype, ml, 1);
     if (!Ax || !Au || !b || !v_out) throw Error{GLX_E_INVALID, "null argument"};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == GLX_F64) launch_admm_v<double>((const double*)Ax, (const double*)Au, (const double*)b, (double*)v_out, ml, rho, st);
-    else launch_admm_v<float>((const float*)Ax, (const float*)Au, (const float*)b, (float*)v_out, ml, rho, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_admm_v<T>((const T*)Ax, (const T*)Au, (const T*)b, (T*)v_out, ml, rho, st);
+    });
     check_launch();
   });
 }
@@ -469,8 +297,10 @@ int glx_admm_fin(int dtype, int64_t ml, int S, const void* P, const void* b, voi
     if (!P || !b || !Ax || !Au || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Red red = glue_red(ws, wsb, sums_dev, st);
-    if (dtype == GLX_F64) launch_admm_fin<double>((const double*)P, S, (const double*)b, (double*)Ax, (double*)Au, (double*)s, ml, red, st);
-    else launch_admm_fin<float>((const float*)P, S, (const float*)b, (float*)Ax, (float*)Au, (float*)s, ml, red, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_admm_fin<T>((const T*)P, S, (const T*)b, (T*)Ax, (T*)Au, (T*)s, ml, red, st);
+    });
     check_launch();
   });
 }
@@ -483,8 +313,10 @@ int glx_gram(int dtype, int64_t rows, int64_t l, const void* R, void* gram_dev, 
     if (!R || !gram_dev) throw Error{GLX_E_INVALID, "null argument"};
     if (!ws || wsb < sizeof(double) * 256 * l * l) throw Error{GLX_E_WORKSPACE, "workspace too small"};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == GLX_F64) launch_gram<double>((const double*)R, rows, l, (double*)ws, (double*)gram_dev, st);
-    else launch_gram<float>((const float*)R, rows, l, (double*)ws, (double*)gram_dev, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_gram<T>((const T*)R, rows, l, (double*)ws, (double*)gram_dev, st);
+    });
     check_launch();
   });
 }

@@ -1,6 +1,6 @@
 // admm_primal.cpp — the native driver of the primal ADMM solver, gl_Admm_primal(x0, A, b, mu, opts)
-// (reference: gl_ADMM_primal.py:10-117), beside admm.cpp, whose carver, pinned record, Jacobi sweep
-// and trace it shares (glx_internal.h, namespace admm).
+// (reference: gl_ADMM_primal.py:10-117), beside admm.cpp, with which it shares the outer iteration's
+// tail (glx_host.h SplitLoop; split_loop.h, namespace split).
 //
 // The reference solves with the Cholesky factor of rho I + A^T A (n x n) at every iteration (:62,
 // :78). Here y+ = (rho I + A^T A)^-1 w, w = A^T b - z + rho x, is a dense product with an explicit
@@ -11,53 +11,19 @@
 //             two over A, the dual solver's schedule.
 // The row step (k_admm_primal) updates x, y, z in place and writes the next w; one record is read
 // back per iteration, as in admm.cpp (both Gram matrices are of n x l iterates here).
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <limits>
 #include <string>
-#include <type_traits>
-#include <vector>
 
-#include "glx.h"
-#include "glx_internal.h"
+#include "glx_host.h"
 
 namespace glx {
 namespace {
 
-using namespace admm;
-
-#define GLX_HIP(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) throw Error{GLX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-
-inline void check_launch() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw Error{GLX_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)};
-}
-
-template <typename F>
-int guarded(F&& f) {
-  try {
-    f();
-    return GLX_OK;
-  } catch (const Error& e) {
-    g_last_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return GLX_E_STATE;
-  } catch (...) {
-    g_last_error = "unknown error";
-    return GLX_E_STATE;
-  }
-}
+using namespace split;
 
 void check_opts(const glx_admm_primal_opts* o) {
   if (!o) throw Error{GLX_E_INVALID, "null opts"};
@@ -78,7 +44,7 @@ bool use_woodbury(int form, int64_t m, int64_t n) {
   return dm * dm + dm * dn < dn * dn;
 }
 
-// The launch plans of a solve: A's is the dual solver's (admm::a_plan); the inverse's is the
+// The launch plans of a solve: A's is the dual solver's (glx_host.h a_plan); the inverse's is the
 // planner's choice for a square matrix, m x m (Woodbury's K) or n x n (direct's Kn).
 struct PrimalPlan {
   int es = 8;
@@ -86,9 +52,9 @@ struct PrimalPlan {
   GemmPlan a{}, k{};
 };
 PrimalPlan primal_plan(int dtype, int64_t m, int64_t n, int64_t l, int form) {
-  if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+  check_dtype(dtype);
   if (m <= 0 || n <= 0 || l <= 0) throw Error{GLX_E_INVALID, "m, n, l must be positive"};
-  if (l > admm::kMaxL) throw Error{GLX_E_INVALID, "the primal ADMM solver takes l <= 32"};
+  if (l > split::kMaxL) throw Error{GLX_E_INVALID, "the primal ADMM solver takes l <= 32"};
   PrimalPlan p;
   p.es = dtype == GLX_F64 ? 8 : 4;
   p.woodbury = use_woodbury(form, m, n);
@@ -97,7 +63,7 @@ PrimalPlan primal_plan(int dtype, int64_t m, int64_t n, int64_t l, int form) {
                 "the primal ADMM solver takes fp32 only for m >= n in the direct form: the conditioning of "
                 "rho I + A^T A (||A||^2 / rho, 1e5 .. 1e6 at the default rho for m < n) is beyond an fp32 "
                 "inverse and fp32 iterates, which never meet the stop rule; use fp64"};
-  p.a = admm::a_plan(dtype, m, n, l);
+  p.a = a_plan(dtype, m, n, l);
   p.k = p.woodbury ? make_plan(p.es, m, m, l, 0) : make_plan(p.es, n, n, l, 0);
   return p;
 }
@@ -154,11 +120,10 @@ template <typename T>
 void primal_solve(const glx_problem& P, const T* K, const T* ATb, const T* AATb, const glx_admm_primal_opts& O,
                   void* ws, size_t wsb, glx_result* res, hipStream_t st) {
   const int64_t m = P.m, n = P.n, l = P.l, nl = n * l, ml = m * l;
-  const int ll = (int)(l * l), nrec = kRecHead + 2 * ll;
+  const int ll = (int)(l * l);
   const PrimalPlan pl = primal_plan(P.dtype, m, n, l, O.form);
-  if (wsb < primal_carve(pl, m, n, l, nullptr, nullptr))
-    throw Error{GLX_E_INVALID, "workspace too small (glx_admm_primal_workspace_bytes)"};
-  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
+  check_workspace(primal_carve(pl, m, n, l, nullptr, nullptr), ws, wsb, GLX_E_INVALID,
+                  "glx_admm_primal_workspace_bytes");
   PrimalWs w;
   primal_carve(pl, m, n, l, ws, &w);
   const bool wb = pl.woodbury;
@@ -170,14 +135,14 @@ void primal_solve(const glx_problem& P, const T* K, const T* ATb, const T* AATb,
   T *v = static_cast<T*>(w.v), *q = static_cast<T*>(w.q), *pa = static_cast<T*>(w.pa), *pk = static_cast<T*>(w.pk);
   T* gp = static_cast<T*>(w.gp);
   double* rec = w.rec;
-  HostRec host((size_t)nrec);
+  const double mu = P.mu0;
+  SplitLoop loop(rec, l, nl, mu, O.thres, O.converge_len, res);
   int64_t maxit = O.maxit;
   if (O.max_total_iters > 0) maxit = std::min<int64_t>(maxit, O.max_total_iters);
-  const double mu = P.mu0;
 
   const auto t0 = std::chrono::steady_clock::now();
   GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
-  GLX_HIP(hipMemsetAsync(rec, 0, sizeof(double) * nrec, st));
+  GLX_HIP(hipMemsetAsync(rec, 0, sizeof(double) * loop.nrec, st));
   GLX_HIP(hipMemcpyAsync(y, x, sizeof(T) * nl, hipMemcpyDeviceToDevice, st));   // y = z = x0 (:53-55)
   GLX_HIP(hipMemcpyAsync(z, x, sizeof(T) * nl, hipMemcpyDeviceToDevice, st));
   auto red = [&](int slot) { return Red{w.part, w.ticket, rec + slot}; };
@@ -190,11 +155,9 @@ void primal_solve(const glx_problem& P, const T* K, const T* ATb, const T* AATb,
   pass_over_a();
   launch_rownorm_max<T>(x, n, l, red(1), st);   // the objective of x0, returned when maxit = 0
   check_launch();
-  int64_t ax_calls = 1, atr_calls = 0, k_calls = 0, syncs = 0;
-  int64_t k = 0, length = 0;
-  double f_best = std::numeric_limits<double>::infinity(), f_now = 0.0;
-  admm::trace().clear();
-  res->n_fhist = 0;
+  int64_t ax_calls = 1, atr_calls = 0, k_calls = 0;
+  int64_t k = 0;
+  loop.begin();
   while (k < maxit) {
     ++k;
     const double eta = step_eta(O, k);
@@ -219,59 +182,16 @@ void primal_solve(const glx_problem& P, const T* K, const T* ATb, const T* AATb,
     launch_count_above<T>(x, nl, rec + 2, red(3), st);
     launch_gram<T>(r, n, l, w.gram_part, rec + kRecHead, st);
     launch_gram<T>(s, n, l, w.gram_part, rec + kRecHead + ll, st);
-    check_launch();
-    GLX_HIP(hipMemcpyAsync(host.p, rec, sizeof(double) * nrec, hipMemcpyDeviceToHost, st));
-    GLX_HIP(hipStreamSynchronize(st));
-    ++syncs;
-    const double* h = host.p;
-    f_now = 0.5 * h[0] + mu * h[1];
-    f_best = f_now < f_best ? f_now : f_best;   // min(f_best, f_now): a NaN f_now is not taken
-    if (res->f_hist && res->n_fhist < res->f_cap) {
-      res->f_hist[res->n_fhist] = f_now;
-      if (res->f_hist_best) res->f_hist_best[res->n_fhist] = f_best;
-      ++res->n_fhist;
-    }
-    admm::trace().push_back(h[3] / (double)nl);
-    const double rn = spectral_norm(h + kRecHead, (int)l), sn = spectral_norm(h + kRecHead + ll, (int)l);
-    if (rn < O.thres && sn < O.thres) ++length;
-    else length = 0;
-    if (length >= O.converge_len) break;
+    if (loop.end_iteration(st)) break;
   }
-  if (k == 0) {
-    GLX_HIP(hipMemcpyAsync(host.p, rec, sizeof(double) * kRecHead, hipMemcpyDeviceToHost, st));
-    GLX_HIP(hipStreamSynchronize(st));
-    f_now = 0.5 * host.p[0] + mu * host.p[1];
-  }
-  GLX_HIP(hipStreamSynchronize(st));
-  res->iters = k;
-  res->fval = f_now;
-  res->tt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  loop.finish(k, t0, st, /*count_maxit0_sync=*/false);
   res->ax_calls = ax_calls;
   res->ax_sources = (wb ? 2 : 1) * ax_calls;
   res->atr_calls = atr_calls;
-  res->syncs = syncs;
-  res->record_waits = 0;
-  for (double& sv : res->stats) sv = 0.0;
   res->stats[0] = (double)k_calls;       // passes over the inverse
   res->stats[1] = wb ? 2.0 : 1.0;        // the resolved form
 }
 
-
-// the workspace of the glue-kernel entries: the reduction's partials and its arrival tickets
-Red glue_red(void* ws, size_t wsb, void* sums_dev, hipStream_t st) {
-  Carver c(ws);
-  double* part = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals * kMaxBlocks));
-  unsigned* ticket = static_cast<unsigned*>(c.take(kTicketBytes));
-  if (!ws || wsb < c.off) throw Error{GLX_E_WORKSPACE, "workspace too small"};
-  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_WORKSPACE, "workspace must be 256-byte aligned"};
-  GLX_HIP(hipMemsetAsync(ticket, 0, kTicketBytes, st));
-  return Red{part, ticket, static_cast<double*>(sums_dev)};
-}
-void check_glue(int dtype, int64_t count, int S) {
-  if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
-  if (count <= 0) throw Error{GLX_E_INVALID, "needs a positive element count"};
-  if (S < 1) throw Error{GLX_E_INVALID, "needs S >= 1 slabs"};
-}
 
 }  // namespace
 }  // namespace glx
@@ -329,14 +249,12 @@ int glx_admm_primal_solve(const glx_problem* prob, const void* K_device, const v
          reinterpret_cast<uintptr_t>(prob->x) | reinterpret_cast<uintptr_t>(K_device) |
          reinterpret_cast<uintptr_t>(ATb_device) | (pl.woodbury ? reinterpret_cast<uintptr_t>(AATb_device) : 0)) & 15)
       throw Error{GLX_E_INVALID, "A, b, x, K, ATb, AATb must be 16-byte aligned"};
-    if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (prob->dtype == GLX_F64)
-      primal_solve<double>(*prob, static_cast<const double*>(K_device), static_cast<const double*>(ATb_device),
-                           static_cast<const double*>(AATb_device), *opts, ws, wsb, res, st);
-    else
-      primal_solve<float>(*prob, static_cast<const float*>(K_device), static_cast<const float*>(ATb_device),
-                          static_cast<const float*>(AATb_device), *opts, ws, wsb, res, st);
+    by_dtype(prob->dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      primal_solve<T>(*prob, static_cast<const T*>(K_device), static_cast<const T*>(ATb_device),
+                      static_cast<const T*>(AATb_device), *opts, ws, wsb, res, st);
+    });
   });
 }
 
@@ -346,30 +264,22 @@ int glx_admm_primal_step(int dtype, int64_t n, int64_t l, int form, int S, const
                          void* r_out, void* s_out, void* w_out, void* sums_dev, void* ws, size_t wsb,
                          void* stream) {
   return guarded([&] {
-    if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
-    if (n <= 0 || l <= 0 || l > admm::kMaxL) throw Error{GLX_E_INVALID, "needs n > 0 and 1 <= l <= 32"};
+    check_dtype(dtype);
+    if (n <= 0 || l <= 0 || l > split::kMaxL) throw Error{GLX_E_INVALID, "needs n > 0 and 1 <= l <= 32"};
     if (form != 1 && form != 2) throw Error{GLX_E_INVALID, "form must be 1 (direct) or 2 (Woodbury)"};
     if (S < 1) throw Error{GLX_E_INVALID, "needs S >= 1 slabs"};
     if (!prod || !x || !y || !z || !ATb || !x_out || !y_out || !z_out || !r_out || !s_out || !w_out || !sums_dev)
       throw Error{GLX_E_INVALID, "null argument"};
     if (form == 2 && !w) throw Error{GLX_E_INVALID, "the Woodbury form reads w"};
-    Carver c(ws);
-    double* part = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals * kMaxBlocks));
-    unsigned* ticket = static_cast<unsigned*>(c.take(kTicketBytes));
-    if (!ws || wsb < c.off) throw Error{GLX_E_WORKSPACE, "workspace too small"};
-    if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_WORKSPACE, "workspace must be 256-byte aligned"};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    GLX_HIP(hipMemsetAsync(ticket, 0, kTicketBytes, st));
-    const Red red{part, ticket, static_cast<double*>(sums_dev)};
+    const Red red = glue_red(ws, wsb, sums_dev, st);
     const AdmmPrimalScalars sc{rho, eta * rho, eta * mu, tau * rho, thres};
-    auto go = [&](auto* tag) {
-      typedef std::remove_pointer_t<decltype(tag)> T;
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
       launch_admm_primal<T>(form == 2, (const T*)prod, S, (const T*)x, (const T*)y, (const T*)z, (const T*)w,
                             (const T*)ATb, (T*)x_out, (T*)y_out, (T*)z_out, (T*)r_out, (T*)s_out, (T*)w_out, n,
                             l, sc, red, st);
-    };
-    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
-    else go(static_cast<float*>(nullptr));
+    });
     check_launch();
   });
 }
@@ -380,8 +290,10 @@ int glx_admm_primal_rhs(int dtype, int64_t nl, const void* ATb, const void* x, c
     check_glue(dtype, nl, 1);
     if (!ATb || !x || !z || !w_out) throw Error{GLX_E_INVALID, "null argument"};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == GLX_F64) launch_admm_primal_w<double>((const double*)ATb, (const double*)x, (const double*)z, (double*)w_out, nl, rho, st);
-    else launch_admm_primal_w<float>((const float*)ATb, (const float*)x, (const float*)z, (float*)w_out, nl, rho, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_admm_primal_w<T>((const T*)ATb, (const T*)x, (const T*)z, (T*)w_out, nl, rho, st);
+    });
     check_launch();
   });
 }
@@ -394,10 +306,10 @@ int glx_admm_primal_fin(int dtype, int64_t ml, int S, const void* P, const void*
     if (AATb && (!Az || !v)) throw Error{GLX_E_INVALID, "the Woodbury half (AATb given) writes Az and v"};
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Red red = glue_red(ws, wsb, sums_dev, st);
-    if (dtype == GLX_F64)
-      launch_admm_primal_fin<double>((const double*)P, S, (const double*)b, (const double*)AATb, (double*)Ax, (double*)Az, (double*)v, ml, rho, red, st);
-    else
-      launch_admm_primal_fin<float>((const float*)P, S, (const float*)b, (const float*)AATb, (float*)Ax, (float*)Az, (float*)v, ml, rho, red, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_admm_primal_fin<T>((const T*)P, S, (const T*)b, (const T*)AATb, (T*)Ax, (T*)Az, (T*)v, ml, rho, red, st);
+    });
     check_launch();
   });
 }

@@ -1,5 +1,6 @@
 // alm.cpp — the native driver of the dual ALM solver, gl_Alm_dual(x0, A, b, mu, opts)
-// (reference: gl_ALM_dual.py:10-158), beside admm.cpp and sharing its record, Jacobi sweep and trace.
+// (reference: gl_ALM_dual.py:10-158), beside admm.cpp, with which it shares the outer iteration's
+// tail (glx_host.h SplitLoop; split_loop.h, namespace split).
 //
 // The reference rebuilds, at every outer iteration, the m x m inverse T, F = rho T A, G = I - A^T F,
 // Q = F^T F + rho G^T G and J (:33-40), then runs 500 Nesterov steps on grad = Q u + J. Two
@@ -14,53 +15,20 @@
 //   record A @ [x+ | u] -> Ax+, ||Ax+ - b||^2, s = Au_prev - Au; the Gram matrices of r and s; one
 //          readback; the host takes the two spectral norms and applies the stop rule (:140-148)
 // fp64 only.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <initializer_list>
-#include <limits>
 #include <string>
-#include <vector>
 
-#include "glx.h"
-#include "glx_internal.h"
+#include "glx_host.h"
 
 namespace glx {
 namespace {
 
-#define GLX_HIP(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) throw Error{GLX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-
-inline void check_launch() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw Error{GLX_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)};
-}
-
-template <typename F>
-int guarded(F&& f) {
-  try {
-    f();
-    return GLX_OK;
-  } catch (const Error& e) {
-    g_last_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return GLX_E_STATE;
-  } catch (...) {
-    g_last_error = "unknown error";
-    return GLX_E_STATE;
-  }
-}
-
-using namespace admm;
+using namespace split;
 
 void check_f64(int dtype) {
   if (dtype == GLX_F32)
@@ -80,15 +48,15 @@ struct InnerPlan {
 InnerPlan inner_plan(int dtype, int64_t n, int64_t l) {
   check_f64(dtype);
   if (n <= 0 || l <= 0) throw Error{GLX_E_INVALID, "n, l must be positive"};
-  if (l > admm::kMaxL) throw Error{GLX_E_INVALID, "the dual ALM solver takes l <= 32"};
+  if (l > split::kMaxL) throw Error{GLX_E_INVALID, "the dual ALM solver takes l <= 32"};
   InnerPlan p;
-  p.q = admm::a_plan(GLX_F64, n, n, l);
+  p.q = a_plan(GLX_F64, n, n, l);
   // The planner splits K up to 64 ways to fill the chip on one long pass; a fused epilogue combines
   // at most 8 slabs (atr_prox_ok). The inner loop is 500 short dependent passes over a matrix that
   // stays in cache, so both of its arms take 8 splits there and the step fuses at every
   // panel-multiple n.
   if (p.q.atr->fam == Fam::Mfma && p.q.atr->wl != 3 && p.q.atr_S > 8) p.q.atr_S = 8;
-  p.fuse_ok = atr_prox_ok(p.q) && (p.q.atr->fused & dtype_bit(8)) != 0;
+  p.fuse_ok = plan_fuses(p.q, 8);
   return p;
 }
 // opts.fused: 0 auto, 1 on (where admitted), 2 off. Auto = on ("Dual ALM").
@@ -135,9 +103,9 @@ struct AlmPlan {
 AlmPlan alm_plan(int dtype, int64_t m, int64_t n, int64_t l) {
   check_f64(dtype);
   if (m <= 0 || n <= 0 || l <= 0) throw Error{GLX_E_INVALID, "m, n, l must be positive"};
-  if (l > admm::kMaxL) throw Error{GLX_E_INVALID, "the dual ALM solver takes l <= 32"};
+  if (l > split::kMaxL) throw Error{GLX_E_INVALID, "the dual ALM solver takes l <= 32"};
   AlmPlan p;
-  p.a = admm::a_plan(GLX_F64, m, n, l);
+  p.a = a_plan(GLX_F64, m, n, l);
   p.k = make_plan(8, m, m, l, 0);
   p.in = inner_plan(dtype, n, l);
   return p;
@@ -194,10 +162,9 @@ void alm_solve(const glx_problem& P, const double* K, const double* Qn, const gl
                size_t wsb, glx_result* res, hipStream_t st) {
   typedef double T;
   const int64_t m = P.m, n = P.n, l = P.l, nl = n * l, ml = m * l;
-  const int ll = (int)(l * l), nrec = kRecHead + 2 * ll;
+  const int ll = (int)(l * l);
   const AlmPlan pl = alm_plan(P.dtype, m, n, l);
-  if (wsb < alm_carve(pl, m, n, l, nullptr, nullptr)) throw Error{GLX_E_INVALID, "workspace too small (glx_alm_workspace_bytes)"};
-  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
+  check_workspace(alm_carve(pl, m, n, l, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_alm_workspace_bytes");
   AlmWs w;
   alm_carve(pl, m, n, l, ws, &w);
   const bool fused = use_fused(pl.in, O.fused);
@@ -206,15 +173,15 @@ void alm_solve(const glx_problem& P, const double* K, const double* Qn, const gl
   const T* b = static_cast<const T*>(P.b);
   T* x = static_cast<T*>(P.x);
   double* rec = w.rec;
-  HostRec host((size_t)nrec);
+  const double mu = P.mu0, rho = O.rho, taurho = O.tau * O.rho;
+  SplitLoop loop(rec, l, nl, mu, O.thres, O.converge_len, res);
   int64_t maxit = O.maxit;
   if (O.max_total_iters > 0) maxit = std::min<int64_t>(maxit, O.max_total_iters);
-  const double mu = P.mu0, rho = O.rho, taurho = O.tau * O.rho;
 
   const auto t0 = std::chrono::steady_clock::now();
   GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
   GLX_HIP(hipMemsetAsync(w.in.pcnt, 0, sizeof(unsigned) * (n / 64 + 64), st));
-  GLX_HIP(hipMemsetAsync(rec, 0, sizeof(double) * nrec, st));
+  GLX_HIP(hipMemsetAsync(rec, 0, sizeof(double) * loop.nrec, st));
   GLX_HIP(hipMemsetAsync(w.u, 0, sizeof(T) * nl, st));   // u = 0 (:106)
   auto red = [&](int slot) { return Red{w.part, w.ticket, rec + slot}; };
   auto batched_pass = [&](T* sout) {   // Ax, Au, ||Ax - b||^2 and s = Au_prev - Au
@@ -230,11 +197,9 @@ void alm_solve(const glx_problem& P, const double* K, const double* Qn, const gl
   batched_pass(nullptr);
   launch_rownorm_max<T>(x, n, l, red(1), st);   // the objective of x0, returned when maxit = 0
   check_launch();
-  int64_t ax_calls = 1, atr_calls = 0, k_calls = 0, syncs = 0, inner = 0;
-  int64_t k = 0, length = 0;
-  double f_best = std::numeric_limits<double>::infinity(), f_now = 0.0;
-  admm::trace().clear();
-  res->n_fhist = 0;
+  int64_t ax_calls = 1, atr_calls = 0, k_calls = 0, inner = 0;
+  int64_t k = 0;
+  loop.begin();
   while (k < maxit) {
     ++k;
     // J = rho (A^T K (Ax - b) - x / rho); (Ax - 0 Ax) - b is Ax - b
@@ -260,39 +225,12 @@ void alm_solve(const glx_problem& P, const double* K, const double* Qn, const gl
     launch_count_above<T>(x, nl, rec + 2, red(3), st);
     launch_gram<T>(w.r, n, l, w.gram_part, rec + kRecHead, st);
     launch_gram<T>(w.s, m, l, w.gram_part, rec + kRecHead + ll, st);
-    check_launch();
-    GLX_HIP(hipMemcpyAsync(host.p, rec, sizeof(double) * nrec, hipMemcpyDeviceToHost, st));
-    GLX_HIP(hipStreamSynchronize(st));
-    ++syncs;
-    const double* h = host.p;
-    f_now = 0.5 * h[0] + mu * h[1];
-    f_best = f_now < f_best ? f_now : f_best;   // min(f_best, f_now): a NaN f_now is not taken
-    if (res->f_hist && res->n_fhist < res->f_cap) {
-      res->f_hist[res->n_fhist] = f_now;
-      if (res->f_hist_best) res->f_hist_best[res->n_fhist] = f_best;
-      ++res->n_fhist;
-    }
-    admm::trace().push_back(h[3] / (double)nl);
-    const double rn = spectral_norm(h + kRecHead, (int)l), sn = spectral_norm(h + kRecHead + ll, (int)l);
-    if (rn < O.thres && sn < O.thres) ++length;
-    else length = 0;
-    if (length >= O.converge_len) break;
+    if (loop.end_iteration(st)) break;
   }
-  if (k == 0) {
-    GLX_HIP(hipMemcpyAsync(host.p, rec, sizeof(double) * kRecHead, hipMemcpyDeviceToHost, st));
-    GLX_HIP(hipStreamSynchronize(st));
-    f_now = 0.5 * host.p[0] + mu * host.p[1];
-  }
-  GLX_HIP(hipStreamSynchronize(st));
-  res->iters = k;
-  res->fval = f_now;
-  res->tt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  loop.finish(k, t0, st, /*count_maxit0_sync=*/false);
   res->ax_calls = ax_calls;
   res->ax_sources = 2 + 3 * k;   // A @ [x0 | 0], then A u and A @ [x+ | u] per iteration
   res->atr_calls = atr_calls;
-  res->syncs = syncs;
-  res->record_waits = 0;
-  for (double& sv : res->stats) sv = 0.0;
   res->stats[0] = (double)k_calls;       // passes over K
   res->stats[1] = fused ? 1.0 : 0.0;     // the inner step ran in the Qn y epilogue
   res->stats[2] = (double)inner;         // inner steps run
@@ -314,22 +252,6 @@ size_t inner_ws(const InnerPlan& p, int64_t n, int64_t l, void* base, InnerWs* o
   return c.off + 256;
 }
 
-
-// the workspace of the glue-kernel entries: the reduction's partials and its arrival tickets
-Red glue_red(void* ws, size_t wsb, void* sums_dev, hipStream_t st) {
-  Carver c(ws);
-  double* part = static_cast<double*>(c.take(sizeof(double) * kMaxRedVals * kMaxBlocks));
-  unsigned* ticket = static_cast<unsigned*>(c.take(kTicketBytes));
-  if (!ws || wsb < c.off) throw Error{GLX_E_WORKSPACE, "workspace too small"};
-  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_WORKSPACE, "workspace must be 256-byte aligned"};
-  GLX_HIP(hipMemsetAsync(ticket, 0, kTicketBytes, st));
-  return Red{part, ticket, static_cast<double*>(sums_dev)};
-}
-void check_glue(int dtype, int64_t count, int S) {
-  check_f64(dtype);
-  if (count <= 0) throw Error{GLX_E_INVALID, "needs a positive element count"};
-  if (S < 1) throw Error{GLX_E_INVALID, "needs S >= 1 slabs"};
-}
 
 }  // namespace
 }  // namespace glx
@@ -377,7 +299,6 @@ int glx_alm_dual_solve(const glx_problem* prob, const void* K_device, const void
     if (prob->comm != nullptr) throw Error{GLX_E_INVALID, "the dual ALM solver is single-GPU: comm must be NULL"};
     alm_plan(prob->dtype, prob->m, prob->n, prob->l);   // validates dtype (fp64 only) and shape, before any pointer
     check_ptr16({prob->A, prob->b, prob->x, K_device, Qn_device}, "A, b, x, K, Qn");
-    if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
     alm_solve(*prob, static_cast<const double*>(K_device), static_cast<const double*>(Qn_device), *opts, ws, wsb,
               res, static_cast<hipStream_t>(stream));
   });
@@ -408,8 +329,7 @@ int glx_alm_inner_step(int dtype, int64_t n, int64_t l, const void* Qn, const vo
       if (!pl.fuse_ok)
         throw Error{GLX_E_INVALID, "form 1: the plan of (n, n, l) takes no fused epilogue (" + describe_plan(pl.q) + ")"};
     }
-    if (!ws || wsb < inner_ws(pl, n, l, nullptr, nullptr)) throw Error{GLX_E_INVALID, "workspace too small (glx_alm_inner_workspace_bytes)"};
-    if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
+    check_workspace(inner_ws(pl, n, l, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_alm_inner_workspace_bytes");
     InnerWs w;
     inner_ws(pl, n, l, ws, &w);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -435,8 +355,7 @@ int glx_alm_inner_run(int dtype, int64_t n, int64_t l, const void* Qn, const voi
     if (iters < 1) throw Error{GLX_E_INVALID, "iters must be at least 1"};
     if (fused < 0 || fused > 2) throw Error{GLX_E_INVALID, "fused must be 0 (auto), 1 (on) or 2 (off)"};
     check_ptr16({Qn, J, u_out}, "Qn, J, u_out");
-    if (!ws || wsb < inner_ws(pl, n, l, nullptr, nullptr)) throw Error{GLX_E_INVALID, "workspace too small (glx_alm_inner_workspace_bytes)"};
-    if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
+    check_workspace(inner_ws(pl, n, l, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_alm_inner_workspace_bytes");
     InnerWs w;
     inner_ws(pl, n, l, ws, &w);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -448,6 +367,7 @@ int glx_alm_inner_run(int dtype, int64_t n, int64_t l, const void* Qn, const voi
 
 int glx_alm_j(int dtype, int64_t nl, int S, const void* h, const void* x, double rho, void* J_out, void* stream) {
   return guarded([&] {
+    check_f64(dtype);
     check_glue(dtype, nl, S);
     if (!h || !x || !J_out) throw Error{GLX_E_INVALID, "null argument"};
     if (!(rho > 0.0)) throw Error{GLX_E_INVALID, "rho must be positive"};
@@ -459,8 +379,9 @@ int glx_alm_j(int dtype, int64_t nl, int S, const void* h, const void* x, double
 int glx_alm_x(int dtype, int64_t n, int64_t l, int S, const void* x, const void* u, const void* g, double taurho,
               void* x_out, void* r_out, void* sums_dev, void* ws, size_t wsb, void* stream) {
   return guarded([&] {
+    check_f64(dtype);
     check_glue(dtype, n, S);
-    if (l < 1 || l > admm::kMaxL) throw Error{GLX_E_INVALID, "the dual ALM x update takes 1 <= l <= 32"};
+    if (l < 1 || l > split::kMaxL) throw Error{GLX_E_INVALID, "the dual ALM x update takes 1 <= l <= 32"};
     if (!x || !u || !g || !x_out || !r_out || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Red red = glue_red(ws, wsb, sums_dev, st);

@@ -5,78 +5,33 @@
 // eight-value record from which the host composes the primal and dual objectives, the duality gap
 // of the rescaled residual theta = s r, s = min(1, mu / max_i ||g_i||), and the KKT violation.
 // Single GPU; beside the solvers' drivers and independent of Session<T>.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <type_traits>
 
-#include "glx.h"
-#include "glx_internal.h"
+#include "glx_host.h"
 
 namespace glx {
 namespace {
 
-#define GLX_HIP(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) throw Error{GLX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-
-inline void check_launch() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw Error{GLX_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)};
-}
-
-template <typename F>
-int guarded(F&& f) {
-  try {
-    f();
-    return GLX_OK;
-  } catch (const Error& e) {
-    g_last_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return GLX_E_STATE;
-  } catch (...) {
-    g_last_error = "unknown error";
-    return GLX_E_STATE;
-  }
-}
-
-using admm::Carver;
-using admm::plan_field;
-
 constexpr int kCertRec = 8;   // the record: [||r||^2, <r, b>] (k_cert_fin), the five row sums, fused
 
-// A's plan is the ADMM solvers' (admm::a_plan), so the fuse condition is theirs: the plan takes a
-// fused epilogue and its tile is built for it.
-struct CertPlan {
-  int es = 8;
-  GemmPlan a{};
-  bool fuse_ok = false;
-};
-CertPlan cert_plan(int dtype, int64_t m, int64_t n, int64_t l) {
-  if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+// A's plan and its fuse condition are glx_host.h's (fuse_plan), behind the certificate's own checks
+FusePlan cert_plan(int dtype, int64_t m, int64_t n, int64_t l) {
+  check_dtype(dtype);
   if (m <= 0 || n <= 0 || l <= 0) throw Error{GLX_E_INVALID, "m, n, l must be positive"};
   if (l > kMaxL) throw Error{GLX_E_INVALID, "the certificate takes l <= 128"};
-  CertPlan p;
-  p.es = dtype == GLX_F64 ? 8 : 4;
-  p.a = admm::a_plan(dtype, m, n, l);
-  p.fuse_ok = atr_prox_ok(p.a) && (p.a.atr->fused & dtype_bit(p.es)) != 0;
-  return p;
+  return fuse_plan(dtype, m, n, l);
 }
 void check_fused(int fused) {
   if (fused < 0 || fused > 2) throw Error{GLX_E_INVALID, "fused must be 0 (auto), 1 (on) or 2 (off)"};
 }
 // fused: 0 auto, 1 on (where admitted), 2 off. Auto = on (DESIGN.md "Certificate": the A/B).
-bool use_fused(const CertPlan& p, int fused) { return p.fuse_ok && fused != 2; }
+bool use_fused(const FusePlan& p, int fused) { return p.fuse_ok && fused != 2; }
 
-std::string describe_cert(const CertPlan& p, int fused) {
+std::string describe_cert(const FusePlan& p, int fused) {
   std::string s = "A x=" + plan_field(p.a, 0) + "; A^T r=" + plan_field(p.a, 3) + "; rows=";
   s += use_fused(p, fused) ? "fused (k_atr_cert, the A^T r epilogue)"
                            : (p.fuse_ok ? "row kernel (k_cert_panel, the epilogue's layout)" : "row kernel (k_cert_row)");
@@ -87,7 +42,7 @@ struct CertWs {
   double* part; unsigned* ticket; unsigned* pcnt; double* rec;
   void *r, *pa, *gp;
 };
-size_t cert_carve(const CertPlan& p, int64_t m, int64_t n, int64_t l, void* base, CertWs* out) {
+size_t cert_carve(const FusePlan& p, int64_t m, int64_t n, int64_t l, void* base, CertWs* out) {
   Carver c(base);
   const size_t es = (size_t)p.es;
   CertWs w;
@@ -101,16 +56,13 @@ size_t cert_carve(const CertPlan& p, int64_t m, int64_t n, int64_t l, void* base
   if (out) *out = w;
   return c.off + 256;
 }
-void check_ws(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const void* ws, size_t wsb) {
-  if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
-  if (wsb < cert_carve(pl, m, n, l, nullptr, nullptr))
-    throw Error{GLX_E_INVALID, "workspace too small (glx_certificate_workspace_bytes)"};
-  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
+void check_ws(const FusePlan& pl, int64_t m, int64_t n, int64_t l, const void* ws, size_t wsb) {
+  check_workspace(cert_carve(pl, m, n, l, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_certificate_workspace_bytes");
 }
 
 // the A^T pass and the row terms: g = A^T R, the five sums into red
 template <typename T>
-void cert_rows(const CertPlan& pl, bool fused, const T* A, const T* R, const T* x, double mu, T* G, double* rn,
+void cert_rows(const FusePlan& pl, bool fused, const T* A, const T* R, const T* x, double mu, T* G, double* rn,
                const CertWs& w, Red red, hipStream_t st) {
   const int SG = pl.a.atr_S;
   T* gp = static_cast<T*>(w.gp);
@@ -126,7 +78,7 @@ void cert_rows(const CertPlan& pl, bool fused, const T* A, const T* R, const T* 
 }
 
 template <typename T>
-void certificate(const CertPlan& pl, int64_t m, int64_t n, int64_t l, const T* A, const T* X, const T* b,
+void certificate(const FusePlan& pl, int64_t m, int64_t n, int64_t l, const T* A, const T* X, const T* b,
                  double mu, int fused_opt, T* G, double* rn, double* out, void* ws, hipStream_t st,
                  const GroupView* grp, const SampleView* sw, double* holdout_sum, const InterceptView* ic) {
   CertWs w;
@@ -185,7 +137,7 @@ void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, 
                      double mu, int fused, void* G_out, double* rownorm_out, double* out, void* ws, size_t wsb,
                      void* stream, const GroupView* grp, const SampleView* sw, double* holdout_sum,
                      const InterceptView* ic) {
-  const CertPlan pl = cert_plan(dtype, m, n, l);
+  const FusePlan pl = cert_plan(dtype, m, n, l);
   check_fused(fused);
   if (sw != nullptr && (!sw->w || !sw->sums)) throw Error{GLX_E_INVALID, "sample weights: null vector or sums"};
   if (ic != nullptr) {
@@ -200,12 +152,11 @@ void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, 
     throw Error{GLX_E_INVALID, "A, X, b, G_out must be 16-byte aligned"};
   check_ws(pl, m, n, l, ws, wsb);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (dtype == GLX_F64)
-    certificate<double>(pl, m, n, l, (const double*)A, (const double*)X, (const double*)b, mu, fused,
-                        (double*)G_out, rownorm_out, out, ws, st, grp, sw, holdout_sum, ic);
-  else
-    certificate<float>(pl, m, n, l, (const float*)A, (const float*)X, (const float*)b, mu, fused,
-                       (float*)G_out, rownorm_out, out, ws, st, grp, sw, holdout_sum, ic);
+  by_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    certificate<T>(pl, m, n, l, (const T*)A, (const T*)X, (const T*)b, mu, fused, (T*)G_out, rownorm_out, out, ws, st,
+                   grp, sw, holdout_sum, ic);
+  });
 }
 
 size_t intercept_carve(size_t head, int es, int64_t m, int64_t l, void* base, InterceptView* out) {
@@ -266,7 +217,7 @@ int glx_certificate_sw(int dtype, int64_t m, int64_t n, int64_t l, const void* A
   return guarded([&] {
     check_sample(sample_w, holdout_w);
     const size_t head = cert_carve(cert_plan(dtype, m, n, l), m, n, l, nullptr, nullptr);
-    if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
+    if (!ws) throw Error{GLX_E_INVALID, "null workspace"};   // (the alignment: certificate_run's check, below)
     if (wsb < sample_bytes(head))
       throw Error{GLX_E_INVALID, "workspace too small (glx_certificate_sw_workspace_bytes)"};
     if (holdout_sum != nullptr) *holdout_sum = 0.0;
@@ -289,7 +240,7 @@ int glx_certificate_sw(int dtype, int64_t m, int64_t n, int64_t l, const void* A
 int glx_certificate_ic_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, size_t* bytes) {
   return guarded([&] {
     if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
-    const CertPlan pl = cert_plan(dtype, m, n, l);
+    const FusePlan pl = cert_plan(dtype, m, n, l);
     *bytes = intercept_carve(sample_bytes(cert_carve(pl, m, n, l, nullptr, nullptr)), pl.es, m, l, nullptr, nullptr);
   });
 }
@@ -310,12 +261,10 @@ int glx_certificate_ic(int dtype, int64_t m, int64_t n, int64_t l, const void* A
   return guarded([&] {
     check_sample(sample_w, holdout_w);
     check_intercept(weight_sum, intercept_out);
-    const CertPlan pl = cert_plan(dtype, m, n, l);
+    const FusePlan pl = cert_plan(dtype, m, n, l);
     const size_t head = cert_carve(pl, m, n, l, nullptr, nullptr);
-    if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
-    if (wsb < intercept_carve(sample_bytes(head), pl.es, m, l, nullptr, nullptr))
-      throw Error{GLX_E_INVALID, "workspace too small (glx_certificate_ic_workspace_bytes)"};
-    if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
+    check_workspace(intercept_carve(sample_bytes(head), pl.es, m, l, nullptr, nullptr), ws, wsb, GLX_E_INVALID,
+                    "glx_certificate_ic_workspace_bytes");
     if (holdout_sum != nullptr) *holdout_sum = 0.0;
     InterceptView ic;
     ic.sigma = weight_sum;
@@ -359,7 +308,7 @@ int glx_certificate_step(int dtype, int64_t m, int64_t n, int64_t l, const void*
                          size_t wsb, void* stream) {
   return guarded([&] {
     if (form != 0 && form != 1) throw Error{GLX_E_INVALID, "form must be 0 (row kernel) or 1 (A^T r epilogue)"};
-    const CertPlan pl = cert_plan(dtype, m, n, l);
+    const FusePlan pl = cert_plan(dtype, m, n, l);
     if (!G || !x || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
     if (form == 1) {
       if (!A || !Z) throw Error{GLX_E_INVALID, "form 1 needs A and Z"};
@@ -373,8 +322,8 @@ int glx_certificate_step(int dtype, int64_t m, int64_t n, int64_t l, const void*
     GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
     GLX_HIP(hipMemsetAsync(w.pcnt, 0, sizeof(unsigned) * (n / 64 + 64), st));
     Red red{w.part, w.ticket, static_cast<double*>(sums_dev)};
-    auto go = [&](auto* tag) {
-      typedef std::remove_pointer_t<decltype(tag)> T;
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
       if (form == 0 && pl.fuse_ok)   // the layout the driver's unfused arm takes at this (m, n, l)
         launch_cert_panel<T>(pl.a, (const T*)x, (const T*)G, 1, nullptr, rownorm_out, mu, red, st);
       else if (form == 0)
@@ -382,9 +331,7 @@ int glx_certificate_step(int dtype, int64_t m, int64_t n, int64_t l, const void*
       else
         launch_atr_cert<T>(pl.a, (const T*)A, (const T*)Z, (T*)G, (const T*)x, rownorm_out, mu, red, st,
                            pl.a.atr_S > 1 ? (T*)w.gp : nullptr, w.pcnt);
-    };
-    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
-    else go(static_cast<float*>(nullptr));
+    });
     check_launch();
   });
 }

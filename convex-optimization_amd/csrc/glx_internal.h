@@ -655,40 +655,6 @@ void group_screen_guard_ic(const double* rec, double mu, int dtype, int64_t m, i
 // the checks every weighted C entry makes of its two vectors: 16-byte aligned, hold only with w
 void check_sample(const void* sample_w, const void* holdout_w);
 
-// ---- shared by the two ADMM drivers (defined in admm.cpp) ----
-namespace admm {
-constexpr int kMaxL = 32;    // the Gram kernel and the host Jacobi sweep
-constexpr int kRecHead = 4;  // record: [||Ax - b||^2, sum_i ||x_i||, max |x|, count] + 2 Grams
-struct Carver {   // 256-byte aligned pieces of a workspace (base == NULL: sizes only)
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-  void* take(size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    void* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  }
-};
-struct HostRec {   // n pinned doubles for the per-iteration readback
-  double* p = nullptr;
-  explicit HostRec(size_t n);
-  ~HostRec();
-  HostRec(const HostRec&) = delete;
-  HostRec& operator=(const HostRec&) = delete;
-};
-// largest eigenvalue of the symmetric l x l matrix G (row-major, l <= kMaxL) by cyclic Jacobi
-// sweeps, NaN where G holds one; the spectral norm of R from gram = R^T R
-double sym_lambda_max(const double* G, int l);
-double spectral_norm(const double* gram, int l);
-// sparsity of the iterate after each iteration of this thread's last solve (glx_admm_trace)
-std::vector<double>& trace();
-// A's plan of an ADMM solve: the session plan of a one-GPU line-search ProxGD at this shape
-GemmPlan a_plan(int dtype, int64_t m, int64_t n, int64_t l);
-// field `idx` of describe_plan's "ax1=..; ax2=..; ax3=..; atr=.." line, without its label
-std::string plan_field(const GemmPlan& p, int idx);
-}  // namespace admm
-
 // ---- split-candidate A e from a transposed copy of A (kernels_gather.hip) ----
 // gather_ok: the shape supports it (l in {16, 32}, n < 65536); gather_split: K splits of the
 // flagged-row list for m output rows (slabs P[S][m][l]).

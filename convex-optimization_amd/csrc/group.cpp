@@ -4,8 +4,6 @@
 // screen.cpp certified_run) with a GroupView: this unit validates the caller's host description of
 // the groups before any launch, uploads it behind the callee's workspace, composes the grouped
 // rounding guard and exposes the four kernels of kernels_group.hip one launch at a time.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -13,44 +11,12 @@
 #include <cstring>
 #include <limits>
 #include <string>
-#include <type_traits>
 #include <vector>
 
-#include "glx.h"
-#include "glx_internal.h"
+#include "glx_host.h"
 
 namespace glx {
 namespace {
-
-#define GLX_HIP(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) throw Error{GLX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-
-inline void check_launch() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw Error{GLX_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)};
-}
-
-template <typename F>
-int guarded(F&& f) {
-  try {
-    f();
-    return GLX_OK;
-  } catch (const Error& e) {
-    g_last_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return GLX_E_STATE;
-  } catch (...) {
-    g_last_error = "unknown error";
-    return GLX_E_STATE;
-  }
-}
-
-using admm::Carver;
 
 // What the host knows of a valid description: the figures the layout and the guard need.
 struct GroupFacts {
@@ -78,17 +44,11 @@ GroupFacts check_groups(int64_t n, int64_t G, const int32_t* ptr, const double* 
   return f;
 }
 void check_dims(int dtype, int64_t n, int64_t l) {
-  if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+  check_dtype(dtype);
   if (n <= 0 || l <= 0) throw Error{GLX_E_INVALID, "n, l must be positive"};
   if (l > kMaxL) throw Error{GLX_E_INVALID, "the group entries take l <= 128"};
   if (n > (int64_t)0x7fffffc0) throw Error{GLX_E_INVALID, "the group entries take n < 2^31 - 64"};
 }
-void check_ws(size_t need, const void* ws, size_t wsb, const char* who) {
-  if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
-  if (wsb < need) throw Error{GLX_E_INVALID, std::string("workspace too small (") + who + ")"};
-  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
-}
-
 // the description's device copy, behind `head` bytes of the callee's workspace
 struct GroupDev {
   void* head;
@@ -271,9 +231,9 @@ int glx_group_certificate_describe(int dtype, int64_t m, int64_t n, int64_t l, i
     if (!out || cap == 0) throw Error{GLX_E_INVALID, "null out"};
     check_dims(dtype, n, l);
     if (max_run < 1 || max_run > n) throw Error{GLX_E_INVALID, "max_run must be in 1 .. n"};
-    const GemmPlan p = admm::a_plan(dtype, m, n, l);
-    std::snprintf(out, cap, "A x=%s; A^T r=%s; groups=group kernel (k_group_cert, %s)", admm::plan_field(p, 0).c_str(),
-                  admm::plan_field(p, 3).c_str(), group_layout(max_run * l).c_str());
+    const GemmPlan p = a_plan(dtype, m, n, l);
+    std::snprintf(out, cap, "A x=%s; A^T r=%s; groups=group kernel (k_group_cert, %s)", plan_field(p, 0).c_str(),
+                  plan_field(p, 3).c_str(), group_layout(max_run * l).c_str());
   });
 }
 
@@ -287,7 +247,8 @@ int glx_group_certificate(int dtype, int64_t m, int64_t n, int64_t l, const void
     if (!A || !X || !b) throw Error{GLX_E_INVALID, "A, X and b must be device pointers"};
     if (!out) throw Error{GLX_E_INVALID, "null out"};
     const size_t head = cert_bytes(dtype, m, n, l);
-    check_ws(group_carve(head, G, nullptr, nullptr), ws, wsb, "glx_group_certificate_workspace_bytes");
+    check_workspace(group_carve(head, G, nullptr, nullptr), ws, wsb, GLX_E_INVALID,
+                    "glx_group_certificate_workspace_bytes");
     GroupDev d;
     group_carve(head, G, ws, &d);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -325,7 +286,8 @@ int glx_group_certified_solve(const glx_problem* prob, int64_t G, const int32_t*
     check_dims(prob->dtype, prob->n, prob->l);
     const GroupFacts f = check_groups(prob->n, G, group_ptr, weights);
     const size_t head = certified_bytes(prob->dtype, prob->m, prob->n, prob->l, screen != 0, G);
-    check_ws(group_carve(head, G, nullptr, nullptr), ws, wsb, "glx_group_certified_workspace_bytes");
+    check_workspace(group_carve(head, G, nullptr, nullptr), ws, wsb, GLX_E_INVALID,
+                    "glx_group_certified_workspace_bytes");
     if (!prob->A || !prob->b || !prob->x) throw Error{GLX_E_INVALID, "A, b and x must be device pointers"};
     GroupDev d;
     group_carve(head, G, ws, &d);
@@ -387,7 +349,7 @@ int glx_group_certificate_sw(int dtype, int64_t m, int64_t n, int64_t l, const v
     if (!out) throw Error{GLX_E_INVALID, "null out"};
     const size_t head = cert_bytes(dtype, m, n, l);
     const size_t grouped = group_carve(head, G, nullptr, nullptr);
-    check_ws(sample_bytes(grouped), ws, wsb, "glx_group_certificate_sw_workspace_bytes");
+    check_workspace(sample_bytes(grouped), ws, wsb, GLX_E_INVALID, "glx_group_certificate_sw_workspace_bytes");
     GroupDev d;
     group_carve(head, G, ws, &d);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -434,7 +396,8 @@ int glx_group_certified_solve_sw(const glx_problem* prob, int64_t G, const int32
     check_sample(sample_w, holdout_w);
     const bool weighted = sample_w != nullptr;   // (NULL: the grouped entry's own layout and calls)
     const size_t head = certified_bytes(prob->dtype, prob->m, prob->n, prob->l, screen != 0, G, weighted);
-    check_ws(group_carve(head, G, nullptr, nullptr), ws, wsb, "glx_group_certified_sw_workspace_bytes");
+    check_workspace(group_carve(head, G, nullptr, nullptr), ws, wsb, GLX_E_INVALID,
+                    "glx_group_certified_sw_workspace_bytes");
     if (!prob->A || !prob->b || !prob->x) throw Error{GLX_E_INVALID, "A, b and x must be device pointers"};
     GroupDev d;
     group_carve(head, G, ws, &d);
@@ -504,8 +467,8 @@ int glx_group_certificate_ic(int dtype, int64_t m, int64_t n, int64_t l, const v
     const int es = dtype == GLX_F64 ? 8 : 4;
     const size_t head = cert_bytes(dtype, m, n, l);
     const size_t grouped = group_carve(head, G, nullptr, nullptr);
-    check_ws(intercept_carve(sample_bytes(grouped), es, m, l, nullptr, nullptr), ws, wsb,
-             "glx_group_certificate_ic_workspace_bytes");
+    check_workspace(intercept_carve(sample_bytes(grouped), es, m, l, nullptr, nullptr), ws, wsb, GLX_E_INVALID,
+                    "glx_group_certificate_ic_workspace_bytes");
     GroupDev d;
     group_carve(head, G, ws, &d);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -554,7 +517,8 @@ int glx_group_certified_solve_ic(const glx_problem* prob, int64_t G, const int32
     check_sample(sample_w, holdout_w);
     check_intercept(weight_sum, intercept_out);
     const size_t head = certified_bytes(prob->dtype, prob->m, prob->n, prob->l, screen != 0, G, true, true);
-    check_ws(group_carve(head, G, nullptr, nullptr), ws, wsb, "glx_group_certified_ic_workspace_bytes");
+    check_workspace(group_carve(head, G, nullptr, nullptr), ws, wsb, GLX_E_INVALID,
+                    "glx_group_certified_ic_workspace_bytes");
     if (!prob->A || !prob->b || !prob->x) throw Error{GLX_E_INVALID, "A, b and x must be device pointers"};
     GroupDev d;
     group_carve(head, G, ws, &d);
@@ -595,7 +559,7 @@ int glx_group_step(int dtype, int64_t n, int64_t rows, int64_t l, int64_t G, con
     if (rows < n || rows > n + 63) throw Error{GLX_E_INVALID, "rows must be in n .. n + 63 (the padded width)"};
     if (S < 1 || S > kMaxSplit) throw Error{GLX_E_INVALID, "S must be in 1 .. 64"};
     if (!y || !g || !xk || !xc || !vnext || !ynext || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
-    check_ws(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, "glx_group_workspace_bytes");
+    check_workspace(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_group_workspace_bytes");
     GroupDev d;
     group_carve(kStepHead, G, ws, &d);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -603,14 +567,11 @@ int glx_group_step(int dtype, int64_t n, int64_t rows, int64_t l, int64_t G, con
     const StepWs w = step_head(d.head);
     GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
     const Red red{w.part, w.ticket, static_cast<double*>(sums_dev)};
-    if (dtype == GLX_F64)
-      launch_group_fista<double>((const double*)y, (const double*)g, S, (const double*)xk, (double*)xc,
-                                 (double*)vnext, (double*)ynext, v.ptr, v.wts, G, rows, l, v.max_run, t, mu, thres,
-                                 theta, theta_next, red, st);
-    else
-      launch_group_fista<float>((const float*)y, (const float*)g, S, (const float*)xk, (float*)xc, (float*)vnext,
-                                (float*)ynext, v.ptr, v.wts, G, rows, l, v.max_run, t, mu, thres, theta, theta_next,
-                                red, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_group_fista<T>((const T*)y, (const T*)g, S, (const T*)xk, (T*)xc, (T*)vnext, (T*)ynext, v.ptr, v.wts, G,
+                            rows, l, v.max_run, t, mu, thres, theta, theta_next, red, st);
+    });
     check_launch();
   });
 }
@@ -624,7 +585,7 @@ int glx_group_certificate_step(int dtype, int64_t n, int64_t l, int64_t G, const
     if (S < 1 || S > kMaxSplit) throw Error{GLX_E_INVALID, "S must be in 1 .. 64"};
     if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
     if (!x || !g || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
-    check_ws(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, "glx_group_workspace_bytes");
+    check_workspace(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_group_workspace_bytes");
     GroupDev d;
     group_carve(kStepHead, G, ws, &d);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -632,12 +593,11 @@ int glx_group_certificate_step(int dtype, int64_t n, int64_t l, int64_t G, const
     const StepWs w = step_head(d.head);
     GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
     const Red red{w.part, w.ticket, static_cast<double*>(sums_dev)};
-    if (dtype == GLX_F64)
-      launch_group_cert<double>((const double*)x, (const double*)g, S, (double*)gout, groupnorm_out, v.ptr, v.wts, G,
-                                n, l, v.max_run, mu, red, st);
-    else
-      launch_group_cert<float>((const float*)x, (const float*)g, S, (float*)gout, groupnorm_out, v.ptr, v.wts, G, n,
-                               l, v.max_run, mu, red, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_group_cert<T>((const T*)x, (const T*)g, S, (T*)gout, groupnorm_out, v.ptr, v.wts, G, n, l, v.max_run, mu,
+                           red, st);
+    });
     check_launch();
   });
 }
@@ -649,7 +609,7 @@ int glx_group_cnorm(int64_t n, int64_t G, const int32_t* group_ptr, const double
     check_dims(GLX_F64, n, 1);
     const GroupFacts f = check_groups(n, G, group_ptr, weights);
     if (!col_norms_dev || !gcn_dev || !max_dev) throw Error{GLX_E_INVALID, "null argument"};
-    check_ws(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, "glx_group_workspace_bytes");
+    check_workspace(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_group_workspace_bytes");
     GroupDev d;
     group_carve(kStepHead, G, ws, &d);
     hipStream_t st = static_cast<hipStream_t>(stream);

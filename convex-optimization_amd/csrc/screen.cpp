@@ -25,8 +25,6 @@
 // + mu Omega(x) with c eliminated exactly: the residual finalizes become the two centring launches
 // (launch_cert_csum, launch_cert_fin_c: r = w (A y - b - 1 mean^T)), the column figures are the centred
 // ones, every certificate centres and the screen runs under screen_guard_ic with its slack off mu.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
@@ -35,10 +33,8 @@
 #include <cstring>
 #include <limits>
 #include <string>
-#include <type_traits>
 
-#include "glx.h"
-#include "glx_internal.h"
+#include "glx_host.h"
 
 namespace glx {
 
@@ -50,37 +46,6 @@ double gamma_k(double k, double u) {
 }
 
 namespace {
-
-#define GLX_HIP(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) throw Error{GLX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-
-inline void check_launch() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw Error{GLX_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)};
-}
-
-template <typename F>
-int guarded(F&& f) {
-  try {
-    f();
-    return GLX_OK;
-  } catch (const Error& e) {
-    g_last_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return GLX_E_STATE;
-  } catch (...) {
-    g_last_error = "unknown error";
-    return GLX_E_STATE;
-  }
-}
-
-using admm::Carver;
-using admm::plan_field;
 
 inline int64_t pad64(int64_t v) { return (v + 63) / 64 * 64; }
 
@@ -124,21 +89,9 @@ void screen_guard(const double* rec, double mu, int dtype, int64_t m, int64_t n,
   out[2] = rho;
 }
 
-// the plan of a (reduced) problem: the certificate's (certificate.cpp cert_plan)
-struct CPlan {
-  int es = 8;
-  GemmPlan a{};
-  bool fuse = false;
-};
-CPlan cplan(int dtype, int64_t m, int64_t w, int64_t l) {
-  CPlan p;
-  p.es = dtype == GLX_F64 ? 8 : 4;
-  p.a = admm::a_plan(dtype, m, w, l);
-  p.fuse = atr_prox_ok(p.a) && (p.a.atr->fused & dtype_bit(p.es)) != 0;
-  return p;
-}
+// the plan of a (reduced) problem is the certificate's: glx_host.h fuse_plan
 void check_shape(int dtype, int64_t m, int64_t n, int64_t l) {
-  if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+  check_dtype(dtype);
   if (m <= 0 || n <= 0 || l <= 0) throw Error{GLX_E_INVALID, "m, n, l must be positive"};
   if (l > kMaxL) throw Error{GLX_E_INVALID, "the certified solve takes l <= 128"};
   if (n > (int64_t)0x7fffffc0) throw Error{GLX_E_INVALID, "the certified solve takes n < 2^31 - 64"};
@@ -159,7 +112,7 @@ Extent extent(int dtype, int64_t m, int64_t n, int64_t l, bool screen) {
     size_t b = 0;
     if (glx_certificate_workspace_bytes(dtype, m, w, l, &b) != GLX_OK) throw Error{GLX_E_INVALID, g_last_error};
     e.cert = std::max(e.cert, b);
-    const CPlan p = cplan(dtype, m, w, l);
+    const FusePlan p = fuse_plan(dtype, m, w, l);
     e.ax_s = std::max(e.ax_s, std::max(1, ax_split(p.a, 1)));
     e.atr_s = std::max(e.atr_s, std::max(1, p.a.atr_S));
   };
@@ -240,11 +193,11 @@ size_t carve(int dtype, int64_t m, int64_t n, int64_t l, bool screen, bool own_n
 }
 
 std::string describe_certified(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run = 0) {
-  const CPlan p = cplan(dtype, m, n, l);
+  const FusePlan p = fuse_plan(dtype, m, n, l);
   std::string s = "FISTA, fixed step, exact prox; A y=" + plan_field(p.a, 0) + "; A^T r=" + plan_field(p.a, 3) +
                   "; step=";
   if (max_run > 0) s += "group kernel (k_group_fista, " + group_layout(max_run * l) + ")";
-  else s += p.fuse ? "fused (k_atr_fista, the A^T r epilogue)" : "row kernel (k_fista_trial)";
+  else s += p.fuse_ok ? "fused (k_atr_fista, the A^T r epilogue)" : "row kernel (k_fista_trial)";
   s += screen ? "; screening=gap-safe, compaction to multiples of 64 at <= 0.9 of the width" : "; screening=off";
   return s;
 }
@@ -389,7 +342,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
   // the current (reduced) problem
   const T* Ac = A;
   int64_t wc = n;
-  CPlan pl = cplan(dtype, m, n, l);
+  FusePlan pl = fuse_plan(dtype, m, n, l);
   int side = 0;              // the buffer the next compaction writes
   const int* map = nullptr;  // reduced row -> full row (NULL: identity)
   int mapi = 0;
@@ -397,7 +350,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     *yn = static_cast<T*>(w.x[3]), *vn = static_cast<T*>(w.x[4]);
   GLX_HIP(hipMemcpyAsync(x, X, es * n * l, hipMemcpyDeviceToDevice, st));
   GLX_HIP(hipMemcpyAsync(y, X, es * n * l, hipMemcpyDeviceToDevice, st));
-  info->fused = pl.fuse && grp == nullptr ? 1 : 0;
+  info->fused = pl.fuse_ok && grp == nullptr ? 1 : 0;
 
   double target = tol;
   int64_t k = 1;       // momentum index: theta = 2 / (k + 1)
@@ -508,7 +461,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     mapi ^= 1;
     side ^= 1;
     wc = wp;
-    pl = cplan(dtype, m, wc, l);
+    pl = fuse_plan(dtype, m, wc, l);
     if (info->compactions < GLX_CERTIFIED_MAX_HIST) info->kept_hist[info->compactions] = kept;
     ++info->compactions;
     listed = -1;   // the composed list alone names them now
@@ -533,7 +486,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
       launch_atr<T>(pl.a, Ac, r, gp, st);
       launch_group_fista<T>(y, gp, pl.a.atr_S, x, xc, vn, yn, gcur.ptr, gcur.wts, gcur.G, wc, l, grp->max_run, t, mu,
                             thres, theta, theta_next, red1, st);
-    } else if (pl.fuse) {
+    } else if (pl.fuse_ok) {
       launch_atr_fista<T>(pl.a, Ac, r, static_cast<T*>(w.g), y, x, xc, vn, yn, t, mu, thres, theta, theta_next, red1,
                           st, Pub{}, pl.a.atr_S > 1 ? gp : nullptr, w.pcnt);
     } else {
@@ -586,12 +539,6 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
   info->iters = it;
   info->width = wc;
   info->tt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-}
-
-void check_ws(size_t need, const void* ws, size_t wsb, const char* who) {
-  if (!ws) throw Error{GLX_E_INVALID, "null workspace"};
-  if (wsb < need) throw Error{GLX_E_INVALID, std::string("workspace too small (") + who + ")"};
-  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_INVALID, "workspace must be 256-byte aligned"};
 }
 
 // the one-launch entries' workspace: [partials | ticket | out | column partials | column counters |
@@ -699,19 +646,18 @@ void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit,
     throw Error{GLX_E_INVALID, "A, b, x must be 16-byte aligned"};
   if ((col_norms_dev != nullptr) != (col_stats != nullptr))
     throw Error{GLX_E_INVALID, "col_norms_dev and col_stats go together"};
-  check_ws(carve(prob->dtype, prob->m, prob->n, prob->l, screen != 0, true, nullptr, nullptr,
-                 grp != nullptr ? grp->G : 0, sw != nullptr || ic != nullptr, ic != nullptr),
-           ws, wsb, grp != nullptr ? "glx_group_certified_workspace_bytes" : "glx_certified_workspace_bytes");
+  check_workspace(carve(prob->dtype, prob->m, prob->n, prob->l, screen != 0, true, nullptr, nullptr,
+                        grp != nullptr ? grp->G : 0, sw != nullptr || ic != nullptr, ic != nullptr),
+                  ws, wsb, GLX_E_INVALID,
+                  grp != nullptr ? "glx_group_certified_workspace_bytes" : "glx_certified_workspace_bytes");
   if (holdout_sum != nullptr) *holdout_sum = 0.0;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (prob->dtype == GLX_F64)
-    solve<double>(prob->dtype, prob->m, prob->n, prob->l, (const double*)prob->A, (const double*)prob->b,
-                  (double*)prob->x, prob->mu0, t, tol, maxit, screen != 0, check_every, col_norms_dev, col_stats,
-                  kept_rows_dev, ws, info, st, grp, kept_groups_dev, listed_groups, sw, holdout_sum, ic);
-  else
-    solve<float>(prob->dtype, prob->m, prob->n, prob->l, (const float*)prob->A, (const float*)prob->b,
-                 (float*)prob->x, prob->mu0, t, tol, maxit, screen != 0, check_every, col_norms_dev, col_stats,
-                 kept_rows_dev, ws, info, st, grp, kept_groups_dev, listed_groups, sw, holdout_sum, ic);
+  by_dtype(prob->dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    solve<T>(prob->dtype, prob->m, prob->n, prob->l, (const T*)prob->A, (const T*)prob->b, (T*)prob->x, prob->mu0, t,
+             tol, maxit, screen != 0, check_every, col_norms_dev, col_stats, kept_rows_dev, ws, info, st, grp,
+             kept_groups_dev, listed_groups, sw, holdout_sum, ic);
+  });
 }
 
 }  // namespace glx
@@ -743,15 +689,17 @@ int glx_col_norms(int dtype, int64_t m, int64_t n, const void* A, double* norms_
   return guarded([&] {
     check_shape(dtype, m, n, 1);
     if (!A || !norms_dev || !stats_dev) throw Error{GLX_E_INVALID, "null argument"};
-    check_ws(step_carve(m, n, nullptr, nullptr), ws, wsb, "glx_screen_workspace_bytes");
+    check_workspace(step_carve(m, n, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_screen_workspace_bytes");
     StepWs w;
     step_carve(m, n, ws, &w);
     hipStream_t st = static_cast<hipStream_t>(stream);
     GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
     GLX_HIP(hipMemsetAsync(w.ccnt, 0, col_norms_count_bytes(n), st));
     const Red red{w.part, w.ticket, stats_dev};
-    if (dtype == GLX_F64) launch_col_norms<double>((const double*)A, m, n, norms_dev, w.cpart, w.ccnt, red, st);
-    else launch_col_norms<float>((const float*)A, m, n, norms_dev, w.cpart, w.ccnt, red, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_col_norms<T>((const T*)A, m, n, norms_dev, w.cpart, w.ccnt, red, st);
+    });
     check_launch();
   });
 }
@@ -761,7 +709,7 @@ int glx_screen_step(int64_t n, const double* row_norms, const double* col_norms,
   return guarded([&] {
     if (n <= 0 || n > (int64_t)0x7fffffc0) throw Error{GLX_E_INVALID, "n must be in 1 .. 2^31 - 65"};
     if (!row_norms || !col_norms || !list || !count) throw Error{GLX_E_INVALID, "null argument"};
-    check_ws(step_carve(1, n, nullptr, nullptr), ws, wsb, "glx_screen_workspace_bytes");
+    check_workspace(step_carve(1, n, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_screen_workspace_bytes");
     StepWs w;
     step_carve(1, n, ws, &w);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -774,14 +722,16 @@ int glx_screen_step(int64_t n, const double* row_norms, const double* col_norms,
 int glx_gather_cols(int dtype, int64_t m, int64_t src_width, const void* src, const int32_t* idx, int64_t width,
                     void* dst, void* stream) {
   return guarded([&] {
-    if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+    check_dtype(dtype);
     if (m <= 0 || src_width <= 0 || width < 0) throw Error{GLX_E_INVALID, "bad shape"};
     if (width % 64 != 0) throw Error{GLX_E_INVALID, "the destination width must be a multiple of 64"};
     if (width == 0) return;
     if (!src || !idx || !dst) throw Error{GLX_E_INVALID, "null argument"};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == GLX_F64) launch_gather_cols<double>((const double*)src, m, src_width, idx, width, (double*)dst, st);
-    else launch_gather_cols<float>((const float*)src, m, src_width, idx, width, (float*)dst, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_gather_cols<T>((const T*)src, m, src_width, idx, width, (T*)dst, st);
+    });
     check_launch();
   });
 }
@@ -829,17 +779,17 @@ int glx_col_norms_sw(int dtype, int64_t m, int64_t n, const void* A, const void*
     check_shape(dtype, m, n, 1);
     if (!A || !sample_w || !norms_dev || !stats_dev) throw Error{GLX_E_INVALID, "null argument"};
     check_sample(sample_w, nullptr);
-    check_ws(step_carve(m, n, nullptr, nullptr), ws, wsb, "glx_screen_workspace_bytes");
+    check_workspace(step_carve(m, n, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_screen_workspace_bytes");
     StepWs w;
     step_carve(m, n, ws, &w);
     hipStream_t st = static_cast<hipStream_t>(stream);
     GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
     GLX_HIP(hipMemsetAsync(w.ccnt, 0, col_norms_count_bytes(n), st));
     const Red red{w.part, w.ticket, stats_dev};
-    if (dtype == GLX_F64)
-      launch_col_norms_w<double>((const double*)A, (const double*)sample_w, m, n, norms_dev, w.cpart, w.ccnt, red, st);
-    else
-      launch_col_norms_w<float>((const float*)A, (const float*)sample_w, m, n, norms_dev, w.cpart, w.ccnt, red, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_col_norms_w<T>((const T*)A, (const T*)sample_w, m, n, norms_dev, w.cpart, w.ccnt, red, st);
+    });
     check_launch();
   });
 }
@@ -853,23 +803,21 @@ int glx_cert_fin_sw(int dtype, int64_t m, int64_t l, const void* P, int S, const
     if ((S > 0) != (P != nullptr)) throw Error{GLX_E_INVALID, "P goes with S > 0"};
     if (!b || !rw_out || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
     check_sample(sample_w, holdout_w);
-    check_ws(step_carve(1, 1, nullptr, nullptr), ws, wsb, "glx_screen_workspace_bytes");
+    check_workspace(step_carve(1, 1, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_screen_workspace_bytes");
     StepWs w;
     step_carve(1, 1, ws, &w);
     hipStream_t st = static_cast<hipStream_t>(stream);
     GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
     const Red red{w.part, w.ticket, sums_dev};
     const int64_t ml = m * l;
-    auto go = [&](auto* tag) {
-      typedef std::remove_pointer_t<decltype(tag)> T;
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
       if (sample_w != nullptr)
         launch_cert_fin_w<T>((const T*)P, S, (const T*)b, (const T*)sample_w, (const T*)holdout_w, (T*)r_out,
                              (T*)rw_out, ml, l, red, st);
       else   // the unweighted finalize, for the bit comparison: rw_out = r, two sums
         launch_cert_fin<T>((const T*)P, S, (const T*)b, (T*)rw_out, ml, red, st);
-    };
-    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
-    else go(static_cast<float*>(nullptr));
+    });
     check_launch();
   });
 }
@@ -959,19 +907,19 @@ int glx_col_norms_ic(int dtype, int64_t m, int64_t n, const void* A, const void*
     check_sample(sample_w, nullptr);
     if (!(weight_sum > 0.0) || !std::isfinite(weight_sum))
       throw Error{GLX_E_INVALID, "intercept: weight_sum must be positive and finite"};
-    check_ws(ic_step_carve(m, n, nullptr, nullptr, nullptr), ws, wsb, "glx_intercept_workspace_bytes");
+    check_workspace(ic_step_carve(m, n, nullptr, nullptr, nullptr), ws, wsb, GLX_E_INVALID,
+                    "glx_intercept_workspace_bytes");
     StepWs w;
     ic_step_carve(m, n, ws, &w, nullptr);
     hipStream_t st = static_cast<hipStream_t>(stream);
     GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
     GLX_HIP(hipMemsetAsync(w.ccnt, 0, col_norms_count_bytes(n), st));
     const Red red{w.part, w.ticket, stats_dev}, red_mean{w.part, w.ticket, stats_dev + 2};
-    if (dtype == GLX_F64)
-      launch_col_norms_c<double>((const double*)A, (const double*)sample_w, weight_sum, m, n, norms_dev, means_dev,
-                                 w.cpart, w.ccnt, red_mean, red, st);
-    else
-      launch_col_norms_c<float>((const float*)A, (const float*)sample_w, weight_sum, m, n, norms_dev, means_dev,
-                                w.cpart, w.ccnt, red_mean, red, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_col_norms_c<T>((const T*)A, (const T*)sample_w, weight_sum, m, n, norms_dev, means_dev, w.cpart, w.ccnt,
+                            red_mean, red, st);
+    });
     check_launch();
   });
 }
@@ -988,7 +936,8 @@ int glx_cert_fin_ic(int dtype, int64_t m, int64_t l, const void* P, int S, const
       throw Error{GLX_E_INVALID, "sample_w and holdout_w must be 16-byte aligned"};
     if (!(weight_sum > 0.0) || !std::isfinite(weight_sum))
       throw Error{GLX_E_INVALID, "intercept: weight_sum must be positive and finite"};
-    check_ws(ic_step_carve(1, 1, nullptr, nullptr, nullptr), ws, wsb, "glx_intercept_workspace_bytes");
+    check_workspace(ic_step_carve(1, 1, nullptr, nullptr, nullptr), ws, wsb, GLX_E_INVALID,
+                    "glx_intercept_workspace_bytes");
     StepWs w;
     IcStepWs iw;
     ic_step_carve(1, 1, ws, &w, &iw);
@@ -996,15 +945,13 @@ int glx_cert_fin_ic(int dtype, int64_t m, int64_t l, const void* P, int S, const
     GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
     GLX_HIP(hipMemsetAsync(iw.cnt, 0, 256, st));
     const Red red{w.part, w.ticket, sums_dev};
-    auto go = [&](auto* tag) {
-      typedef std::remove_pointer_t<decltype(tag)> T;
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
       launch_cert_csum<T>((const T*)P, S, (const T*)b, (const T*)sample_w, (T*)rhat_out, m, l, weight_sum, iw.part,
                           iw.cnt, means_dev, st);
       launch_cert_fin_c<T>((const T*)rhat_out, (const T*)b, (const T*)sample_w, (const T*)holdout_w, means_dev,
                            (T*)rc_out, (T*)rw_out, m * l, l, red, st);
-    };
-    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
-    else go(static_cast<float*>(nullptr));
+    });
     check_launch();
   });
 }

@@ -13,8 +13,6 @@
 //           (+1 A@x when the hard threshold changed x, +1 A@x in exact_objective mode)
 //   FProxGD reference 4 A@x + 1 A^T r;    here 1 A@y + 1 A@x per trial + 1 A^T r
 //   SGD/GD  reference 2 A@x + 1 A^T r;    here 1 A@x (+1 when the threshold changed x) + 1 A^T r
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <atomic>
 #include <cstdio>
@@ -24,28 +22,15 @@
 #include <cstring>
 #include <memory>
 #include <string>
-#include <type_traits>
 #include <vector>
 
-#include "glx.h"
 #include "glx_comm.h"
-#include "glx_internal.h"
+#include "glx_host.h"
 
 namespace glx {
 
 thread_local std::string g_last_error;
 thread_local LaunchTiming g_launch_timing;
-
-#define GLX_HIP(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) throw Error{GLX_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)}; \
-  } while (0)
-
-static inline void check_launch() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw Error{GLX_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e)};
-}
 
 // scalar slots in the device scalar array
 enum {
@@ -62,18 +47,6 @@ enum {
   S_SNAP = 24,  // snapshot of S_TR..S_TR+5 taken by a finalize (packet remap, not copied itself)
   S_SPX = 30,   // SGD/GD log sparsity every 100 iterations: [sum ||x_i||, max |x|] of the new x
   NSCAL_DEV = 32
-};
-
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-  void* take(size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    void* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  }
 };
 
 static int method_bufs(int method) {
@@ -103,7 +76,7 @@ static int64_t shard_blk_doubles(int64_t n, int64_t l) {
 
 static void validate(const glx_problem* P, const glx_opts* O) {
   if (!P || !O) throw Error{GLX_E_INVALID, "null problem/opts"};
-  if (P->dtype != GLX_F32 && P->dtype != GLX_F64) throw Error{GLX_E_INVALID, "dtype must be GLX_F32 or GLX_F64"};
+  check_dtype(P->dtype);
   if (P->method < GLX_PROXGD || P->method > GLX_FGD) throw Error{GLX_E_INVALID, "unknown method"};
   if (P->m <= 0 || P->n <= 0 || P->l <= 0) throw Error{GLX_E_INVALID, "m, n, l must be positive"};
   if (P->l > kMaxL) throw Error{GLX_E_INVALID, "l > 128 is not supported"};
@@ -2279,24 +2252,9 @@ class Session : public SessionBase {
 
 static size_t session_bytes(const glx_problem& P, const glx_opts& O) {
   const SessionMode md = session_mode(P, O);
-  return P.dtype == GLX_F64 ? Session<double>::carve(md, nullptr, nullptr) : Session<float>::carve(md, nullptr, nullptr);
-}
-
-template <typename F>
-static int guarded(F&& f) {
-  try {
-    f();
-    return GLX_OK;
-  } catch (const Error& e) {
-    g_last_error = e.msg;
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return GLX_E_STATE;
-  } catch (...) {
-    g_last_error = "unknown error";
-    return GLX_E_STATE;
-  }
+  return by_dtype(P.dtype, [&](auto tag) {
+    return Session<typename decltype(tag)::type>::carve(md, nullptr, nullptr);
+  });
 }
 
 // ---- single-kernel workspace: P slabs + Gp slabs + reduction scratch
@@ -2422,10 +2380,9 @@ int glx_session_create(glx_session** out, const glx_problem* prob, const glx_opt
     validate(prob, opts);
     auto s = std::make_unique<glx_session>();
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (prob->dtype == GLX_F64)
-      s->impl = std::make_unique<Session<double>>(*prob, *opts, workspace, workspace_bytes, st);
-    else
-      s->impl = std::make_unique<Session<float>>(*prob, *opts, workspace, workspace_bytes, st);
+    by_dtype(prob->dtype, [&](auto tag) {
+      s->impl = std::make_unique<Session<typename decltype(tag)::type>>(*prob, *opts, workspace, workspace_bytes, st);
+    });
     *out = s.release();
   });
 }
@@ -2546,8 +2503,7 @@ static KernelWs kernel_setup(int dtype, int64_t m, int64_t n, int64_t l, void* w
   if (m <= 0 || n <= 0 || l <= 0 || l > kMaxL) throw Error{GLX_E_INVALID, "bad shape"};
   const int es = dtype == GLX_F64 ? 8 : 4;
   *plan = make_plan(es, m, n, l, variant);
-  if (!ws || wsb < kernel_ws(es, *plan, nullptr, nullptr, trial)) throw Error{GLX_E_WORKSPACE, "workspace too small"};
-  if (reinterpret_cast<uintptr_t>(ws) & 255) throw Error{GLX_E_WORKSPACE, "workspace must be 256-byte aligned"};
+  check_workspace(kernel_ws(es, *plan, nullptr, nullptr, trial), ws, wsb, GLX_E_WORKSPACE, nullptr);
   KernelWs k;
   kernel_ws(es, *plan, ws, &k, trial);
   GLX_HIP(hipMemsetAsync(k.ticket, 0, kTicketBytes, st));
@@ -2562,19 +2518,14 @@ int glx_residual(int dtype, int64_t m, int64_t n, int64_t l, const void* A, cons
     GemmPlan p;
     KernelWs k = kernel_setup(dtype, m, n, l, ws, wsb, variant, st, &p);
     Red r{k.part, k.ticket, k.scal};
-    if (dtype == GLX_F64) {
-      const double* xs[3] = {(const double*)X, nullptr, nullptr};
-      double* rs[3] = {(double*)R, nullptr, nullptr};
-      launch_ax<double>(p, 1, (const double*)A, xs, (double*)k.pp, nullptr, 0, st);
-      launch_finalize_residual<double>((const double*)k.pp, p.ax_S, (const double*)B, 1, rs, m * l,
-                                       nullptr, 0, 1, nullptr, 0, nullptr, nullptr, 0.0, nullptr, r, st);
-    } else {
-      const float* xs[3] = {(const float*)X, nullptr, nullptr};
-      float* rs[3] = {(float*)R, nullptr, nullptr};
-      launch_ax<float>(p, 1, (const float*)A, xs, (float*)k.pp, nullptr, 0, st);
-      launch_finalize_residual<float>((const float*)k.pp, p.ax_S, (const float*)B, 1, rs, m * l,
-                                      nullptr, 0, 1, nullptr, 0, nullptr, nullptr, 0.0, nullptr, r, st);
-    }
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      const T* xs[3] = {(const T*)X, nullptr, nullptr};
+      T* rs[3] = {(T*)R, nullptr, nullptr};
+      launch_ax<T>(p, 1, (const T*)A, xs, (T*)k.pp, nullptr, 0, st);
+      launch_finalize_residual<T>((const T*)k.pp, p.ax_S, (const T*)B, 1, rs, m * l, nullptr, 0, 1, nullptr, 0,
+                                  nullptr, nullptr, 0.0, nullptr, r, st);
+    });
     check_launch();
     if (half_sumsq_dev) {
       // 0.5 * sum: scale on device with a tiny record kernel (fh[0] = 0.5*s + 0*s)
@@ -2593,21 +2544,15 @@ int glx_residual_batch(int dtype, int64_t m, int64_t n, int64_t l, const void* A
     GemmPlan p;
     KernelWs k = kernel_setup(dtype, m, n, l, ws, wsb, variant, st, &p);
     Red r{k.part, k.ticket, sumsq_dev ? static_cast<double*>(sumsq_dev) : k.scal};
-    if (dtype == GLX_F64) {
-      const double* xs[3] = {nullptr, nullptr, nullptr};
-      double* rs[3] = {nullptr, nullptr, nullptr};
-      for (int i = 0; i < nsrc; ++i) { xs[i] = (const double*)X[i]; rs[i] = (double*)R[i]; }
-      launch_ax<double>(p, nsrc, (const double*)A, xs, (double*)k.pp, nullptr, 0, st);
-      launch_finalize_residual<double>((const double*)k.pp, ax_split(p, nsrc), (const double*)B, nsrc, rs, m * l,
-                                       nullptr, 0, 1, nullptr, 0, nullptr, nullptr, 0.0, nullptr, r, st);
-    } else {
-      const float* xs[3] = {nullptr, nullptr, nullptr};
-      float* rs[3] = {nullptr, nullptr, nullptr};
-      for (int i = 0; i < nsrc; ++i) { xs[i] = (const float*)X[i]; rs[i] = (float*)R[i]; }
-      launch_ax<float>(p, nsrc, (const float*)A, xs, (float*)k.pp, nullptr, 0, st);
-      launch_finalize_residual<float>((const float*)k.pp, ax_split(p, nsrc), (const float*)B, nsrc, rs, m * l,
-                                      nullptr, 0, 1, nullptr, 0, nullptr, nullptr, 0.0, nullptr, r, st);
-    }
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      const T* xs[3] = {nullptr, nullptr, nullptr};
+      T* rs[3] = {nullptr, nullptr, nullptr};
+      for (int i = 0; i < nsrc; ++i) { xs[i] = (const T*)X[i]; rs[i] = (T*)R[i]; }
+      launch_ax<T>(p, nsrc, (const T*)A, xs, (T*)k.pp, nullptr, 0, st);
+      launch_finalize_residual<T>((const T*)k.pp, ax_split(p, nsrc), (const T*)B, nsrc, rs, m * l, nullptr, 0, 1,
+                                  nullptr, 0, nullptr, nullptr, 0.0, nullptr, r, st);
+    });
     check_launch();
   });
 }
@@ -2618,15 +2563,12 @@ int glx_gradient(int dtype, int64_t m, int64_t n, int64_t l, const void* A, cons
     hipStream_t st = static_cast<hipStream_t>(stream);
     GemmPlan p;
     KernelWs k = kernel_setup(dtype, m, n, l, ws, wsb, 0, st, &p);
-    if (dtype == GLX_F64) {
-      double* gp = p.atr_S > 1 ? (double*)k.gp : (double*)G;
-      launch_atr<double>(p, (const double*)A, (const double*)R, gp, st);
-      if (p.atr_S > 1) launch_sum_partials<double>(gp, p.atr_S, (double*)G, n * l, st);
-    } else {
-      float* gp = p.atr_S > 1 ? (float*)k.gp : (float*)G;
-      launch_atr<float>(p, (const float*)A, (const float*)R, gp, st);
-      if (p.atr_S > 1) launch_sum_partials<float>(gp, p.atr_S, (float*)G, n * l, st);
-    }
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      T* gp = p.atr_S > 1 ? (T*)k.gp : (T*)G;
+      launch_atr<T>(p, (const T*)A, (const T*)R, gp, st);
+      if (p.atr_S > 1) launch_sum_partials<T>(gp, p.atr_S, (T*)G, n * l, st);
+    });
     check_launch();
   });
 }
@@ -2642,8 +2584,8 @@ int glx_flagged_rows_product(int dtype, int64_t m, int64_t n, int64_t l, const v
     if (form < 0 || form > 2) throw Error{GLX_E_INVALID, "form must be 0 (MFMA rows), 1 (lists), 2 (bitmaps)"};
     if (form == 0 && !gather_rows_ok(m, n)) throw Error{GLX_E_INVALID, "the row form needs m % 64 == 0"};
     const int S0 = form == 0 ? gather_split(m, n) : 1;
-    auto go = [&](auto* tag) {
-      typedef std::remove_pointer_t<decltype(tag)> T;
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
       T* slabs = static_cast<T*>(k.fr_slabs);
       if (form == 0) {
         launch_at_rows<T>(static_cast<const T*>(At), static_cast<const T*>(E), row_masks, m, n, l, slabs,
@@ -2659,9 +2601,7 @@ int glx_flagged_rows_product(int dtype, int64_t m, int64_t n, int64_t l, const v
                                k.fr_lists, st);
       }
       launch_sum_partials<T>(slabs, S0, static_cast<T*>(Y), m * l, st);
-    };
-    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
-    else go(static_cast<float*>(nullptr));
+    });
     check_launch();
   });
 }
@@ -2774,8 +2714,8 @@ int glx_trial_proxgd(int dtype, int64_t m, int64_t n, int64_t l, const void* A, 
     if (emode == 0 && zf != nullptr && form != 2)
       throw Error{GLX_E_INVALID, "forms 0 and 1 write zf only with emode"};
     Red red{k.part, k.ticket, static_cast<double*>(sums_dev)};
-    auto go = [&](auto* tag) {
-      typedef std::remove_pointer_t<decltype(tag)> T;
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
       if (form == 0)
         launch_prox_pgd<T>((const T*)x, (const T*)G, 1, nullptr, (T*)p, (T*)pthr, (T*)z, n, l, t, mu, thres,
                            red, st, Pub{}, zf);
@@ -2785,9 +2725,7 @@ int glx_trial_proxgd(int dtype, int64_t m, int64_t n, int64_t l, const void* A, 
       else
         launch_trial_split<T>((const T*)p, (const T*)x, (T*)pthr, (T*)z, zf, n, l, t, thres, emode != 0,
                               ShardPub{}, st);
-    };
-    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
-    else go(static_cast<float*>(nullptr));
+    });
     check_launch();
   });
 }
@@ -2870,8 +2808,8 @@ int glx_trial_fista(int dtype, int64_t m, int64_t n, int64_t l, const void* A, c
     if (ec != nullptr && (prox == 0 || form == 2)) throw Error{GLX_E_INVALID, "ec and zf need prox = 1 in form 0 or 1"};
     if (form == 1 && prox == 0) throw Error{GLX_E_INVALID, "form 1 is the prox form"};
     Red red{k.part, k.ticket, static_cast<double*>(sums_dev)};
-    auto go = [&](auto* tag) {
-      typedef std::remove_pointer_t<decltype(tag)> T;
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
       if (form == 0)
         launch_fista_trial<T>(prox != 0, (const T*)y, (const T*)G, 1, nullptr, (const T*)xk, (T*)xc, (T*)vnext,
                               (T*)ynext, n, l, t, mu, thres, theta, theta_next, delta, red, st, Pub{}, (T*)ec,
@@ -2883,9 +2821,7 @@ int glx_trial_fista(int dtype, int64_t m, int64_t n, int64_t l, const void* A, c
       else
         launch_fista_split<T>((const T*)xc, (const T*)xk, (T*)vnext, (T*)ynext, n * l, thres, theta, theta_next,
                               ShardPub{}, st);
-    };
-    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
-    else go(static_cast<float*>(nullptr));
+    });
     check_launch();
   });
 }
@@ -2919,29 +2855,17 @@ int glx_residual_gradient(int dtype, int64_t m, int64_t n, int64_t l, const void
       }
       if (fused_out) *fused_out = 0;
     }
-    const int es = dtype == GLX_F64 ? 8 : 4;
-    (void)es;
-    if (dtype == GLX_F64) {
-      const double* xs[3] = {(const double*)X, nullptr, nullptr};
-      double* rs[3] = {(double*)R, nullptr, nullptr};
-      launch_ax<double>(p, 1, (const double*)A, xs, (double*)k.pp, nullptr, 0, st);
-      launch_finalize_residual<double>((const double*)k.pp, p.ax_S, (const double*)B, 1, rs, m * l,
-                                       nullptr, 0, 1, nullptr, 0, nullptr, nullptr, 0.0, nullptr,
-                                       Red{k.part, k.ticket, k.scal}, st);
-      double* gp = p.atr_S > 1 ? (double*)k.gp : (double*)G;
-      launch_atr<double>(p, (const double*)A, (const double*)R, gp, st);
-      if (p.atr_S > 1) launch_sum_partials<double>(gp, p.atr_S, (double*)G, n * l, st);
-    } else {
-      const float* xs[3] = {(const float*)X, nullptr, nullptr};
-      float* rs[3] = {(float*)R, nullptr, nullptr};
-      launch_ax<float>(p, 1, (const float*)A, xs, (float*)k.pp, nullptr, 0, st);
-      launch_finalize_residual<float>((const float*)k.pp, p.ax_S, (const float*)B, 1, rs, m * l,
-                                      nullptr, 0, 1, nullptr, 0, nullptr, nullptr, 0.0, nullptr,
-                                      Red{k.part, k.ticket, k.scal}, st);
-      float* gp = p.atr_S > 1 ? (float*)k.gp : (float*)G;
-      launch_atr<float>(p, (const float*)A, (const float*)R, gp, st);
-      if (p.atr_S > 1) launch_sum_partials<float>(gp, p.atr_S, (float*)G, n * l, st);
-    }
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      const T* xs[3] = {(const T*)X, nullptr, nullptr};
+      T* rs[3] = {(T*)R, nullptr, nullptr};
+      launch_ax<T>(p, 1, (const T*)A, xs, (T*)k.pp, nullptr, 0, st);
+      launch_finalize_residual<T>((const T*)k.pp, p.ax_S, (const T*)B, 1, rs, m * l, nullptr, 0, 1, nullptr, 0,
+                                  nullptr, nullptr, 0.0, nullptr, Red{k.part, k.ticket, k.scal}, st);
+      T* gp = p.atr_S > 1 ? (T*)k.gp : (T*)G;
+      launch_atr<T>(p, (const T*)A, (const T*)R, gp, st);
+      if (p.atr_S > 1) launch_sum_partials<T>(gp, p.atr_S, (T*)G, n * l, st);
+    });
     check_launch();
   });
 }
@@ -2975,8 +2899,9 @@ int glx_residual_gradient2(int dtype, int64_t m, int64_t n, int64_t l, const voi
       if (herr == 0) return;
       if (one_pass_ran) *one_pass_ran = 0;
     }
-    auto two = [&](auto* Ap) {
-      typedef std::remove_const_t<std::remove_pointer_t<decltype(Ap)>> T;
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      const T* Ap = (const T*)A;
       const T* xs[3] = {(const T*)X0, (const T*)X1, nullptr};
       T* rs[3] = {(T*)R0, (T*)R1, nullptr};
       launch_ax<T>(p, 2, Ap, xs, (T*)k.pp, nullptr, 0, st);
@@ -2986,9 +2911,7 @@ int glx_residual_gradient2(int dtype, int64_t m, int64_t n, int64_t l, const voi
       T* gp = p.atr_S > 1 ? (T*)k.gp : (T*)G;
       launch_atr<T>(p, Ap, (const T*)R1, gp, st);
       if (p.atr_S > 1) launch_sum_partials<T>(gp, p.atr_S, (T*)G, n * l, st);
-    };
-    if (dtype == GLX_F64) two((const double*)A);
-    else two((const float*)A);
+    });
     check_launch();
   });
 }
@@ -3000,10 +2923,10 @@ int glx_prox(int dtype, int64_t n, int64_t l, const void* W, double t, double mu
     GemmPlan p;
     KernelWs k = kernel_setup(dtype, 1, n, l, ws, wsb, 0, st, &p);
     Red r{k.part, k.ticket, sums_dev ? static_cast<double*>(sums_dev) : k.scal};
-    if (dtype == GLX_F64)
-      launch_prox_plain<double>((const double*)W, (double*)X_out, n, l, t, mu, thres, r, st);
-    else
-      launch_prox_plain<float>((const float*)W, (float*)X_out, n, l, t, mu, thres, r, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_prox_plain<T>((const T*)W, (T*)X_out, n, l, t, mu, thres, r, st);
+    });
     check_launch();
   });
 }
@@ -3038,10 +2961,10 @@ int glx_descent_step(int dtype, int64_t n, int64_t l, int mode, const void* g, i
     GemmPlan p;
     KernelWs k = kernel_setup(dtype, 1, n, l, ws, wsb, 0, st, &p);
     Red r{k.part, k.ticket, static_cast<double*>(sum_dev)};
-    if (dtype == GLX_F64)
-      launch_descent<double>((double*)x, (double*)xt, (const double*)g, S, n, l, alpha, mu, thres, delta, mode, r, st);
-    else
-      launch_descent<float>((float*)x, (float*)xt, (const float*)g, S, n, l, alpha, mu, thres, delta, mode, r, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_descent<T>((T*)x, (T*)xt, (const T*)g, S, n, l, alpha, mu, thres, delta, mode, r, st);
+    });
     check_launch();
   });
 }
@@ -3054,10 +2977,10 @@ int glx_fgd_gradient(int dtype, int64_t n, int64_t l, const void* y, const void*
     GemmPlan p;
     KernelWs k = kernel_setup(dtype, 1, n, l, ws, wsb, 0, st, &p);
     Red r{k.part, k.ticket, static_cast<double*>(sum_dev)};
-    if (dtype == GLX_F64)
-      launch_fgd_grad<double>((const double*)y, (const double*)gp, S, (double*)g, n, l, mu, delta, r, st);
-    else
-      launch_fgd_grad<float>((const float*)y, (const float*)gp, S, (float*)g, n, l, mu, delta, r, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_fgd_grad<T>((const T*)y, (const T*)gp, S, (T*)g, n, l, mu, delta, r, st);
+    });
     check_launch();
   });
 }
@@ -3070,14 +2993,12 @@ int glx_row_stats(int dtype, int64_t n, int64_t l, const void* x, void* stats_de
     GemmPlan p;
     KernelWs k = kernel_setup(dtype, 1, n, l, ws, wsb, 0, st, &p);
     double* s = static_cast<double*>(stats_dev);
-    auto go = [&](auto* tag) {
-      typedef std::remove_pointer_t<decltype(tag)> T;
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
       launch_rownorm_max<T>((const T*)x, n, l, Red{k.part, k.ticket, s}, st);
       check_launch();
       launch_count_above<T>((const T*)x, n * l, s + 1, Red{k.part, k.ticket, s + 2}, st);
-    };
-    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
-    else go(static_cast<float*>(nullptr));
+    });
     check_launch();
   });
 }
@@ -3088,8 +3009,10 @@ int glx_threshold(int dtype, int64_t count, const void* x, void* xo, double thre
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "bad dtype"};
     if (count <= 0 || !x || !xo || !flag_dev) throw Error{GLX_E_INVALID, "bad argument"};
-    if (dtype == GLX_F64) launch_threshold<double>((const double*)x, (double*)xo, count, thres, flag_dev, epoch, st);
-    else launch_threshold<float>((const float*)x, (float*)xo, count, thres, flag_dev, epoch, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_threshold<T>((const T*)x, (T*)xo, count, thres, flag_dev, epoch, st);
+    });
     check_launch();
   });
 }
@@ -3100,8 +3023,10 @@ int glx_thr_combine(int dtype, int64_t count, void* xk, const void* vk, void* y,
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (dtype != GLX_F32 && dtype != GLX_F64) throw Error{GLX_E_INVALID, "bad dtype"};
     if (count <= 0 || !xk || !vk || !y) throw Error{GLX_E_INVALID, "bad argument"};
-    if (dtype == GLX_F64) launch_thr_axpby<double>((double*)xk, (const double*)vk, (double*)y, count, thres, a, b, st);
-    else launch_thr_axpby<float>((float*)xk, (const float*)vk, (float*)y, count, thres, a, b, st);
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_thr_axpby<T>((T*)xk, (const T*)vk, (T*)y, count, thres, a, b, st);
+    });
     check_launch();
   });
 }
@@ -3128,15 +3053,13 @@ int glx_descent_pass(int dtype, int64_t m, int64_t n, const void* A, const void*
     KernelWs k = kernel_setup(dtype, m, n, 1, ws, wsb, 0, st, &p);
     void* slabs = static_cast<char*>(ws) + off;
     Red r{k.part, k.ticket, static_cast<double*>(sums_dev)};
-    auto go = [&](auto* tag) {
-      typedef std::remove_pointer_t<decltype(tag)> T;
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
       launch_gemv_fused<T>(nb, (const T*)A, (const T*)x, (const T*)xt, (const T*)b, (T*)slabs, m, n,
                            static_cast<double*>(fh_dev), fh_mu, static_cast<const double*>(rn_dev), r, st, nt);
       check_launch();
       launch_sum_cols<T>((const T*)slabs, nb, (T*)G, n, st);
-    };
-    if (dtype == GLX_F64) go(static_cast<double*>(nullptr));
-    else go(static_cast<float*>(nullptr));
+    });
     check_launch();
     if (blocks) *blocks = nb;
   });
