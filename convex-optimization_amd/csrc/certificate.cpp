@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <string>
 
 #include "glx_host.h"
@@ -109,7 +110,19 @@ void certificate(const FusePlan& pl, int64_t m, int64_t n, int64_t l, const T* A
   } else {
     launch_cert_fin<T>(pa, ax_split(pl.a, 1), b, r, ml, Red{w.part, w.ticket, w.rec}, st);
   }
-  if (grp != nullptr) {   // the group terms on the slabs of the plain product
+  const bool sgl = grp != nullptr && grp->row_ratio > 0.0;
+  if (sgl) {
+    // the sparse-group terms (DESIGN.md "Sparse-group lasso"): the row norms and six sums, then the two
+    // dual solves on the row norms. rec[8], rec[9] lie in the record's own 256-byte piece of the workspace
+    const double tau = grp->row_ratio;
+    double* rho = rn != nullptr ? rn : grp->rho;
+    if (rho == nullptr) throw Error{GLX_E_INVALID, "sparse-group certificate: no room for the row norms"};
+    launch_atr<T>(pl.a, A, r, static_cast<T*>(w.gp), st);
+    launch_sgl_cert<T>(X, static_cast<const T*>(w.gp), pl.a.atr_S, G, rho, grp->ptr, grp->wts, grp->G, n, l, mu, tau,
+                       Red{w.part, w.ticket, w.rec + 2}, st);
+    launch_sgl_dual_scale(rho, grp->ptr, grp->wts, grp->G, tau * mu, (1.0 - tau) * mu, 1.0, 0.0, grp->pad_mul,
+                          grp->pad_add, hold ? sw->sums : w.rec, nullptr, Red{w.part, w.ticket, w.rec + 8}, st);
+  } else if (grp != nullptr) {   // the group terms on the slabs of the plain product
     launch_atr<T>(pl.a, A, r, static_cast<T*>(w.gp), st);
     launch_group_cert<T>(X, static_cast<const T*>(w.gp), pl.a.atr_S, G, rn, grp->ptr, grp->wts, grp->G, n, l,
                          grp->max_run, mu, Red{w.part, w.ticket, w.rec + 2}, st);
@@ -119,11 +132,29 @@ void certificate(const FusePlan& pl, int64_t m, int64_t n, int64_t l, const T* A
   check_launch();
   double hs[3] = {0.0, 0.0, 0.0};
   GLX_HIP(hipMemcpyAsync(out, w.rec, sizeof(double) * kCertRec, hipMemcpyDeviceToHost, st));
+  double sd[2] = {0.0, 0.0};
+  if (sgl) GLX_HIP(hipMemcpyAsync(sd, w.rec + 8, sizeof sd, hipMemcpyDeviceToHost, st));
   if (hold) GLX_HIP(hipMemcpyAsync(hs, sw->sums, sizeof hs, hipMemcpyDeviceToHost, st));
   if (ic != nullptr)
     GLX_HIP(hipMemcpyAsync(ic->mean_host, ic->mean, sizeof(double) * l, hipMemcpyDeviceToHost, st));
   GLX_HIP(hipStreamSynchronize(st));
-  out[7] = fused ? 1.0 : 0.0;
+  if (sgl) {
+    // the record in compose's terms: out[3] = mu / s with s = min_g s_g, nudged up so that the mu / out[3]
+    // compose forms is at most s (s = +inf: 0; s <= 0: +inf); out[7] = the nonzero rows
+    const double s0 = -sd[0], s1 = -sd[1], rmax = out[3];
+    double ge = s0 > 0.0 ? mu / s0 : (s0 <= 0.0 ? std::numeric_limits<double>::infinity() : s0);
+    for (int k = 0; k < 4 && ge > 0.0 && std::isfinite(ge) && mu / ge > s0; ++k)
+      ge = std::nextafter(ge, std::numeric_limits<double>::infinity());
+    out[3] = ge;
+    if (grp->extra != nullptr) {
+      grp->extra[0] = s0;
+      grp->extra[1] = s1;
+      grp->extra[2] = rmax;
+      grp->extra[3] = 0.0;
+    }
+  } else {
+    out[7] = fused ? 1.0 : 0.0;
+  }
   if (hold) {
     out[0] = hs[0];
     out[1] = hs[1];
@@ -144,6 +175,10 @@ void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, 
     check_intercept(ic->sigma, ic->mean_host);
     if (!ic->rhat || !ic->mean || !ic->part || !ic->cnt) throw Error{GLX_E_INVALID, "intercept: null workspace piece"};
   }
+  if (grp != nullptr && !(grp->row_ratio >= 0.0 && grp->row_ratio <= 1.0))
+    throw Error{GLX_E_INVALID, "row_ratio must be in [0, 1] (and not NaN)"};
+  if (grp != nullptr && grp->row_ratio > 0.0 && ic != nullptr)
+    throw Error{GLX_E_INVALID, "the sparse-group penalty (row_ratio > 0) takes no intercept"};
   if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
   if (!A || !X || !b) throw Error{GLX_E_INVALID, "A, X and b must be device pointers"};
   if (!out) throw Error{GLX_E_INVALID, "null out"};

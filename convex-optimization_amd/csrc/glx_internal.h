@@ -566,6 +566,37 @@ void launch_group_expand(const int* klist, const int* kcnt, const int* ptr, cons
                          const int* map, int* rows_out, int* ptr_out, double* w_out, double* gcn_out, int* map_out,
                          int* ecnt, hipStream_t st);
 
+// ---- the sparse-group lasso (kernels_sgl.hip; DESIGN.md "Sparse-group lasso") ----
+// mu Omega_tau(x) = a sum_i ||x_i|| + sum_g c_g ||x_[g]||_F with a = tau mu, c_g = (1 - tau) mu w_g.
+//   launch_sgl_fista: launch_group_fista with the two-level prox; red.out[2] = Omega_tau(xc)
+//   launch_sgl_cert: red.out = [Omega_tau(x), max_i ||g_i||, max kkt, sum kkt^2, nonzero groups, nonzero
+//       rows]; rn (may be NULL) receives ||g_i|| as n doubles, gout (may be NULL) g
+//   launch_sgl_dual_scale: two solves q = 0, 1 of s_g = sup{s: sqrt(sum_{i in g} (s p_i - a)_+^2) <= cb w_g}
+//       on p_i = mul_q rho_i + add_q sqrt(*rr) (rr NULL: add_q): sg (may be NULL, 2 G) the unclamped s_g,
+//       red.out[q] = max_g (-s_g)
+//   launch_sgl_screen: keep[i] = 0 where s p_i + cn_i rad < a_lo or (group_test) the row's group has
+//       sqrt(sum (s p_i - a_lo)_+^2) / w_g + gcn_g rad < cb_lo; gkeep (may be NULL) per group;
+//       red.out = [groups that keep a row, kept rows]
+//   launch_sgl_expand: keep -> rows_out (ascending, -1 up to ecnt[3]), the reduced ptr_out / w_out /
+//       gcn_out / map_out over the groups that keep a row, ecnt = [groups, rows, rows, rows padded to 64]
+std::string sgl_layout(int64_t l);
+template <typename T>
+void launch_sgl_fista(const T* y, const T* g, int S, const T* xk, T* xc, T* vnext, T* ynext, const int* ptr,
+                      const double* wts, int64_t G, int64_t nrows, int64_t l, double t, double mu, double tau,
+                      double thres, double theta, double theta_next, Red red, hipStream_t st);
+template <typename T>
+void launch_sgl_cert(const T* x, const T* g, int S, T* gout, double* rn, const int* ptr, const double* wts, int64_t G,
+                     int64_t nrows, int64_t l, double mu, double tau, Red red, hipStream_t st);
+void launch_sgl_dual_scale(const double* rho, const int* ptr, const double* wts, int64_t G, double a, double cb,
+                           double mul0, double add0, double mul1, double add1, const double* rr, double* sg, Red red,
+                           hipStream_t st);
+void launch_sgl_screen(const double* rho, const double* cn, const double* gcn, const int* ptr, const double* wts,
+                       int64_t G, double s, double mul, double add, const double* rr, double rad, double a_lo,
+                       double cb_lo, int group_test, int* keep, int* gkeep, Red red, hipStream_t st);
+void launch_sgl_expand(const int* keep, const int* ptr, const double* wts, const double* gcn, const int* map,
+                       int64_t G, int* rows_out, int* ptr_out, double* w_out, double* gcn_out, int* map_out, int* ecnt,
+                       hipStream_t st);
+
 // The groups of a problem as the drivers pass them on: device ptr / wts as above, and the host's
 // figures of the FULL problem (a reduced problem keeps them: they only have to bound its own).
 struct GroupView {
@@ -574,6 +605,12 @@ struct GroupView {
   int64_t G = 0;
   int64_t max_run = 1;
   double w_min = 1.0;
+  // the sparse-group lasso (DESIGN.md "Sparse-group lasso"; 0: the group problem, nothing below is read)
+  double row_ratio = 0.0;
+  double* rho = nullptr;            // device, n doubles: the row norms of a certificate that returns none
+  double pad_mul = 1.0, pad_add = 0.0;   // the guard's padding of the second dual solve (sgl_guard_pad)
+  double* extra = nullptr;          // host, 4 doubles a certificate fills: [s, s of the padded solve, max rho, 0]
+  int64_t* row_hist = nullptr;      // host, GLX_CERTIFIED_MAX_HIST: kept rows after each compaction
 };
 // glx_certificate's body (certificate.cpp): grp == NULL is the row certificate; with groups the
 // A^T pass is launch_atr and the group terms follow (launch_group_cert), rownorm_out then takes G
@@ -630,8 +667,9 @@ void certificate_run(int dtype, int64_t m, int64_t n, int64_t l, const void* A, 
 // every certificate centres and the screen runs under screen_guard_ic; ic->mean_host holds the means
 // of the final certificate on return.
 size_t certified_bytes(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t G, bool weighted = false,
-                       bool intercept = false);
-std::string certified_describe(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run);
+                       bool intercept = false, bool sgl = false);
+std::string certified_describe(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run,
+                               bool sgl = false);
 void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit, int screen, int check_every,
                    const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev, void* ws,
                    size_t wsb, glx_certified_info* info, void* stream, const GroupView* grp,
@@ -652,6 +690,14 @@ void screen_guard_ic(const double* rec, double mu, int dtype, int64_t m, int64_t
 void group_screen_guard_ic(const double* rec, double mu, int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run,
                            double w_min, double gcol_max, const double* cstats, double bn, double sigma,
                            double mean_sq, double* out);
+// The sparse-group guard (group.cpp; DESIGN.md "Sparse-group lasso", "The guard"). sgl_guard_pad: pad =
+// [mul, add coefficient]: mul rho^_i + add ||r^|| bounds the exact ||a_i^T r^|| for every row (cmax = the
+// largest column norm). sgl_screen_guard: rec = the sparse-group record, s_pad = min_g s_g of the padded
+// solve; out = [mul, add ||r^||, s_safe, gap+, rho+].
+void sgl_guard_pad(int dtype, int64_t m, int64_t l, int64_t max_run, double cmax, bool weighted, double* pad);
+void sgl_screen_guard(const double* rec, double s_pad, double mu, double tau, int dtype, int64_t m, int64_t n,
+                      int64_t l, int64_t max_run, double w_min, double cmax, double csq, double bn, double* out,
+                      bool weighted);
 // the checks every weighted C entry makes of its two vectors: 16-byte aligned, hold only with w
 void check_sample(const void* sample_w, const void* holdout_w);
 

@@ -197,6 +197,91 @@ void group_screen_guard_ic(const double* rec, double mu, int dtype, int64_t m, i
   out[3] = s * (gm * gcu * rn + gK * (1.0 + gm) * gcu * rn + dep) * (1.0 + 8.0 * u64);
 }
 
+// The sparse-group guard (DESIGN.md "Sparse-group lasso", "The guard"). Feasibility is no single maximum
+// here: the guard pads the row norms, p_i = mul rho^_i + add ||r^|| >= ||a_i^T r^|| for every row, and the
+// dual-scale kernel's solve on the p_i gives an s that is feasible for the exact problem.
+//   mul: ||g^_i|| <= rho^_i (1 + gl), the l-term norm in A's dtype; times ev, which covers phi's own
+//        evaluation in fp64 (a sum of max_run squares, a root, a product and a difference per row) and the
+//        roundings of a = tau mu and c_g = (1 - tau) mu w_g: phi(s; (1 + e) p) >= (1 + e) phi(s; p) for a >= 0
+//   add: ||a_i^T r^ - g^_i|| <= gm ||a_i|| ||r^||, the per-column bounds summed in squares, with the stored
+//        column norms low by gamma64_{m+k} and ||r^|| <= sqrt(rec[0]) (1 + g_ml); the device's root: 4 u64
+void sgl_guard_pad(int dtype, int64_t m, int64_t l, int64_t max_run, double cmax, bool weighted, double* pad) {
+  const double k = weighted ? 3.0 : 2.0;
+  const double u = dtype == GLX_F64 ? DBL_EPSILON : (double)FLT_EPSILON;
+  const double u64 = DBL_EPSILON;
+  const double gm = gamma_k((double)m + k, u), gl = gamma_k((double)l + 2.0, u);
+  const double ev = 1.0 + gamma_k((double)max_run + 16.0, u64);
+  const double g_ml = gamma_k((double)m * (double)l + k, u64);
+  pad[0] = (1.0 + gl) * ev;
+  pad[1] = gm * cmax * (1.0 + gamma_k((double)m + k, u64)) * (1.0 + g_ml) * ev * (1.0 + 4.0 * u64);
+}
+
+// rec: the sparse-group record [||r^||^2, <r^, b>, Omega_tau(x), ...]; s_pad: min_g s_g of the padded
+// solve. out = [mul, add ||r^||, s_safe, gap+, rho+]; group_screen_guard's items 2 and 3 with
+//   - ||x||_F <= Omega_tau(x) / (tau + (1 - tau) w_min), both terms of Omega_tau bounding ||x||_F from above;
+//   - Omega_tau's own error: a (max_run l)-term norm, the weight's and the ratio's products in A's dtype,
+//     at most 2 n terms in the fp64 sum;
+//   - the row's and the group's own values carried by the padding, so rho+ is the ball's radius lifted by
+//     what the stored column and group norms may be low by.
+// NaN propagates (and then keeps every row and group in k_sgl_screen).
+void sgl_screen_guard(const double* rec, double s_pad, double mu, double tau, int dtype, int64_t m, int64_t n,
+                      int64_t l, int64_t max_run, double w_min, double cmax, double csq, double bn_in, double* out,
+                      bool weighted) {
+  const double k = weighted ? 3.0 : 2.0;
+  const double u = dtype == GLX_F64 ? DBL_EPSILON : (double)FLT_EPSILON;
+  const double u64 = DBL_EPSILON;
+  const double rr = rec[0], rb = rec[1], om = rec[2];
+  const double rn = std::sqrt(rr);
+  const double K = (double)max_run * (double)l;
+  const double gn = gamma_k((double)n + 2.0, u);
+  const double gK = gamma_k(K + 4.0, u);
+  const double g_ml = gamma_k((double)m * (double)l + k, u64);
+  const double bn = weighted ? bn_in * (1.0 + g_ml) : bn_in;
+  const double up = (1.0 + gamma_k((double)m + k, u64)) * (1.0 + gamma_k((double)max_run + 3.0, u64));
+  double pad[2];
+  sgl_guard_pad(dtype, m, l, max_run, cmax, weighted, pad);
+  const double s = s_pad < 1.0 ? s_pad : (s_pad >= 1.0 ? 1.0 : s_pad);   // (NaN: NaN)
+  const double wq = tau + (1.0 - tau) * w_min;
+  const double dr = gn * std::sqrt(csq) * (om / wq) + u * (rn + 2.0 * bn);
+  const double bar_rr = g_ml * rr;
+  const double bar_rb = g_ml * rn * bn;
+  const double bar_sx = (gK + gamma_k(2.0 * (double)n + 2.0, u64)) * om;
+  const double gap = 0.5 * (1.0 + s * s) * rr + s * rb + mu * om;
+  const double bars = rn * dr + 0.5 * dr * dr + 0.5 * (1.0 + s * s) * bar_rr + s * bar_rb + mu * bar_sx;
+  const double gap_p = (gap > 0.0 ? gap : (gap <= 0.0 ? 0.0 : gap)) + bars;
+  out[0] = pad[0];
+  out[1] = pad[1] * rn;
+  out[2] = s;
+  out[3] = gap_p;
+  out[4] = std::sqrt(2.0 * gap_p) * up;
+}
+
+namespace {
+
+void check_ratio(double tau) {
+  if (!(tau >= 0.0 && tau <= 1.0)) throw Error{GLX_E_INVALID, "row_ratio must be in [0, 1] (and not NaN)"};
+}
+// the sparse-group entries' workspaces: the grouped ones with n doubles of row norms behind them
+size_t sgl_carve(size_t grouped, int64_t n, void* base, double** rho) {
+  Carver c(base);
+  c.take(grouped);
+  double* p = static_cast<double*>(c.take(sizeof(double) * (size_t)n));
+  if (rho) *rho = p;
+  return c.off + 256;
+}
+void guard_args(const double* rec, const double* out, double mu, double tau, int dtype, int64_t m, int64_t n,
+                int64_t l, int64_t max_run, double w_min) {
+  if (!rec || !out) throw Error{GLX_E_INVALID, "null argument"};
+  check_dims(dtype, n, l);
+  check_ratio(tau);
+  if (m <= 0) throw Error{GLX_E_INVALID, "m must be positive"};
+  if (max_run < 1 || max_run > n) throw Error{GLX_E_INVALID, "max_run must be in 1 .. n"};
+  if (!(w_min > 0.0) || !std::isfinite(w_min)) throw Error{GLX_E_INVALID, "w_min must be positive and finite"};
+  if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+}
+
+}  // namespace
+
 }  // namespace glx
 
 using namespace glx;
@@ -631,6 +716,269 @@ int glx_group_expand(const int32_t* kept_dev, const int32_t* kept_count_dev, con
       throw Error{GLX_E_INVALID, "null argument"};
     launch_group_expand(kept_dev, kept_count_dev, group_ptr_dev, weights_dev, gcn_dev, map_dev, rows_out,
                         group_ptr_out, weights_out, gcn_out, map_out, count_out, static_cast<hipStream_t>(stream));
+    check_launch();
+  });
+}
+
+/* ---- the sparse-group lasso (DESIGN.md "Sparse-group lasso"): the grouped entries with a row term,
+ * mu (row_ratio sum_i ||x_i|| + (1 - row_ratio) sum_g w_g ||x_[g]||_F). Workspaces: the grouped _sw ones
+ * with n doubles of row norms behind them. row_ratio = 0 is the grouped entry's path, call for call ---- */
+
+int glx_sgl_screen_guard(const double* rec, double s_pad, double mu, double row_ratio, int dtype, int64_t m,
+                         int64_t n, int64_t l, int64_t max_run, double w_min, double col_max, double col_sumsq,
+                         double b_norm, double* out) {
+  return guarded([&] {
+    guard_args(rec, out, mu, row_ratio, dtype, m, n, l, max_run, w_min);
+    sgl_screen_guard(rec, s_pad, mu, row_ratio, dtype, m, n, l, max_run, w_min, col_max, col_sumsq, b_norm, out,
+                     false);
+  });
+}
+
+int glx_sgl_screen_guard_sw(const double* rec, double s_pad, double mu, double row_ratio, int dtype, int64_t m,
+                            int64_t n, int64_t l, int64_t max_run, double w_min, double col_max, double col_sumsq,
+                            double b_norm, double* out) {
+  return guarded([&] {
+    guard_args(rec, out, mu, row_ratio, dtype, m, n, l, max_run, w_min);
+    sgl_screen_guard(rec, s_pad, mu, row_ratio, dtype, m, n, l, max_run, w_min, col_max, col_sumsq, b_norm, out,
+                     true);
+  });
+}
+
+int glx_sgl_certificate_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    if (G < 1 || G > n) throw Error{GLX_E_INVALID, "groups: G must be in 1 .. n"};
+    *bytes = sgl_carve(sample_bytes(group_carve(cert_bytes(dtype, m, n, l), G, nullptr, nullptr)), n, nullptr, nullptr);
+  });
+}
+
+int glx_sgl_certificate_describe(int dtype, int64_t m, int64_t n, int64_t l, int weighted, char* out, size_t cap) {
+  return guarded([&] {
+    if (!out || cap == 0) throw Error{GLX_E_INVALID, "null out"};
+    check_dims(dtype, n, l);
+    const GemmPlan p = a_plan(dtype, m, n, l);
+    std::snprintf(out, cap, "A x=%s; A^T r=%s; groups=sparse-group kernels (k_sgl_cert, k_sgl_dual_scale: %s)%s",
+                  plan_field(p, 0).c_str(), plan_field(p, 3).c_str(), sgl_layout(l).c_str(),
+                  weighted != 0 ? "; residual=weighted finalize (k_cert_fin_w)" : "");
+  });
+}
+
+int glx_sgl_certificate_sw(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                           double mu, double row_ratio, int64_t G, const int32_t* group_ptr, const double* weights,
+                           const void* sample_w, const void* holdout_w, void* G_out, double* rownorm_out,
+                           double* out, double* holdout_sum, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_dims(dtype, n, l);
+    check_ratio(row_ratio);
+    const GroupFacts f = check_groups(n, G, group_ptr, weights);
+    check_sample(sample_w, holdout_w);
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    if (!A || !X || !b) throw Error{GLX_E_INVALID, "A, X and b must be device pointers"};
+    if (!out) throw Error{GLX_E_INVALID, "null out"};
+    const size_t head = cert_bytes(dtype, m, n, l);
+    const size_t grouped = group_carve(head, G, nullptr, nullptr);
+    check_workspace(sgl_carve(sample_bytes(grouped), n, nullptr, nullptr), ws, wsb, GLX_E_INVALID,
+                    "glx_sgl_certificate_workspace_bytes");
+    GroupDev d;
+    group_carve(head, G, ws, &d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    GroupView v = upload(dtype, d, G, group_ptr, weights, f, st);
+    v.row_ratio = row_ratio;
+    sgl_carve(sample_bytes(grouped), n, ws, &v.rho);
+    for (int k = 8; k < 12; ++k) out[k] = 0.0;
+    v.extra = out + 8;
+    if (holdout_sum != nullptr) *holdout_sum = 0.0;
+    const SampleView sw{sample_w, holdout_w, reinterpret_cast<double*>(static_cast<char*>(ws) + sample_off(grouped))};
+    certificate_run(dtype, m, n, l, A, X, b, mu, 0, G_out, rownorm_out, out, d.head, head, stream, &v,
+                    sample_w != nullptr ? &sw : nullptr, holdout_sum);
+  });
+}
+
+int glx_sgl_certificate(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                        double mu, double row_ratio, int64_t G, const int32_t* group_ptr, const double* weights,
+                        void* G_out, double* rownorm_out, double* out, void* ws, size_t wsb, void* stream) {
+  return glx_sgl_certificate_sw(dtype, m, n, l, A, X, b, mu, row_ratio, G, group_ptr, weights, nullptr, nullptr,
+                                G_out, rownorm_out, out, nullptr, ws, wsb, stream);
+}
+
+int glx_sgl_certified_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, int screen,
+                                      int weighted, size_t* bytes) {
+  return guarded([&] {
+    if (!bytes) throw Error{GLX_E_INVALID, "null bytes"};
+    if (G < 1 || G > n) throw Error{GLX_E_INVALID, "groups: G must be in 1 .. n"};
+    const size_t head = certified_bytes(dtype, m, n, l, screen != 0, G, weighted != 0, false, true);
+    *bytes = sgl_carve(group_carve(head, G, nullptr, nullptr), n, nullptr, nullptr);
+  });
+}
+
+int glx_sgl_certified_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, int screen, int weighted,
+                               char* out, size_t cap) {
+  return guarded([&] {
+    if (!out || cap == 0) throw Error{GLX_E_INVALID, "null out"};
+    if (max_run < 1 || max_run > n) throw Error{GLX_E_INVALID, "max_run must be in 1 .. n"};
+    std::snprintf(out, cap, "%s%s", certified_describe(dtype, m, n, l, screen != 0, max_run, true).c_str(),
+                  weighted != 0 ? "; residual=weighted finalize (k_cert_fin_w)" : "");
+  });
+}
+
+int glx_sgl_certified_solve_sw(const glx_problem* prob, double row_ratio, int64_t G, const int32_t* group_ptr,
+                               const double* weights, const void* sample_w, const void* holdout_w, double t,
+                               double tol, int64_t maxit, int screen, int check_every, const double* col_norms_dev,
+                               const double* col_stats, int32_t* kept_rows_dev, int32_t* kept_groups_dev, void* ws,
+                               size_t wsb, glx_sgl_certified_info* info, double* holdout_sum, void* stream) {
+  return guarded([&] {
+    if (!prob || !info) throw Error{GLX_E_INVALID, "null problem/info"};
+    if (prob->comm != nullptr) throw Error{GLX_E_INVALID, "the certified solve is single-GPU: comm must be NULL"};
+    check_dims(prob->dtype, prob->n, prob->l);
+    check_ratio(row_ratio);
+    const GroupFacts f = check_groups(prob->n, G, group_ptr, weights);
+    check_sample(sample_w, holdout_w);
+    const bool weighted = sample_w != nullptr;
+    const size_t head = certified_bytes(prob->dtype, prob->m, prob->n, prob->l, screen != 0, G, weighted, false, true);
+    const size_t grouped = group_carve(head, G, nullptr, nullptr);
+    check_workspace(sgl_carve(grouped, prob->n, nullptr, nullptr), ws, wsb, GLX_E_INVALID,
+                    "glx_sgl_certified_workspace_bytes");
+    if (!prob->A || !prob->b || !prob->x) throw Error{GLX_E_INVALID, "A, b and x must be device pointers"};
+    GroupDev d;
+    group_carve(head, G, ws, &d);
+    GroupView v = upload(prob->dtype, d, G, group_ptr, weights, f, static_cast<hipStream_t>(stream));
+    std::memset(info, 0, sizeof *info);
+    v.row_ratio = row_ratio;
+    v.row_hist = info->kept_row_hist;
+    sgl_carve(grouped, prob->n, ws, &v.rho);
+    int64_t listed_groups = 0;
+    const SampleView sw{sample_w, holdout_w, nullptr};
+    // (row_ratio = 0: the grouped solve on a workspace that is merely larger)
+    certified_run(prob, t, tol, maxit, screen, check_every, col_norms_dev, col_stats, kept_rows_dev, d.head, head,
+                  &info->base.base, stream, &v, kept_groups_dev, &listed_groups, weighted ? &sw : nullptr,
+                  holdout_sum);
+    info->base.kept_groups = screen != 0 ? info->base.base.kept : G;
+    info->base.listed_groups = listed_groups;
+    info->base.max_run = f.max_run;
+    info->row_ratio = row_ratio;
+  });
+}
+
+int glx_sgl_certified_solve(const glx_problem* prob, double row_ratio, int64_t G, const int32_t* group_ptr,
+                            const double* weights, double t, double tol, int64_t maxit, int screen, int check_every,
+                            const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev,
+                            int32_t* kept_groups_dev, void* ws, size_t wsb, glx_sgl_certified_info* info,
+                            void* stream) {
+  return glx_sgl_certified_solve_sw(prob, row_ratio, G, group_ptr, weights, nullptr, nullptr, t, tol, maxit, screen,
+                                    check_every, col_norms_dev, col_stats, kept_rows_dev, kept_groups_dev, ws, wsb,
+                                    info, nullptr, stream);
+}
+
+/* ---- one launch at a time (workspace: glx_group_workspace_bytes) ---- */
+
+int glx_sgl_step(int dtype, int64_t n, int64_t rows, int64_t l, int64_t G, const int32_t* group_ptr,
+                 const double* weights, const void* y, const void* g, int S, const void* xk, double t, double mu,
+                 double row_ratio, double thres, double theta, double theta_next, void* xc, void* vnext, void* ynext,
+                 void* sums_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_dims(dtype, n, l);
+    check_ratio(row_ratio);
+    const GroupFacts f = check_groups(n, G, group_ptr, weights);
+    if (rows < n || rows > n + 63) throw Error{GLX_E_INVALID, "rows must be in n .. n + 63 (the padded width)"};
+    if (S < 1 || S > kMaxSplit) throw Error{GLX_E_INVALID, "S must be in 1 .. 64"};
+    if (!y || !g || !xk || !xc || !vnext || !ynext || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
+    check_workspace(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_group_workspace_bytes");
+    GroupDev d;
+    group_carve(kStepHead, G, ws, &d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const GroupView v = upload(dtype, d, G, group_ptr, weights, f, st);
+    const StepWs w = step_head(d.head);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    const Red red{w.part, w.ticket, static_cast<double*>(sums_dev)};
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_sgl_fista<T>((const T*)y, (const T*)g, S, (const T*)xk, (T*)xc, (T*)vnext, (T*)ynext, v.ptr, v.wts, G,
+                          rows, l, t, mu, row_ratio, thres, theta, theta_next, red, st);
+    });
+    check_launch();
+  });
+}
+
+int glx_sgl_certificate_step(int dtype, int64_t n, int64_t l, int64_t G, const int32_t* group_ptr,
+                             const double* weights, const void* x, const void* g, int S, double mu, double row_ratio,
+                             void* gout, double* rownorm_out, void* sums_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_dims(dtype, n, l);
+    check_ratio(row_ratio);
+    const GroupFacts f = check_groups(n, G, group_ptr, weights);
+    if (S < 1 || S > kMaxSplit) throw Error{GLX_E_INVALID, "S must be in 1 .. 64"};
+    if (!(mu >= 0.0)) throw Error{GLX_E_INVALID, "mu must be >= 0 (and not NaN)"};
+    if (!x || !g || !sums_dev) throw Error{GLX_E_INVALID, "null argument"};
+    check_workspace(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_group_workspace_bytes");
+    GroupDev d;
+    group_carve(kStepHead, G, ws, &d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const GroupView v = upload(dtype, d, G, group_ptr, weights, f, st);
+    const StepWs w = step_head(d.head);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    const Red red{w.part, w.ticket, static_cast<double*>(sums_dev)};
+    by_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      launch_sgl_cert<T>((const T*)x, (const T*)g, S, (T*)gout, rownorm_out, v.ptr, v.wts, G, n, l, mu, row_ratio, red,
+                         st);
+    });
+    check_launch();
+  });
+}
+
+int glx_sgl_dual_scale(int64_t n, int64_t G, const int32_t* group_ptr, const double* weights,
+                       const double* rownorms_dev, double a, double cb, double mul0, double add0, double mul1,
+                       double add1, double* sg_dev, double* negmin_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_dims(GLX_F64, n, 1);
+    const GroupFacts f = check_groups(n, G, group_ptr, weights);
+    if (!rownorms_dev || !negmin_dev) throw Error{GLX_E_INVALID, "null argument"};
+    if (!(a >= 0.0) || !(cb >= 0.0)) throw Error{GLX_E_INVALID, "a and cb must be >= 0 (and not NaN)"};
+    check_workspace(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_group_workspace_bytes");
+    GroupDev d;
+    group_carve(kStepHead, G, ws, &d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const GroupView v = upload(GLX_F64, d, G, group_ptr, weights, f, st);
+    const StepWs w = step_head(d.head);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    launch_sgl_dual_scale(rownorms_dev, v.ptr, v.wts, G, a, cb, mul0, add0, mul1, add1, nullptr, sg_dev,
+                          Red{w.part, w.ticket, negmin_dev}, st);
+    check_launch();
+  });
+}
+
+int glx_sgl_screen(int64_t n, int64_t G, const int32_t* group_ptr, const double* weights, const double* rownorms_dev,
+                   const double* col_norms_dev, const double* gcn_dev, double s, double mul, double add, double rad,
+                   double a_lo, double cb_lo, int group_test, int32_t* keep_dev, int32_t* group_keep_dev,
+                   double* counts_dev, void* ws, size_t wsb, void* stream) {
+  return guarded([&] {
+    check_dims(GLX_F64, n, 1);
+    const GroupFacts f = check_groups(n, G, group_ptr, weights);
+    if (!rownorms_dev || !col_norms_dev || !gcn_dev || !keep_dev || !counts_dev)
+      throw Error{GLX_E_INVALID, "null argument"};
+    check_workspace(group_carve(kStepHead, G, nullptr, nullptr), ws, wsb, GLX_E_INVALID, "glx_group_workspace_bytes");
+    GroupDev d;
+    group_carve(kStepHead, G, ws, &d);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const GroupView v = upload(GLX_F64, d, G, group_ptr, weights, f, st);
+    const StepWs w = step_head(d.head);
+    GLX_HIP(hipMemsetAsync(w.ticket, 0, kTicketBytes, st));
+    launch_sgl_screen(rownorms_dev, col_norms_dev, gcn_dev, v.ptr, v.wts, G, s, mul, add, nullptr, rad, a_lo, cb_lo,
+                      group_test, keep_dev, group_keep_dev, Red{w.part, w.ticket, counts_dev}, st);
+    check_launch();
+  });
+}
+
+int glx_sgl_expand(int64_t G, const int32_t* keep_dev, const int32_t* group_ptr_dev, const double* weights_dev,
+                   const double* gcn_dev, const int32_t* map_dev, int32_t* rows_out, int32_t* group_ptr_out,
+                   double* weights_out, double* gcn_out, int32_t* map_out, int32_t* count_out, void* stream) {
+  return guarded([&] {
+    if (G < 1) throw Error{GLX_E_INVALID, "groups: G must be >= 1"};
+    if (!keep_dev || !group_ptr_dev || !weights_dev || !gcn_dev || !rows_out || !group_ptr_out || !weights_out ||
+        !gcn_out || !map_out || !count_out)
+      throw Error{GLX_E_INVALID, "null argument"};
+    launch_sgl_expand(keep_dev, group_ptr_dev, weights_dev, gcn_dev, map_dev, G, rows_out, group_ptr_out, weights_out,
+                      gcn_out, map_out, count_out, static_cast<hipStream_t>(stream));
     check_launch();
   });
 }

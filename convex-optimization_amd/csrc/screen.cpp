@@ -21,6 +21,11 @@
 // (r = w (A y - b) is the R every step already takes), ||b~|| and the column figures are the weighted
 // ones, every certificate takes the weights and the guards count their roundings; the final
 // certificate also reduces the hold-out sum. Without one, again, nothing differs.
+// A GroupView with row_ratio > 0 (DESIGN.md "Sparse-group lasso") adds a row term to the group penalty:
+// the step is launch_atr + launch_sgl_fista, the certificate takes the view (its dual scaling is a
+// per-group solve, done twice: plain, and on the row norms padded by sgl_guard_pad), the screen is
+// launch_sgl_screen on rows and groups under sgl_screen_guard and launch_sgl_expand turns its row flags
+// into the row list and the reduced groups. It composes with a SampleView and refuses an InterceptView.
 // With an InterceptView (DESIGN.md "Intercept") the loop solves min_c 1/2 sum_j w_j ||(A x + 1 c^T - b)_j||^2
 // + mu Omega(x) with c eliminated exactly: the residual finalizes become the two centring launches
 // (launch_cert_csum, launch_cert_fin_c: r = w (A y - b - 1 mean^T)), the column figures are the centred
@@ -143,9 +148,10 @@ struct Ws {
   double* ssums;   // sample weights: the weighted finalize's sums of a certificate (SampleView::sums)
   InterceptView ic;   // intercept: the centring finalize's device pieces
   double* cmean;      // intercept: the column means of A
+  int* skeep;         // sparse-group lasso: k_sgl_screen's flag per row
 };
 size_t carve(int dtype, int64_t m, int64_t n, int64_t l, bool screen, bool own_norms, void* base, Ws* out,
-             int64_t G = 0, bool weighted = false, bool intercept = false) {
+             int64_t G = 0, bool weighted = false, bool intercept = false, bool sgl = false) {
   const size_t es = dtype == GLX_F64 ? 8 : 4;
   const Extent e = extent(dtype, m, n, l, screen);
   const int64_t np = pad64(n);
@@ -188,15 +194,19 @@ size_t carve(int dtype, int64_t m, int64_t n, int64_t l, bool screen, bool own_n
     w.cmean = static_cast<double*>(c.take(sizeof(double) * np));
     c.off = intercept_carve(c.off, (int)es, m, l, base, &w.ic) - 256;
   }
+  w.skeep = nullptr;
+  if (sgl) w.skeep = static_cast<int*>(c.take(sizeof(int) * np));   // (behind everything else, and only then)
   if (out) *out = w;
   return c.off + 256;
 }
 
-std::string describe_certified(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run = 0) {
+std::string describe_certified(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run = 0,
+                               bool sgl = false) {
   const FusePlan p = fuse_plan(dtype, m, n, l);
   std::string s = "FISTA, fixed step, exact prox; A y=" + plan_field(p.a, 0) + "; A^T r=" + plan_field(p.a, 3) +
                   "; step=";
-  if (max_run > 0) s += "group kernel (k_group_fista, " + group_layout(max_run * l) + ")";
+  if (sgl) s += "sparse-group kernel (k_sgl_fista, " + sgl_layout(l) + ")";
+  else if (max_run > 0) s += "group kernel (k_group_fista, " + group_layout(max_run * l) + ")";
   else s += p.fuse_ok ? "fused (k_atr_fista, the A^T r epilogue)" : "row kernel (k_fista_trial)";
   s += screen ? "; screening=gap-safe, compaction to multiples of 64 at <= 0.9 of the width" : "; screening=off";
   return s;
@@ -240,8 +250,11 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
            int32_t* kept_groups, int64_t* listed_groups, const SampleView* sw, double* holdout_sum,
            const InterceptView* icv) {
   Ws w;
+  // the sparse-group lasso (DESIGN.md "Sparse-group lasso"): the view's row_ratio > 0
+  const bool sgl = grp != nullptr && grp->row_ratio > 0.0;
+  const double tau = sgl ? grp->row_ratio : 0.0;
   carve(dtype, m, n, l, screen, cn_in == nullptr, wsp, &w, grp != nullptr ? grp->G : 0,
-        sw != nullptr || icv != nullptr, icv != nullptr);
+        sw != nullptr || icv != nullptr, icv != nullptr, sgl);
   // the intercept (DESIGN.md "Intercept"): the caller's sigma and host means, this workspace's device pieces
   InterceptView icw = w.ic;
   if (icv != nullptr) {
@@ -334,6 +347,16 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
   }
   // the groups of the current (reduced) problem; gmap: its groups -> the full problem's (NULL: identity)
   GroupView gcur = grp != nullptr ? *grp : GroupView{};
+  double sgl_extra[4] = {0.0, 0.0, 0.0, 0.0};   // [s, s of the padded solve, max rho, 0] of the last check
+  if (sgl) {
+    gcur.extra = sgl_extra;
+    if (screen) {   // the padding of the second dual solve is the guard's, fixed for the whole solve
+      double pad[2];
+      sgl_guard_pad(dtype, m, l, grp->max_run, cmax, sw != nullptr, pad);
+      gcur.pad_mul = pad[0];
+      gcur.pad_add = pad[1];
+    }
+  }
   const double* gcn = w.gcn_full;
   const int* gmap = nullptr;
   int gside = 0;             // the description the next k_group_expand writes
@@ -406,7 +429,19 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     // the test's own three roundings in fp64 (intercept: and the guard's slack, gd[3], off mu)
     const double mu_lo = (mu - gd[3]) * (1.0 - 4.0 * DBL_EPSILON);
     int hc[4] = {0, 0, 0, 0};
-    if (grp != nullptr) {   // the same test on the G "rows" of groups, then their rows
+    if (sgl) {   // the two-level test on the rows and the groups, then the rows that stay
+      double g5[5];
+      sgl_screen_guard(rec, sgl_extra[1], mu, tau, dtype, m, wc, l, grp->max_run, grp->w_min, cmax, csq, bn, g5,
+                       sw != nullptr);
+      const double shave = 1.0 - 8.0 * DBL_EPSILON;   // the tests' own roundings in fp64
+      launch_sgl_screen(w.rn, cn, gcn, gcur.ptr, gcur.wts, gcur.G, g5[2], g5[0], g5[1], nullptr, g5[4],
+                        tau * mu * shave, (1.0 - tau) * mu * shave, tau < 1.0 ? 1 : 0, w.skeep, nullptr,
+                        Red{w.part, w.ticket, w.red + 14}, st);
+      launch_sgl_expand(w.skeep, gcur.ptr, gcur.wts, gcn, gmap, gcur.G, w.list, w.gptr[gside], w.gw[gside],
+                        w.ggcn[gside], w.gmap[gside], w.cnt, st);
+      check_launch();
+      GLX_HIP(hipMemcpyAsync(hc, w.cnt, sizeof hc, hipMemcpyDeviceToHost, st));
+    } else if (grp != nullptr) {   // the same test on the G "rows" of groups, then their rows
       if (ic == nullptr)
         group_screen_guard(rec, mu, dtype, m, wc, l, grp->max_run, grp->w_min, gcol_max, csq, bn, gd, sw != nullptr);
       launch_screen(w.rn, gcn, gcur.G, gd[0], gd[2], mu_lo, nullptr, w.glist, w.cnt, w.bal, w.sticket, st);
@@ -431,6 +466,8 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
       wc = 0;
       listed = -1;
       if (info->compactions < GLX_CERTIFIED_MAX_HIST) info->kept_hist[info->compactions] = 0;
+      if (sgl && grp->row_hist != nullptr && info->compactions < GLX_CERTIFIED_MAX_HIST)
+        grp->row_hist[info->compactions] = 0;
       ++info->compactions;
       return true;
     }
@@ -439,7 +476,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     launch_gather_cols<T>(Ac, m, wc, w.list, wp, An, st);
     launch_gather_rows<T>(x, w.list, wp, l, xc, st);
     double* cnn = w.cn[cn == w.cn[0] ? 1 : 0];
-    if (grp == nullptr) launch_gather_rows<double>(cn, w.list, wp, 1, cnn, st);
+    if (grp == nullptr || sgl) launch_gather_rows<double>(cn, w.list, wp, 1, cnn, st);
     int* mapn = w.map[mapi ^ 1];
     launch_compose_list(map, w.list, wp, mapn, st);
     check_launch();
@@ -448,7 +485,7 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     GLX_HIP(hipMemcpyAsync(y, x, es * wp * l, hipMemcpyDeviceToDevice, st));   // the momentum restarts
     k = 1;
     Ac = An;
-    if (grp == nullptr) cn = cnn;
+    if (grp == nullptr || sgl) cn = cnn;
     if (grp != nullptr) {   // k_group_expand wrote the reduced description beside the row list
       gcur.ptr = w.gptr[gside];
       gcur.wts = w.gw[gside];
@@ -463,6 +500,8 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     wc = wp;
     pl = fuse_plan(dtype, m, wc, l);
     if (info->compactions < GLX_CERTIFIED_MAX_HIST) info->kept_hist[info->compactions] = kept;
+    if (sgl && grp->row_hist != nullptr && info->compactions < GLX_CERTIFIED_MAX_HIST)
+      grp->row_hist[info->compactions] = hc[1];
     ++info->compactions;
     listed = -1;   // the composed list alone names them now
     return false;
@@ -482,7 +521,11 @@ void solve(int dtype, int64_t m, int64_t n, int64_t l, const T* A, const T* b, T
     else
       launch_cert_fin<T>(static_cast<T*>(w.pa), ax_split(pl.a, 1), b, r, ml, red0, st);
     T* gp = static_cast<T*>(w.gp);
-    if (grp != nullptr) {   // the grouped step is never fused: A^T r, then the group kernel on its slabs
+    if (sgl) {   // the sparse-group step: A^T r, then the two-level prox on its slabs
+      launch_atr<T>(pl.a, Ac, r, gp, st);
+      launch_sgl_fista<T>(y, gp, pl.a.atr_S, x, xc, vn, yn, gcur.ptr, gcur.wts, gcur.G, wc, l, t, mu, tau, thres, theta,
+                          theta_next, red1, st);
+    } else if (grp != nullptr) {   // the grouped step is never fused: A^T r, then the group kernel on its slabs
       launch_atr<T>(pl.a, Ac, r, gp, st);
       launch_group_fista<T>(y, gp, pl.a.atr_S, x, xc, vn, yn, gcur.ptr, gcur.wts, gcur.G, wc, l, grp->max_run, t, mu,
                             thres, theta, theta_next, red1, st);
@@ -614,14 +657,14 @@ void screen_guard_ic(const double* rec, double mu, int dtype, int64_t m, int64_t
 }
 
 size_t certified_bytes(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t G, bool weighted,
-                       bool intercept) {
+                       bool intercept, bool sgl) {
   check_shape(dtype, m, n, l);
-  return carve(dtype, m, n, l, screen, true, nullptr, nullptr, G, weighted, intercept);
+  return carve(dtype, m, n, l, screen, true, nullptr, nullptr, G, weighted, intercept, sgl);
 }
 
-std::string certified_describe(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run) {
+std::string certified_describe(int dtype, int64_t m, int64_t n, int64_t l, bool screen, int64_t max_run, bool sgl) {
   check_shape(dtype, m, n, l);
-  return describe_certified(dtype, m, n, l, screen, max_run);
+  return describe_certified(dtype, m, n, l, screen, max_run, sgl);
 }
 
 void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit, int screen, int check_every,
@@ -631,6 +674,10 @@ void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit,
                    const InterceptView* ic) {
   if (!prob || !info) throw Error{GLX_E_INVALID, "null problem/info"};
   if (ic != nullptr) check_intercept(ic->sigma, ic->mean_host);
+  if (grp != nullptr && !(grp->row_ratio >= 0.0 && grp->row_ratio <= 1.0))
+    throw Error{GLX_E_INVALID, "row_ratio must be in [0, 1] (and not NaN)"};
+  if (grp != nullptr && grp->row_ratio > 0.0 && ic != nullptr)
+    throw Error{GLX_E_INVALID, "the sparse-group penalty (row_ratio > 0) takes no intercept"};
   if (sw != nullptr) check_sample(sw->w, sw->hold);
   if (sw != nullptr && sw->w == nullptr) throw Error{GLX_E_INVALID, "sample weights: null vector"};
   if (prob->comm != nullptr) throw Error{GLX_E_INVALID, "the certified solve is single-GPU: comm must be NULL"};
@@ -647,7 +694,8 @@ void certified_run(const glx_problem* prob, double t, double tol, int64_t maxit,
   if ((col_norms_dev != nullptr) != (col_stats != nullptr))
     throw Error{GLX_E_INVALID, "col_norms_dev and col_stats go together"};
   check_workspace(carve(prob->dtype, prob->m, prob->n, prob->l, screen != 0, true, nullptr, nullptr,
-                        grp != nullptr ? grp->G : 0, sw != nullptr || ic != nullptr, ic != nullptr),
+                        grp != nullptr ? grp->G : 0, sw != nullptr || ic != nullptr, ic != nullptr,
+                        grp != nullptr && grp->row_ratio > 0.0),
                   ws, wsb, GLX_E_INVALID,
                   grp != nullptr ? "glx_group_certified_workspace_bytes" : "glx_certified_workspace_bytes");
   if (holdout_sum != nullptr) *holdout_sum = 0.0;

@@ -83,6 +83,12 @@ class GlxGroupCertifiedInfo(ctypes.Structure):
                 ("max_run", c_int64), ("reserved", c_int64)]
 
 
+class GlxSglCertifiedInfo(ctypes.Structure):
+    """glx_sgl_certified_info (include/glx.h): what glx_sgl_certified_solve reports."""
+    _fields_ = [("base", GlxGroupCertifiedInfo), ("row_ratio", c_double), ("reserved", c_int64 * 3),
+                ("kept_row_hist", c_int64 * 64)]
+
+
 class GlxError(RuntimeError):
     """Error returned by libglx (message from glx_last_error())."""
 
@@ -336,6 +342,44 @@ _SIGS = {
                                  c_void_p, c_void_p, c_size_t, c_void_p]),
     "glx_cert_fin_ic": (c_int, [c_int, c_int64, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_double,
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_sgl_certificate_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "glx_sgl_certificate_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_int, c_char_p, c_size_t]),
+    "glx_sgl_certificate": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double,
+                                    c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_double),
+                                    c_void_p, c_size_t, c_void_p]),
+    "glx_sgl_certificate_sw": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double,
+                                       c_double, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, POINTER(c_double), POINTER(c_double), c_void_p, c_size_t,
+                                       c_void_p]),
+    "glx_sgl_certified_workspace_bytes": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int,
+                                                  POINTER(c_size_t)]),
+    "glx_sgl_certified_describe": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_char_p,
+                                           c_size_t]),
+    "glx_sgl_certified_solve": (c_int, [POINTER(GlxProblem), c_double, c_int64, c_void_p, c_void_p, c_double,
+                                        c_double, c_int64, c_int, c_int, c_void_p, POINTER(c_double), c_void_p,
+                                        c_void_p, c_void_p, c_size_t, POINTER(GlxSglCertifiedInfo), c_void_p]),
+    "glx_sgl_certified_solve_sw": (c_int, [POINTER(GlxProblem), c_double, c_int64, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_double, c_double, c_int64, c_int, c_int, c_void_p,
+                                           POINTER(c_double), c_void_p, c_void_p, c_void_p, c_size_t,
+                                           POINTER(GlxSglCertifiedInfo), POINTER(c_double), c_void_p]),
+    "glx_sgl_screen_guard": (c_int, [POINTER(c_double), c_double, c_double, c_double, c_int, c_int64, c_int64,
+                                     c_int64, c_int64, c_double, c_double, c_double, c_double, POINTER(c_double)]),
+    "glx_sgl_screen_guard_sw": (c_int, [POINTER(c_double), c_double, c_double, c_double, c_int, c_int64, c_int64,
+                                        c_int64, c_int64, c_double, c_double, c_double, c_double,
+                                        POINTER(c_double)]),
+    "glx_sgl_step": (c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_int, c_void_p, c_double, c_double, c_double, c_double, c_double, c_double, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_sgl_certificate_step": (c_int, [c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_int, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_size_t, c_void_p]),
+    "glx_sgl_dual_scale": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double,
+                                   c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_sgl_screen": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+                               c_double, c_double, c_double, c_double, c_double, c_int, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_size_t, c_void_p]),
+    "glx_sgl_expand": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "glx_comm_unique_id": (c_int, [POINTER(c_uint8)]),
     "glx_comm_create": (c_int, [POINTER(c_void_p), POINTER(c_uint8), c_int, c_int]),
     "glx_comm_create_host": (c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, c_void_p]),

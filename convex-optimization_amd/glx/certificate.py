@@ -107,6 +107,24 @@ def check_groups(groups, weights, n: int, l: int = 1):
     return np.ascontiguousarray(ptr, dtype=np.int32), np.ascontiguousarray(w)
 
 
+def check_row_ratio(row_ratio, gw, fit_intercept: bool = False) -> float:
+    """The host-side check of ``row_ratio`` (the sparse-group penalty's tau), before any device work.
+    None and 0 come back as 0.0: the group problem, today's path. ValueError for a value outside [0, 1] or
+    NaN, for a ratio without ``groups`` / ``weights`` (``gw`` is :func:`check_groups`' pair) and for a
+    non-zero ratio together with ``fit_intercept``, which the sparse-group guard does not cover."""
+    if row_ratio is None:
+        return 0.0
+    tau = float(row_ratio)
+    if not 0.0 <= tau <= 1.0:   # (NaN fails both comparisons)
+        raise ValueError("row_ratio must be in [0, 1], got %r" % (row_ratio,))
+    if gw is None:
+        raise ValueError("row_ratio goes with groups and/or weights (without them the penalty is the row norm)")
+    if tau > 0.0 and fit_intercept:
+        raise ValueError("fit_intercept=True with a non-zero row_ratio is not supported: the intercept guard's "
+                         "slack has no sparse-group derivation yet")
+    return tau
+
+
 def check_sample_weight(sample_weight, m: int, dtype=np.float64, name: str = "sample_weight"):
     """The host-side check of observation weights for an m-row A, before any device work. None stays
     None (the unweighted problem, today's path and bits); anything else must be m finite values >= 0
@@ -294,6 +312,48 @@ def _group_record(xd: torch.Tensor, Ad: torch.Tensor, bd: torch.Tensor, mu: floa
     return list(rec), gn, _lib.group_certificate_describe(gdt, m, n, l, int(np.diff(ptr).max()))
 
 
+def compose_sgl(rec, mu: float, row_ratio: float) -> Dict[str, Any]:
+    """:func:`compose_groups` for the sparse-group record (glx_sgl_certificate's 12 values): rec[3] is
+    mu / min_g s_g, so the scale composes as before; ``nonzero_rows`` (rec[7]) stands beside
+    ``nonzero_groups``, ``fused`` is False, ``scale_min`` is the unclamped min_g s_g and ``row_norm_max``
+    max_i ||g_i||."""
+    rec = [float(v) for v in rec]
+    nzr = rec[7]
+    out = compose_groups(rec[:7] + [0.0], mu)
+    out["nonzero_rows"] = nzr if math.isnan(nzr) else int(nzr)
+    out["row_ratio"] = float(row_ratio)
+    out["scale_min"] = rec[8]
+    out["row_norm_max"] = rec[10]
+    return out
+
+
+def _sgl_record(xd, Ad, bd, mu: float, tau: float, gw, norms: bool, sw=None, hw=None):
+    """glx_sgl_certificate_sw: (rec (12), row norms (n) or None, plan, holdout_sum)."""
+    ptr, w = gw
+    m, n = Ad.shape
+    l = xd.shape[1]
+    G = int(w.size)
+    device = Ad.device
+    gdt = _lib.GLX_F64 if Ad.dtype == torch.float64 else _lib.GLX_F32
+    rec = (ctypes.c_double * 12)()
+    hs = ctypes.c_double(0.0)
+    with torch.cuda.device(device):
+        nb = ctypes.c_size_t(0)
+        check(lib().glx_sgl_certificate_workspace_bytes(gdt, m, n, l, G, ctypes.byref(nb)))
+        ws = torch.empty(int(nb.value), dtype=torch.uint8, device=device)
+        rn = torch.empty(n, dtype=torch.float64, device=device) if norms else None
+        check(lib().glx_sgl_certificate_sw(gdt, m, n, l, Ad.data_ptr(), xd.data_ptr(), bd.data_ptr(), float(mu),
+                                           float(tau), G, ptr.ctypes.data, w.ctypes.data,
+                                           None if sw is None else sw.data_ptr(),
+                                           None if hw is None else hw.data_ptr(), None,
+                                           None if rn is None else rn.data_ptr(), rec, ctypes.byref(hs),
+                                           ws.data_ptr(), ws.numel(),
+                                           ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
+    buf = ctypes.create_string_buffer(2048)
+    check(lib().glx_sgl_certificate_describe(gdt, m, n, l, int(sw is not None), buf, len(buf)))
+    return list(rec), rn, buf.value.decode(), float(hs.value)
+
+
 def _inputs(x, A, b):
     lib()  # fail loudly before touching data if the library is missing
     device = A.device if isinstance(A, torch.Tensor) and A.is_cuda else _device({})
@@ -324,8 +384,17 @@ def record(x, A, b, mu, *, fused: int = 0) -> np.ndarray:
 
 
 def certificate(x, A, b, mu, groups=None, weights=None, *, fused: int = 0, row_norms: bool = False,
-                sample_weight=None, fit_intercept: bool = False) -> Dict[str, Any]:
+                sample_weight=None, fit_intercept: bool = False, row_ratio=None) -> Dict[str, Any]:
     """The duality gap and KKT violation of the iterate ``x`` at ``mu`` (module docstring).
+
+    ``row_ratio`` (None or 0: today's group path, call for call; needs ``groups`` / ``weights``): tau in
+    [0, 1], the certificate of the sparse-group penalty ``mu (tau sum_i ||x_i||_2 + (1 - tau) sum_g w_g
+    ||x_[g]||_F)`` (DESIGN.md "Sparse-group lasso"). The dual point is ``s r`` with ``s = min(1, min_g s_g)``,
+    ``s_g`` the largest scaling at which group g's constraint ``||S_a((A^T theta)_[g])||_F <= c_g`` holds
+    (a = tau mu, c_g = (1 - tau) mu w_g, S_a the row-wise shrinkage). The result carries the group keys plus
+    ``row_ratio``, ``nonzero_rows``, ``scale_min`` and ``row_norm_max``; ``gmax`` is ``mu / min_g s_g`` and
+    ``row_norms=True`` returns ``row_norms``, ||g_i|| of the n rows. It composes with ``sample_weight``;
+    with ``fit_intercept=True`` it raises ValueError.
 
     ``x`` (n x l), ``A`` (m x n) and ``b`` (m x l) are NumPy arrays or torch tensors and are not
     modified; the computation runs in A's dtype. ``fused``: 0 auto, 1 the row terms in the epilogue of
@@ -356,9 +425,17 @@ def certificate(x, A, b, mu, groups=None, weights=None, *, fused: int = 0, row_n
         raise ValueError("mu must be >= 0")
     gw = check_groups(groups, weights, np.shape(A)[1] if len(np.shape(A)) == 2 else -1,
                       np.shape(b)[1] if len(np.shape(b)) == 2 else 1)
+    tau = check_row_ratio(row_ratio, gw, fit_intercept)
     sw = check_sample_weight(sample_weight, _rows_of(A), _np_dtype(A))
     xd, Ad, bd = _inputs(x, A, b)
     swd = _sw_device(sw, Ad.device)
+    if tau > 0.0:
+        rec, rn, plan, _ = _sgl_record(xd, Ad, bd, mu, tau, gw, row_norms, swd)
+        out = compose_sgl(rec, mu, tau)
+        out["plan"] = plan
+        if row_norms:
+            out["row_norms"] = rn if isinstance(A, torch.Tensor) else rn.cpu().numpy()
+        return out
     if fit_intercept:
         rec, nrm, plan, _, icpt = _record_ic(xd, Ad, bd, mu, fused, row_norms, swd, _sigma(sw, Ad.shape[0]), None, gw)
         out = compose(rec, mu) if gw is None else compose_groups(rec, mu)
@@ -389,15 +466,21 @@ def certificate(x, A, b, mu, groups=None, weights=None, *, fused: int = 0, row_n
     return out
 
 
-def mu_max(A, b, groups=None, weights=None, sample_weight=None, fit_intercept: bool = False) -> float:
+def mu_max(A, b, groups=None, weights=None, sample_weight=None, fit_intercept: bool = False,
+           row_ratio=None) -> float:
     """The smallest mu for which x = 0 is optimal, max_i ||(A^T b)_i||_2: the certificate's gmax at
     x = 0, where r = -b. With ``groups`` / ``weights``: max_g ||(A^T b)_[g]||_F / w_g. With
     ``sample_weight``: of A^T W b. With ``fit_intercept``: of A^T W (b - 1 b-bar^T), b-bar the weighted
-    column mean of b (at and above it the solution is x = 0 with the intercept b-bar)."""
+    column mean of b (at and above it the solution is x = 0 with the intercept b-bar). With ``row_ratio``
+    (tau > 0, the sparse-group penalty): 1 / min_g s_g from the dual-scale launch on g = A^T b at mu = 1."""
     gw = check_groups(groups, weights, np.shape(A)[1] if len(np.shape(A)) == 2 else -1,
                       np.shape(b)[1] if len(np.shape(b)) == 2 else 1)
+    tau = check_row_ratio(row_ratio, gw, fit_intercept)
     sw = check_sample_weight(sample_weight, _rows_of(A), _np_dtype(A))
     xd, Ad, bd = _inputs(None, A, b)
+    if tau > 0.0:
+        smin = _sgl_record(xd, Ad, bd, 1.0, tau, gw, False, _sw_device(sw, Ad.device))[0][8]
+        return 1.0 / smin if smin > 0.0 else float("inf")
     if fit_intercept:
         return float(_record_ic(xd, Ad, bd, 0.0, 0, False, _sw_device(sw, Ad.device), _sigma(sw, Ad.shape[0]), None,
                                 gw)[0][3])

@@ -104,7 +104,7 @@ def check_cv_args(A, b, folds, mus, n_mus, mu_min_ratio, sample_weight, groups, 
 def cv_path(A, b, folds=5, mus: Optional[Sequence[float]] = None, n_mus: int = 10, mu_min_ratio: float = 1e-2,
             sample_weight=None, groups=None, weights=None, tol: float = 1e-6, maxit: Optional[int] = None,
             screen: bool = True, check_every: int = 10, refit: bool = False,
-            fit_intercept: bool = False) -> Dict[str, Any]:
+            fit_intercept: bool = False, row_ratio=None) -> Dict[str, Any]:
     """K-fold cross-validation of :func:`glx.path` over mu.
 
     ``folds``: an int K (row j goes to fold j mod K) or m fold labels 0 .. K - 1 (:func:`fold_labels`).
@@ -115,7 +115,9 @@ def cv_path(A, b, folds=5, mus: Optional[Sequence[float]] = None, n_mus: int = 1
     ``tol``, ``maxit``, ``screen`` and ``check_every`` are the solves'. ``fit_intercept`` is passed
     through: every fold then fits its own unpenalised intercept (the weighted mean differs from fold to
     fold, and no fold centres or copies A), the grid starts at ``glx.mu_max(..., fit_intercept=True)`` of
-    the full data and a fold's validation loss is taken with its training intercept.
+    the full data and a fold's validation loss is taken with its training intercept. ``row_ratio`` (the
+    sparse-group penalty of :func:`glx.solve_certified`) is passed through as well; the grid then starts at
+    ``glx.mu_max(..., row_ratio=...)``.
 
     Returns a dict: ``mus``, ``fold_loss`` (K x n_mus: each fold's ``holdout_loss``), ``mean``, ``se``
     (standard error over folds, ddof 1), ``best`` (index of the smallest mean), ``one_se`` (the
@@ -127,8 +129,10 @@ def cv_path(A, b, folds=5, mus: Optional[Sequence[float]] = None, n_mus: int = 1
     maxit = _screen.DEFAULT_MAXIT if maxit is None else maxit
     gw, sw, labels, K, mus = check_cv_args(A, b, folds, mus, n_mus, mu_min_ratio, sample_weight, groups, weights,
                                            tol, maxit, check_every)
+    from .certificate import check_row_ratio
+    tau = check_row_ratio(row_ratio, gw, bool(fit_intercept))
     dt = _np_dtype(A)
-    prep = _screen._Prepared(A, b, screen, None, gw, sw, weighted=True, intercept=bool(fit_intercept))
+    prep = _screen._Prepared(A, b, screen, None, gw, sw, weighted=True, intercept=bool(fit_intercept), tau=tau)
     if mus is None:
         mus = _screen.mu_grid(_screen._top(prep, gw, sw), n_mus, mu_min_ratio)
     fold_loss = np.zeros((K, len(mus)), dtype=np.float64)

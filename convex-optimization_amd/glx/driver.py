@@ -129,13 +129,17 @@ def solve_routine(mode: str, func: Callable, x0, A, b, mu, opts, errfun, errfun_
 
 
 def certified_rows(mode: str, x0, A, b, mu, errfun, errfun_exact, sparsity, xstar=None, certify=False,
-                   headers=None, intercept: bool = False, intercepts=None) -> Dict[str, Dict[str, str]]:
+                   headers=None, intercept: bool = False, intercepts=None,
+                   row_ratio: Optional[float] = None) -> Dict[str, Dict[str, str]]:
     """The rows ``--certified`` appends: ``mode`` "solve" gives one row "Certified" (glx.solve_certified
     at mu from x0), "path" one row per mu of glx.path's default grid. Same keys as solve_routine's.
     ``intercept``: the solves fit an unpenalised intercept (``fit_intercept=True``); ``intercepts`` (a
-    dict) then receives each row's intercept."""
+    dict) then receives each row's intercept. ``row_ratio``: the sparse-group penalty on
+    :func:`demo_groups`' groups of four rows."""
     from glx.screen import path, solve_certified
     kw = {"fit_intercept": True} if intercept else {}
+    if row_ratio is not None:
+        kw.update(demo_groups(np.shape(A)[1]), row_ratio=float(row_ratio))
     if mode == "solve":
         x, info = solve_certified(A, b, mu, x0=x0, **kw)
         results = [("Certified", x, info)]
@@ -162,6 +166,13 @@ def certified_rows(mode: str, x0, A, b, mu, errfun, errfun_exact, sparsity, xsta
         if intercept and intercepts is not None:
             intercepts[name] = info["intercept"]
     return rows
+
+
+def demo_groups(n: int, size: int = 4) -> Dict[str, Any]:
+    """The groups ``--row-ratio`` runs on: consecutive runs of ``size`` rows (the last one cut to fit) with
+    the weights sqrt(run), as ``groups`` / ``weights`` keywords."""
+    ptr = np.unique(np.concatenate((np.arange(0, int(n), int(size)), [int(n)]))).astype(np.int32)
+    return {"groups": ptr, "weights": np.sqrt(np.diff(ptr).astype(np.float64))}
 
 
 def write_to_table(log_dicts: Dict[str, Dict[str, str]], stream: TextIO = sys.stdout) -> str:
@@ -199,7 +210,8 @@ def setup_logger(log_file: Optional[str], level=logging.INFO) -> logging.Logger:
 def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Dict[str, dict]] = None,
         xstar: Optional[np.ndarray] = None, dest_dir: Optional[str] = None, seed: int = SEED,
         size=(256, 512, 2), stream: TextIO = sys.stdout, certify: bool = False,
-        certified: Optional[str] = None, cv: int = 0, intercept: bool = False) -> Dict[str, Any]:
+        certified: Optional[str] = None, cv: int = 0, intercept: bool = False,
+        row_ratio: Optional[float] = None) -> Dict[str, Any]:
     """The body of main.py's __main__ block (main.py:141-235) without the CVX solvers and plots.
 
     ``solvers`` defaults to the GPU solvers; tests pass other callables with the same signature.
@@ -210,9 +222,14 @@ def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Di
     per mu with the mean validation loss, its standard error and a marker on the best and on the
     one-standard-error choice. ``intercept`` passes ``fit_intercept=True`` to the certified solves and to
     cv_path and appends one line with the largest magnitude of the fitted intercepts behind each.
+    ``row_ratio`` = T passes the sparse-group penalty (``row_ratio=T`` on :func:`demo_groups`) to the
+    certified solves and to cv_path; it is checked before anything runs.
     Returns {"log_dicts", "f_hists", "f_star", "xs"} (and "cv": glx.cv_path's dict with ``cv``).
     """
     m, n, l = size
+    if row_ratio is not None:
+        from glx.certificate import check_row_ratio
+        check_row_ratio(row_ratio, (None, None), intercept)
     n, m, l, mu, A, b, u, x0, errfun, errfun_exact, sparsity = gen_data(seed, m, n, l)
     if xstar is not None and np.shape(xstar) != (n, l):
         raise ValueError(f"x* has shape {np.shape(xstar)}, the instance needs {(n, l)}")
@@ -229,7 +246,8 @@ def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Di
     icpts: Dict[str, Any] = {}
     if certified:
         for mode, d in certified_rows(certified, x0, A, b, mu, errfun, errfun_exact, sparsity, xstar,
-                                      certify, intercept=intercept, intercepts=icpts).items():
+                                      certify, intercept=intercept, intercepts=icpts,
+                                      row_ratio=row_ratio).items():
             log_dicts[mode] = d
     write_to_table(log_dicts, stream)
     if certified and intercept:
@@ -238,7 +256,10 @@ def run(solvers: Optional[Dict[str, Callable]] = None, solvers_opts: Optional[Di
     cv_out = None
     if cv:
         from glx.cv import cv_path, format_table
-        cv_out = cv_path(A, b, folds=int(cv), fit_intercept=True) if intercept else cv_path(A, b, folds=int(cv))
+        if row_ratio is not None:
+            cv_out = cv_path(A, b, folds=int(cv), row_ratio=float(row_ratio), **demo_groups(n))
+        else:
+            cv_out = cv_path(A, b, folds=int(cv), fit_intercept=True) if intercept else cv_path(A, b, folds=int(cv))
         stream.write("# Cross-validation (%d folds)\n%s\n" % (int(cv), format_table(cv_out)))
         if intercept:
             stream.write("# Intercept (cross-validation): max |c| over folds and mu = %.6e\n"
@@ -276,6 +297,9 @@ def main(argv=None) -> int:
     p.add_argument("--intercept", action="store_true",
                    help="With --certified and --cv: fit an unpenalised intercept (fit_intercept=True) and "
                         "print the largest magnitude of the fitted intercepts.")
+    p.add_argument("--row-ratio", type=float, default=None, metavar="T", dest="row_ratio",
+                   help="With --certified and --cv: the sparse-group penalty mu (T sum_i ||x_i|| + (1 - T) "
+                        "sum_g w_g ||x_[g]||_F) on groups of four consecutive rows with weights sqrt(size).")
     a = p.parse_args(argv)
     setup_logger(a.log)
     size = tuple(int(v) for v in a.size.split(","))
@@ -288,7 +312,7 @@ def main(argv=None) -> int:
             p.error(f"unknown solver(s) {unknown}; choose from {list(solvers)}")
         solvers = {k: solvers[k] for k in keep}
     run(solvers, xstar=xstar, dest_dir=a.dest_dir, seed=a.seed, size=size, stream=sys.stdout,
-        certify=a.certify, certified=a.certified, cv=a.cv, intercept=a.intercept)
+        certify=a.certify, certified=a.certified, cv=a.cv, intercept=a.intercept, row_ratio=a.row_ratio)
     return 0
 
 

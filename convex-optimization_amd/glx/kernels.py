@@ -958,6 +958,133 @@ def group_screen_guard(rec, mu: float, dtype: int, m: int, n: int, l: int, max_r
     return float(out[0]), float(out[1]), float(out[2])
 
 
+# ---- the sparse-group lasso (glx.h "the sparse-group lasso"; csrc/kernels_sgl.hip) ----
+def sgl_step(y: torch.Tensor, G: torch.Tensor, xk: torch.Tensor, groups, weights, t: float, mu: float,
+             row_ratio: float, thres: float, theta: float, theta_next: float,
+             out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """:func:`group_step` with the two-level prox of the sparse-group penalty (glx_sgl_step, k_sgl_fista);
+    ``sums[2]`` is row_ratio sum_i ||xc_i|| + (1 - row_ratio) sum_g w_g ||xc_[g]||."""
+    rows, l = y.shape
+    ptr, w, ng = _group_args(groups, weights, int(groups[-1]) if groups is not None else rows, l)
+    n = int(ptr[-1])
+    dev = y.device
+    S = _slabs(G, rows, l)
+    o = out if out is not None else {k: torch.full_like(y, float("nan")) for k in ("xc", "v_next", "y_next")}
+    sums = o.get("sums") if out is not None and "sums" in o else _nan_sums(4, dev)
+    ws = _group_ws(ng, dev)
+    check(lib().glx_sgl_step(_dt(y), n, rows, l, ng, ptr.ctypes.data, w.ctypes.data, y.data_ptr(), G.data_ptr(), S,
+                             xk.data_ptr(), float(t), float(mu), float(row_ratio), float(thres), float(theta),
+                             float(theta_next), o["xc"].data_ptr(), o["v_next"].data_ptr(), o["y_next"].data_ptr(),
+                             sums.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return {"xc": o["xc"], "v_next": o["v_next"], "y_next": o["y_next"], "sums": sums}
+
+
+def sgl_certificate_step(x: torch.Tensor, G: torch.Tensor, groups, weights, mu: float, row_ratio: float,
+                         want_g: bool = False) -> Dict[str, torch.Tensor]:
+    """The certificate's sparse-group terms in one launch (glx_sgl_certificate_step, k_sgl_cert). Returns
+    {"sums": [penalty, max_i ||g_i||, kkt_max, sum kkt^2, nonzero groups, nonzero rows], "row_norms":
+    ||g_i|| (n float64)} and, with ``want_g``, "g": the summed gradient."""
+    n, l = x.shape
+    ptr, w, ng = _group_args(groups, weights, n, l)
+    dev = x.device
+    S = _slabs(G, n, l)
+    sums = _nan_sums(6, dev)
+    rn = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    gout = torch.full_like(x, float("nan")) if want_g else None
+    ws = _group_ws(ng, dev)
+    check(lib().glx_sgl_certificate_step(_dt(x), n, l, ng, ptr.ctypes.data, w.ctypes.data, x.data_ptr(), G.data_ptr(),
+                                         S, float(mu), float(row_ratio), _ptr(gout), rn.data_ptr(), sums.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _stream(dev)))
+    out = {"sums": sums, "row_norms": rn}
+    if want_g:
+        out["g"] = gout
+    return out
+
+
+def sgl_dual_scale(row_norms: torch.Tensor, groups, weights, a: float, cb: float,
+                   pads=((1.0, 0.0), (1.0, 0.0))) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The per-group dual scalings in one launch (glx_sgl_dual_scale, k_sgl_dual_scale) on the float64 row
+    norms: two solves, ``pads[q] = (mul, add)`` applied to every norm first. Returns (s_g (2, G), unclamped;
+    min_g s_g (2,)), device tensors."""
+    n = int(row_norms.shape[0])
+    assert row_norms.dtype == torch.float64 and row_norms.is_contiguous()
+    ptr, w, ng = _group_args(groups, weights, n)
+    dev = row_norms.device
+    sg = torch.full((2, ng), float("nan"), dtype=torch.float64, device=dev)
+    neg = torch.full((2,), float("nan"), dtype=torch.float64, device=dev)
+    ws = _group_ws(ng, dev)
+    check(lib().glx_sgl_dual_scale(n, ng, ptr.ctypes.data, w.ctypes.data, row_norms.data_ptr(), float(a), float(cb),
+                                   float(pads[0][0]), float(pads[0][1]), float(pads[1][0]), float(pads[1][1]),
+                                   sg.data_ptr(), neg.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return sg, -neg
+
+
+def sgl_screen(row_norms: torch.Tensor, col_norms: torch.Tensor, gcn: torch.Tensor, groups, weights, s: float,
+               mul: float, add: float, rad: float, a_lo: float, cb_lo: float, group_test: bool = True
+               ) -> Dict[str, torch.Tensor]:
+    """The two-level screening test in one launch (glx_sgl_screen, k_sgl_screen). Returns {"keep": int32
+    (n), "group_keep": int32 (G), "counts": float64 [groups that keep a row, kept rows]}."""
+    n = int(row_norms.shape[0])
+    for v in (row_norms, col_norms, gcn):
+        assert v.dtype == torch.float64 and v.is_contiguous()
+    ptr, w, ng = _group_args(groups, weights, n)
+    assert int(col_norms.shape[0]) >= n and int(gcn.shape[0]) == ng
+    dev = row_norms.device
+    keep = torch.full((n,), -2, dtype=torch.int32, device=dev)
+    gkeep = torch.full((ng,), -2, dtype=torch.int32, device=dev)
+    counts = _nan_sums(2, dev)
+    ws = _group_ws(ng, dev)
+    check(lib().glx_sgl_screen(n, ng, ptr.ctypes.data, w.ctypes.data, row_norms.data_ptr(), col_norms.data_ptr(),
+                               gcn.data_ptr(), float(s), float(mul), float(add), float(rad), float(a_lo),
+                               float(cb_lo), int(bool(group_test)), keep.data_ptr(), gkeep.data_ptr(),
+                               counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
+    return {"keep": keep, "group_keep": gkeep, "counts": counts}
+
+
+def sgl_expand(keep: torch.Tensor, group_ptr: torch.Tensor, weights: torch.Tensor, gcn: torch.Tensor,
+               gmap: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """Kept rows to the reduced problem (glx_sgl_expand, k_sgl_expand). Device tensors: ``keep`` int32 (a
+    0/1 flag per row, :func:`sgl_screen`'s), ``group_ptr`` int32 (G + 1), ``weights`` / ``gcn`` float64 (G),
+    ``gmap`` int32 (G) or None. Returns {"rows": int32, n rounded up to 64 entries (the kept rows ascending,
+    -1 up to count[3], -2 behind), "group_ptr" (G + 1, the first K + 1 written), "weights", "gcn", "map" (G,
+    the first K written), "count": int32 [K, rows, rows, rows rounded up to 64]}."""
+    dev = keep.device
+    G = int(weights.shape[0])
+    for t in (keep, group_ptr) + ((gmap,) if gmap is not None else ()):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert weights.dtype == torch.float64 and gcn.dtype == torch.float64
+    assert int(group_ptr.shape[0]) == G + 1 and int(gcn.shape[0]) == G
+    n = int(group_ptr[-1])
+    if int(keep.shape[0]) < n:
+        raise ValueError("sgl_expand: keep must hold a flag per row")
+    hp = group_ptr.cpu()
+    if int(hp[0]) != 0 or not bool((hp[1:] > hp[:-1]).all()):
+        raise ValueError("sgl_expand: group_ptr must start at 0 and increase strictly")
+    rows = torch.full(((n + 63) // 64 * 64,), -2, dtype=torch.int32, device=dev)
+    ptr_o = torch.full((G + 1,), -2, dtype=torch.int32, device=dev)
+    map_o = torch.full((G,), -2, dtype=torch.int32, device=dev)
+    w_o = torch.full((G,), float("nan"), dtype=torch.float64, device=dev)
+    gcn_o = torch.full((G,), float("nan"), dtype=torch.float64, device=dev)
+    cnt = torch.full((4,), -2, dtype=torch.int32, device=dev)
+    check(lib().glx_sgl_expand(G, keep.data_ptr(), group_ptr.data_ptr(), weights.data_ptr(), gcn.data_ptr(),
+                               _ptr(gmap), rows.data_ptr(), ptr_o.data_ptr(), w_o.data_ptr(), gcn_o.data_ptr(),
+                               map_o.data_ptr(), cnt.data_ptr(), _stream(dev)))
+    return {"rows": rows, "group_ptr": ptr_o, "weights": w_o, "gcn": gcn_o, "map": map_o, "count": cnt}
+
+
+def sgl_screen_guard(rec, s_pad: float, mu: float, row_ratio: float, dtype: int, m: int, n: int, l: int,
+                     max_run: int, w_min: float, col_max: float, col_sumsq: float, b_norm: float,
+                     weighted: bool = False) -> Tuple[float, float, float, float, float]:
+    """The sparse-group rounding guard (glx_sgl_screen_guard[_sw], host only, needs no device): (mul, add,
+    s_safe, gap+, rho+) from the record's first three entries and the padded solve's minimum."""
+    r = (ctypes.c_double * 8)(*[float(v) for v in list(rec)[:8]])
+    out = (ctypes.c_double * 5)()
+    fn = lib().glx_sgl_screen_guard_sw if weighted else lib().glx_sgl_screen_guard
+    check(fn(r, float(s_pad), float(mu), float(row_ratio), int(dtype), int(m), int(n), int(l), int(max_run),
+             float(w_min), float(col_max), float(col_sumsq), float(b_norm), out))
+    return tuple(float(v) for v in out)
+
+
 # ---- sample weights (glx.h "sample weights"; the weighted guards, host only) ----
 def screen_guard_sw(rec, mu: float, dtype: int, m: int, n: int, l: int, col_max: float, col_sumsq: float,
                     b_norm: float) -> Tuple[float, float, float]:

@@ -36,9 +36,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import GlxCertifiedInfo, GlxGroupCertifiedInfo, GlxProblem, check, lib
-from .certificate import (_inputs, _np_dtype, _rows_of, _sigma, _sw_device, check_groups, check_sample_weight,
-                          compose, compose_groups, mu_max)
+from ._lib import GlxCertifiedInfo, GlxGroupCertifiedInfo, GlxProblem, GlxSglCertifiedInfo, check, lib
+from .certificate import (_inputs, _np_dtype, _rows_of, _sigma, _sw_device, check_groups, check_row_ratio,
+                          check_sample_weight, compose, compose_groups, mu_max)
 
 DEFAULT_MAXIT = 100000
 
@@ -120,11 +120,13 @@ class _Prepared:
     and the workspace."""
 
     def __init__(self, A, b, screen: bool, comm=None, gw=None, sw=None, weighted: bool = False,
-                 intercept: bool = False):
+                 intercept: bool = False, tau: float = 0.0):
         """``sw``: the checked host sample weights (None: the unweighted problem). ``weighted=True``
         sizes the workspace for weights that arrive later (:meth:`set_weights`, one per fold).
         ``intercept=True``: the problem with an unpenalised intercept (libglx's ``_ic`` entries, which
-        take the weights or none)."""
+        take the weights or none). ``tau`` > 0: the sparse-group penalty (the checked ``row_ratio``; libglx's
+        ``glx_sgl`` entries, which take the weights or none)."""
+        self.tau = float(tau)
         if comm is not None:
             raise ValueError("the certified solve is single-GPU: it takes no communicator")
         _, self.Ad, self.bd = _inputs(None, A, b)
@@ -142,7 +144,10 @@ class _Prepared:
         with torch.cuda.device(self.device):
             nb = ctypes.c_size_t(0)   # (first: it refuses what the solve would, before any launch)
             suffix = "_ic" if self.intercept else ("_sw" if self.weighted else "")
-            if gw is None:
+            if self.tau > 0.0:
+                check(lib().glx_sgl_certified_workspace_bytes(self.gdt, self.m, self.n, self.l, self.G,
+                                                              int(self.screen), int(self.weighted), ctypes.byref(nb)))
+            elif gw is None:
                 check(getattr(lib(), "glx_certified%s_workspace_bytes" % suffix)(
                     self.gdt, self.m, self.n, self.l, int(self.screen), ctypes.byref(nb)))
             else:
@@ -244,14 +249,22 @@ class _Prepared:
 
     def _solve_groups(self, mu, xd, p, rows, tol, maxit, check_every, hold=None):
         ptr, w = self.gw
-        ginfo = GlxGroupCertifiedInfo()
+        sinfo = GlxSglCertifiedInfo()
+        ginfo = sinfo.base if self.tau > 0.0 else GlxGroupCertifiedInfo()
         hs = ctypes.c_double(0.0)
         grps = torch.full((self.G,), -1, dtype=torch.int32, device=self.device)
         icpt = (ctypes.c_double * self.l)()
         with torch.cuda.device(self.device):
             stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             cn = None if self.cn is None else self.cn.data_ptr()
-            if self.intercept:
+            if self.tau > 0.0:
+                check(lib().glx_sgl_certified_solve_sw(
+                    ctypes.byref(p), self.tau, self.G, ptr.ctypes.data, w.ctypes.data,
+                    None if self.sw is None else self.sw.data_ptr(), None if hold is None else hold.data_ptr(),
+                    self.t, float(tol), int(maxit), int(self.screen), int(check_every), cn, self.cstats,
+                    rows.data_ptr(), grps.data_ptr(), self.ws.data_ptr(), self.ws.numel(), ctypes.byref(sinfo),
+                    ctypes.byref(hs), stream))
+            elif self.intercept:
                 check(lib().glx_group_certified_solve_ic(
                     ctypes.byref(p), self.G, ptr.ctypes.data, w.ctypes.data,
                     None if self.sw is None else self.sw.data_ptr(), None if hold is None else hold.data_ptr(),
@@ -272,7 +285,14 @@ class _Prepared:
                     self.ws.numel(), ctypes.byref(ginfo), ctypes.byref(hs), stream))
         info = ginfo.base
         out: Dict[str, Any] = compose_groups(list(info.cert), mu)
-        if self.intercept:
+        if self.tau > 0.0:   # the sparse-group record: cert[7] counts the nonzero rows
+            nzr = float(info.cert[7])
+            out["fused"] = False
+            out["nonzero_rows"] = nzr if math.isnan(nzr) else int(nzr)
+            out["row_ratio"] = self.tau
+            out["plan"] = _describe(lib().glx_sgl_certified_describe, self.gdt, self.m, self.n, self.l, self.max_run,
+                                    int(self.screen), int(self.sw is not None))
+        elif self.intercept:
             out["plan"] = _describe(lib().glx_group_certified_ic_describe, self.gdt, self.m, self.n, self.l,
                                     self.max_run, int(self.screen))
             out["intercept"] = np.array(list(icpt), dtype=np.float64)
@@ -300,6 +320,8 @@ class _Prepared:
                    rounds=int(info.rounds), passes=float(info.passes), tt=float(info.tt),
                    inner_rel_gap=float(info.inner_rel_gap), step_fused=False, screen=self.screen, tol=float(tol),
                    step=self.t, mu=mu)
+        if self.tau > 0.0:
+            out["kept_row_history"] = [int(sinfo.kept_row_hist[i]) for i in range(min(nc, 64))]
         return xd, out
 
     def result(self, xd: torch.Tensor):
@@ -308,7 +330,7 @@ class _Prepared:
 
 def solve_certified(A, b, mu, x0=None, tol: float = 1e-6, maxit: int = DEFAULT_MAXIT, screen: bool = True,
                     check_every: int = 10, comm=None, groups=None, weights=None, sample_weight=None,
-                    holdout_weight=None, fit_intercept: bool = False) -> Tuple[Any, Dict[str, Any]]:
+                    holdout_weight=None, fit_intercept: bool = False, row_ratio=None) -> Tuple[Any, Dict[str, Any]]:
     """Solve min_x 1/2 ||A x - b||_F^2 + mu sum_i ||x_i||_2 until the duality gap is at most ``tol``
     of the primal objective (or ``maxit`` iterations in total).
 
@@ -345,12 +367,22 @@ def solve_certified(A, b, mu, x0=None, tol: float = 1e-6, maxit: int = DEFAULT_M
     runs on the centred weighted column norms; A is not centred or copied. ``info["intercept"]`` holds c
     (l float64 values), ``primal`` / ``dual`` / ``gap`` / ``rel_gap`` speak of the minimum over c, and
     ``holdout_loss`` = 1/2 sum_j v_j ||(A x + c - b)_j||^2 / sum_j v_j. It composes with ``groups`` /
-    ``weights``, ``sample_weight`` and ``holdout_weight``."""
+    ``weights``, ``sample_weight`` and ``holdout_weight``.
+
+    ``row_ratio`` (None or 0: today's group path, call for call and bit for bit; needs ``groups`` /
+    ``weights``): tau in [0, 1], the sparse-group lasso ``mu (tau sum_i ||x_i||_2 + (1 - tau) sum_g w_g
+    ||x_[g]||_F)`` (DESIGN.md "Sparse-group lasso"): the step is the two-level prox, the test screens groups
+    and, inside a surviving group, rows, and a compaction removes both. ``info`` carries the group keys plus
+    ``row_ratio``, ``nonzero_rows`` beside ``nonzero_groups`` and ``kept_row_history`` (rows after each
+    compaction; ``kept`` and ``kept_history`` keep counting groups). It composes with ``sample_weight`` and
+    ``holdout_weight``; with ``fit_intercept=True`` it raises ValueError (the intercept guard's slack has no
+    sparse-group derivation yet)."""
     gw = _check_args(A, b, x0, tol, maxit, check_every, groups, weights)
+    tau = check_row_ratio(row_ratio, gw, fit_intercept)
     sw, hw = _check_sample(A, sample_weight, holdout_weight)
     if not float(mu) >= 0.0:
         raise ValueError("mu must be >= 0")
-    prep = _Prepared(A, b, screen, comm, gw, sw, intercept=bool(fit_intercept))
+    prep = _Prepared(A, b, screen, comm, gw, sw, intercept=bool(fit_intercept), tau=tau)
     xd, info = prep.solve(mu, x0, tol, maxit, check_every, _sw_device(hw, prep.device))
     _holdout_info(info, hw)
     return prep.result(xd), info
@@ -362,30 +394,33 @@ def path(A, b, mus: Optional[Sequence[float]] = None, n_mus: int = 10, mu_min_ra
     values from ``glx.mu_max(A, b)`` down to ``mu_min_ratio`` of it (:func:`mu_grid`). Each solve is
     warm-started from the one before; the column norms and lambda_max are computed once. ``kw``:
     ``tol``, ``maxit``, ``screen``, ``check_every``, ``groups``, ``weights``, ``sample_weight``,
-    ``holdout_weight``, ``fit_intercept`` of :func:`solve_certified` (with groups, sample weights or an
-    intercept the grid starts at their ``mu_max``). Returns the list of ``(mu, x, info)``; at mu = mu_max
+    ``holdout_weight``, ``fit_intercept``, ``row_ratio`` of :func:`solve_certified` (with groups, sample
+    weights, an intercept or a row ratio the grid starts at their ``mu_max``). Returns the list of ``(mu, x, info)``; at mu = mu_max
     the entry is x = 0 with gap 0 and no iterations (with an intercept the gap there is rounding dust:
     the centred residual sums to zero only up to its own rounding)."""
     unknown = set(kw) - {"tol", "maxit", "screen", "check_every", "comm", "groups", "weights", "sample_weight",
-                         "holdout_weight", "fit_intercept"}
+                         "holdout_weight", "fit_intercept", "row_ratio"}
     if unknown:
         raise TypeError("path() got unexpected keyword arguments %s" % sorted(unknown))
     tol, maxit = kw.get("tol", 1e-6), kw.get("maxit", DEFAULT_MAXIT)
     check_every = kw.get("check_every", 10)
     gw = _check_args(A, b, None, tol, maxit, check_every, kw.get("groups"), kw.get("weights"))
+    tau = check_row_ratio(kw.get("row_ratio"), gw, bool(kw.get("fit_intercept", False)))
     sw, hw = _check_sample(A, kw.get("sample_weight"), kw.get("holdout_weight"))
     if mus is not None:
         mus = _check_mus(mus)
     else:
         mu_grid(1.0, n_mus, mu_min_ratio)   # the grid's own checks, before any device work
     prep = _Prepared(A, b, kw.get("screen", True), kw.get("comm"), gw, sw,
-                     intercept=bool(kw.get("fit_intercept", False)))
+                     intercept=bool(kw.get("fit_intercept", False)), tau=tau)
     if mus is None:
         mus = mu_grid(_top(prep, gw, sw), n_mus, mu_min_ratio)
     return _run_path(prep, mus, tol, maxit, check_every, hw)
 
 
 def _top(prep: "_Prepared", gw, sw) -> float:
+    if prep.tau > 0.0:
+        return mu_max(prep.Ad, prep.bd, gw[0], gw[1], sample_weight=sw, row_ratio=prep.tau)
     if prep.intercept:
         return mu_max(prep.Ad, prep.bd, None if gw is None else gw[0], None if gw is None else gw[1],
                       sample_weight=sw, fit_intercept=True)

@@ -1036,6 +1036,102 @@ int  glx_comm_all_gather(glx_comm* c, void* buf, int64_t count, int dtype, void*
 int  glx_comm_progress(glx_comm* c, int64_t out[4]);
 void glx_comm_destroy(glx_comm* c);
 
+/* ---- the sparse-group lasso (DESIGN.md "Sparse-group lasso"; csrc/kernels_sgl.hip, csrc/group.cpp) ----
+ *   P(x) = 1/2 ||A x - b||_F^2 + mu (row_ratio sum_i ||x_i||_2 + (1 - row_ratio) sum_g w_g ||x_[g]||_F)
+ * with the groups of the grouped entries (host group_ptr / weights, validated the same way) and
+ * row_ratio in [0, 1] (GLX_E_INVALID otherwise, NaN included). Write a = row_ratio mu and c_g =
+ * (1 - row_ratio) mu w_g. The dual constraint is phi_g(1) <= c_g on A^T theta for every group, phi_g(s) =
+ * sqrt(sum_{i in g} (s rho_i - a)_+^2) with rho_i = ||(A^T theta)_i||; theta = s r with s = min(1, min_g s_g),
+ * s_g = sup{s : phi_g(s) <= c_g}. row_ratio = 0 takes the grouped entry's path, call for call. No entry takes
+ * an intercept. Single GPU.
+ *
+ * glx_sgl_certificate[_sw]: out = 12 doubles. out[0..7] is the grouped record with out[2] = the penalty
+ *   row_ratio sum ||x_i|| + (1 - row_ratio) sum w_g ||x_[g]||, out[3] = mu / min_g s_g (so that the grouped
+ *   composition of the scale, min(1, mu / out[3]), holds; 0 where every s_g is +inf), out[4], out[5] the
+ *   largest KKT distance and the sum of their squares (a nonzero row of a nonzero group: ||g_i + a x_i /
+ *   ||x_i|| + c_g x_i / ||x_[g]|| ||; a zero row of one: (rho_i - a)_+; a zero group: (phi_g(1) - c_g)_+,
+ *   one term), out[6] nonzero groups, out[7] nonzero rows; out[8] = min_g s_g (unclamped), out[9] = the
+ *   same of the padded solve (here unpadded), out[10] = max_i rho_i, out[11] = 0. rownorm_out (may be
+ *   NULL): rho_i, n doubles. _sw: sample weights as in glx_group_certificate_sw (sample_w NULL: none).
+ * glx_sgl_certified_solve[_sw]: glx_group_certified_solve[_sw] with the two-level prox, the two-level
+ *   gap-safe test (row: s rho_i + ||a_i|| R < a; group: phi_g(s) + ||A_[g]||_F R < c_g) under
+ *   glx_sgl_screen_guard, and compactions that remove rows from inside groups. info->base counts groups in
+ *   kept and kept_hist as the grouped solve does; kept_row_hist counts rows. */
+typedef struct glx_sgl_certified_info {
+  glx_group_certified_info base;
+  double row_ratio;
+  int64_t reserved[3];
+  int64_t kept_row_hist[GLX_CERTIFIED_MAX_HIST];   /* kept rows after each of the first 64 compactions */
+} glx_sgl_certified_info;
+int glx_sgl_certificate_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, size_t* bytes);
+int glx_sgl_certificate_describe(int dtype, int64_t m, int64_t n, int64_t l, int weighted, char* out, size_t cap);
+int glx_sgl_certificate(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                        double mu, double row_ratio, int64_t G, const int32_t* group_ptr, const double* weights,
+                        void* G_out, double* rownorm_out, double* out, void* ws, size_t wsb, void* stream);
+int glx_sgl_certificate_sw(int dtype, int64_t m, int64_t n, int64_t l, const void* A, const void* X, const void* b,
+                           double mu, double row_ratio, int64_t G, const int32_t* group_ptr, const double* weights,
+                           const void* sample_w, const void* holdout_w, void* G_out, double* rownorm_out,
+                           double* out, double* holdout_sum, void* ws, size_t wsb, void* stream);
+int glx_sgl_certified_workspace_bytes(int dtype, int64_t m, int64_t n, int64_t l, int64_t G, int screen,
+                                      int weighted, size_t* bytes);
+int glx_sgl_certified_describe(int dtype, int64_t m, int64_t n, int64_t l, int64_t max_run, int screen, int weighted,
+                               char* out, size_t cap);
+int glx_sgl_certified_solve(const glx_problem* prob, double row_ratio, int64_t G, const int32_t* group_ptr,
+                            const double* weights, double t, double tol, int64_t maxit, int screen, int check_every,
+                            const double* col_norms_dev, const double* col_stats, int32_t* kept_rows_dev,
+                            int32_t* kept_groups_dev, void* ws, size_t wsb, glx_sgl_certified_info* info,
+                            void* stream);
+int glx_sgl_certified_solve_sw(const glx_problem* prob, double row_ratio, int64_t G, const int32_t* group_ptr,
+                               const double* weights, const void* sample_w, const void* holdout_w, double t,
+                               double tol, int64_t maxit, int screen, int check_every, const double* col_norms_dev,
+                               const double* col_stats, int32_t* kept_rows_dev, int32_t* kept_groups_dev, void* ws,
+                               size_t wsb, glx_sgl_certified_info* info, double* holdout_sum, void* stream);
+/* The sparse-group rounding guard (host only, needs no device). rec: the record above; s_pad: min_g s_g of
+ * the dual solve on the padded row norms. out = [mul, add, s_safe, gap+, rho+]: mul rho_i + add bounds the
+ * exact ||a_i^T r^|| of every row (the padding of the dual solve and of the screening test), s_safe =
+ * min(1, s_pad), gap+ and rho+ as in glx_group_screen_guard with ||x||_F <= rec[2] / (row_ratio +
+ * (1 - row_ratio) w_min). col_max = the largest column norm. NaN propagates. _sw: the weighted figures. */
+int glx_sgl_screen_guard(const double* rec, double s_pad, double mu, double row_ratio, int dtype, int64_t m,
+                         int64_t n, int64_t l, int64_t max_run, double w_min, double col_max, double col_sumsq,
+                         double b_norm, double* out);
+int glx_sgl_screen_guard_sw(const double* rec, double s_pad, double mu, double row_ratio, int dtype, int64_t m,
+                            int64_t n, int64_t l, int64_t max_run, double w_min, double col_max, double col_sumsq,
+                            double b_norm, double* out);
+/* One launch at a time (ws: glx_group_workspace_bytes(G)):
+ * glx_sgl_step: glx_group_step with the two-level prox: w = y - t g, u_i = (1 - t a / ||w_i||)_+ w_i,
+ *   q_g = sqrt(sum_{i in g} (||w_i|| - t a)_+^2), x_[g] = (1 - t c_g / q_g)_+ u_[g]; sums[2] = the penalty of
+ *   xc. A zero row or group is +0.
+ * glx_sgl_certificate_step: sums = [penalty, max_i rho_i, max kkt, sum kkt^2, nonzero groups, nonzero rows]
+ *   (6 doubles); rownorm_out (may be NULL): rho_i = ||g_i||, n doubles; gout (may be NULL): g.
+ * glx_sgl_dual_scale: two solves q = 0, 1 on p_i = mul_q rho_i + add_q: sg_dev (may be NULL, 2 G doubles)
+ *   = the unclamped s_g, +inf where every p_i = 0, a / max_i p_i where cb = 0; negmin_dev[q] = -min_g s_g.
+ *   s_g is the feasible end of the bracket [0, (a + c_g) / max_i p_i] after 56 halvings: a point at which
+ *   the kernel evaluated phi_g <= c_g, at most (a + c_g) / max_i p_i * 2^-56 below the exact value.
+ * glx_sgl_screen: keep_dev[i] = 0 where s p_i + col_norms[i] rad < a_lo or, with group_test != 0, where the
+ *   row's group has sqrt(sum_i (s p_i - a_lo)_+^2) / w_g + gcn_g rad < cb_lo; p_i = mul rho_i + add;
+ *   group_keep_dev (may be NULL, G): the group keeps a row; counts_dev = [such groups, kept rows]. NaN keeps.
+ * glx_sgl_expand (device arrays only): keep_dev -> rows_out (the kept rows, ascending, then -1 up to
+ *   count_out[3]), the reduced group_ptr_out / weights_out / gcn_out / map_out over the groups that keep a
+ *   row (gcn carried over: the larger value is the safe one), count_out = [groups, rows, rows, rows
+ *   rounded up to 64]. */
+int glx_sgl_step(int dtype, int64_t n, int64_t rows, int64_t l, int64_t G, const int32_t* group_ptr,
+                 const double* weights, const void* y, const void* g, int S, const void* xk, double t, double mu,
+                 double row_ratio, double thres, double theta, double theta_next, void* xc, void* vnext, void* ynext,
+                 void* sums_dev, void* ws, size_t wsb, void* stream);
+int glx_sgl_certificate_step(int dtype, int64_t n, int64_t l, int64_t G, const int32_t* group_ptr,
+                             const double* weights, const void* x, const void* g, int S, double mu, double row_ratio,
+                             void* gout, double* rownorm_out, void* sums_dev, void* ws, size_t wsb, void* stream);
+int glx_sgl_dual_scale(int64_t n, int64_t G, const int32_t* group_ptr, const double* weights,
+                       const double* rownorms_dev, double a, double cb, double mul0, double add0, double mul1,
+                       double add1, double* sg_dev, double* negmin_dev, void* ws, size_t wsb, void* stream);
+int glx_sgl_screen(int64_t n, int64_t G, const int32_t* group_ptr, const double* weights, const double* rownorms_dev,
+                   const double* col_norms_dev, const double* gcn_dev, double s, double mul, double add, double rad,
+                   double a_lo, double cb_lo, int group_test, int32_t* keep_dev, int32_t* group_keep_dev,
+                   double* counts_dev, void* ws, size_t wsb, void* stream);
+int glx_sgl_expand(int64_t G, const int32_t* keep_dev, const int32_t* group_ptr_dev, const double* weights_dev,
+                   const double* gcn_dev, const int32_t* map_dev, int32_t* rows_out, int32_t* group_ptr_out,
+                   double* weights_out, double* gcn_out, int32_t* map_out, int32_t* count_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
