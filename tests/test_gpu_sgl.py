@@ -83,6 +83,12 @@ def _many_groups(g, G, pool):
 # lane), n no multiple of 64, runs of 64 and 65 rows, and 4101 groups: five past one trip of 1024 workgroups
 STEP_CASES = [(130, 130, 3, gr.POOL_RAGGED), (475, 512, 32, gr.POOL_SMALL), (203, 256, 3, gr.POOL_LONG),
               (70, 70, 1, (1, 2)), (90, 128, 128, (1, 3, 5)), (0, 0, 1, (1, 2))]
+# every lane layout of sgl_dispatch by itself, at both ends of its range of l: (4, 1) at l = 4, (16, 1) at 5 and
+# 16, (32, 1) at 17, (64, 1) at 33 and 64, (64, 2) at 65 and at 127, where the second element of the last lanes
+# is masked. About 130 rows in groups of up to 5: more rows than the 4, 2 or 1 sub-teams of a wave from l = 5 on.
+STEP_CASES += [(129, 129, 4, gr.POOL_RAGGED), (130, 192, 5, (1, 3, 5)), (131, 131, 16, gr.POOL_RAGGED),
+               (129, 129, 17, (1, 3, 5)), (130, 192, 33, gr.POOL_RAGGED), (131, 131, 64, (1, 3, 5)),
+               (129, 129, 65, gr.POOL_RAGGED), (130, 192, 127, (1, 3, 5))]
 T_STEP, MU_STEP = 0.3, 0.7
 
 
@@ -212,6 +218,7 @@ def test_sgl_step(case, dt, tau):
 # ------------------------------------------------------------------------------------------ 2
 CERT_CASES = [(130, 3, gr.POOL_RAGGED), (475, 32, gr.POOL_SMALL), (203, 3, gr.POOL_LONG), (70, 1, (1, 2)),
               (90, 128, (1, 3, 5)), (0, 1, (1, 2))]
+CERT_CASES += [(n, l, pool) for n, _, l, pool in STEP_CASES[6:]]      # (every lane layout by itself: STEP_CASES)
 
 
 @pytest.mark.parametrize("tau", TAUS)
